@@ -8,6 +8,8 @@
     python bench.py --config2                         # BASELINE configs[1]: single-image latency (graf img1, 2000 kp, H2D included)
     python bench.py --config5                         # BASELINE configs[4]: 3840x2160, 8000 kp
     python bench.py --include-h2d                     # headline loop with every step's images uploaded on a copy stream
+    python bench.py --full                            # + cpu_baseline, parity_check, the other arithmetic modes, other_configs, secondary_rooflines
+    python bench.py --dump-outputs DIR                # + the rows the last timed step returned, as DIR/*.npy (dump_outputs)
 
 A "step" = one pass of the whole hot path (pyramid -> Hessian/NMS detector -> AffNet -> filter ->
 OriNet -> level select -> HardNet) over one batch of 64 synthetic 1024x768 images, 2000 keypoints
@@ -20,6 +22,7 @@ all ranks / max-over-ranks time.
 roofline           : dominant kernel = fused HardNet trunk (cnn32_trunk_kernel<2>, fp32 MFMA).  achieved = algorithmic FLOPs
                      per launch / mean launch duration measured with HIP events around that launch on its own stream inside
                      the timed region (affnet_profile_*).
+--full only:
 secondary_rooflines: the HBM-bound scale-space / sampler kernels: algorithmic bytes / HIP-event time, fraction of 8 TB/s.
 cpu_baseline       : the CPU oracle (port of the reference, same torch CPU operators) on this host's cores on a bounded
                      sample of the same workload (rank 0, N == 1 only): thread-count sweep, then median of 5 images.
@@ -367,6 +370,40 @@ def parity_check(kept, fetch, tag=None, golden_batch=0):
     return tot
 
 
+DUMP_BYTES = {"rows": 24 << 20, "descriptors": 32 << 20}     # --dump-outputs: beyond these sizes a seeded sample of whole images
+
+
+def dump_outputs(results, out_dir):
+    """--dump-outputs: the rows the last timed step returned to its caller (one dict per fused call: capacity-sized device tensors + row
+    counts), images in step order, rows past an image's count set to NaN.  counts (B,); ids (n, NKP, 3) as float64, LAFs (n, NKP, 2, 3) and
+    responses (n, NKP) of the images row_images (n,); descriptors (m, NKP, 128) of the images descriptor_images (m,).  Each image set is every
+    image while it fits its DUMP_BYTES budget, else a fixed seeded sample (the 64-image step: all rows, descriptors of 32 images), so that
+    the files stay below 64 MB together."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    batched = lambda r, k: r[k] if r["count"].numel() > 1 else r[k].unsqueeze(0)
+    where = [(r, b) for r in results for b in range(r["count"].numel())]            # image i of the step -> (call, index in that call)
+    counts = np.array([int(r["count"].view(-1)[b]) for r, b in where], dtype=np.int64)
+    B = len(where)
+
+    def images(per_image, budget):
+        n = int(min(B, max(1, budget // per_image)))
+        return np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+
+    def rows(key, pick, dt):
+        a = np.stack([batched(where[i][0], key)[where[i][1], :NKP].cpu().numpy() for i in pick]).astype(dt)
+        a[np.arange(NKP)[None, :] >= counts[pick][:, None]] = np.nan
+        return a
+    pick = images(NKP * (3 * 8 + 6 * 4 + 4), DUMP_BYTES["rows"])
+    arrays = {"counts": counts.astype(np.float64), "row_images": pick.astype(np.float64), "ids": rows("ids", pick, np.float64),
+              "lafs": rows("LAFs", pick, np.float32), "responses": rows("responses", pick, np.float32)}
+    if results[0]["descriptors"] is not None:
+        pick = images(NKP * 128 * 4, DUMP_BYTES["descriptors"])
+        arrays.update(descriptor_images=pick.astype(np.float64), descriptors=rows("descriptors", pick, np.float32))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 LINE_LIMIT = 4096                  # bytes of the ONE stdout line (VERDICT round 5: the driver could not parse a 31 KB line)
 DETAIL_FILE = "bench_detail.json"
@@ -581,6 +618,14 @@ def main():
     ap.add_argument("--no-split3", action="store_true", help="skip the co-reported `arith_fp32_split3` / `arith_fp32_split2h` steps of the default line")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short BASELINE configs[1] (single-image latency) and configs[4] (4K) samples behind `other_configs`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline and parity_check, the co-reported arithmetic modes, "
+                         "other_configs, secondary_rooflines, the stand-alone exchange timing and gather check of the N-rank path, gpu_state "
+                         "(the --no-* options above drop single parts of it).  Without it a run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (rank 0's images) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB (see dump_outputs)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)        # child process of cpu_node_throughput()
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: ranks rendezvous (backend from AFFNET_BENCH_BACKEND, default gloo here), exchange fake records and "
@@ -593,6 +638,8 @@ def main():
         return cpu_worker(args.cpu_worker)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -900,7 +947,9 @@ def run(args, world):
     barrier()
     dt = time.perf_counter() - t0
     gpu_sections.append({"what": "timed region (%d steps)" % args.steps, "unix_start_s": w0, "unix_end_s": time.time()})
-    smi = gpu_state("right after the timed region") if (rank == 0 and not DIST) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    smi = gpu_state("right after the timed region") if (args.full and rank == 0 and not DIST) else None
     kp = int(kp_dev.item())
     # a list that overflowed would have truncated the keypoint set the rate is computed on: fail instead of reporting it.  The
     # per-image flags are cleared at the start of every call, so they are summed on the device after each step (the contexts' own
@@ -941,7 +990,7 @@ def run(args, world):
         dist.all_reduce(kp_all, op=dist.ReduceOp.SUM)
     # ---- the exchange on its own (outside the timed region): bytes, stand-alone duration, and the content check ----------------------
     exchange = None
-    if DIST:
+    if DIST and args.full:
         rec_local = sharded.pack_batched_records(last, NKP)                      # this rank's records of the last step
         times = []
         for _ in range(5):
@@ -977,7 +1026,7 @@ def run(args, world):
             exchange["n8_volume_1rank"] = {"records": int(rec8.size(0)), "bytes": int(rec8.numel()) * 4, "gather_ms": t8[len(t8) // 2], "gather_ms_min": t8[0],
                                            "note": "one rank, no link crossed: software floor of the exchange at the N = 8 record volume"}
             del rec8
-    mode = args.verify_gather or ("sample" if world > 1 else ("sample" if SELF else "off"))
+    mode = args.verify_gather or ("sample" if args.full and DIST else "off")
     gather_check = None
     if DIST and mode != "off":
         gather_check = verify_gather(gathered[0], mode, world, rank, args.batch, dev, (A, O, Hn), ONEPASS)
@@ -1056,13 +1105,13 @@ def run(args, world):
             out["stage_ms_per_image"]["detector"] = round(stage_ms[1], 4)
             out["config"]["workload"] = ("OnePassSIR path (SURVEY section 8f row 4) on the BASELINE configs[2] images: batch of %d synthetic %dx%d images, %d kp, "
                                          "border 15; the detector stage includes the dense AffNetFastFullConv of every octave" % (args.batch, W, H, NKP))
-        if not args.no_secondary and not ONEPASS and world == 1:
+        if args.full and not args.no_secondary and not ONEPASS and world == 1:
             out["secondary_rooflines"] = secondary_rooflines(dets, chunks, stage_ms, dev)
         # Co-reported, NOT `value`: the same step in the other arithmetic mode of the boundary (AFFNET_ARITH_FP32_SPLIT3: every CNN contraction
         # on split operands, fp32 = three bf16 terms on the bf16 matrix cores, fp32 accumulate) - a few steps on the same contexts after
         # the timed region, with its own stage events, roofline (bf16 peak), dtype and parity_check
         last_split = {}
-        if world == 1 and not ONEPASS and not args.split3 and not args.no_split3:
+        if args.full and world == 1 and not ONEPASS and not args.split3 and not args.no_split3:
             for mode in SPLIT:
                 key = "arith_" + mode
                 try:
@@ -1101,7 +1150,7 @@ def run(args, world):
             _lib.lib.affnet_profile_enable(d._ctx.handle, 0)
         # BASELINE configs[1] and configs[4] in the default line (short samples after the timed region; `--config2` / `--config5` are the full runs)
         t_oc = time.time()
-        if world == 1 and not ONEPASS and not args.config5 and not args.no_other_configs and args.batch == BATCH:
+        if args.full and world == 1 and not ONEPASS and not args.config5 and not args.no_other_configs and args.batch == BATCH:
             try:
                 out["other_configs"] = other_configs((A, O, Hn), dev, args.arith, gpu_sections, with_cpu=not args.no_cpu_baseline)
             except Exception as e:                                   # noqa: BLE001
@@ -1110,7 +1159,7 @@ def run(args, world):
         if smi is not None:
             out["gpu_state"] = smi
         wall["other_configs_s"] = round(time.time() - t_oc, 1)          # incl. the one-image 4K CPU baseline
-        if world == 1 and not args.no_cpu_baseline and not args.config5 and not ONEPASS:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.config5 and not ONEPASS:
             t_cb = time.time()
             base, kept = cpu_baseline()
             out["cpu_baseline"] = base

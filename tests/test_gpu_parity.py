@@ -1526,7 +1526,7 @@ def test_bench_n_rank_gather_with_real_kernels(ranks, gather):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"AFFNET_BENCH_ONE_DEVICE": "1", "AFFNET_BENCH_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--batch", "4", "--chunk", "2",
-                        "--no-secondary", "--gather", gather, "--verify-gather", "all"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-secondary", "--gather", gather, "--verify-gather", "all"], env=env, capture_output=True, text=True, timeout=900)
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
     d = lines[0]
@@ -1541,6 +1541,38 @@ def test_bench_n_rank_gather_with_real_kernels(ranks, gather):
     assert len(full["ms_per_step_per_rank"]["all"]) == ranks and full["gather_check"]["identical"] is True
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A run without --full: the timed steps and the line, nothing co-reported; --dump-outputs holds the rows the last timed step returned
+    (rank 0 of 4 images in 2 fused calls), equal to single-image calls on the same seeds."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import affnet_amd
+    from affnet_amd.synthetic import synthetic_image
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--chunk", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.rstrip("\n").splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert not {"cpu_baseline", "parity", "other"} & set(d), sorted(d)
+    dump = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("counts", "row_images", "lafs", "responses", "descriptor_images", "descriptors")}
+    assert dump["row_images"].tolist() == [0, 1, 2, 3] and dump["descriptor_images"].tolist() == [0, 1, 2, 3]
+    dev = torch.device("cuda:0")
+    sd = {k: torch.load(os.path.join(root, "pretrained", k + ".pth"), map_location="cpu", weights_only=False)["state_dict"] for k in ("AffNet", "OriNet")}
+    A = affnet_amd.AffNetFast(PS=32); A.load_state_dict(sd["AffNet"]); A.to(dev)
+    O = affnet_amd.OriNetFast(PS=32); O.load_state_dict(sd["OriNet"]); O.to(dev)
+    Hn = affnet_amd.HardNet(); Hn.load_state_dict(affnet_amd.synthetic_hardnet_state(0)); Hn.to(dev)
+    det = affnet_amd.ScaleSpaceAffinePatchExtractor(mrSize=5.192, num_features=2000, border=5, num_Baum_iters=1, AffNet=A, OriNet=O).to(dev)
+    for i in range(4):
+        r = det.run(synthetic_image(768, 1024, i).to(dev), do_ori=True, desc=Hn)
+        n = int(r["LAFs"].shape[0])
+        assert dump["counts"][i] == n and np.isnan(dump["lafs"][i, n:]).all()
+        assert np.array_equal(dump["lafs"][i, :n], r["LAFs"].cpu().numpy()) and np.array_equal(dump["responses"][i, :n], r["responses"].cpu().numpy())
+        assert np.array_equal(dump["descriptors"][i, :n], r["descriptors"].cpu().numpy())
+
+
 def test_bench_line_is_the_last_stdout_line_with_rccl():
     """The driver parses the LAST stdout line.  RCCL writes a version banner ("RCCL version : ... Librccl path : ...") to the C stdout, which - buffered -
     landed AFTER the JSON line when stdout is a file (round 6 evidence run).  bench.py destroys the process group first, flushes the C buffers and prints its
@@ -1552,7 +1584,7 @@ def test_bench_line_is_the_last_stdout_line_with_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"AFFNET_BENCH_SELF_GATHER": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "4", "--chunk", "2", "--no-cpu-baseline",
-                        "--no-secondary", "--no-other-configs", "--no-split3", "--verify-gather", "all"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-secondary", "--no-other-configs", "--no-split3", "--verify-gather", "all"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     last = p.stdout.rstrip("\n").splitlines()[-1]
     d = json.loads(last)                      # fails on a banner line

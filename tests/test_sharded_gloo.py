@@ -155,6 +155,41 @@ def test_compact_line_from_the_recorded_round5_record():
     assert len(t2) < 4096 and json.loads(t2)["exchange"]["bytes_per_step"] == 1 << 29
 
 
+def test_dump_outputs_of_a_step(tmp_path):
+    """bench.py --dump-outputs on the shape of one step's results (fused calls of 32, 30 and 1 images, capacity rows past NKP): the rows each
+    image returns, NaN past its count, descriptors of a seeded image sample, under 64 MB for the 64-image step, and --steps 0 refused."""
+    import glob
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    F = bench.NKP + 7
+    results = []
+    for i, b in enumerate((32, 30, 1)):
+        g = torch.Generator().manual_seed(i)
+        r = {"count": torch.randint(F // 2, bench.NKP + 1, (b,), generator=g, dtype=torch.int32), "LAFs": torch.rand(b, F, 2, 3, generator=g),
+             "responses": torch.rand(b, F, generator=g), "ids": torch.randint(0, 1 << 20, (b, F, 3), generator=g, dtype=torch.int32),
+             "descriptors": torch.rand(b, F, 128, generator=g)}
+        results.append(r if b > 1 else {k: (v if k == "count" else v[0]) for k, v in r.items()})
+    bench.dump_outputs(results, str(tmp_path))
+    files = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(str(tmp_path / "*.npy"))}
+    assert set(files) == {"counts", "row_images", "ids", "lafs", "responses", "descriptor_images", "descriptors"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(f) for f in glob.glob(str(tmp_path / "*.npy"))) < 64e6
+    where = [(r, b) for r in results for b in range(r["count"].numel())]
+    assert files["row_images"].tolist() == list(range(63)) and len(files["descriptor_images"]) == 32
+    for key, name, picked in (("LAFs", "lafs", files["row_images"]), ("ids", "ids", files["row_images"]), ("descriptors", "descriptors", files["descriptor_images"])):
+        for j, i in enumerate(picked.astype(int)):
+            r, b = where[i]
+            n = int(r["count"].view(-1)[b])
+            want = (r[key] if r["count"].numel() > 1 else r[key][None])[b, :n].numpy()
+            assert files["counts"][i] == n and np.array_equal(files[name][j, :n], want) and np.isnan(files[name][j, n:]).all()
+    rc, out, err = _bench("--steps", "0", "--dry-run")
+    assert rc == 2 and not out and "--steps" in err
+
+
 def test_gather_to_rank_in_a_subgroup_uses_global_ranks():
     """_gather_to_rank_async compared the group-LOCAL rank with the GLOBAL dst.  World of 3, sub-group {1, 2}, gather to
     global rank 2: rank 2 must receive both records in order, rank 1 gets None, rank 0 is not involved."""

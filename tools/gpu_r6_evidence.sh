@@ -13,12 +13,12 @@ bench() { # name, args...: stdout / stderr apart, the detail file next to them
   ( time timeout 900 python3 bench.py "$@" ) > gpurun_out/$n.out 2> gpurun_out/$n.err; echo "$n exit: $?"; cp gpurun_out/bench_detail.json gpurun_out/$n.detail.json 2>/dev/null
   tail -n 1 gpurun_out/$n.out | cut -c1-330; grep "^real" gpurun_out/$n.err
 }
-bench bench_driver --gpus 1 --steps 20 --warmup 5
+bench bench_driver --gpus 1 --steps 20 --warmup 5 --full
 bench bench_config2 --config2
-bench bench_config5 --config5 --no-cpu-baseline
-bench bench_onepass --onepass --no-cpu-baseline
-AFFNET_BENCH_BACKEND=gloo AFFNET_BENCH_ONE_DEVICE=1 bench bench_gpus2_onedevice_gloo --gpus 2 --steps 2 --warmup 1 --batch 8 --chunk 8 --no-secondary --verify-gather all
-AFFNET_BENCH_SELF_GATHER=1 bench bench_self_gather_rccl_1rank --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-other-configs --no-split3 --verify-gather all
+bench bench_config5 --config5 --full --no-cpu-baseline
+bench bench_onepass --onepass --full --no-cpu-baseline
+AFFNET_BENCH_BACKEND=gloo AFFNET_BENCH_ONE_DEVICE=1 bench bench_gpus2_onedevice_gloo --gpus 2 --steps 2 --warmup 1 --batch 8 --chunk 8 --full --no-secondary --verify-gather all
+AFFNET_BENCH_SELF_GATHER=1 bench bench_self_gather_rccl_1rank --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary --no-other-configs --no-split3 --verify-gather all
 timeout 120 python bench.py --gpus 2 --steps 1 --warmup 0 > gpurun_out/bench_gpus2_refused.log 2>&1; echo "gpus2 on a 1-GPU box exit (2 = refused loudly): $?"
 # profiles
 COMMON="--steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-other-configs --no-split3"
