@@ -803,10 +803,30 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
 
     // Every layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading
     // the input) -> zero the halo of the OUTPUT layout, bias + ReLU + store in place -> barrier.
+    // HardNet on the exact path: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the
+    // MFMAs; each wave runs NB (tile block, channel block) passes of a layer.  AffNet / OriNet set LAF geometry and keep the direct form.
+    constexpr bool WINO = (KIND == AFFNET_NET_HARDNET && S3 == 0);
+    constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
     // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
     f32x4 b2[G2][T2N];
     f32x4 bias2[T2N];
-    {
+    if constexpr (WINO) {
+        f32x4 y[NB1][4], bw[NB1];
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w[1], y, wave, lane);
+        if (PRIO) __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(3);
+        prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G2>(a.packed + a.off.w[2], b2, wave, lane);
+        prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+        wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
+        __syncthreads();
+        CNN_STAMP(21);
+        zero_halo<LayC1, NTHR>(act, CB);
+        wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
+        CNN_STAMP(22);
+        __syncthreads();
+        CNN_STAMP(4);
+    } else {
         f32x4 acc[T1M][T1N];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         if (ROLL1) conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], reinterpret_cast<const f32x4 (&)[1][T1N]>(b1), acc, wave, lane);
@@ -847,7 +867,21 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
     f32x4 b4[G4][T4N];
     f32x4 bias4[T4N];
-    {
+    if constexpr (WINO) {
+        f32x4 y[NB3][4], bw[NB3];
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w[3], y, wave, lane);
+        if (PRIO) __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(7);
+        prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G4>(a.packed + a.off.w[4], b4, wave, lane);
+        prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+        wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
+        __syncthreads();
+        zero_halo<LayC3, NTHR>(act, 2 * CB);
+        wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
+        __syncthreads();
+        CNN_STAMP(8);
+    } else {
         f32x4 acc[T2M][T2N];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
@@ -883,7 +917,23 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
 
     // ---- conv5: 4CB -> 4CB @8x8 ------------------------------------------------------------------------
-    {
+    if constexpr (WINO) {
+        f32x4 y[NB5][4], bw[NB5];
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        conv3x3_wino_mfma<NW, 4 * CB, 4 * CB, LayC4, NB5>(act, a.packed + a.off.w[5], y, wave, lane);
+        if (PRIO) __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(11);
+        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
+        if (!STAMPS || a.dbg_layer < 0) {
+            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
+            CNN_STAMP(13);
+            return;
+        }
+        __syncthreads();
+        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
+        __syncthreads();
+        CNN_STAMP(12);
+    } else {
         f32x4 acc[T4M][T4N];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         conv3x3_mfma<NW, 4 * CB, 4 * CB, LayC4, 1, T4M, T4N, G5>(act, a.packed + a.off.w[5], b5, acc, wave, lane);

@@ -1249,3 +1249,161 @@ __device__ __forceinline__ void store_tiles_global(float* __restrict__ dst, cons
     }
 }
 
+
+// ---- Winograd F(2x2, 3x3) on v_mfma_f32_16x16x4_f32 (HardNet's stride-1 layers on the exact path) ----------------------------------
+// A 2x2 output tile is  Y = A^T [ (G g G^T) (.) (B^T d B) ] A  over its 4x4 input window d: 16 products per (cin, cout) instead of 36,
+// i.e. 16 GEMMs (one per transform position xi = 4 i + j) of [cout x cin] x [cin x tile], 4/9 of the direct form's MFMAs.
+//   B^T d along an axis: (d0 - d2, d1 + d2, d2 - d1, d1 - d3)             (y first, then x)
+//   G g  along an axis: s = g0 + g2: (g0, 0.5 (s + g1), 0.5 (s - g1), g2)   (x first, then y)
+//   A^T m along an axis: ((m0 + m1) + m2, (m1 - m2) - m3)                   (y first, then x)
+// tools/winograd_numerics.py mirrors this operation order in fp32 (tests/test_winograd_numerics.py).
+// Work split: the layer's 2x2 tiles form blocks of 16 (MFMA columns), its output channels blocks of 16 (MFMA rows); every wave runs NB
+// (tile block, channel block) passes one after the other.  A pass walks K in groups of 16 input channels: lane (m, kq) reads the 4x4
+// window of tile m for its four interleaved channels 16 G + 4 kq + e (16 ds_read_b128 from the direct loop's layouts), the 9 taps of
+// cout m for the same channels (the packed fp32 weights, 9 buffer loads), transforms both in registers (V, U: 16 xi x 4 channels each)
+// and issues 16 xi x 4 k-steps.  The output transform is lane-local (the lane holds 4 couts x 16 xi of its tile): a pass ends with 16
+// floats per lane, so earlier passes' results wait in registers for the barrier in front of the in-place store at little cost.
+// The transforms are written one scalar f32 add / mul at a time through wadd / wsub / wmul: left to itself the compiler SLP-packs
+// neighbouring adds into v_pk_add_f32, which beside MFMAs costs more issue cycles than two plain adds.
+__device__ __forceinline__ float wadd(float a, float b) { float r = a + b; asm("" : "+v"(r)); return r; }
+__device__ __forceinline__ float wsub(float a, float b) { float r = a - b; asm("" : "+v"(r)); return r; }
+__device__ __forceinline__ float wmul(float a, float b) { float r = a * b; asm("" : "+v"(r)); return r; }
+
+// (tile row, tile column, channel block) of lane m's tile in pass q of `wave`
+template <int H, int COUT, int NB>
+__device__ __forceinline__ void wino_tile(int wave, int q, int m, int& ty, int& tx, int& cb) {
+    constexpr int HT = H / 2, NCB = COUT / 16;
+    const int p = wave * NB + q, tb = p / NCB;
+    cb = p - tb * NCB;
+    const int t = tb * 16 + m;
+    ty = t / HT;
+    tx = t - ty * HT;
+}
+
+// Pre-activation outputs (no bias) of the NB passes: y[q][2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3 of pixel (2 ty + dy, 2 tx + dx).
+template <int NW, int CIN, int COUT, typename LI, int NB>
+__device__ __forceinline__ void conv3x3_wino_mfma(const float* act, const float* __restrict__ Wg, f32x4 (&y)[NB][4], int wave, int lane) {
+    constexpr int H = LI::H, HT = H / 2, NGRP = CIN / 16;
+    static_assert(H % 2 == 0 && (HT * HT) % 16 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "Winograd tiling");
+    static_assert((HT * HT / 16) * (COUT / 16) == NW * NB, "the waves' passes must tile the layer exactly");
+    const int m = lane & 15, kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wg, 9 * CIN * COUT);
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        int ty, tx, cb;
+        wino_tile<H, COUT, NB>(wave, q, m, ty, tx, cb);
+        // top-left cell of the window = output pixel (2 ty - 1, 2 tx - 1), i.e. the halo cell (2 ty, 2 tx) of the padded layout
+        const unsigned a0 = lds_byte_addr(act) + (kq * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4;
+        const int w_lane = (kq * COUT + cb * 16 + m) * 16;
+        f32x4 acc[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int G = 0; G < NGRP; ++G) {
+            f32x4 w[9];
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) w[tap] = buf_read4(wrsrc, w_lane, (tap * NGRP + G) * 16 * COUT * 4);
+            unsigned ab = a0 + G * 16 * LI::PSG;          // 4 plane groups of PSG floats per K group
+            asm("" : "+v"(ab));
+            f32x4 d[4][4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) d[r][c] = lds_read4(ab + (r * LI::WP + c) * 16);
+            f32x4 U[16], V[16];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t[4][4];
+                // U = G g G^T: along x (taps 3 ky + 0..2), then along y
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+                    const float g0 = w[3 * ky][e], g1 = w[3 * ky + 1][e], g2 = w[3 * ky + 2][e];
+                    const float s = wadd(g0, g2);
+                    t[ky][0] = g0; t[ky][1] = wmul(0.5f, wadd(s, g1)); t[ky][2] = wmul(0.5f, wsub(s, g1)); t[ky][3] = g2;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float s = wadd(t[0][j], t[2][j]);
+                    U[j][e] = t[0][j]; U[4 + j][e] = wmul(0.5f, wadd(s, t[1][j])); U[8 + j][e] = wmul(0.5f, wsub(s, t[1][j])); U[12 + j][e] = t[2][j];
+                }
+                // V = B^T d B: along y, then along x
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    t[0][c] = wsub(d[0][c][e], d[2][c][e]); t[1][c] = wadd(d[1][c][e], d[2][c][e]);
+                    t[2][c] = wsub(d[2][c][e], d[1][c][e]); t[3][c] = wsub(d[1][c][e], d[3][c][e]);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    V[4 * i][e] = wsub(t[i][0], t[i][2]); V[4 * i + 1][e] = wadd(t[i][1], t[i][2]);
+                    V[4 * i + 2][e] = wsub(t[i][2], t[i][1]); V[4 * i + 3][e] = wsub(t[i][1], t[i][3]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
+        }
+        // Y = A^T M A, per output channel e of the lane
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                t[0][j] = wadd(wadd(acc[j][e], acc[4 + j][e]), acc[8 + j][e]);
+                t[1][j] = wsub(wsub(acc[4 + j][e], acc[8 + j][e]), acc[12 + j][e]);
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                y[q][2 * r][e] = wadd(wadd(t[r][0], t[r][1]), t[r][2]);
+                y[q][2 * r + 1][e] = wsub(wsub(t[r][1], t[r][2]), t[r][3]);
+            }
+        }
+    }
+}
+
+// bias of the lane's four output channels in each pass
+template <int NW, int H, int COUT, int NB>
+__device__ __forceinline__ void wino_bias(const float* __restrict__ bias, f32x4 (&bv)[NB], int wave, int lane) {
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        int ty, tx, cb;
+        wino_tile<H, COUT, NB>(wave, q, lane & 15, ty, tx, cb);
+        bv[q] = *reinterpret_cast<const f32x4*>(&bias[cb * 16 + 4 * (lane >> 4)]);
+    }
+}
+
+// + bias, ReLU, store the 2x2 pixels x 4 channels of every pass into the LDS layout LO (H = LO::H, one ds_write_b128 per pixel)
+template <int COUT, typename LO, int NB>
+__device__ __forceinline__ void wino_store_lds(float* act, const f32x4 (&bias)[NB], const f32x4 (&y)[NB][4], int wave, int lane) {
+    const int g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        int ty, tx, cb;
+        wino_tile<LO::H, COUT, NB>(wave, q, lane & 15, ty, tx, cb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int oy = 2 * ty + (k >> 1), ox = 2 * tx + (k & 1);
+            f32x4 v = y[q][k] + bias[q];
+            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            *reinterpret_cast<f32x4*>(&act[(cb * 4 + g) * LO::PSG + ((oy + 1) * LO::WP + ox + 1) * 4]) = v;
+        }
+    }
+}
+
+// Same for HardNet's last trunk layer: global [pixel p][channel c] (store_tiles_global's order)
+template <int COUT, int H, int NB>
+__device__ __forceinline__ void wino_store_global(float* __restrict__ dst, const f32x4 (&bias)[NB], const f32x4 (&y)[NB][4], int wave, int lane) {
+    const int g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        int ty, tx, cb;
+        wino_tile<H, COUT, NB>(wave, q, lane & 15, ty, tx, cb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p = (2 * ty + (k >> 1)) * H + 2 * tx + (k & 1);
+            f32x4 v = y[q][k] + bias[q];
+            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            *reinterpret_cast<f32x4*>(dst + p * COUT + cb * 16 + 4 * g) = v;
+        }
+    }
+}

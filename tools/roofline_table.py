@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Regenerates the bandwidth / FLOP-rate table of DESIGN.md section 4 from tracked files:
     python tools/roofline_table.py profiles/r02_s2          (prefix of *_kernel_stats.csv, *_traffic.json, *_bench_default.json or, since round 6, *_bench_driver_detail.json)
+    python tools/roofline_table.py --winograd PREFIX         evidence of a build whose exact HardNet trunk runs conv1 / conv3 / conv5 as Winograd F(2x2, 3x3):
+                                                             that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
 FETCH_SIZE / WRITE_SIZE passes scaled by the calibration measured for the kernel's access width (tools/fetch_calib.py), the
 resulting GB/s and its fraction of 8 TB/s; for the CNN kernels the algorithmic FLOP rate against the 157.3 TFLOP/s fp32 MFMA peak.
@@ -15,6 +17,10 @@ IMGS, H, W, NKP, C = 32, 768, 1024, 2000, 3000
 # few us when no image needs it, so a per-launch mean charged with 3000 patches printed 204 % of the peak in round 2.
 FLOP = {"cnn32_trunk_kernel<0": C * 19193856.0, "cnn32_trunk_kernel<1": NKP * 19316736.0, "cnn32_trunk_kernel<2": NKP * (78184448.0 - 2.0 * 8192 * 128),
         "hardnet_head_kernel": NKP * 2.0 * 8192 * 128}
+
+# Exact HardNet trunk with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3): each of the three layers is 2 * 9 * cin * cout * H^2 = 18874368 FLOPs per patch in
+# the direct form and executes 16 / 36 of them on the MFMA (the transforms run on the VALU and are not counted)
+WINO_HARDNET = NKP * (78184448.0 - 2.0 * 8192 * 128 - 3 * 18874368.0 * (1.0 - 16.0 / 36.0))
 
 
 def octave_pixels(h, w, border=5):
@@ -40,7 +46,7 @@ def split_terms(name):
     return 0
 
 
-def main(prefix):
+def main(prefix, winograd=False):
     stats = {}
     for r in csv.DictReader(open(prefix + "_kernel_stats.csv")):
         stats[r["Name"].split("(")[0]] = (int(r["Calls"]), float(r["AverageNs"]))
@@ -80,8 +86,12 @@ def main(prefix):
                         "the 2517 bf16 / fp16 MFMA peak" % ("fp32_split3" if split == 3 else "fp32_split2h", tf, "bf16" if split == 3 else "fp16", prod, prod * tf,
                                                           100 * prod * tf / 2516.8))
             elif key in name:
+                if winograd and key == "cnn32_trunk_kernel<2":
+                    fl = WINO_HARDNET
                 tf = fl * IMGS / (per_call * avg_ns * 1e-9) / 1e12            # all launches of the kernel in one 32-image call
                 algs = "%.1f TFLOP/s = %.1f %% of 157.3" % (tf, 100 * tf / 157.3)
+                if winograd and key == "cnn32_trunk_kernel<2":
+                    algs += " (executed MFMA FLOPs of the Winograd trunk; direct-form equivalent %.1f TFLOP/s)" % (tf * FLOP[key] / fl)
                 if per_call > 1.01:
                     algs += " (over its %.0f launches per call; %.0f patches / image evaluated)" % (per_call, FLOP[key] / 19193856.0)
         for key in alg:
@@ -104,4 +114,5 @@ def main(prefix):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    args = [a for a in sys.argv[1:] if a != "--winograd"]
+    main(args[0], winograd="--winograd" in sys.argv[1:])

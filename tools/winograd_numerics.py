@@ -1,0 +1,119 @@
+#!/usr/bin/env python
+"""CPU mirror of HardNet's Winograd F(2x2, 3x3) layers (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma) and the error it adds.
+
+The transforms follow the kernel's operation order one add / multiply at a time in the input's dtype:
+    U = G g G^T   along x, then y:  s = g0 + g2;  (g0, 0.5 (s + g1), 0.5 (s - g1), g2)
+    V = B^T d B   along y, then x:  (d0 - d2, d1 + d2, d2 - d1, d1 - d3)
+    Y = A^T M A   along y, then x:  ((m0 + m1) + m2, (m1 - m2) - m3)
+The contraction over input channels is one matmul per transform position (the kernel sums it on the fp32 MFMA in its own order; the
+summation order changes the last bits, not the size of the error).  BatchNorm is folded into the conv weights and a bias, as the packed
+weights of the kernel are.
+
+    python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32 and Winograd fp32
+"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+import affnet_oracle as orc  # noqa: E402
+
+WINO_LAYERS = (1, 3, 5)          # HardNet's stride-1 layers after conv0: conv1, conv3, conv5
+
+
+def _g_axis(g0, g1, g2):
+    s = g0 + g2
+    return [g0, 0.5 * (s + g1), 0.5 * (s - g1), g2]
+
+
+def _bt_axis(d0, d1, d2, d3):
+    return [d0 - d2, d1 + d2, d2 - d1, d1 - d3]
+
+
+def _at_axis(m0, m1, m2, m3):
+    return [(m0 + m1) + m2, (m1 - m2) - m3]
+
+
+def weight_transform(w):
+    """w [co][ci][3][3] -> U [4][4][co][ci] (x first, then y)"""
+    t = [_g_axis(w[:, :, ky, 0], w[:, :, ky, 1], w[:, :, ky, 2]) for ky in range(3)]       # t[ky][j]
+    cols = [_g_axis(t[0][j], t[1][j], t[2][j]) for j in range(4)]                            # cols[j][i]
+    return torch.stack([torch.stack([cols[j][i] for j in range(4)]) for i in range(4)])
+
+
+def input_transform(x):
+    """x [n][c][H][H] (H even) -> V [4][4][n][c][H/2][H/2] over the zero-padded 4x4 windows at stride 2 (y first, then x)"""
+    xp = F.pad(x, (1, 1, 1, 1))
+    H = x.shape[-1]
+    d = [[xp[:, :, r:r + H:2, c:c + H:2] for c in range(4)] for r in range(4)]             # d[r][c]: window element (r, c) of every tile
+    t = [_bt_axis(d[0][c], d[1][c], d[2][c], d[3][c]) for c in range(4)]                     # t[c][i]
+    return torch.stack([torch.stack(_bt_axis(t[0][i], t[1][i], t[2][i], t[3][i])) for i in range(4)])
+
+
+def wino_conv3x3(x, w):
+    """3x3 convolution, padding 1, stride 1 (no bias) as F(2x2, 3x3) in the dtype of x / w: [n][ci][H][H] -> [n][co][H][H]"""
+    n, _, H, _ = x.shape
+    U = weight_transform(w)                                 # [4][4][co][ci]
+    V = input_transform(x)                                  # [4][4][n][ci][HT][HT]
+    M = torch.einsum("ijoc,ijncyx->ijnoyx", U, V)           # one contraction over ci per transform position
+    t = [_at_axis(M[0, j], M[1, j], M[2, j], M[3, j]) for j in range(4)]                     # t[j][r]
+    Y = [[_at_axis(t[0][r], t[1][r], t[2][r], t[3][r])[c] for c in range(2)] for r in range(2)]
+    out = torch.empty(n, w.shape[0], H, H, dtype=x.dtype)
+    for r in range(2):
+        for c in range(2):
+            out[:, :, r::2, c::2] = Y[r][c]
+    return out
+
+
+def folded(sd, dtype):
+    """BatchNorm (eval, affine=False, eps 1e-5) folded into the six conv layers: [(weight, bias, stride)]"""
+    layers = []
+    for ci, bi, st in orc._TRUNK:
+        w = sd["features.%d.weight" % ci].to(dtype)
+        inv = 1.0 / torch.sqrt(sd["features.%d.running_var" % bi].to(dtype) + 1e-5)
+        layers.append((w * inv.view(-1, 1, 1, 1), -sd["features.%d.running_mean" % bi].to(dtype) * inv, st))
+    return layers
+
+
+def hardnet_forward(sd, patches, wino=True, dtype=torch.float32):
+    """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`"""
+    x = orc.input_norm(patches.to(dtype))
+    for li, (w, b, st) in enumerate(folded(sd, dtype)):
+        y = wino_conv3x3(x, w) if (wino and li in WINO_LAYERS) else F.conv2d(x, w, None, stride=st, padding=1)
+        x = F.relu(y + b.view(1, -1, 1, 1))
+    y = F.conv2d(x, sd["features.19.weight"].to(dtype), None)
+    y = F.batch_norm(y, sd["features.20.running_mean"].to(dtype), sd["features.20.running_var"].to(dtype), None, None, False, 0.1, 1e-5)
+    y = y.view(y.size(0), -1)
+    return y / torch.sqrt(torch.sum(y * y, dim=1) + 1e-8).unsqueeze(-1)
+
+
+def errors(sd, patches):
+    """(max, mean) |descriptor - float64 forward| of direct fp32 and of Winograd fp32"""
+    with torch.no_grad():
+        ref = orc.hardnet_forward({k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}, patches.double())
+        out = {}
+        for name, wino in (("direct", False), ("winograd", True)):
+            d = (hardnet_forward(sd, patches, wino=wino).double() - ref).abs()
+            out[name] = (float(d.max()), float(d.mean()))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=2000)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    sd = orc.synthetic_hardnet_state(0)
+    p = torch.rand(args.n, 1, 32, 32, generator=torch.Generator().manual_seed(args.seed)) * 255
+    for name, (mx, mean) in errors(sd, p).items():
+        print("%-9s max %.3g  mean %.3g" % (name, mx, mean))
+
+
+if __name__ == "__main__":
+    main()
