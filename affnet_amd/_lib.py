@@ -86,6 +86,7 @@ SYMBOLS = {
     "affnet_laf_grid_sample": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "affnet_pyr_grid_sample": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "affnet_cnn32_packed_floats": (_SZ, [_I]),
+    "affnet_cnn32_winograd_offset": (C.c_int64, [_I, _I]),
     "affnet_cnn32_pack_weights": (_I, [_I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P]),
     "affnet_cnn32_forward": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "affnet_cnn32_forward_pyr": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),

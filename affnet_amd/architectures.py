@@ -51,7 +51,7 @@ class _HipPatchNet(nn.Module):
         """BN-folded, MFMA-ordered weight blob on `device` (cached until the parameters / buffers change)."""
         stamp = self._weights_stamp()
         if self._packed is None or self._packed_version != stamp or self._packed.device != device:
-            blob = engine.pack_state_dict(self.KIND, self.state_dict())
+            blob = engine.pack_state_dict(self.KIND, self.state_dict(), winograd=True)
             self._packed = blob.to(device)
             self._packed_version = stamp
         return self._packed

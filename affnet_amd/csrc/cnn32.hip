@@ -36,6 +36,12 @@ extern "C" size_t affnet_cnn32_packed_floats(int net_kind) {
     return net_layout(net_kind).total;
 }
 
+extern "C" int64_t affnet_cnn32_winograd_offset(int net_kind, int layer) {
+    if (net_kind < 0 || net_kind > AFFNET_NET_AFFNET_FULLCONV || layer < 0 || layer > 5) return -1;
+    const NetLayout L = net_layout(net_kind);
+    return L.w_wino[layer] ? (int64_t)L.w_wino[layer] : -1;
+}
+
 extern "C" int affnet_cnn32_pack_weights(int kind, const float* const* conv_w, const float* const* bn_mean, const float* const* bn_var,
                                          const float* head_w, const float* head_b, const float* head_bn_mean, const float* head_bn_var,
                                          float* out) {
@@ -54,6 +60,31 @@ extern "C" int affnet_cnn32_pack_weights(int kind, const float* const* conv_w, c
                     else                                                                // [tap][G = c/16][kq = (c/4)%4][n][j = c%4]
                         out[L.w_off[i] + ((((size_t)t * (ci / 16) + c / 16) * 4 + (c / 4) % 4) * co + n) * 4 + c % 4] = w;
                 }
+        }
+    }
+    // Winograd F(2x2, 3x3) copies of HardNet's stride-1 layers: U = G g G^T of the same BN-folded fp32 taps, in conv3x3_wino_mfma's former operation
+    // order (along x: s = g0 + g2; (g0, 0.5 (s + g1), 0.5 (s - g1), g2), then the same along y; one rounding per operation, no contraction), so the
+    // values are bit for bit what the loop used to compute per K group.  [xi = 4 i + j][G = c/16][kq = (c/4)%4][n][c%4]
+    for (int i = 1; i < 6; ++i) {
+        if (!L.w_wino[i]) continue;
+        const int ci = L.cin[i], co = L.cout[i];
+        for (int n = 0; n < co; ++n) {
+            const float sc = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);
+            for (int c = 0; c < ci; ++c) {
+                volatile float t[3][4], U[16];                              // volatile: every intermediate is a rounded fp32 value in memory
+                for (int ky = 0; ky < 3; ++ky) {
+                    const float g0 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky] * sc, g1 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky + 1] * sc;
+                    const float g2 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky + 2] * sc;
+                    const float s = g0 + g2;
+                    t[ky][0] = g0; t[ky][1] = 0.5f * (s + g1); t[ky][2] = 0.5f * (s - g1); t[ky][3] = g2;
+                }
+                for (int j = 0; j < 4; ++j) {
+                    const float s = t[0][j] + t[2][j];
+                    U[j] = t[0][j]; U[4 + j] = 0.5f * (s + t[1][j]); U[8 + j] = 0.5f * (s - t[1][j]); U[12 + j] = t[2][j];
+                }
+                for (int xi = 0; xi < 16; ++xi)
+                    out[L.w_wino[i] + ((((size_t)xi * (ci / 16) + c / 16) * 4 + (c / 4) % 4) * co + n) * 4 + c % 4] = U[xi];
+            }
         }
     }
     // split copies for AFFNET_ARITH_FP32_SPLIT3 (conv1 .. conv5 = S3_LAYER_MASK, all three nets): the same BN-folded fp32 weight as three bf16 terms (nearest even,
@@ -439,8 +470,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     float w0[3][T1N];
     f32x4 bias0[T1N];
     conv0_load_w<NW, CB, T1M, T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
+    // HardNet on the exact path: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the
+    // MFMAs; each wave runs NB (tile block, channel block) passes of a layer.  AffNet / OriNet set LAF geometry and keep the direct form.
+    constexpr bool WINO = (KIND == AFFNET_NET_HARDNET && S3 == 0);
+    constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
     f32x4 b1[ROLL1 ? 1 : G1][T1N];
-    prefetch_b0<NW, CB, 32, T1M, T1N, (ROLL1 ? 1 : G1)>(a.packed + a.off.w[1], b1, wave, lane);
+    if constexpr (!WINO) prefetch_b0<NW, CB, 32, T1M, T1N, (ROLL1 ? 1 : G1)>(a.packed + a.off.w[1], b1, wave, lane);
 
     // ---- input: load or sample 1024 pixels (PPT per thread), standardise, store padded ----------------
     float v[PPT];
@@ -505,6 +540,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
 
     // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
     f32x4 bias1[T1N];
+    f32x4 Uw[16];                                                 // WINO: the rolling U register set of conv1 / conv3 / conv5
     if constexpr (!HALF) {
         f32x4 acc[T1M][T1N];
         conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
@@ -512,6 +548,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
         store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
         CNN_STAMP(20);
+        if constexpr (WINO) wino_prefetch_u<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Uw, wave, lane);
         __syncthreads();
     }
     if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
@@ -803,17 +840,15 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
 
     // Every layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading
     // the input) -> zero the halo of the OUTPUT layout, bias + ReLU + store in place -> barrier.
-    // HardNet on the exact path: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the
-    // MFMAs; each wave runs NB (tile block, channel block) passes of a layer.  AffNet / OriNet set LAF geometry and keep the direct form.
-    constexpr bool WINO = (KIND == AFFNET_NET_HARDNET && S3 == 0);
-    constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
+    // The Winograd layers (WINO, above) load their transformed weights U from the blob (NetLayout::w_wino), one K group ahead; the first
+    // group of a layer is requested in front of the barrier before it, where the direct-form layers request their first weight chunk.
     // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
     f32x4 b2[G2][T2N];
     f32x4 bias2[T2N];
     if constexpr (WINO) {
         f32x4 y[NB1][4], bw[NB1];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w[1], y, wave, lane);
+        conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Uw, y, wave, lane);
         if (PRIO) __builtin_amdgcn_s_setprio(3);
         CNN_STAMP(3);
         prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G2>(a.packed + a.off.w[2], b2, wave, lane);
@@ -854,8 +889,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
         if (PRIO) __builtin_amdgcn_s_setprio(3);
         CNN_STAMP(5);
-        prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G3>(a.packed + a.off.w[3], b3, wave, lane);
-        prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
+        if constexpr (WINO) wino_prefetch_u<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Uw, wave, lane);
+        else {
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G3>(a.packed + a.off.w[3], b3, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
+        }
         __syncthreads();
         zero_halo<LayC2, NTHR>(act, 2 * CB);
         store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
@@ -870,7 +908,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     if constexpr (WINO) {
         f32x4 y[NB3][4], bw[NB3];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w[3], y, wave, lane);
+        conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Uw, y, wave, lane);
         if (PRIO) __builtin_amdgcn_s_setprio(3);
         CNN_STAMP(7);
         prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G4>(a.packed + a.off.w[4], b4, wave, lane);
@@ -906,8 +944,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
         if (PRIO) __builtin_amdgcn_s_setprio(3);
         CNN_STAMP(9);
-        prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G5>(a.packed + a.off.w[5], b5, wave, lane);
-        prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
+        if constexpr (WINO) wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
+        else {
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G5>(a.packed + a.off.w[5], b5, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
+        }
         __syncthreads();
         zero_halo<LayC4, NTHR>(act, 4 * CB);
         store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
@@ -920,7 +961,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     if constexpr (WINO) {
         f32x4 y[NB5][4], bw[NB5];
         if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_wino_mfma<NW, 4 * CB, 4 * CB, LayC4, NB5>(act, a.packed + a.off.w[5], y, wave, lane);
+        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
+        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
         if (PRIO) __builtin_amdgcn_s_setprio(3);
         CNN_STAMP(11);
         wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);

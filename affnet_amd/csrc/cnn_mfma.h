@@ -74,6 +74,8 @@ struct NetLayout {
     size_t w_h2[6];         // AFFNET_ARITH_FP32_SPLIT2H (0 = none): the same layers as TWO fp16 terms of 2^e * w (e per layer: the largest |w| of the layer lands in
                             // [2^13, 2^14)), same fragment order with 2 terms, followed by 4 floats whose first is 2^-e (the loop's output scale)
     size_t head_h2;         // HardNet only: the head weights as two fp16 terms, [k/32][term][kq][n 128][8] + 4 floats (2^-e first)
+    size_t w_wino[6];       // HardNet conv1 / conv3 / conv5 (0 = none): the Winograd-transformed fp32 weights U = G g G^T, [xi = 4 i + j (16)][cin/16][kq][cout][4] - the
+                            // tap layout with 16 transform positions in place of 9 taps.  LAST in the blob: every older offset keeps its value
     size_t total;
 };
 
@@ -113,6 +115,10 @@ static inline NetLayout net_layout(int kind) {
     }
     L.head_h2 = 0;
     if (kind == AFFNET_NET_HARDNET) { L.head_h2 = off; off += (size_t)HEAD_K * 128 + H2_TAIL; }
+    for (int i = 0; i < 6; ++i) {
+        L.w_wino[i] = 0;
+        if (kind == AFFNET_NET_HARDNET && (i == 1 || i == 3 || i == 5)) { L.w_wino[i] = off; off += (size_t)16 * L.cin[i] * L.cout[i]; }
+    }
     L.total = off;
     return L;
 }
@@ -121,6 +127,7 @@ struct NetOffsets {        // device-side copy of the offsets (by-value kernel a
     int w[6], b[6], head_w, head_b;
     int w_s3[6];           // the split copy of the ACTIVE arithmetic mode (three bf16 terms or two fp16 terms)
     int head_s3;
+    int w_wino[3];         // Winograd-transformed weights of conv1 / conv3 / conv5 (HardNet; 0 = none)
 };
 
 static inline NetOffsets to_offsets(const NetLayout& L, int arith = AFFNET_ARITH_FP32_SPLIT3) {
@@ -130,6 +137,7 @@ static inline NetOffsets to_offsets(const NetLayout& L, int arith = AFFNET_ARITH
     o.head_w = (int)L.head_w; o.head_b = (int)L.head_b;
     for (int i = 0; i < 6; ++i) o.w_s3[i] = (int)(h2 ? L.w_h2[i] : L.w_s3[i]);
     o.head_s3 = (int)(h2 ? L.head_h2 : L.head_s3);
+    for (int i = 0; i < 3; ++i) o.w_wino[i] = (int)L.w_wino[2 * i + 1];
     return o;
 }
 
@@ -1259,10 +1267,10 @@ __device__ __forceinline__ void store_tiles_global(float* __restrict__ dst, cons
 // tools/winograd_numerics.py mirrors this operation order in fp32 (tests/test_winograd_numerics.py).
 // Work split: the layer's 2x2 tiles form blocks of 16 (MFMA columns), its output channels blocks of 16 (MFMA rows); every wave runs NB
 // (tile block, channel block) passes one after the other.  A pass walks K in groups of 16 input channels: lane (m, kq) reads the 4x4
-// window of tile m for its four interleaved channels 16 G + 4 kq + e (16 ds_read_b128 from the direct loop's layouts), the 9 taps of
-// cout m for the same channels (the packed fp32 weights, 9 buffer loads), transforms both in registers (V, U: 16 xi x 4 channels each)
-// and issues 16 xi x 4 k-steps.  The output transform is lane-local (the lane holds 4 couts x 16 xi of its tile): a pass ends with 16
-// floats per lane, so earlier passes' results wait in registers for the barrier in front of the in-place store at little cost.
+// window of tile m for its four interleaved channels 16 G + 4 kq + e (16 ds_read_b128 from the direct loop's layouts) and transforms it
+// in registers (V: 16 xi x 4 channels), loads U of cout m for the same channels (16 buffer loads, one per xi: U is a constant of the
+// network, transformed once at pack time - NetLayout::w_wino, in the G g order above) and issues 16 xi x 4 k-steps.  The output
+// transform is lane-local (the lane holds 4 couts x 16 xi of its tile): a pass ends with 16 floats per lane, so earlier passes' results wait in registers for the barrier in front of the in-place store at little cost.
 // The transforms are written one scalar f32 add / mul at a time through wadd / wsub / wmul: left to itself the compiler SLP-packs
 // neighbouring adds into v_pk_add_f32, which beside MFMAs costs more issue cycles than two plain adds.
 __device__ __forceinline__ float wadd(float a, float b) { float r = a + b; asm("" : "+v"(r)); return r; }
@@ -1280,85 +1288,170 @@ __device__ __forceinline__ void wino_tile(int wave, int q, int m, int& ty, int& 
     tx = t - ty * HT;
 }
 
+// Weight operand of pass q of `wave`: byte offset of lane (cout m, kq) inside one (xi, K group) block [kq][cout][4] of the transformed weights
+template <int H, int COUT, int NB>
+__device__ __forceinline__ int wino_u_lane(int wave, int q, int lane) {
+    int ty, tx, cb;
+    wino_tile<H, COUT, NB>(wave, q, lane & 15, ty, tx, cb);
+    return ((lane >> 4) * COUT + cb * 16 + (lane & 15)) * 16;
+}
+
+// U of K group G: one buffer_load_dwordx4 per transform position = the A operand of its four k-steps.  Wu = the packed U = G g G^T
+// [xi][CIN/16][kq][COUT][4] (NetLayout::w_wino), computed once at pack time with the operation order above.
+template <int CIN, int COUT>
+__device__ __forceinline__ f32x4 wino_load_u(__amdgpu_buffer_rsrc_t r, int u_lane, int k, int G) {
+    return buf_read4(r, u_lane, (k * (CIN / 16) + G) * 16 * COUT * 4);
+}
+
+// U of the first K group of the wave's first pass: does not depend on the activations, so the kernel requests it BEFORE the barrier in
+// front of the layer (what prefetch_b0 is to the direct loop).
+template <int NW, int CIN, int COUT, int H, int NB>
+__device__ __forceinline__ void wino_prefetch_u(const float* __restrict__ Wu, f32x4 (&U)[16], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);
+    const int u_lane = wino_u_lane<H, COUT, NB>(wave, 0, lane);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) U[k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0);
+}
+
+// V = B^T d B of the 4x4 window at LDS byte address `ab` (16 ds_read_b128: the lane's four interleaved channels), along y, then along x
+template <typename LI>
+__device__ __forceinline__ void wino_window(unsigned ab, f32x4 (&V)[16]) {
+    f32x4 d[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[r][c] = lds_read4(ab + (r * LI::WP + c) * 16);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[4][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            t[0][c] = wsub(d[0][c][e], d[2][c][e]); t[1][c] = wadd(d[1][c][e], d[2][c][e]);
+            t[2][c] = wsub(d[2][c][e], d[1][c][e]); t[3][c] = wsub(d[1][c][e], d[3][c][e]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            V[4 * i][e] = wsub(t[i][0], t[i][2]); V[4 * i + 1][e] = wadd(t[i][1], t[i][2]);
+            V[4 * i + 2][e] = wsub(t[i][2], t[i][1]); V[4 * i + 3][e] = wsub(t[i][1], t[i][3]);
+        }
+    }
+}
+
+// Y = A^T M A of the lane's 4 output channels x 16 positions: yq[2 dy + dx]
+__device__ __forceinline__ void wino_output(const f32x4 (&acc)[16], f32x4 (&yq)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[2][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            t[0][j] = wadd(wadd(acc[j][e], acc[4 + j][e]), acc[8 + j][e]);
+            t[1][j] = wsub(wsub(acc[4 + j][e], acc[8 + j][e]), acc[12 + j][e]);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            yq[2 * r][e] = wadd(wadd(t[r][0], t[r][1]), t[r][2]);
+            yq[2 * r + 1][e] = wsub(wsub(t[r][1], t[r][2]), t[r][3]);
+        }
+    }
+}
+
 // Pre-activation outputs (no bias) of the NB passes: y[q][2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3 of pixel (2 ty + dy, 2 tx + dx).
+// U enters holding the first K group of pass 0 (wino_prefetch_u) and rolls ONE K group ahead in a single register set: once the four
+// MFMAs of position k have issued, U[k] of the next group (the last group of a pass: the first group of the next pass) is requested into
+// the same registers, so a group's weights travel while the window transform and the other 60 MFMAs run.
 template <int NW, int CIN, int COUT, typename LI, int NB>
-__device__ __forceinline__ void conv3x3_wino_mfma(const float* act, const float* __restrict__ Wg, f32x4 (&y)[NB][4], int wave, int lane) {
+__device__ __forceinline__ void conv3x3_wino_mfma(const float* act, const float* __restrict__ Wu, f32x4 (&U)[16], f32x4 (&y)[NB][4], int wave, int lane) {
     constexpr int H = LI::H, HT = H / 2, NGRP = CIN / 16;
     static_assert(H % 2 == 0 && (HT * HT) % 16 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "Winograd tiling");
     static_assert((HT * HT / 16) * (COUT / 16) == NW * NB, "the waves' passes must tile the layer exactly");
     const int m = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wg, 9 * CIN * COUT);
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
         int ty, tx, cb;
         wino_tile<H, COUT, NB>(wave, q, m, ty, tx, cb);
         // top-left cell of the window = output pixel (2 ty - 1, 2 tx - 1), i.e. the halo cell (2 ty, 2 tx) of the padded layout
         const unsigned a0 = lds_byte_addr(act) + (kq * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4;
-        const int w_lane = (kq * COUT + cb * 16 + m) * 16;
+        const int u_lane = wino_u_lane<H, COUT, NB>(wave, q, lane);
+        const int u_next = wino_u_lane<H, COUT, NB>(wave, q + 1 < NB ? q + 1 : q, lane);   // (the layer's last group re-requests its own first group: unused)
         f32x4 acc[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int G = 0; G < NGRP; ++G) {
-            f32x4 w[9];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) w[tap] = buf_read4(wrsrc, w_lane, (tap * NGRP + G) * 16 * COUT * 4);
             unsigned ab = a0 + G * 16 * LI::PSG;          // 4 plane groups of PSG floats per K group
             asm("" : "+v"(ab));
-            f32x4 d[4][4];
+            f32x4 V[16];
+            wino_window<LI>(ab, V);
+            const bool last = G == NGRP - 1;
+            const int ul = last ? u_next : u_lane, Gn = last ? 0 : G + 1;
+            // the schedule is pinned (sched_barrier): left alone, the compiler issues the MFMAs in the order the transform delivers V (by
+            // channel, all positions), every U register then lives to the end of the group and the 16 loads land in a heap behind the
+            // last MFMA, a few instructions in front of their first use.  Two positions' accumulation chains interleave.
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+            for (int k = 0; k < 16; k += 2) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) d[r][c] = lds_read4(ab + (r * LI::WP + c) * 16);
-            f32x4 U[16], V[16];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t[4][4];
-                // U = G g G^T: along x (taps 3 ky + 0..2), then along y
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const float g0 = w[3 * ky][e], g1 = w[3 * ky + 1][e], g2 = w[3 * ky + 2][e];
-                    const float s = wadd(g0, g2);
-                    t[ky][0] = g0; t[ky][1] = wmul(0.5f, wadd(s, g1)); t[ky][2] = wmul(0.5f, wsub(s, g1)); t[ky][3] = g2;
+                for (int s4 = 0; s4 < 4; ++s4) {
+                    acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
+                    acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[k + 1], 0, 0, 0);
                 }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float s = wadd(t[0][j], t[2][j]);
-                    U[j][e] = t[0][j]; U[4 + j][e] = wmul(0.5f, wadd(s, t[1][j])); U[8 + j][e] = wmul(0.5f, wsub(s, t[1][j])); U[12 + j][e] = t[2][j];
-                }
-                // V = B^T d B: along y, then along x
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    t[0][c] = wsub(d[0][c][e], d[2][c][e]); t[1][c] = wadd(d[1][c][e], d[2][c][e]);
-                    t[2][c] = wsub(d[2][c][e], d[1][c][e]); t[3][c] = wsub(d[1][c][e], d[3][c][e]);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    V[4 * i][e] = wsub(t[i][0], t[i][2]); V[4 * i + 1][e] = wadd(t[i][1], t[i][2]);
-                    V[4 * i + 2][e] = wsub(t[i][2], t[i][1]); V[4 * i + 3][e] = wsub(t[i][1], t[i][3]);
-                }
+                U[k] = wino_load_u<CIN, COUT>(wrsrc, ul, k, Gn);
+                U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, ul, k + 1, Gn);
+                __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
         }
-        // Y = A^T M A, per output channel e of the lane
+        wino_output(acc, y[q]);
+    }
+}
+
+// conv5 (one block of 16 tiles, NW channel blocks, NGRP == NW K groups): every wave would transform the same windows for all K groups.
+// Instead wave w transforms K group w once and the workgroup shares V through LDS, [G][xi][kq][m][4] floats (1 KB contiguous per (G, xi):
+// conflict-free both ways), written over the layer's input after a barrier (every wave has read its group by then, so the input is
+// consumed).  The loop then has no VALU transform: V rolls through one register set like U (16 ds_read_b128 per group, as before).
+// The caller owns NGRP * 4096 floats at `act`.
+template <int NW, int CIN, int COUT, typename LI>
+__device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const float* __restrict__ Wu, f32x4 (&U)[16], f32x4 (&y)[1][4], int wave, int lane) {
+    constexpr int NGRP = CIN / 16;
+    static_assert(LI::H == 8 && COUT == 16 * NW && NGRP == NW, "one tile block, one channel block and one K group per wave");
+    const int m = lane & 15, kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
+    int ty, tx, cb;
+    wino_tile<8, COUT, 1>(wave, 0, m, ty, tx, cb);
+    const int u_lane = wino_u_lane<8, COUT, 1>(wave, 0, lane);
+    f32x4 V[16];
+    wino_window<LI>(lds_byte_addr(act) + ((wave * 4 + kq) * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4, V);
+    __syncthreads();                                      // the whole input has been read
+    const unsigned v0 = lds_byte_addr(act) + lane * 16;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float t[2][4];
+    for (int k = 0; k < 16; ++k) *reinterpret_cast<f32x4*>(&act[((wave * 16 + k) * 64 + lane) * 4]) = V[k];
+    __syncthreads();
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                t[0][j] = wadd(wadd(acc[j][e], acc[4 + j][e]), acc[8 + j][e]);
-                t[1][j] = wsub(wsub(acc[4 + j][e], acc[8 + j][e]), acc[12 + j][e]);
+    for (int k = 0; k < 16; ++k) V[k] = lds_read4(v0 + k * 1024);
+    f32x4 acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int G = 0; G < NGRP; ++G) {
+        const int Gn = G == NGRP - 1 ? G : G + 1;         // (the last group re-requests itself: unused)
+        unsigned vb = v0 + Gn * 16 * 1024;
+        asm("" : "+v"(vb));
+        __builtin_amdgcn_sched_barrier(0);                // pinned as in conv3x3_wino_mfma
+#pragma unroll
+        for (int k = 0; k < 16; k += 2) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);
+                acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[k + 1], 0, 0, 0);
             }
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                y[q][2 * r][e] = wadd(wadd(t[r][0], t[r][1]), t[r][2]);
-                y[q][2 * r + 1][e] = wsub(wsub(t[r][1], t[r][2]), t[r][3]);
-            }
+            U[k] = wino_load_u<CIN, COUT>(wrsrc, u_lane, k, Gn);
+            U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, u_lane, k + 1, Gn);
+            V[k] = lds_read4(vb + k * 1024);
+            V[k + 1] = lds_read4(vb + (k + 1) * 1024);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
+    wino_output(acc, y[0]);
 }
 
 // bias of the lane's four output channels in each pass

@@ -111,8 +111,14 @@ class Context(object):
             pass
 
 
-def pack_state_dict(kind, sd):
-    """state dict (reference key layout) -> packed fp32 blob (CPU tensor)."""
+def pack_state_dict(kind, sd, winograd=False):
+    """state dict (reference key layout) -> packed fp32 blob (CPU tensor).
+
+    The library's blob (affnet_cnn32_packed_floats floats) is the weight sections - fp32 trunk and head, the split copies - followed, for
+    HardNet, by the Winograd section that the exact path's conv1 / conv3 / conv5 read (affnet_cnn32_winograd_offset).  winograd=True returns
+    all of it: THE BLOB THE KERNELS NEED (what the modules upload, architectures.py: packed_weights).  The default returns the weight
+    sections alone, as this function always did: the view the host-side layout checks walk section by section; it must not be uploaded
+    for HardNet."""
     conv_idx, bn_idx = (0, 3, 6, 9, 12, 15), (1, 4, 7, 10, 13, 16)
 
     def f32(name):
@@ -135,6 +141,11 @@ def pack_state_dict(kind, sd):
     rc = lib.affnet_cnn32_pack_weights(kind, arr(convs), arr(means), arr(vars_), ptr(head_w), ptr(head_b), ptr(hbm), ptr(hbv), ptr(out))
     check(rc, None, "affnet_cnn32_pack_weights")
     del keep
+    if not winograd:
+        offs = [lib.affnet_cnn32_winograd_offset(kind, i) for i in range(6)]
+        offs = [o for o in offs if o >= 0]
+        if offs:
+            out = out[:min(offs)].clone()
     return out
 
 
@@ -165,6 +176,9 @@ def cnn_forward(kind, packed, patches, scratch=None, arith=0):
     if tuple(patches.shape[1:]) != (32, 32):
         raise ValueError("the HIP CNN kernels are specialised for 32x32 patches, got %s" % (tuple(patches.shape),))
     patches = patches.contiguous().float()
+    if packed.numel() != lib.affnet_cnn32_packed_floats(kind):        # e.g. pack_state_dict without its Winograd section: the kernels would read past it
+        raise ValueError("packed blob of %d floats, the kernels of net kind %d read %d (pack_state_dict(..., winograd=True))"
+                         % (packed.numel(), kind, lib.affnet_cnn32_packed_floats(kind)))
     n = patches.size(0)
     dev = patches.device
     out = torch.empty((n, 128) if kind == _lib.NET_HARDNET else (n, 2, 2), dtype=torch.float32, device=dev)

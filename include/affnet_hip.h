@@ -241,8 +241,17 @@ int affnet_pyr_grid_sample(affnet_ctx* ctx, const float* d_lafs, const int32_t* 
 
 /* ---- CNNs ---------------------------------------------------------------------------------- */
 
-/* Number of floats of the packed (BN-folded, MFMA-ordered) weight blob of a network. */
+/* Number of floats of the packed (BN-folded, MFMA-ordered) weight blob of a network.  Sections, in this order: the fp32 trunk
+ * (per layer [tap][cin/16][(c/4)%4][cout][c%4] + bias) and head, the three-bf16-term and two-fp16-term copies of the split
+ * arithmetic modes, and LAST - HardNet only, every older offset keeps its value - the Winograd F(2x2, 3x3) weights of the
+ * stride-1 layers conv1 / conv3 / conv5: U = G g G^T of the same BN-folded fp32 taps (s = g0 + g2; (g0, 0.5 (s + g1),
+ * 0.5 (s - g1), g2) along x, then along y; one fp32 rounding per operation), 16 * cin * cout floats per layer as
+ * [xi = 4 i + j (16)][cin/16][(c/4)%4][cout][c%4].  The exact path's Winograd loops read these; the tap copies of the same
+ * layers serve the split modes and the debug paths. */
 size_t affnet_cnn32_packed_floats(int net_kind);
+/* Offset (in floats) of the Winograd section of trunk layer `layer` (0..5) inside the packed blob of `net_kind`; -1 when the
+ * layer has none (every layer of AffNet / OriNet / FullConv, the stride-2 layers and conv0 of HardNet). */
+int64_t affnet_cnn32_winograd_offset(int net_kind, int layer);
 /* Packs a state dict on the HOST.  conv_w[i] (i=0..5): trunk conv weights (Cout,Cin,3,3);
  * bn_mean[i], bn_var[i]: running stats (eps 1e-5, affine=False) folded into weight+bias;
  * head_w / head_b: final conv (AffNet (3,64,8,8)+bias, OriNet (2,64,8,8)+bias,

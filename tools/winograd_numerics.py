@@ -81,6 +81,30 @@ def folded(sd, dtype):
     return layers
 
 
+def packed_taps(sd, i):
+    """BN-folded fp32 taps [co][ci][3][3] of trunk layer i with the packer's own roundings (affnet_cnn32_pack_weights:
+    w * (1.0f / sqrtf(var + 1e-5f)), every operation correctly rounded - numpy's float32 sqrt and divide are; torch's vectorised CPU sqrt is
+    an ulp off on a few inputs, which is why `folded` above is not used where bits are compared)"""
+    import numpy as np
+    ci, bi, _ = orc._TRUNK[i]
+    var = sd["features.%d.running_var" % bi].detach().to(torch.float32).numpy()
+    inv = np.float32(1.0) / np.sqrt(var + np.float32(1e-5))
+    w = sd["features.%d.weight" % ci].detach().to(torch.float32).numpy() * inv.reshape(-1, 1, 1, 1)
+    assert w.dtype == np.float32
+    return torch.from_numpy(w)
+
+
+def packed_weight_transform(sd):
+    """{layer: U} of HardNet's Winograd layers as the packed blob stores them (NetLayout::w_wino, affnet_cnn32_winograd_offset): the
+    fp32 weight_transform of the BN-folded fp32 taps, flat float32 [xi = 4 i + j (16)][ci / 16][(c / 4) % 4][co][c % 4]"""
+    out = {}
+    for i in WINO_LAYERS:
+        U = weight_transform(packed_taps(sd, i))             # [4][4][co][ci]
+        co, ci = U.shape[2:]
+        out[i] = U.reshape(16, co, ci // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+    return out
+
+
 def hardnet_forward(sd, patches, wino=True, dtype=torch.float32):
     """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`"""
     x = orc.input_norm(patches.to(dtype))
