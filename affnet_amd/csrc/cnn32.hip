@@ -8,9 +8,11 @@
 // Design (one workgroup = 8 wavefronts = one patch, whole trunk resident on the CU; details in DESIGN.md section 4):
 //   * the patch is sampled from the pyramid (or loaded), standardised (mean / unbiased std + 1e-7, DPP wave reductions)
 //     and stored as a zero-haloed 34 x 34 LDS tile;
-//   * ALL six convolutions run on v_mfma_f32_16x16x4_f32 (exact fp32): conv0 with K = 9 taps padded to 12 and the
-//     accumulators initialised with the bias, conv1..5 as implicit GEMMs (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the
-//     MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4 consecutive channels of one pixel;
+//   * the exact path runs all six convolutions on v_mfma_f32_16x16x4_f32 (exact fp32): conv0 with K = 9 taps padded to 12 and the
+//     accumulators initialised with the bias; the direct layers (AffNet / OriNet conv1..5, HardNet conv2 / conv4) as implicit GEMMs
+//     (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4
+//     consecutive channels of one pixel; HardNet's stride-1 conv1 / conv3 / conv5 as Winograd F(2x2, 3x3) (conv3x3_wino_mfma).  The
+//     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
 //     the activation operands of four k-steps, one ds_write_b128 per tile in the epilogue (bias + ReLU), written IN PLACE
 //     over the layer's input after a barrier.  No HBM traffic between layers;
@@ -18,8 +20,8 @@
 //     lane = the weight operands of four k-steps), software-pipelined one chunk ahead, loads interleaved between the MFMAs;
 //   * heads: HardNet stores its conv5 tile [pixel][channel] to HBM and an 8192 x 128 split-K MFMA GEMM over all patches
 //     (hardnet_head_kernel + hardnet_finish_kernel: BN bias + L2 norm) follows; AffNet / OriNet reduce their heads' dot
-//     products per wave straight from the conv5 accumulators (head_partials) and cnn16_finish_kernel combines the eight
-//     partials per patch in fixed order (tanh, rectification / atan2).
+//     products per wave straight from the conv5 accumulators (head_partials, head_partials_ori_lds) and affnet_finish_kernel /
+//     orinet_finish_kernel combine the eight partials per patch in fixed order (tanh, rectification / atan2).
 #include <math.h>
 #include <stdlib.h>
 
@@ -221,15 +223,14 @@ extern "C" int affnet_cnn32_pack_weights(int kind, const float* const* conv_w, c
     return AFFNET_OK;
 }
 
-// AffNet / OriNet heads, first half, straight from the conv5 accumulators (no conv5 tensor in HBM): a lane owns channels
-// c4..c4+3 of pixel p of each of its tiles = one float4 of the head weights [o][pixel][channel]; it forms its share of
-// every head dot product, the wave reduces them and lane 0 writes the wave's partial sums to part[wave][*].  The eight
-// partials per patch are combined in fixed order by cnn16_finish_kernel (bit-reproducible, no atomics).
-//   AffNet: 3 outputs  = conv 64 -> 3, 8x8 valid                   (architectures.py:227-229)      part[8][4]
-//   OriNet: 2 x 9      = conv 64 -> 2, 8x8, padding 1 -> 3x3 map   (architectures.py:56-58)        part[8][18]
+// AffNet head, first half, straight from the conv5 accumulators (no conv5 tensor in HBM): a lane owns channels c4..c4+3 of pixel p of
+// each of its tiles = one float4 of the head weights [o][pixel][channel]; it forms its share of the 3 outputs (conv 64 -> 3, 8x8 valid,
+// architectures.py:227-229), the wave reduces them and lane 0 writes the wave's partial sums to part[wave][4].  The eight partials per
+// patch are combined in fixed order by affnet_finish_kernel (bit-reproducible, no atomics).  OriNet's head (2 x 9 outputs, part[8][18]):
+// head_partials_ori_lds below.
 #define HEAD_PART_AFF 32
 #define HEAD_PART_ORI 144
-template <int KIND, int TM>
+template <int TM>
 __device__ __forceinline__ void head_partials(const float* __restrict__ hw, const f32x4 (&bias)[1], const f32x4 (&acc)[TM][1],
                                               float* __restrict__ part, int wave, int lane) {
     constexpr int MT = 4, MG = MT / TM;
@@ -242,59 +243,25 @@ __device__ __forceinline__ void head_partials(const float* __restrict__ hw, cons
         v[i] = acc[i][0] + bias[0];
         v[i].x = fmaxf(v[i].x, 0.0f); v[i].y = fmaxf(v[i].y, 0.0f); v[i].z = fmaxf(v[i].z, 0.0f); v[i].w = fmaxf(v[i].w, 0.0f);
     }
-    if (KIND == AFFNET_NET_AFFNET) {
-        const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 3 * 4096);
-        f32x4 w[3][TM];
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 3 * 4096);
+    f32x4 w[3][TM];
 #pragma unroll
-        for (int o = 0; o < 3; ++o)
+    for (int o = 0; o < 3; ++o)
 #pragma unroll
-            for (int i = 0; i < TM; ++i) w[o][i] = buf_read4(r, (n * 64 + c4) * 4, (o * 4096 + (mg * TM + i) * 16 * 64) * 4);
+        for (int i = 0; i < TM; ++i) w[o][i] = buf_read4(r, (n * 64 + c4) * 4, (o * 4096 + (mg * TM + i) * 16 * 64) * 4);
 #pragma unroll
-        for (int o = 0; o < 3; ++o) {
-            float sacc = 0.f;
+    for (int o = 0; o < 3; ++o) {
+        float sacc = 0.f;
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sacc = fmaf(v[i][j], w[o][i][j], sacc);
-            sacc = wave_sum(sacc);
-            if (lane == 0) part[wave * 4 + o] = sacc;
-        }
-    } else {
-        // taps outside the 8x8 kernel: the lane offset is pushed past the end of the buffer, the load returns 0 (no branch,
-        // no 64-bit address arithmetic, no memory traffic for those lanes)
-        const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 2 * 4096);
-        int toff[9][TM];
-#pragma unroll
-        for (int q = 0; q < 9; ++q)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int p = (mg * TM + i) * 16 + n, py = p >> 3, px = p & 7;
-                const int ky = py - q / 3 + 1, kx = px - q % 3 + 1;                    // padding 1: tap that sees this pixel
-                const bool ok = ky >= 0 && ky < 8 && kx >= 0 && kx < 8;
-                toff[q][i] = ok ? ((ky * 8 + kx) * 64 + c4) * 4 : 0x40000000;
-            }
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-            f32x4 w[9][TM];
-#pragma unroll
-            for (int q = 0; q < 9; ++q)
-#pragma unroll
-                for (int i = 0; i < TM; ++i) w[q][i] = buf_read4(r, toff[q][i], o * 4096 * 4);
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-                float sacc = 0.f;
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) sacc = fmaf(v[i][j], w[q][i][j], sacc);
-                sacc = wave_sum(sacc);
-                if (lane == 0) part[wave * 18 + o * 9 + q] = sacc;
-            }
-        }
+            for (int j = 0; j < 4; ++j) sacc = fmaf(v[i][j], w[o][i][j], sacc);
+        sacc = wave_sum(sacc);
+        if (lane == 0) part[wave * 4 + o] = sacc;
     }
 }
 
-// OriNet head through LDS (round 4).  head_partials<ORINET> makes every lane fetch the weight vector of each of the 2 x 9 (output, tap)
+// OriNet head through LDS (round 4).  The direct form (as in head_partials) made every lane fetch the weight vector of each of the 2 x 9 (output, tap)
 // pairs for its own pixel: 36 buffer_load_dwordx4 per wave, 295 KB of L2 -> L1 traffic per patch for 32 KB of distinct weights - the head
 // took 14.4 k cycles per workgroup against AffNet's 3.3 k (tools/s3_phase_timing.py), L1-bound.  Here the roles are swapped: a lane owns
 // the WEIGHT position (ky, kx) = its tile pixel and 4 channels, loads those weights once per output (4 loads) and reads the nine shifted
@@ -405,6 +372,24 @@ struct TrunkLds {
     static constexpr int TOTAL = ACT + PATCH + RED;
 };
 
+// Per-net constants of the trunk: CB channels after conv0, NW wavefronts, per-wave register blocking (TM x TN tiles of 16 px x 16 ch;
+// MG * NG == NW for every layer) and plane groups per pipeline chunk of the direct-form layers.
+template <int KIND, int NW>
+struct TrunkShape {
+    static constexpr int CB = (KIND == AFFNET_NET_HARDNET) ? 32 : 16;
+    static constexpr int NTHR = NW * 64;
+    static constexpr int T1M = (CB == 16) ? 8 : 64 / NW, T1N = CB / 16;
+    // conv2 / conv3: ONE channel tile per wave and as many pixel tiles as that allows - activation fragments come from LDS
+    // (nearly free), weight fragments are 1 KB global loads whose cost shows in the MFMA rate: 4 x 1 instead of 2 x 2 took the
+    // isolated AffNet conv3 loop from 121 to 146 TFLOP/s (tools/clock_probe.py 13 / 14)
+    static constexpr int T2M = (CB == 16) ? 4 : 64 / NW, T2N = 1;
+    static constexpr int T4M = (CB == 16) ? 2 : 32 / NW, T4N = 1;
+    // plane groups (4 k-steps each) per pipeline chunk; VGPR budget 128 at 4 waves / SIMD, 256 at 2
+    static constexpr int AREG = (NW == 8 && CB == 32) ? 128 : 48;
+    static constexpr int G2 = pick_groups(CB, T2M, T2N, 32, AREG), G3 = pick_groups(2 * CB, T2M, T2N, 32, AREG);
+    static constexpr int G4 = pick_groups(2 * CB, T4M, T4N, 32, AREG), G5 = pick_groups(4 * CB, T4M, T4N, 32, AREG);
+};
+
 template <int C, typename L, int NTHR>
 __device__ __forceinline__ void dump_planes(const float* act, float* dst) {
     constexpr int H = L::H;
@@ -414,30 +399,37 @@ __device__ __forceinline__ void dump_planes(const float* act, float* dst) {
     }
 }
 
-// One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts.
+// Activation layouts of the split-operand flows of cnn32_trunk_kernel.  Three bf16 terms: term-interleaved 48-byte cells (LayQ), conv0 .. conv2 in two
+// half-patch passes; two fp16 terms (AFFNET_ARITH_FP32_SPLIT2H): 16-byte pixels, the two terms of a row side by side (LayR; per-reader row
+// pitch / group stride), conv0 once for the whole patch.
+template <int CB>
+struct SplitLays {
+    typedef LayQ<16, 32, 34, CB, 0, 3> LQH;                      // three terms: conv0 output of half a patch, pre-split; read by conv1 (stride 1)
+    typedef LayQ<16, 32, 34, CB, 16, 3> LQH2;                    // three terms: conv1 output of half a patch; read by conv2 at stride 2
+    // two-term arithmetic: LayR's 16-byte pixels hold conv0's / conv1's output of the WHOLE patch (145 KB for 32 channels, 72.5 KB for 16), so conv0 runs once; conv1 / conv2
+    // keep their two half-patch LOOPS (same register blockings) on 16-row views of the whole layouts - no second conv0 pass, no halo-row fix-ups between the halves
+    using LR0 = LayR<32, 32, 34, CB, 0>;                          // conv0 output, read by conv1 (stride 1)
+    using LR0H = LayR<16, 32, 34, CB, 0, 34>;                     // its 16-row view
+    using LR1 = LayR<32, 32, 34, CB, 16>;                         // conv1 output, read by conv2 at stride 2
+    using LR1H = LayR<16, 32, 34, CB, 16, 34>;
+    static_assert(LR0::BYTES <= TrunkLds<CB>::ACT * 4 && LR1::BYTES <= TrunkLds<CB>::ACT * 4 && LR0H::GS == LR0::GS && LR1H::GS == LR1::GS, "whole-patch split layouts");
+    static_assert(LQH::BYTES <= TrunkLds<CB>::ACT * 4 && LQH2::BYTES <= TrunkLds<CB>::ACT * 4, "pre-split layouts must fit the activation buffer");
+};
+
+// One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
+// 3 / 2 = terms of the split-operand arithmetic.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// kernel is one straight-line body per flow: exact HardNet (Winograd), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
+// layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
+// the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
 // AffNet / OriNet: 79 KB LDS -> 2 workgroups per CU (4 waves / SIMD, 128 VGPRs); HardNet: 154 KB LDS -> 1 workgroup per
 // CU (2 waves / SIMD, 256 VGPRs).
 // STAMPS = debug instantiation: the s_memtime phase stamps of tools/cnn_phase_timing.py and the per-layer activation dumps
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    constexpr int CB = (KIND == AFFNET_NET_HARDNET) ? 32 : 16;
-    constexpr int NTHR = NW * 64;
-    constexpr int PPT = 1024 / NTHR;                    // input pixels per thread (2 or 1)
-    constexpr int RPT = 32 / PPT;                       // patch rows covered by one pass of the workgroup
-    // per-wave register blocking (TM x TN tiles of 16 px x 16 ch); MG * NG == NW for every layer
-    constexpr int T1M = (CB == 16) ? 8 : 64 / NW, T1N = CB / 16;
-    // conv2 / conv3: ONE channel tile per wave and as many pixel tiles as that allows - activation fragments come from LDS
-    // (nearly free), weight fragments are 1 KB global loads whose cost shows in the MFMA rate: 4 x 1 instead of 2 x 2 took the
-    // isolated AffNet conv3 loop from 121 to 146 TFLOP/s (tools/clock_probe.py 13 / 14)
-    constexpr int T2M = (CB == 16) ? 4 : 64 / NW, T2N = 1;
-    constexpr int T4M = (CB == 16) ? 2 : 32 / NW, T4N = 1;
-    // plane groups (4 k-steps each) per pipeline chunk; VGPR budget 128 at 4 waves / SIMD, 256 at 2
-    constexpr int AREG = (NW == 8 && CB == 32) ? 128 : 48;
-    constexpr bool ROLL1 = (T1M * 8 > AREG);            // conv1: two A sets of T1M float4 do not fit -> rolling single set
-    constexpr int G1 = pick_groups(CB, T1M, T1N, 32, AREG), G2 = pick_groups(CB, T2M, T2N, 32, AREG);
-    constexpr int G3 = pick_groups(2 * CB, T2M, T2N, 32, AREG), G4 = pick_groups(2 * CB, T4M, T4N, 32, AREG);
-    constexpr int G5 = pick_groups(4 * CB, T4M, T4N, 32, AREG);
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3, "S3 = number of terms of the split arithmetic");
+    using S = TrunkShape<KIND, NW>;
+    constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
     __shared__ __attribute__((aligned(16))) float lds[TrunkLds<CB>::TOTAL];
     float* act = lds;
@@ -459,25 +451,22 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     // zero-sum: the non-MFMA phases of one workgroup get 2x faster (with equal priorities the arbiter prefers the OLDER
     // waves, so a young workgroup next to an older one in its MFMA loop crawls: 3.7k vs 0.5k cycles per block reduction),
     // but their VALU instructions then displace the other workgroup's MFMA issue slots (-5% overall), so it stays off.
-    constexpr bool PRIO = (KIND == AFFNET_NET_HARDNET);
-    if (PRIO) __builtin_amdgcn_s_setprio(3);
+    if (KIND == AFFNET_NET_HARDNET) __builtin_amdgcn_s_setprio(3);
     CNN_STAMP(0);
     if (STAMPS && a.dbg_time && lane == 0) {   // where this workgroup runs (tuning aid: per-CU timelines)
         a.dbg_time[((size_t)pidx * NW + wave) * 32 + 14] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
         a.dbg_time[((size_t)pidx * NW + wave) * 32 + 15] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
     }
-    // conv0 taps + bias and the first weight chunk of conv1: requested now, consumed after the input phase
-    float w0[3][T1N];
-    f32x4 bias0[T1N];
-    conv0_load_w<NW, CB, T1M, T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
-    // HardNet on the exact path: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the
-    // MFMAs; each wave runs NB (tile block, channel block) passes of a layer.  AffNet / OriNet set LAF geometry and keep the direct form.
-    constexpr bool WINO = (KIND == AFFNET_NET_HARDNET && S3 == 0);
-    constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
-    f32x4 b1[ROLL1 ? 1 : G1][T1N];
-    if constexpr (!WINO) prefetch_b0<NW, CB, 32, T1M, T1N, (ROLL1 ? 1 : G1)>(a.packed + a.off.w[1], b1, wave, lane);
+    // conv0 taps + bias (and for exact AffNet / OriNet the first weight chunk of conv1): requested now, consumed after the input phase
+    float w0[3][S::T1N];
+    f32x4 bias0[S::T1N];
+    conv0_load_w<NW, CB, S::T1M, S::T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
+    f32x4 b1[1][S::T1N];
+    if constexpr (S3 == 0 && KIND != AFFNET_NET_HARDNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
 
     // ---- input: load or sample 1024 pixels (PPT per thread), standardise, store padded ----------------
+    constexpr int PPT = 1024 / NTHR;                    // input pixels per thread (2 or 1)
+    constexpr int RPT = 32 / PPT;                       // patch rows covered by one pass of the workgroup
     float v[PPT];
     if (a.patches) {
         const float* src = a.patches + pidx * 1024;
@@ -498,30 +487,15 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             v[q] = aff_sample_bilinear(img, h, w, t00, t01, t02, t10, t11, t12, ps.base[tid & 31], ps.base[(tid >> 5) + q * RPT]);
     }
     CNN_STAMP(16);
-    // halo of the padded patch (4 x 33 cells) and of the CB activation planes; interiors are written below / by conv0
+    // halo of the padded patch (4 x 33 cells) and of the activation planes; interiors are written below / by conv0
     if (tid < 4 * 33) {
         const int e = tid;
         const int y = e < 34 ? 0 : (e < 68 ? 33 : 1 + ((e - 68) >> 1)), x = e < 34 ? e : (e < 68 ? e - 34 : ((e - 68) & 1) * 33);
         patch[y * WP32 + x] = 0.0f;
     }
-    constexpr bool HALF = S3 != 0;                                // split-operand arithmetic: conv0 .. conv2 in two half-patch passes
-    constexpr int TERMS = S3 ? S3 : 3;                            // terms per operand of the split arithmetic (3 bf16 / 2 fp16)
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3, "S3 = number of terms of the split arithmetic");
-    // three bf16 terms: term-interleaved 48-byte cells (LayQ), conv0 .. conv2 in two half-patch passes; two fp16 terms: 16-byte pixels, the two terms of a row side by
-    // side (LayR; per-reader row pitch / group stride), conv0 once for the whole patch
-    typedef LayQ<16, 32, 34, CB, 0, 3> LQH;                      // three terms: conv0 output of half a patch, pre-split; read by conv1 (stride 1)
-    typedef LayQ<16, 32, 34, CB, 16, 3> LQH2;                    // three terms: conv1 output of half a patch; read by conv2 at stride 2
-    // two-term arithmetic: LayR's 16-byte pixels hold conv0's / conv1's output of the WHOLE patch (145 KB for 32 channels, 72.5 KB for 16), so conv0 runs once; conv1 / conv2
-    // keep their two half-patch LOOPS (same register blockings) on 16-row views of the whole layouts - no second conv0 pass, no halo-row fix-ups between the halves
-    using LR0 = LayR<32, 32, 34, CB, 0>;                          // conv0 output, read by conv1 (stride 1)
-    using LR0H = LayR<16, 32, 34, CB, 0, 34>;                     // its 16-row view
-    using LR1 = LayR<32, 32, 34, CB, 16>;                         // conv1 output, read by conv2 at stride 2
-    using LR1H = LayR<16, 32, 34, CB, 16, 34>;
-    constexpr bool WHOLE = (TERMS == 2) && HALF;
-    static_assert(!WHOLE || (LR0::BYTES <= TrunkLds<CB>::ACT * 4 && LR1::BYTES <= TrunkLds<CB>::ACT * 4 && LR0H::GS == LR0::GS && LR1H::GS == LR1::GS), "whole-patch split layouts");
-    if constexpr (WHOLE) zero_halo_q<LR0, NTHR>(act);
-    else if constexpr (HALF) zero_halo_q<LQH, NTHR>(act);
-    else zero_halo<LayC0, NTHR>(act, CB);
+    if constexpr (S3 == 0) zero_halo<LayC0, NTHR>(act, CB);                          // the halo of the flow's conv0 output layout
+    else if constexpr (S3 == 2) zero_halo_q<typename SplitLays<CB>::LR0, NTHR>(act);
+    else zero_halo_q<typename SplitLays<CB>::LQH, NTHR>(act);
     float sum = 0.f;
 #pragma unroll
     for (int q = 0; q < PPT; ++q) sum += v[q];
@@ -538,38 +512,250 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     __syncthreads();
     CNN_STAMP(1);
 
-    // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-    f32x4 bias1[T1N];
-    f32x4 Uw[16];                                                 // WINO: the rolling U register set of conv1 / conv3 / conv5
-    if constexpr (!HALF) {
-        f32x4 acc[T1M][T1N];
-        conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
-        CNN_STAMP(19);
-        prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
-        store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
-        CNN_STAMP(20);
-        if constexpr (WINO) wino_prefetch_u<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Uw, wave, lane);
-        __syncthreads();
-    }
-    if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-    if (!HALF) CNN_STAMP(2);
+    // ---- one straight-line body per flow ----------------------------------------------------------------
+    if constexpr (S3 == 0 && KIND == AFFNET_NET_HARDNET) {
+        // Exact HardNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the MFMAs; each wave
+        // runs NB (tile block, channel block) passes of a layer.  The Winograd layers load their transformed weights U from the blob
+        // (NetLayout::w_wino), one K group ahead; the first group of a layer is requested in front of the barrier before it, where the direct-form
+        // layers (conv0, conv2, conv4) request their first weight chunk.  conv5's tensor goes to HBM for the head GEMM.
+        constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
+        constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
 
-    // AFFNET_ARITH_FP32_SPLIT3 (affnet_set_arith): conv1 .. conv5 on split operands - every fp32 operand as three bf16 terms, six
-    // v_mfma_f32_16x16x32_bf16 per product, fp32 accumulate.  conv0 .. conv4 write their outputs PRE-SPLIT into term-interleaved cells (LayQ),
-    // conv1 .. conv5 read ready fragments (conv3x3_mfma_s3q): no VALU work inside the MFMA loops ("Split-operand trunks").
-    // The first weight fragments of a loop are requested before the barriers / epilogue in front of it.
-    // HardNet (one workgroup per CU): optionally (affnet_debug_split3_variant bit 0) the two waves of a SIMD take turns at the higher priority
-    // inside the loops.  Round 3's tile-major loops gained 2.5 % from it; with the term-major loops it costs 1 % (default off).
-    const int s3_alt = KIND == AFFNET_NET_HARDNET ? a.s3_alt : 0;       // variant bits for the loops (conv3x3_mfma_s3q)
-    if constexpr (S3 != 0 && KIND == AFFNET_NET_HARDNET) {
+        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+        f32x4 Uw[16];                                                 // the rolling U register set of conv1 / conv3 / conv5
+        {
+            f32x4 acc[T1M][T1N];
+            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+            CNN_STAMP(19);
+            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+            CNN_STAMP(20);
+            wino_prefetch_u<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Uw, wave, lane);
+            __syncthreads();
+        }
+        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+        CNN_STAMP(2);
+
+        // ---- conv1: CB -> CB @32x32, Winograd -------------------------------------------------------------
+        f32x4 b2[S::G2][T2N];
+        f32x4 bias2[T2N];
+        {
+            f32x4 y[NB1][4], bw[NB1];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Uw, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(3);
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
+            __syncthreads();
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
+        }
+        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
+        {
+            f32x4 acc[T2M][T2N];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(5);
+            wino_prefetch_u<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Uw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
+        }
+        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
+        f32x4 b4[S::G4][T4N];
+        f32x4 bias4[T4N];
+        {
+            f32x4 y[NB3][4], bw[NB3];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Uw, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(7);
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        }
+        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
+        {
+            f32x4 acc[T4M][T4N];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(9);
+            wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC4, NTHR>(act, 4 * CB);
+            store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(10);
+        }
+        if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv5: 4CB -> 4CB @8x8, Winograd; conv5 tensor -> HBM as [pixel][channel], the head GEMM runs over all patches ----
+        f32x4 y[NB5][4], bw[NB5];
+        __builtin_amdgcn_s_setprio(0);
+        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
+        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
+        __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(11);
+        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
+        if (!STAMPS || a.dbg_layer < 0) {
+            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
+            CNN_STAMP(13);
+            return;
+        }
+        __syncthreads();
+        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
+        __syncthreads();
+        CNN_STAMP(12);
+        if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
+    } else if constexpr (S3 == 0) {
+        // Exact AffNet / OriNet: conv1 .. conv5 in the direct form (AffNet / OriNet set the LAF geometry), conv5 straight into the heads.
+        constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
+        static_assert(T1M * 8 > S::AREG, "conv1: two A sets of T1M float4 do not fit -> rolling single set (conv3x3_mfma_roll)");
+
+        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+        f32x4 bias1[T1N];
+        {
+            f32x4 acc[T1M][T1N];
+            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+            CNN_STAMP(19);
+            prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
+            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+            CNN_STAMP(20);
+            __syncthreads();
+        }
+        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+        CNN_STAMP(2);
+
+        // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
+        f32x4 b2[S::G2][T2N];
+        f32x4 bias2[T2N];
+        {
+            f32x4 acc[T1M][T1N];
+            conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], b1, acc, wave, lane);
+            CNN_STAMP(3);
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            __syncthreads();
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
+        }
+        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
+        f32x4 b3[S::G3][T2N];
+        f32x4 bias3[T2N];
+        {
+            f32x4 acc[T2M][T2N];
+            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+            CNN_STAMP(5);
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G3>(a.packed + a.off.w[3], b3, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
+        }
+        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
+        f32x4 b4[S::G4][T4N];
+        f32x4 bias4[T4N];
+        {
+            f32x4 acc[T2M][T2N];
+            conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, S::G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
+            CNN_STAMP(7);
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            __syncthreads();
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        }
+        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
+        f32x4 b5[S::G5][T4N];
+        f32x4 bias5[T4N];
+        {
+            f32x4 acc[T4M][T4N];
+            conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
+            CNN_STAMP(9);
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G5>(a.packed + a.off.w[5], b5, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
+            __syncthreads();
+            zero_halo<LayC4, NTHR>(act, 4 * CB);
+            store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(10);
+        }
+        if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv5: 4CB -> 4CB @8x8, then the head's per-wave partial sums ---------------------------------
+        f32x4 acc[T4M][T4N];
+        conv3x3_mfma<NW, 4 * CB, 4 * CB, LayC4, 1, T4M, T4N, S::G5>(act, a.packed + a.off.w[5], b5, acc, wave, lane);
+        CNN_STAMP(11);
+        if (!STAMPS || a.dbg_layer < 0) {
+            if constexpr (KIND == AFFNET_NET_ORINET)   // weights once, shifted activations from LDS
+                head_partials_ori_lds<T4M, NTHR>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_ORI, act, wave, lane, tid);
+            else
+                head_partials<T4M>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_AFF, wave, lane);
+            CNN_STAMP(13);
+            return;
+        }
+        __syncthreads();
+        store_tiles_lds<4 * CB, LayC5, T4M, T4N>(act, bias5, acc, wave, lane);   // debug dump only
+        __syncthreads();
+        CNN_STAMP(12);
+        if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
+    } else if constexpr (KIND == AFFNET_NET_HARDNET) {
+        // Split HardNet.  AFFNET_ARITH_FP32_SPLIT3 (affnet_set_arith): conv1 .. conv5 on split operands - every fp32 operand as three bf16 terms, six
+        // v_mfma_f32_16x16x32_bf16 per product, fp32 accumulate (SPLIT2H: two fp16 terms).  conv0 .. conv4 write their outputs PRE-SPLIT (SplitLays, LayQ / LayR),
+        // conv1 .. conv5 read ready fragments (conv3x3_mfma_s3q): no VALU work inside the MFMA loops ("Split-operand trunks").
+        // The first weight fragments of a loop are requested before the barriers / epilogue in front of it.
+        // One workgroup per CU: optionally (affnet_debug_split3_variant bit 0) the two waves of a SIMD take turns at the higher priority
+        // inside the loops.  Round 3's tile-major loops gained 2.5 % from it; with the term-major loops it costs 1 % (default off).
+        using SL = SplitLays<CB>;
+        using LQH = typename SL::LQH;
+        using LQH2 = typename SL::LQH2;
+        using LR0 = typename SL::LR0;
+        using LR1 = typename SL::LR1;
+        constexpr int TERMS = S3;
+        constexpr bool WHOLE = TERMS == 2;
+        f32x4 bias1[2];
+        const int s3_alt = a.s3_alt;                                        // variant bits for the loops (conv3x3_mfma_s3q)
         // conv2 / conv3 outputs, 64 channels @16x16 (122 KB / 90 KB): read at stride 1 (conv3) and, conv3's output written in place, at stride 2 (conv4).  No group
         // stride serves both readers (tools/lds_bank_model.py): GS = 0 (mod 256) leaves conv4's two-row reader with 2-way conflicts, GS = 16 conv3's one-row reader.
         // LayR takes conv4's here: its 4 x 1 tiles are the more LDS-bound (probe: -1350 cycles for conv4, +300 for conv3's 4 x 2); a second layout for conv3's
         // output with the other stride cost 0.8 k cycles per patch for zeroing its halo again (measured)
         using LQ2 = std::conditional_t<TERMS == 2, LayR<16, 16, 20, 2 * CB, 16>, LayQ<16, 16, 18, 2 * CB, 0, 3>>;
         using LQ4 = std::conditional_t<TERMS == 2, LayR<8, 8, 12, 4 * CB, 0>, LayQ<8, 8, 16, 4 * CB, 128, 3>>;        // conv4 output: 128 channels @8x8 (122 KB / 60 KB)
-        static_assert(LQ2::BYTES <= TrunkLds<CB>::ACT * 4 && LQ4::BYTES <= TrunkLds<CB>::ACT * 4 && LQH::BYTES <= TrunkLds<CB>::ACT * 4 &&
-                      LQH2::BYTES <= TrunkLds<CB>::ACT * 4, "pre-split layouts must fit the activation buffer");
+        static_assert(LQ2::BYTES <= TrunkLds<CB>::ACT * 4 && LQ4::BYTES <= TrunkLds<CB>::ACT * 4, "pre-split layouts must fit the activation buffer");
         char* base = reinterpret_cast<char*>(act);
         // three terms: conv0 + conv1 in two half-patch passes - the pre-split conv0 output of 32 channels @32x32 would be 222 KB, half of it (16 rows +
         // a halo row either side) is 115 KB; two terms (WHOLE): 145 KB, conv0 runs once and the two half loops of conv1 / conv2 read 16-row views
@@ -591,9 +777,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             conv0_whole_split_q<NW, LR0, 2>(patch, w0, bias0, act, wave, lane);
             __syncthreads();
             CNN_STAMP(2);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, CB, LR0, 1, 8, 2>(act, a.packed + a.off.w_s3[1], wf1, acc1, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(3);
             s3_prefetch_w0<NW, CB, 2 * CB, 16, 4, 2, TERMS>(a.packed + a.off.w_s3[2], wf2w, wave, lane);
             prefetch_bias<NW, 16, 4, 2>(a.packed + a.off.b[2], bias2w, wave, lane);
@@ -602,18 +788,18 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             store_tiles_split_q<CB, LR1, 8, 2>(act, bias1, acc1, wave, lane);
             __syncthreads();
             CNN_STAMP(4);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, 2 * CB, LR1, 2, 4, 2>(act, a.packed + a.off.w_s3[2], wf2w, acc2w, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
         } else {
             s3_prefetch_w0<NW, CB, CB, 32, 4, 2, TERMS>(a.packed + a.off.w_s3[1], wf1, wave, lane);
             prefetch_bias<NW, 32, 8, 2>(a.packed + a.off.b[1], bias1, wave, lane);
             conv0_half_split_q<NW, LQH, 2>(patch, w0, bias0, act, 0, wave, lane);
             __syncthreads();
             CNN_STAMP(2);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, CB, LQH, 1, 4, 2>(act, a.packed + a.off.w_s3[1], wf1, acc_a, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             __syncthreads();
             if (tid < LQH::SLOTS * 4 * 32) {                             // pass 0 left conv0 row 16 in the bottom halo row: zero again (slots x 4 groups x 32 cells)
                 const int t = tid / 128, g = (tid >> 5) & 3, x = tid & 31;
@@ -621,9 +807,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             }
             conv0_half_split_q<NW, LQH, 2>(patch, w0, bias0, act, 1, wave, lane);
             __syncthreads();
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, CB, LQH, 1, 4, 2>(act, a.packed + a.off.w_s3[1], wf1, acc_b, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(3);
             s3_prefetch_w0<NW, CB, 2 * CB, 8, 4, 1, TERMS>(a.packed + a.off.w_s3[2], wf2, wave, lane);
             bias2[0] = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[2] + (wave >> 1) * 16 + 4 * (lane >> 4)]);      // MG = 8 tiles / 4 = 2: channel tile = wave / 2
@@ -634,9 +820,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             store_tiles_split_q<CB, LQH2, 4, 2>(act, bias1, acc_a, wave, lane);
             __syncthreads();
             CNN_STAMP(4);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, 2 * CB, LQH2, 2, 4, 1>(act, a.packed + a.off.w_s3[2], wf2, acc2_a, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             __syncthreads();
             store_tiles_split_q<CB, LQH2, 4, 2>(act, bias1, acc_b, wave, lane);
             if (wave == 7) {                                             // conv1 row 15 (tiles 2, 3 of wave 7 in pass 0) = the top halo row of pass 1
@@ -645,9 +831,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
                 for (int i = 2; i < 4; ++i) split_store_tile_q<LQH2, 2>(base, LQH2::at(0, (i - 2) * 16 + n + 1), 0, bias1, acc_a[i], lane >> 4);
             }
             __syncthreads();
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, CB, 2 * CB, LQH2, 2, 4, 1>(act, a.packed + a.off.w_s3[2], wf2, acc2_b, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
         }
         CNN_STAMP(5);
         S3W<2> wf3;
@@ -666,9 +852,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         CNN_STAMP(6);
         {
             f32x4 acc_[4][2];                                            // conv3: 64 -> 64 @16x16
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, 2 * CB, 2 * CB, LQ2, 1, 4, 2>(act, a.packed + a.off.w_s3[3], wf3, acc_, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(7);
             s3_prefetch_w0<NW, 2 * CB, 4 * CB, 4, 4, 1, TERMS>(a.packed + a.off.w_s3[4], wf4, wave, lane);
             prefetch_bias<NW, 8, 4, 1>(a.packed + a.off.b[4], bias4, wave, lane);
@@ -679,9 +865,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         {
             f32x4 acc_[4][1];                                            // conv4: 64 -> 128, stride 2 -> 8x8
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             conv3x3_mfma_s3q<NW, 2 * CB, 4 * CB, LQ2, 2, 4, 1>(act, a.packed + a.off.w_s3[4], wf4, acc_, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
+            __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(9);
             s3_prefetch_w0<NW, 4 * CB, 4 * CB, 4, 4, 1, TERMS>(a.packed + a.off.w_s3[5], wf5, wave, lane);
             prefetch_bias<NW, 8, 4, 1>(a.packed + a.off.b[5], bias5s, wave, lane);
@@ -691,30 +877,35 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             __syncthreads();
             CNN_STAMP(10);
         }
-        {
-            f32x4 acc5[4][1];                                            // conv5: 128 -> 128 @8x8, conv5 tensor -> HBM for the head GEMM
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
-            conv3x3_mfma_s3q<NW, 4 * CB, 4 * CB, LQ4, 1, 4, 1>(act, a.packed + a.off.w_s3[5], wf5, acc5, wave, lane, s3_alt);
-            if (PRIO) __builtin_amdgcn_s_setprio(3);
-            CNN_STAMP(11);
-            store_tiles_global<4 * CB, 4, 1>(a.out + pidx * (64 * 4 * CB), bias5s, acc5, wave, lane);
-        }
-        return;
-    }
-
-    if constexpr (S3 != 0 && CB == 16) {
-        // AffNet / OriNet on split operands, same structure as the HardNet branch: conv0 .. conv2 in two half-patch passes on pre-split
-        // layouts (conv1 / conv2 have 16 input channels: two taps per k = 32 step), conv3 .. conv5 whole.
+        f32x4 acc5[4][1];                                                // conv5: 128 -> 128 @8x8, conv5 tensor -> HBM for the head GEMM
+        __builtin_amdgcn_s_setprio(0);
+        conv3x3_mfma_s3q<NW, 4 * CB, 4 * CB, LQ4, 1, 4, 1>(act, a.packed + a.off.w_s3[5], wf5, acc5, wave, lane, s3_alt);
+        __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(11);
+        store_tiles_global<4 * CB, 4, 1>(a.out + pidx * (64 * 4 * CB), bias5s, acc5, wave, lane);
+    } else {
+        // Split AffNet / OriNet, same structure as split HardNet: conv0 .. conv2 in two half-patch passes on pre-split layouts (conv1 / conv2 have
+        // 16 input channels: two taps per k = 32 step), conv3 .. conv5 whole.
+        // (tried in round 4: the phases outside the MFMA loops at a higher issue priority than the loops - with two workgroups per CU a young
+        // workgroup crawls through input / conv0 / epilogues next to an older one in its loops, conv0 of half a patch takes 9 - 10 k cycles for
+        // ~150 instructions per wave.  Zero-sum as in the exact path: 4.12 vs 4.10 - 4.13 ms per 48000 patches.  Removed.)
+        constexpr int T4M = S::T4M, T4N = S::T4N;
+        using SL = SplitLays<CB>;
+        using LQH = typename SL::LQH;
+        using LQH2 = typename SL::LQH2;
+        using LR0 = typename SL::LR0;
+        using LR0H = typename SL::LR0H;
+        using LR1 = typename SL::LR1;
+        using LR1H = typename SL::LR1H;
+        constexpr int TERMS = S3;
+        constexpr bool WHOLE = TERMS == 2;
+        f32x4 bias1[1];
         // conv2 / conv3 outputs: 32 channels @16x16 (61 KB / 45 KB).  LayR: GS = 0 (mod 256) here - with two workgroups per CU conv3's one-row reader is LDS-bound and
         // the 2-way conflicts of the HardNet branch's choice cost it 10 % (probe: 7.1 k vs 6.5 k cycles), while conv4 (2 x 1 tiles) is the same with or without its own
         using LQ2 = std::conditional_t<TERMS == 2, LayR<16, 16, 20, 2 * CB, 0>, LayQ<16, 16, 18, 2 * CB, 0, 3>>;
         using LQ4 = std::conditional_t<TERMS == 2, LayR<8, 8, 12, 4 * CB, 0>, LayQ<8, 8, 16, 4 * CB, 128, 3>>;        // conv4 output: 64 channels @8x8 (61 KB / 30 KB)
-        static_assert(LQH::BYTES <= TrunkLds<CB>::ACT * 4 && LQH2::BYTES <= TrunkLds<CB>::ACT * 4 && LQ2::BYTES <= TrunkLds<CB>::ACT * 4 && LQ4::BYTES <= TrunkLds<CB>::ACT * 4,
-                      "pre-split layouts must fit the activation buffer");
+        static_assert(LQ2::BYTES <= TrunkLds<CB>::ACT * 4 && LQ4::BYTES <= TrunkLds<CB>::ACT * 4, "pre-split layouts must fit the activation buffer");
         char* base = reinterpret_cast<char*>(act);
-        // (tried in round 4: the phases outside the MFMA loops at a higher issue priority than the loops - with two workgroups per CU a young
-        // workgroup crawls through input / conv0 / epilogues next to an older one in its loops, conv0 of half a patch takes 9 - 10 k cycles for
-        // ~150 instructions per wave.  Zero-sum as in the exact path: 4.12 vs 4.10 - 4.13 ms per 48000 patches.  Removed.)
         f32x4 acc_a[4][1], acc_b[4][1];
         // (128 VGPRs at two workgroups per CU: a loop's first weight fragments are requested right in front of it here - held across the
         // previous epilogue like in the HardNet branch they cost 17 / 23 spilled registers)
@@ -821,183 +1012,17 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             __syncthreads();
             CNN_STAMP(10);
         }
-        {
-            f32x4 acc5[T4M][T4N];                                        // conv5: 64 -> 64 @8x8 in the exact path's tiling (the heads read it)
-            conv3x3_mfma_s3q<NW, 4 * CB, 4 * CB, LQ4, 1, T4M, T4N>(act, a.packed + a.off.w_s3[5], wf5, acc5, wave, lane, false);
-            CNN_STAMP(11);
-            if constexpr (KIND != AFFNET_NET_HARDNET) {
-                int lane_h = lane;                                       // opaque: 4 * (lane >> 4) is recomputed here, not carried (and spilled) from the kernel's top
-                asm volatile("" : "+v"(lane_h));
-                if constexpr (KIND == AFFNET_NET_ORINET)
-                    head_partials_ori_lds<T4M, NTHR>(a.packed + a.off.head_w, bias5s, acc5, a.out + pidx * HEAD_PART_ORI, act, wave, lane_h, tid);
-                else
-                    head_partials<KIND, T4M>(a.packed + a.off.head_w, bias5s, acc5, a.out + pidx * HEAD_PART_AFF, wave, lane_h);
-            }
-            CNN_STAMP(13);
-        }
-        return;
-    }
-
-    // Every layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading
-    // the input) -> zero the halo of the OUTPUT layout, bias + ReLU + store in place -> barrier.
-    // The Winograd layers (WINO, above) load their transformed weights U from the blob (NetLayout::w_wino), one K group ahead; the first
-    // group of a layer is requested in front of the barrier before it, where the direct-form layers request their first weight chunk.
-    // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
-    f32x4 b2[G2][T2N];
-    f32x4 bias2[T2N];
-    if constexpr (WINO) {
-        f32x4 y[NB1][4], bw[NB1];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Uw, y, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(3);
-        prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G2>(a.packed + a.off.w[2], b2, wave, lane);
-        prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-        wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
-        __syncthreads();
-        CNN_STAMP(21);
-        zero_halo<LayC1, NTHR>(act, CB);
-        wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
-        CNN_STAMP(22);
-        __syncthreads();
-        CNN_STAMP(4);
-    } else {
-        f32x4 acc[T1M][T1N];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        if (ROLL1) conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], reinterpret_cast<const f32x4 (&)[1][T1N]>(b1), acc, wave, lane);
-        else conv3x3_mfma<NW, CB, CB, LayC0, 1, T1M, T1N, G1>(act, a.packed + a.off.w[1], reinterpret_cast<const f32x4 (&)[G1][T1N]>(b1), acc, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(3);
-        prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G2>(a.packed + a.off.w[2], b2, wave, lane);
-        prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-        __syncthreads();
-        CNN_STAMP(21);
-        zero_halo<LayC1, NTHR>(act, CB);
-        store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
-        CNN_STAMP(22);
-        __syncthreads();
-        CNN_STAMP(4);
-    }
-    if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
-
-    // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-    f32x4 b3[G3][T2N];
-    f32x4 bias3[T2N];
-    {
-        f32x4 acc[T2M][T2N];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(5);
-        if constexpr (WINO) wino_prefetch_u<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Uw, wave, lane);
-        else {
-            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, G3>(a.packed + a.off.w[3], b3, wave, lane);
-            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
-        }
-        __syncthreads();
-        zero_halo<LayC2, NTHR>(act, 2 * CB);
-        store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
-        __syncthreads();
-        CNN_STAMP(6);
-    }
-    if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
-
-    // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
-    f32x4 b4[G4][T4N];
-    f32x4 bias4[T4N];
-    if constexpr (WINO) {
-        f32x4 y[NB3][4], bw[NB3];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Uw, y, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(7);
-        prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G4>(a.packed + a.off.w[4], b4, wave, lane);
-        prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-        wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
-        __syncthreads();
-        zero_halo<LayC3, NTHR>(act, 2 * CB);
-        wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
-        __syncthreads();
-        CNN_STAMP(8);
-    } else {
-        f32x4 acc[T2M][T2N];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(7);
-        prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G4>(a.packed + a.off.w[4], b4, wave, lane);
-        prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-        __syncthreads();
-        zero_halo<LayC3, NTHR>(act, 2 * CB);
-        store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
-        __syncthreads();
-        CNN_STAMP(8);
-    }
-    if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
-
-    // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
-    f32x4 b5[G5][T4N];
-    f32x4 bias5[T4N];
-    {
-        f32x4 acc[T4M][T4N];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(9);
-        if constexpr (WINO) wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
-        else {
-            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, G5>(a.packed + a.off.w[5], b5, wave, lane);
-            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
-        }
-        __syncthreads();
-        zero_halo<LayC4, NTHR>(act, 4 * CB);
-        store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
-        __syncthreads();
-        CNN_STAMP(10);
-    }
-    if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
-
-    // ---- conv5: 4CB -> 4CB @8x8 ------------------------------------------------------------------------
-    if constexpr (WINO) {
-        f32x4 y[NB5][4], bw[NB5];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
-        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
+        f32x4 acc5[T4M][T4N];                                            // conv5: 64 -> 64 @8x8 in the exact path's tiling (the heads read it)
+        conv3x3_mfma_s3q<NW, 4 * CB, 4 * CB, LQ4, 1, T4M, T4N>(act, a.packed + a.off.w_s3[5], wf5, acc5, wave, lane, false);
         CNN_STAMP(11);
-        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
-        if (!STAMPS || a.dbg_layer < 0) {
-            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
-            CNN_STAMP(13);
-            return;
-        }
-        __syncthreads();
-        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
-        __syncthreads();
-        CNN_STAMP(12);
-    } else {
-        f32x4 acc[T4M][T4N];
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        conv3x3_mfma<NW, 4 * CB, 4 * CB, LayC4, 1, T4M, T4N, G5>(act, a.packed + a.off.w[5], b5, acc, wave, lane);
-        if (PRIO) __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(11);
-        if (!STAMPS || a.dbg_layer < 0) {
-            if constexpr (KIND == AFFNET_NET_HARDNET)   // conv5 tensor -> HBM as [pixel][channel]; the head GEMM runs over all patches
-                store_tiles_global<4 * CB, T4M, T4N>(a.out + pidx * (64 * 4 * CB), bias5, acc, wave, lane);
-            else if constexpr (KIND == AFFNET_NET_ORINET)   // per-wave partial sums of the head's dot products: weights once, shifted activations from LDS
-                head_partials_ori_lds<T4M, NTHR>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_ORI, act, wave, lane, tid);
-            else
-                head_partials<KIND, T4M>(a.packed + a.off.head_w, bias5, acc,
-                                         a.out + pidx * (KIND == AFFNET_NET_AFFNET ? HEAD_PART_AFF : HEAD_PART_ORI), wave, lane);
-            CNN_STAMP(13);
-            return;
-        }
-        __syncthreads();
-        store_tiles_lds<4 * CB, LayC5, T4M, T4N>(act, bias5, acc, wave, lane);   // debug dump only
-        __syncthreads();
-        CNN_STAMP(12);
+        int lane_h = lane;                                               // opaque: 4 * (lane >> 4) is recomputed here, not carried (and spilled) from the kernel's top
+        asm volatile("" : "+v"(lane_h));
+        if constexpr (KIND == AFFNET_NET_ORINET)
+            head_partials_ori_lds<T4M, NTHR>(a.packed + a.off.head_w, bias5s, acc5, a.out + pidx * HEAD_PART_ORI, act, wave, lane_h, tid);
+        else
+            head_partials<T4M>(a.packed + a.off.head_w, bias5s, acc5, a.out + pidx * HEAD_PART_AFF, wave, lane_h);
+        CNN_STAMP(13);
     }
-    if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
 }
 
 // ---- AffNet / OriNet heads, second half: combine the eight per-wave partials of a patch ---------------------------------
@@ -1352,26 +1377,20 @@ static int cnn_launch(affnet_ctx* ctx, int kind, const float* packed, const floa
     const dim3 grid(row_count, B);
     // (Tried and removed: two AffNet patches per persistent 16-wave workgroup in anti-phase - correct but 8 % slower, the
     // small-tile loops reach 85-90 % of the pipe rate with two waves per SIMD; 16-wave HardNet workgroups - slower too.)
-#define TRUNK_LAUNCH(K) do { if (a.dbg_time || dbg_layer >= 0) hipLaunchKernelGGL((cnn32_trunk_kernel<K, 8, true>), grid, dim3(512), 0, st, a, ps); \
-                             else hipLaunchKernelGGL((cnn32_trunk_kernel<K, 8, false>), grid, dim3(512), 0, st, a, ps); } while (0)
     a.s3_alt = ctx->split3_variant;
     const bool h2 = ctx->arith == AFFNET_ARITH_FP32_SPLIT2H;
     const bool split = ctx->arith == AFFNET_ARITH_FP32_SPLIT3 || h2;
     a.off = to_offsets(L, ctx->arith);                                   // the split copy of the active mode
-    const bool s3 = split && !a.dbg_time && dbg_layer < 0;             // conv1 .. conv5 on split operands (affnet_set_arith)
-#define SPLIT_LAUNCH(K, ST) do { if (h2) hipLaunchKernelGGL((cnn32_trunk_kernel<K, 8, ST, 2>), grid, dim3(512), 0, st, a, ps); \
-                                 else hipLaunchKernelGGL((cnn32_trunk_kernel<K, 8, ST, 3>), grid, dim3(512), 0, st, a, ps); } while (0)
-    if (split && a.dbg_time && dbg_layer < 0 && kind == AFFNET_NET_HARDNET) SPLIT_LAUNCH(AFFNET_NET_HARDNET, true);      // phase stamps of the split-operand trunks (tuning aid)
-    else if (split && a.dbg_time && dbg_layer < 0 && kind == AFFNET_NET_AFFNET) SPLIT_LAUNCH(AFFNET_NET_AFFNET, true);
-    else if (split && a.dbg_time && dbg_layer < 0 && kind == AFFNET_NET_ORINET) SPLIT_LAUNCH(AFFNET_NET_ORINET, true);
-    else if (s3 && kind == AFFNET_NET_AFFNET) SPLIT_LAUNCH(AFFNET_NET_AFFNET, false);
-    else if (s3 && kind == AFFNET_NET_ORINET) SPLIT_LAUNCH(AFFNET_NET_ORINET, false);
-    else if (s3) SPLIT_LAUNCH(AFFNET_NET_HARDNET, false);
-#undef SPLIT_LAUNCH
-    else if (kind == AFFNET_NET_AFFNET) TRUNK_LAUNCH(AFFNET_NET_AFFNET);
-    else if (kind == AFFNET_NET_ORINET) TRUNK_LAUNCH(AFFNET_NET_ORINET);
-    else TRUNK_LAUNCH(AFFNET_NET_HARDNET);
-#undef TRUNK_LAUNCH
+    // trunk instantiation [net kind][exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see above)
+    static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk table order");
+    static void (*const trunks[3][3][2])(CnnArgs, PyrSrc) = {
+        {{cnn32_trunk_kernel<0, 8, false>, cnn32_trunk_kernel<0, 8, true>}, {cnn32_trunk_kernel<0, 8, false, 3>, cnn32_trunk_kernel<0, 8, true, 3>},
+         {cnn32_trunk_kernel<0, 8, false, 2>, cnn32_trunk_kernel<0, 8, true, 2>}},
+        {{cnn32_trunk_kernel<1, 8, false>, cnn32_trunk_kernel<1, 8, true>}, {cnn32_trunk_kernel<1, 8, false, 3>, cnn32_trunk_kernel<1, 8, true, 3>},
+         {cnn32_trunk_kernel<1, 8, false, 2>, cnn32_trunk_kernel<1, 8, true, 2>}},
+        {{cnn32_trunk_kernel<2, 8, false>, cnn32_trunk_kernel<2, 8, true>}, {cnn32_trunk_kernel<2, 8, false, 3>, cnn32_trunk_kernel<2, 8, true, 3>},
+         {cnn32_trunk_kernel<2, 8, false, 2>, cnn32_trunk_kernel<2, 8, true, 2>}}};
+    hipLaunchKernelGGL(trunks[kind][h2 ? 2 : (split ? 1 : 0)][a.dbg_time || dbg_layer >= 0], grid, dim3(512), 0, st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     if (kind != AFFNET_NET_HARDNET && dbg_layer < 0) {       // combine the per-wave head partials in `scratch`
         if (kind == AFFNET_NET_AFFNET) {
