@@ -20,7 +20,11 @@ fi
 mkdir -p "$OBJ"
 pids=()
 for f in $FILES; do
-  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ "$HERE/common.h" -nt "$OBJ/$f.o" ] || [ "$HERE/cnn_mfma.h" -nt "$OBJ/$f.o" ] || [ "$HERE/shape_filter.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/affnet_hip.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/affnet_hip_debug.h" -nt "$OBJ/$f.o" ] || [ "$HERE/../../include/affnet_hip_probes.h" -nt "$OBJ/$f.o" ]; then
+  stale=0      # no object yet, or the source or ANY header (internal or public) is newer than it
+  for dep in "$HERE/$f.hip" "$HERE"/*.h "$HERE"/../../include/*.h; do
+    if [ ! -f "$OBJ/$f.o" ] || [ "$dep" -nt "$OBJ/$f.o" ]; then stale=1; break; fi
+  done
+  if [ $stale = 1 ]; then
     $HIPCC $FLAGS -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
     pids+=($!)
   fi

@@ -22,6 +22,8 @@
 //     (hardnet_head_kernel + hardnet_finish_kernel: BN bias + L2 norm) follows; AffNet / OriNet reduce their heads' dot
 //     products per wave straight from the conv5 accumulators (head_partials, head_partials_ori_lds) and affnet_finish_kernel /
 //     orinet_finish_kernel combine the eight partials per patch in fixed order (tanh, rectification / atan2).
+// Host side (end of the file): every entry point fills a CnnCall and cnn_launch runs cnn_check -> trunk_launch -> finish_affnet /
+// finish_orinet / hardnet_head; the prototypes other files call are in common.h.
 #include <math.h>
 #include <stdlib.h>
 
@@ -318,10 +320,7 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
 }
 
 struct PyrSrc {            // pyramid sampling source (fused sampler)
-    const float* lvl[AFFNET_MAX_OCTAVES][AFFNET_MAX_LEVELS];
-    int h[AFFNET_MAX_OCTAVES], w[AFFNET_MAX_OCTAVES];
-    int n_octaves, n_levels;
-    size_t img_stride;     // floats between the pyramids of consecutive images (batch)
+    PyrTable t;            // the samplers' level table (common.h)
     float base[32];        // affine_grid base coordinates for PS = 32
 };
 
@@ -474,10 +473,10 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         for (int q = 0; q < PPT; ++q) v[q] = src[tid + q * NTHR];
     } else {
         int o = a.ids[3 * pidx], l = a.ids[3 * pidx + 1];
-        o = o < 0 ? 0 : (o >= ps.n_octaves ? ps.n_octaves - 1 : o);
-        l = l < 0 ? 0 : (l >= ps.n_levels ? ps.n_levels - 1 : l);
-        const float* img = ps.lvl[o][l] + blockIdx.y * ps.img_stride;
-        const int h = ps.h[o], w = ps.w[o];
+        o = o < 0 ? 0 : (o >= ps.t.n_octaves ? ps.t.n_octaves - 1 : o);
+        l = l < 0 ? 0 : (l >= ps.t.n_levels ? ps.t.n_levels - 1 : l);
+        const float* img = ps.t.lvl[o][l] + blockIdx.y * ps.t.img_stride;
+        const int h = ps.t.h[o], w = ps.t.w[o];
         const float* L = a.lafs + 6 * pidx;
         const float m = (float)(h < w ? h : w);
         const float t00 = L[0] * m, t01 = L[1] * m, t02 = L[2] * (float)w;
@@ -1334,54 +1333,67 @@ __global__ __launch_bounds__(256) void hardnet_finish_kernel(const float* __rest
 }
 
 // ---- host entry points -------------------------------------------------------------------------------
-void aff_fill_pyr_src(const affnet_ctx* ctx, PyrSrc* t) {
-    memset(t, 0, sizeof(*t));
-    if (ctx->ws) {
-        t->n_octaves = ctx->cfg.n_octaves; t->n_levels = ctx->cfg.levels_per_octave;
-        t->img_stride = ctx->pyr_stride;
-        for (int o = 0; o < t->n_octaves; ++o) {
-            const OctaveGeom& g = ctx->oct[o];
-            t->h[o] = g.h; t->w[o] = g.w;
-            for (int l = 0; l < t->n_levels; ++l) t->lvl[o][l] = ctx->pyr + g.pyr_off + (size_t)l * g.h * g.w;
-        }
-    }
-    aff_base_grid(32, t->base);
+static void aff_fill_pyr_src(const affnet_ctx* ctx, PyrSrc* s) {
+    memset(s, 0, sizeof(*s));                            // no workspace bound (patch-tensor calls): an all-zero table
+    if (ctx->ws) aff_fill_pyr_table(ctx, &s->t);
+    aff_base_grid(32, s->base);
 }
 
-static int cnn_launch(affnet_ctx* ctx, int kind, const float* packed, const float* patches, const float* lafs, const int32_t* ids,
-                      const int32_t* count, int n_max, float* out, float* scratch, int dbg_layer, float* dbg_out, hipStream_t st,
-                      bool mark_head = false, int row_begin = 0, int row_count = -1, const int32_t* skip_cnt = nullptr, int skip_n = 0,
-                      const ShapeFuse* fuse = nullptr, int shape_op = 0, float* rot_lafs = nullptr, const DenormSel* denorm = nullptr) {
-    if (kind < 0 || kind > 2) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: unknown net kind %d", kind);
-    if (!packed || !out || n_max < 0 || (!patches && (!lafs || !ids))) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: null argument");
-    if (!patches && !ctx->ws) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: sampling from the pyramid needs a bound workspace");
-    if (dbg_layer < 0 && !scratch)
+// One CNN call: trunk launch + the net's finish stage.  Callers set the fields they mean by name; the rest keep these defaults.
+struct CnnCall {
+    int kind = -1;                                                   // AFFNET_NET_AFFNET / _ORINET / _HARDNET
+    const float* packed = nullptr;
+    const float* patches = nullptr;                                  // (n,32,32), or NULL: sample from the pyramid with lafs / ids
+    const float* lafs = nullptr; const int32_t* ids = nullptr;
+    const int32_t* count = nullptr; int n_max = 0;
+    float* out = nullptr; float* scratch = nullptr;
+    hipStream_t st = nullptr;
+    int dbg_layer = -1; float* dbg_out = nullptr;                    // layer >= 0: dump this trunk layer of patch 0, no finish stage
+    bool mark_head = false;                                          // stage mark 7 between trunk and head (affnet_describe_detected)
+    int row_begin = 0, row_count = -1;                               // row window of every image; -1 = up to n_max
+    const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
+    const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
+    float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
+};
+
+// Argument checks, in this order.  *rows = rows per image to launch; 0 with AFFNET_OK = nothing to do.
+static int cnn_check(affnet_ctx* ctx, const CnnCall& c, int* rows) {
+    *rows = 0;
+    if (c.kind < 0 || c.kind > 2) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: unknown net kind %d", c.kind);
+    if (!c.packed || !c.out || c.n_max < 0 || (!c.patches && (!c.lafs || !c.ids))) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: null argument");
+    if (!c.patches && !ctx->ws) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: sampling from the pyramid needs a bound workspace");
+    if (c.dbg_layer < 0 && !c.scratch)
         return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: d_scratch is required (HardNet n*(8192+512) floats, AffNet / OriNet n*144 floats)");
-    if (dbg_layer >= 0 && ctx->arith != AFFNET_ARITH_FP32_MFMA)       // the split trunks have no per-layer dump: the exact kernel would answer
+    if (c.dbg_layer >= 0 && ctx->arith != AFFNET_ARITH_FP32_MFMA)     // the split trunks have no per-layer dump: the exact kernel would answer
         return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: layer dumps exist for AFFNET_ARITH_FP32_MFMA only (context is in arithmetic mode %d)", ctx->arith);
-    if (n_max == 0) return AFFNET_OK;
-    if (kind == AFFNET_NET_HARDNET && n_max > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: n_max=%d (HardNet head: max 65535 rows per image)", n_max);
-    const NetLayout L = net_layout(kind);
+    if (c.n_max == 0) return AFFNET_OK;
+    if (c.kind == AFFNET_NET_HARDNET && c.n_max > 65535)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: n_max=%d (HardNet head: max 65535 rows per image)", c.n_max);
+    const int row_count = c.row_count < 0 ? c.n_max - c.row_begin : c.row_count;
+    if (c.row_begin < 0 || row_count < 0 || c.row_begin + row_count > c.n_max) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: bad row window");
+    *rows = row_count;
+    return AFFNET_OK;
+}
+
+// 0 = exact fp32, 1 = three bf16 terms, 2 = two fp16 terms: second index of the trunk and head kernel tables
+static int arith_index(const affnet_ctx* ctx) {
+    return ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);
+}
+
+static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid) {
     CnnArgs a;
-    a.packed = packed; a.off = to_offsets(L); a.patches = patches; a.lafs = lafs; a.ids = ids; a.count = count; a.n_max = n_max;
-    a.out = (dbg_layer < 0) ? scratch : out;              // trunk kernels: HardNet conv5 tensor / AffNet, OriNet head partials
-    a.dbg_layer = dbg_layer; a.dbg_out = dbg_out; a.dbg_time = ctx->dbg_time;
-    a.row_begin = row_begin; a.skip_cnt = skip_cnt; a.skip_n = skip_n;
-    a.shape_cnt = (fuse && shape_op) ? fuse->cnt : nullptr; a.shape_op = shape_op;
-    if (row_count < 0) row_count = n_max - row_begin;
-    if (row_begin < 0 || row_count < 0 || row_begin + row_count > n_max) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: bad row window");
-    if (row_count == 0) return AFFNET_OK;
+    a.packed = c.packed; a.off = to_offsets(L, ctx->arith);            // the split copy of the active mode
+    a.patches = c.patches; a.lafs = c.lafs; a.ids = c.ids; a.count = c.count; a.n_max = c.n_max;
+    a.out = (c.dbg_layer < 0) ? c.scratch : c.out;      // trunk kernels: HardNet conv5 tensor / AffNet, OriNet head partials
+    a.dbg_layer = c.dbg_layer; a.dbg_out = c.dbg_out; a.dbg_time = ctx->dbg_time;
+    a.row_begin = c.row_begin; a.skip_cnt = c.skip_cnt; a.skip_n = c.skip_n;
+    a.shape_cnt = (c.fuse && c.shape_op) ? c.fuse->cnt : nullptr; a.shape_op = c.shape_op;
+    a.s3_alt = ctx->split3_variant;
     PyrSrc ps;
     aff_fill_pyr_src(ctx, &ps);
-    const int B = patches ? 1 : ctx->B;                  // patch tensors are single-"image"; pyramid sampling covers the batch
-    const dim3 grid(row_count, B);
     // (Tried and removed: two AffNet patches per persistent 16-wave workgroup in anti-phase - correct but 8 % slower, the
     // small-tile loops reach 85-90 % of the pipe rate with two waves per SIMD; 16-wave HardNet workgroups - slower too.)
-    a.s3_alt = ctx->split3_variant;
-    const bool h2 = ctx->arith == AFFNET_ARITH_FP32_SPLIT2H;
-    const bool split = ctx->arith == AFFNET_ARITH_FP32_SPLIT3 || h2;
-    a.off = to_offsets(L, ctx->arith);                                   // the split copy of the active mode
-    // trunk instantiation [net kind][exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see above)
+    // trunk instantiation [net kind][exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see cnn_check)
     static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk table order");
     static void (*const trunks[3][3][2])(CnnArgs, PyrSrc) = {
         {{cnn32_trunk_kernel<0, 8, false>, cnn32_trunk_kernel<0, 8, true>}, {cnn32_trunk_kernel<0, 8, false, 3>, cnn32_trunk_kernel<0, 8, true, 3>},
@@ -1390,48 +1402,68 @@ static int cnn_launch(affnet_ctx* ctx, int kind, const float* packed, const floa
          {cnn32_trunk_kernel<1, 8, false, 2>, cnn32_trunk_kernel<1, 8, true, 2>}},
         {{cnn32_trunk_kernel<2, 8, false>, cnn32_trunk_kernel<2, 8, true>}, {cnn32_trunk_kernel<2, 8, false, 3>, cnn32_trunk_kernel<2, 8, true, 3>},
          {cnn32_trunk_kernel<2, 8, false, 2>, cnn32_trunk_kernel<2, 8, true, 2>}}};
-    hipLaunchKernelGGL(trunks[kind][h2 ? 2 : (split ? 1 : 0)][a.dbg_time || dbg_layer >= 0], grid, dim3(512), 0, st, a, ps);
+    hipLaunchKernelGGL(trunks[c.kind][arith_index(ctx)][a.dbg_time || c.dbg_layer >= 0], grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
-    if (kind != AFFNET_NET_HARDNET && dbg_layer < 0) {       // combine the per-wave head partials in `scratch`
-        if (kind == AFFNET_NET_AFFNET) {
-            ShapeFuse sf;
-            memset(&sf, 0, sizeof(sf));
-            if (fuse) sf = *fuse;
-            hipLaunchKernelGGL(affnet_finish_kernel, dim3(aff_cdiv(row_count, 256), B), dim3(256), 0, st, scratch, packed + L.head_b, count, n_max, out,
-                               row_begin, row_begin + row_count, skip_cnt, skip_n, sf);
-        } else {
-            DenormSel ds;
-            memset(&ds, 0, sizeof(ds));
-            if (denorm && rot_lafs) ds = *denorm;
-            hipLaunchKernelGGL(orinet_finish_kernel, dim3(aff_cdiv(row_count, 4), B), dim3(256), 0, st, scratch, packed + L.head_b, count, n_max, out,
-                               row_begin, row_begin + row_count, rot_lafs, ds);
-        }
-        AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// AffNet / OriNet: combine the per-wave head partials in `scratch` (rows of the window)
+static int finish_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B) {
+    ShapeFuse sf;
+    memset(&sf, 0, sizeof(sf));
+    if (c.fuse) sf = *c.fuse;
+    hipLaunchKernelGGL(affnet_finish_kernel, dim3(aff_cdiv(rows, 256), B), dim3(256), 0, c.st, c.scratch, c.packed + L.head_b, c.count, c.n_max, c.out,
+                       c.row_begin, c.row_begin + rows, c.skip_cnt, c.skip_n, sf);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+static int finish_orinet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B) {
+    DenormSel ds;
+    memset(&ds, 0, sizeof(ds));
+    if (c.denorm && c.rot_lafs) ds = *c.denorm;
+    hipLaunchKernelGGL(orinet_finish_kernel, dim3(aff_cdiv(rows, 4), B), dim3(256), 0, c.st, c.scratch, c.packed + L.head_b, c.count, c.n_max, c.out,
+                       c.row_begin, c.row_begin + rows, c.rot_lafs, ds);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// HardNet: head GEMM over all rows of the trunk output in `scratch` + finish kernel
+static int hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int B) {
+    const int n_max = c.n_max;
+    float* partial = c.scratch + (size_t)B * n_max * HEAD_K;   // [HEAD_KSPLIT][B * n_max][128] behind the trunk output
+    // patches per workgroup: the 64-patch shape once it gives every CU a workgroup, else 32 / 16 (same sums, more workgroups)
+    int mp = (aff_cdiv(n_max, 64) * HEAD_KSPLIT * B >= 256) ? 64 : ((aff_cdiv(n_max, 32) * HEAD_KSPLIT * B >= 256) ? 32 : 16);
+    if (const char* e = getenv("AFFNET_HEAD_MP")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) mp = v; }   // tuning aid
+    // head instantiation [exact, three bf16 terms, two fp16 terms][MP 64, 32, 16]; the split modes run the head GEMM on split operands as well
+    static void (*const heads[3][3])(const float*, const float*, const int32_t*, int, float*) = {
+        {hardnet_head_kernel<64>, hardnet_head_kernel<32>, hardnet_head_kernel<16>},
+        {hardnet_head_s3_kernel<64, 3>, hardnet_head_s3_kernel<32, 3>, hardnet_head_s3_kernel<16, 3>},
+        {hardnet_head_s3_kernel<64, 2>, hardnet_head_s3_kernel<32, 2>, hardnet_head_s3_kernel<16, 2>}};
+    const int ai = arith_index(ctx);
+    const float* hw = c.packed + (ai == 2 ? L.head_h2 : (ai == 1 ? L.head_s3 : L.head_w));
+    hipLaunchKernelGGL(heads[ai][mp == 64 ? 0 : (mp == 32 ? 1 : 2)], dim3(aff_cdiv(n_max, mp), HEAD_KSPLIT, B), dim3(256), 0, c.st, c.scratch, hw, c.count,
+                       n_max, partial);
+    AFF_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(hardnet_finish_kernel, dim3(aff_cdiv(n_max, 4), B), dim3(256), 0, c.st, partial, c.packed + L.head_b, c.count, n_max, c.out);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+static int cnn_launch(affnet_ctx* ctx, const CnnCall& c) {
+    int rows;
+    int rc = cnn_check(ctx, c, &rows);
+    if (rc || rows == 0) return rc;
+    const NetLayout L = net_layout(c.kind);
+    const int B = c.patches ? 1 : ctx->B;                // patch tensors are single-"image"; pyramid sampling covers the batch
+    rc = trunk_launch(ctx, c, L, dim3(rows, B));
+    if (rc) return rc;
+    if (c.dbg_layer < 0 && c.kind != AFFNET_NET_HARDNET) {
+        rc = c.kind == AFFNET_NET_AFFNET ? finish_affnet(ctx, c, L, rows, B) : finish_orinet(ctx, c, L, rows, B);
+        if (rc) return rc;
     }
-    if (mark_head) aff_prof_mark(ctx, 7, st);
-    if (kind == AFFNET_NET_HARDNET && dbg_layer < 0) {
-        float* partial = scratch + (size_t)B * n_max * HEAD_K;   // [HEAD_KSPLIT][B * n_max][128] behind the trunk output
-        // patches per workgroup: the 64-patch shape once it gives every CU a workgroup, else 32 / 16 (same sums, more workgroups)
-        int mp = (aff_cdiv(n_max, 64) * HEAD_KSPLIT * B >= 256) ? 64 : ((aff_cdiv(n_max, 32) * HEAD_KSPLIT * B >= 256) ? 32 : 16);
-        if (const char* e = getenv("AFFNET_HEAD_MP")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) mp = v; }   // tuning aid
-        if (split) {              // AFFNET_ARITH_FP32_SPLIT3 / _SPLIT2H: the head GEMM on split operands as well
-            const float* hw = packed + (h2 ? L.head_h2 : L.head_s3);
-#define HEAD_LAUNCH(MPV) do { if (h2) hipLaunchKernelGGL((hardnet_head_s3_kernel<MPV, 2>), dim3(aff_cdiv(n_max, MPV), HEAD_KSPLIT, B), dim3(256), 0, st, scratch, hw, count, n_max, partial); \
-                              else hipLaunchKernelGGL((hardnet_head_s3_kernel<MPV, 3>), dim3(aff_cdiv(n_max, MPV), HEAD_KSPLIT, B), dim3(256), 0, st, scratch, hw, count, n_max, partial); } while (0)
-            if (mp == 64) HEAD_LAUNCH(64);
-            else if (mp == 32) HEAD_LAUNCH(32);
-            else HEAD_LAUNCH(16);
-#undef HEAD_LAUNCH
-        } else if (mp == 64)
-            hipLaunchKernelGGL(hardnet_head_kernel<64>, dim3(aff_cdiv(n_max, 64), HEAD_KSPLIT, B), dim3(256), 0, st, scratch, packed + L.head_w, count, n_max, partial);
-        else if (mp == 32)
-            hipLaunchKernelGGL(hardnet_head_kernel<32>, dim3(aff_cdiv(n_max, 32), HEAD_KSPLIT, B), dim3(256), 0, st, scratch, packed + L.head_w, count, n_max, partial);
-        else
-            hipLaunchKernelGGL(hardnet_head_kernel<16>, dim3(aff_cdiv(n_max, 16), HEAD_KSPLIT, B), dim3(256), 0, st, scratch, packed + L.head_w, count, n_max, partial);
-        AFF_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(hardnet_finish_kernel, dim3(aff_cdiv(n_max, 4), B), dim3(256), 0, st, partial, packed + L.head_b, count, n_max, out);
-        AFF_LAUNCH_CHECK(ctx);
-    }
+    if (c.mark_head) aff_prof_mark(ctx, 7, c.st);
+    if (c.dbg_layer < 0 && c.kind == AFFNET_NET_HARDNET) return hardnet_head(ctx, c, L, B);
     return AFFNET_OK;
 }
 
@@ -1439,31 +1471,33 @@ extern "C" int affnet_cnn32_forward(affnet_ctx* ctx, int net_kind, const float* 
                                     int n_max, float* d_out, float* d_scratch, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !d_patches) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_forward: null argument");
-    return cnn_launch(ctx, net_kind, d_packed, d_patches, nullptr, nullptr, d_count, n_max, d_out, d_scratch, -1, nullptr, (hipStream_t)stream);
+    CnnCall c;
+    c.kind = net_kind; c.packed = d_packed; c.patches = d_patches; c.count = d_count; c.n_max = n_max; c.out = d_out; c.scratch = d_scratch; c.st = (hipStream_t)stream;
+    return cnn_launch(ctx, c);
 }
 
 extern "C" int affnet_cnn32_forward_pyr(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_lafs, const int32_t* d_ids,
                                         const int32_t* d_count, int n_max, float* d_out, float* d_scratch, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx) return AFFNET_ERR_INVALID;
-    return cnn_launch(ctx, net_kind, d_packed, nullptr, d_lafs, d_ids, d_count, n_max, d_out, d_scratch, -1, nullptr, (hipStream_t)stream);
-}
-
-// Rows [row_begin, row_begin + row_count) of every image only, optionally under the lazy-evaluation predicate (see CnnArgs).
-int aff_cnn_forward_pyr_rows(affnet_ctx* ctx, int kind, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count, int n_max,
-                             float* out, float* scratch, int row_begin, int row_count, const int32_t* skip_cnt, int skip_n, hipStream_t st) {
-    if (kind == AFFNET_NET_HARDNET) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: row windows are for the AffNet / OriNet trunks");
-    return cnn_launch(ctx, kind, packed, nullptr, lafs, ids, count, n_max, out, scratch, -1, nullptr, st, false, row_begin, row_count, skip_cnt, skip_n);
+    CnnCall c;
+    c.kind = net_kind; c.packed = d_packed; c.lafs = d_lafs; c.ids = d_ids; c.count = d_count; c.n_max = n_max; c.out = d_out; c.scratch = d_scratch; c.st = (hipStream_t)stream;
+    return cnn_launch(ctx, c);
 }
 
 // AffNet on a row window with the shape filter of every evaluated row fused into the finish kernel (key / good / survivor count in
-// the context's stage buffers) and the shape-stage counter bookkeeping done by the trunk launch (shape_op: see CnnArgs).
+// the context's stage buffers) and the shape-stage counter bookkeeping done by the trunk launch (shape_op: see CnnArgs); lazy = under
+// the lazy-evaluation predicate.
 int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,
                            float* out, float* scratch, int row_begin, int row_count, bool lazy, int shape_op, hipStream_t st) {
     ShapeFuse sf;
     sf.resp = resp; sf.lafs = lafs; sf.key = ctx->st_key; sf.good = ctx->st_good; sf.cnt = ctx->cnt;
-    return cnn_launch(ctx, AFFNET_NET_AFFNET, packed, nullptr, lafs, ids, count, ctx->cap_pre, out, scratch, -1, nullptr, st, false, row_begin, row_count,
-                      lazy ? ctx->cnt : nullptr, ctx->cfg.num_features, &sf, shape_op);
+    CnnCall c;
+    c.kind = AFFNET_NET_AFFNET; c.packed = packed; c.lafs = lafs; c.ids = ids; c.count = count; c.n_max = ctx->cap_pre; c.out = out; c.scratch = scratch; c.st = st;
+    c.row_begin = row_begin; c.row_count = row_count;
+    c.skip_cnt = lazy ? ctx->cnt : nullptr; c.skip_n = ctx->cfg.num_features;
+    c.fuse = &sf; c.shape_op = shape_op;
+    return cnn_launch(ctx, c);
 }
 
 // OriNet with LAF <- LAF * R applied by the finish kernel (d_lafs rotated in place).
@@ -1471,13 +1505,18 @@ int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* re
 // work, one launch less per call).
 int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const int32_t* ids, const int32_t* count, int n_max, float* out, float* scratch,
                       hipStream_t st, const DenormSel* denorm) {
-    return cnn_launch(ctx, AFFNET_NET_ORINET, packed, nullptr, lafs, ids, count, n_max, out, scratch, -1, nullptr, st, false, 0, -1, nullptr, 0, nullptr, 0,
-                      lafs, denorm);
+    CnnCall c;
+    c.kind = AFFNET_NET_ORINET; c.packed = packed; c.lafs = lafs; c.ids = ids; c.count = count; c.n_max = n_max; c.out = out; c.scratch = scratch; c.st = st;
+    c.rot_lafs = lafs; c.denorm = denorm;
+    return cnn_launch(ctx, c);
 }
 
 int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
                                    int n_max, float* out, float* scratch, hipStream_t st) {
-    return cnn_launch(ctx, AFFNET_NET_HARDNET, packed, nullptr, lafs, ids, count, n_max, out, scratch, -1, nullptr, st, true);
+    CnnCall c;
+    c.kind = AFFNET_NET_HARDNET; c.packed = packed; c.lafs = lafs; c.ids = ids; c.count = count; c.n_max = n_max; c.out = out; c.scratch = scratch; c.st = st;
+    c.mark_head = true;
+    return cnn_launch(ctx, c);
 }
 
 extern "C" int affnet_debug_split3_variant(affnet_ctx* ctx, int bits) {
@@ -1496,7 +1535,10 @@ extern "C" int affnet_cnn32_debug_layer(affnet_ctx* ctx, int net_kind, const flo
                                         void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !d_patch || !d_out || layer < 0 || layer > 5) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_debug_layer: bad argument");
-    return cnn_launch(ctx, net_kind, d_packed, d_patch, nullptr, nullptr, nullptr, 1, d_out, nullptr, layer, d_out, (hipStream_t)stream);
+    CnnCall c;
+    c.kind = net_kind; c.packed = d_packed; c.patches = d_patch; c.n_max = 1; c.out = d_out; c.st = (hipStream_t)stream;
+    c.dbg_layer = layer; c.dbg_out = d_out;
+    return cnn_launch(ctx, c);
 }
 
 #ifdef AFFNET_PROBES   // libaffnet_hip_probes.so only (include/affnet_hip_probes.h)

@@ -142,10 +142,6 @@ struct AffDeviceGuard {
 
 #define PROF_RING 256
 #define PROF_EVENTS (AFFNET_PROFILE_STAGES + 2)   // 9 stage boundaries + end-of-detector (index 9)
-// pipeline.hip / cnn32.hip: record stage boundary `idx` of the current call (no-op when disabled)
-void aff_prof_mark(affnet_ctx* ctx, int idx, hipStream_t st);
-
-int aff_fail(affnet_ctx* ctx, int code, const char* fmt, ...);
 
 #define AFF_HIP(ctx, expr)                                                                         \
     do {                                                                                           \
@@ -163,11 +159,7 @@ int aff_fail(affnet_ctx* ctx, int code, const char* fmt, ...);
                             hipGetErrorString(e_), __FILE__, __LINE__);                            \
     } while (0)
 
-// Device-side fills and copies as plain kernels of this library (context.hip) instead of hipMemsetAsync / hipMemcpyAsync: the
-// runtime's blit path shares per-queue state with captured graph nodes (replaying a captured graph after eager null-stream
-// memsets faulted on ROCm 7.2), and a kernel of our own is also what a stream capture records most cheaply.
-int aff_zero_async(affnet_ctx* ctx, void* dst, size_t bytes, hipStream_t st);
-// up to 8 fills in one launch
+// up to 8 device-side fills in one launch (aff_zero_multi_async)
 struct AffZeroSegs {
     unsigned char* p[8];
     size_t bytes[8];
@@ -179,10 +171,6 @@ struct AffZeroSegs {
         p[n] = (unsigned char*)ptr; bytes[n] = nbytes; ++n;
     }
 };
-int aff_zero_multi_async(affnet_ctx* ctx, const AffZeroSegs& z, hipStream_t st);
-int aff_copy_async(affnet_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st);
-// rows x width_bytes, row r at dst + r * dpitch / src + r * spitch (all multiples of 4 bytes)
-int aff_copy2d_async(affnet_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows, hipStream_t st);
 
 static inline size_t aff_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int aff_cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -194,14 +182,68 @@ struct PyrTable {
     int n_octaves, n_levels;
     size_t img_stride;
 };
-void aff_fill_pyr_table(const affnet_ctx* ctx, PyrTable* t);
 
-// ---- sampler math shared by sampler.hip and cnn32.hip -------------------------------------------
-// Host: fills base[ps] = (linspace(-1,1,ps) * (ps-1)) / ps exactly as torch does on CPU
-// (linspace = fma(step, i, start) / fma(-step, ps-1-i, end); verified bit-for-bit in
-// tests/test_host_mirror.py).
+// Constants of the denormalisation + pyramid-level choice of one row (device helpers: shape_filter.h); filled by aff_denorm_sel_fill
+struct LevelTable { double sig[AFFNET_MAX_OCTAVES * AFFNET_MAX_LEVELS]; int n_oct, n_lvl; };
+struct DenormSel {           // per-launch constants + outputs (pointers of image 0, rows of image b at b * n_max); out_px == NULL: not fused
+    float* out_px; int32_t* ids; float* lafs_norm;
+    float c_a, c_x, c_y, ps, ca, cx, cy;
+    LevelTable lt;
+};
+
+// ---- internal interface: every function that crosses a file boundary -----------------------------------------------------
+// Each non-static aff_* function of the library is declared HERE, once, under the file that defines it.  The .hip files carry no
+// declarations of their own, so a definition and its callers are compiled against the same prototype.  No default arguments.
+
+// context.hip
+int aff_fail(affnet_ctx* ctx, int code, const char* fmt, ...);
+// Device-side fills and copies as plain kernels of this library instead of hipMemsetAsync / hipMemcpyAsync: the runtime's blit
+// path shares per-queue state with captured graph nodes (replaying a captured graph after eager null-stream memsets faulted on
+// ROCm 7.2), and a kernel of our own is also what a stream capture records most cheaply.
+int aff_zero_async(affnet_ctx* ctx, void* dst, size_t bytes, hipStream_t st);
+int aff_zero_multi_async(affnet_ctx* ctx, const AffZeroSegs& z, hipStream_t st);
+int aff_copy_async(affnet_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st);
+// rows x width_bytes, row r at dst + r * dpitch / src + r * spitch (all multiples of 4 bytes)
+int aff_copy2d_async(affnet_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, size_t rows, hipStream_t st);
+// base[ps] = (linspace(-1,1,ps) * (ps-1)) / ps exactly as torch does on CPU (linspace = fma(step, i, start) /
+// fma(-step, ps-1-i, end); verified bit-for-bit in tests/test_host_mirror.py)
 void aff_base_grid(int ps, float* base);
 
+// pipeline.hip: record stage boundary `idx` of the current call (no-op when disabled)
+void aff_prof_mark(affnet_ctx* ctx, int idx, hipStream_t st);
+
+// detect.hip: the two detector halves; candidates of the one-pass form go to the context's internal detection list
+int aff_detect_impl(affnet_ctx* ctx, const float* d_responses, float* d_resp, float* d_lafs, int32_t* d_ids, int32_t* d_count, void* stream);
+int aff_detect_onepass_impl(affnet_ctx* ctx, const float* d_packed_fullconv, const float* d_responses, hipStream_t st);
+
+// fullconv.hip: dense AffNetFastFullConv maps of B images of one size
+int aff_fullconv_launch(affnet_ctx* ctx, const float* packed, const float* img, size_t img_stride, int h, int w, float* out, size_t out_stride,
+                        float* scratch, size_t scratch_stride, int B, hipStream_t st);
+
+// handcrafted.hip: hand-crafted slot fillers (AFFNET_HC_*)
+int aff_handcrafted_launch(affnet_ctx* ctx, int kind, const float* patches, const float* lafs, const int32_t* ids, const int32_t* count,
+                           int n_max, const float* h_weights, float* out, float* out_angle, hipStream_t st);
+
+// laf_ops.hip: pyramid table of the samplers, selection of the shape stage, AffNet iterations > 1, denormalisation + level choice
+void aff_fill_pyr_table(const affnet_ctx* ctx, PyrTable* t);
+int aff_shape_select(affnet_ctx* ctx, const float* d_resp_in, const float* d_lafs_in, const int32_t* d_ids_in, const float* d_A,
+                     const int32_t* d_count_in, float* d_resp_out, float* d_lafs_out, int32_t* d_ids_out, int32_t* d_count_out, hipStream_t st);
+int aff_shape_iterate(affnet_ctx* ctx, const float* A, float* base, const float* lafs, const int32_t* count, int mode, float* lafs_out,
+                      hipStream_t st);
+void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_ids, float* d_lafs_norm, DenormSel* ds);
+int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
+                            float* d_lafs_norm, hipStream_t st);
+
+// cnn32.hip: the fused launches of affnet_describe_detected (AffNet + shape filter on a row window, OriNet + rotation, HardNet with
+// the stage mark between trunk and head)
+int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,
+                           float* out, float* scratch, int row_begin, int row_count, bool lazy, int shape_op, hipStream_t st);
+int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const int32_t* ids, const int32_t* count, int n_max, float* out, float* scratch,
+                      hipStream_t st, const DenormSel* denorm);
+int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
+                                   int n_max, float* out, float* scratch, hipStream_t st);
+
+// ---- sampler math shared by laf_ops.hip, handcrafted.hip and cnn32.hip ----------------------------
 // LDS-staged footprint of one patch (north_star: "coalesced HBM reads and LDS-staged image tiles"): the affine frame of a PS x PS
 // patch covers an axis-aligned box of the level image; when that box is small its rows are loaded once with coalesced row-segment
 // loads (zeros outside the image = grid_sample's zero padding) and the four bilinear taps of every sample come from LDS.  The

@@ -1176,9 +1176,6 @@ int aff_detect_impl(affnet_ctx* ctx, const float* d_responses, float* d_resp, fl
     return AFFNET_OK;
 }
 
-int aff_fullconv_launch(affnet_ctx* ctx, const float* packed, const float* img, size_t img_stride, int h, int w, float* out, size_t out_stride,
-                        float* scratch, size_t scratch_stride, int B, hipStream_t st);
-
 // OnePassSIR.multiScaleDetectorAff (OnePassSIR.py:53-115) on the pyramid in the workspace.  d_packed_fullconv != NULL: the dense
 // AffNetFastFullConv maps of every octave are computed here (level 0 of each octave, OnePassSIR.py:69); NULL: the caller has written
 // them into the workspace (affnet_affmap_offset) - the slot form for a foreign dense AffNet.  Results go to the context's internal

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void shape_filter_kernel(const float* __restri
     bool skip = false;
     if (skip_cnt) {
         const int32_t* c = skip_cnt + (size_t)blockIdx.y * CNT_TOTAL;
-        skip = c[CNT_SEL_MODE] == 1 && c[CNT_SURVIVED1] >= skip_n;      // frozen after the first pass (shape_freeze_kernel)
+        skip = c[CNT_SEL_MODE] == 1 && c[CNT_SURVIVED1] >= skip_n;      // frozen by the second AffNet trunk launch (cnn32.hip, shape_op == 2)
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) cnt[CNT_AFF_EVAL] = skip ? min(n, row_begin) : min(n, row_end);
     if (skip || i >= row_end || i >= n) return;
@@ -222,42 +222,9 @@ __global__ __launch_bounds__(1024) void shape_select_kernel(const float* __restr
     }
 }
 
-__global__ void shape_freeze_kernel(int32_t* cnt) {        // survivors of the first pass, read by the second pass's predicates
-    cnt += blockIdx.x * CNT_TOTAL;
-    cnt[CNT_SURVIVED1] = cnt[CNT_SURVIVED];
-}
-
 __global__ void shape_begin_kernel(int32_t* cnt) {
     cnt += blockIdx.x * CNT_TOTAL;
     cnt[CNT_SURVIVED] = 0; cnt[CNT_SURVIVED1] = 0; cnt[CNT_AFF_EVAL] = 0;
-}
-
-// The shape stage in three steps, so that the fused pipeline can evaluate the shape CNN lazily (pipeline.hip):
-//   begin  : key / good of every row = 0 ("not evaluated, not good"), survivor counters = 0
-//   rows   : filter rows [row_begin, row_end) of every image (optionally under the lazy predicate), counting survivors;
-//            freeze = true publishes the survivor count for the predicates of a following pass
-//   select : top-N / compaction of the good rows -> outputs
-int aff_shape_filter_begin(affnet_ctx* ctx, hipStream_t st) {
-    const size_t P = (size_t)ctx->B * ctx->cap_pre;
-    int rc = aff_zero_async(ctx, ctx->st_key, P * 2 * sizeof(float), st);        // st_key and st_good are adjacent (context.hip)
-    if (rc) return rc;
-    hipLaunchKernelGGL(shape_begin_kernel, dim3(ctx->B), dim3(1), 0, st, ctx->cnt);
-    AFF_LAUNCH_CHECK(ctx);
-    return AFFNET_OK;
-}
-
-int aff_shape_filter_rows(affnet_ctx* ctx, const float* resp, const float* lafs, const float* A, const int32_t* count, int row_begin, int row_end,
-                          bool lazy, hipStream_t st, bool freeze = false) {
-    if (row_end > row_begin) {
-        hipLaunchKernelGGL(shape_filter_kernel, dim3(aff_cdiv(row_end - row_begin, 256), ctx->B), dim3(256), 0, st, resp, lafs, A, count, ctx->cap_pre,
-                           ctx->st_key, ctx->st_good, row_begin, row_end, ctx->cnt, lazy ? ctx->cnt : nullptr, ctx->cfg.num_features);
-        AFF_LAUNCH_CHECK(ctx);
-    }
-    if (freeze) {
-        hipLaunchKernelGGL(shape_freeze_kernel, dim3(ctx->B), dim3(1), 0, st, ctx->cnt);
-        AFF_LAUNCH_CHECK(ctx);
-    }
-    return AFFNET_OK;
 }
 
 int aff_shape_select(affnet_ctx* ctx, const float* d_resp_in, const float* d_lafs_in, const int32_t* d_ids_in, const float* d_A,
@@ -276,10 +243,19 @@ extern "C" int affnet_shape_filter_select(affnet_ctx* ctx, const float* d_resp_i
         !d_count_out)
         return aff_fail(ctx, AFFNET_ERR_INVALID, "shape_filter_select: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    int rc = aff_shape_filter_begin(ctx, st);
+    // begin: key / good of every row = 0 ("not evaluated, not good"), survivor counters = 0
+    int rc = aff_zero_async(ctx, ctx->st_key, (size_t)ctx->B * ctx->cap_pre * 2 * sizeof(float), st);   // st_key and st_good are adjacent (context.hip)
     if (rc) return rc;
-    rc = aff_shape_filter_rows(ctx, d_resp_in, d_lafs_in, d_A, d_count_in, 0, ctx->cap_pre, false, st);
-    if (rc) return rc;
+    hipLaunchKernelGGL(shape_begin_kernel, dim3(ctx->B), dim3(1), 0, st, ctx->cnt);
+    AFF_LAUNCH_CHECK(ctx);
+    // rows: filter every row of every image, counting survivors (the lazy path of affnet_describe_detected does these two steps inside its
+    // AffNet launches - cnn32.hip, aff_affnet_filter_rows - and calls only the selection)
+    if (ctx->cap_pre > 0) {
+        hipLaunchKernelGGL(shape_filter_kernel, dim3(aff_cdiv(ctx->cap_pre, 256), ctx->B), dim3(256), 0, st, d_resp_in, d_lafs_in, d_A, d_count_in, ctx->cap_pre,
+                           ctx->st_key, ctx->st_good, 0, ctx->cap_pre, ctx->cnt, (const int32_t*)nullptr, ctx->cfg.num_features);
+        AFF_LAUNCH_CHECK(ctx);
+    }
+    // select: top-N / compaction of the good rows -> outputs
     return aff_shape_select(ctx, d_resp_in, d_lafs_in, d_ids_in, d_A, d_count_in, d_resp_out, d_lafs_out, d_ids_out, d_count_out, st);
 }
 
@@ -425,14 +401,10 @@ void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_i
 int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
                             float* d_lafs_norm, hipStream_t st) {
     if (n_max == 0) return AFFNET_OK;
-    LevelTable lt;
-    const affnet_config& c = ctx->cfg;
-    lt.n_oct = c.n_octaves; lt.n_lvl = c.levels_per_octave;
-    for (int o = 0; o < lt.n_oct; ++o)
-        for (int l = 0; l < lt.n_lvl; ++l) lt.sig[o * lt.n_lvl + l] = c.level_sigma_px[o][l];
-    const float fw = (float)c.width, fh = (float)c.height, m = fw < fh ? fw : fh;
-    hipLaunchKernelGGL(denorm_level_select_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, st, d_lafs_norm_in, d_lafs_px, d_count, n_max, m, fw,
-                       fh, (float)ps, lt, 1.0f / m, (float)(1.0 / (double)fw), (float)(1.0 / (double)fh), d_ids, d_lafs_norm);
+    DenormSel ds;
+    aff_denorm_sel_fill(ctx, ps, d_lafs_px, d_ids, d_lafs_norm, &ds);
+    hipLaunchKernelGGL(denorm_level_select_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, st, d_lafs_norm_in, d_lafs_px, d_count, n_max, ds.c_a,
+                       ds.c_x, ds.c_y, ds.ps, ds.lt, ds.ca, ds.cx, ds.cy, d_ids, d_lafs_norm);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -442,14 +414,10 @@ extern "C" int affnet_level_select(affnet_ctx* ctx, const float* d_lafs_px, cons
     AFF_DEVICE(ctx);
     if (!ctx || !d_lafs_px || !d_ids || !d_lafs_norm || n_max < 0 || ps < 1) return aff_fail(ctx, AFFNET_ERR_INVALID, "level_select: bad argument");
     if (n_max == 0) return AFFNET_OK;
-    LevelTable lt;
-    const affnet_config& c = ctx->cfg;
-    lt.n_oct = c.n_octaves; lt.n_lvl = c.levels_per_octave;
-    for (int o = 0; o < lt.n_oct; ++o)
-        for (int l = 0; l < lt.n_lvl; ++l) lt.sig[o * lt.n_lvl + l] = c.level_sigma_px[o][l];
-    const float fw = (float)c.width, fh = (float)c.height, m = fw < fh ? fw : fh;
-    hipLaunchKernelGGL(level_select_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, (hipStream_t)stream, d_lafs_px, d_count, n_max,
-                       (float)ps, lt, 1.0f / m, (float)(1.0 / (double)fw), (float)(1.0 / (double)fh), d_ids, d_lafs_norm);
+    DenormSel ds;                                     // its level table and re-normalisation constants; nothing is denormalised here
+    aff_denorm_sel_fill(ctx, ps, nullptr, d_ids, d_lafs_norm, &ds);
+    hipLaunchKernelGGL(level_select_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, (hipStream_t)stream, d_lafs_px, d_count, n_max, ds.ps,
+                       ds.lt, ds.ca, ds.cx, ds.cy, d_ids, d_lafs_norm);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

@@ -9,7 +9,6 @@
 // num_survived (SparseImgRepresenter.py:151) and round-trips LAF scales through scipy on the
 // host (LAF.py:466).  The reference's discarded extra patch extraction (:178-179) is dropped.
 #include "common.h"
-#include "shape_filter.h"
 
 void aff_prof_mark(affnet_ctx* ctx, int idx, hipStream_t st) {
     if (!ctx->prof_on || ctx->prof_calls >= PROF_RING) return;
@@ -44,68 +43,37 @@ extern "C" int affnet_profile_read(affnet_ctx* ctx, double sum_ms[AFFNET_PROFILE
     return AFFNET_OK;
 }
 
-// AffNet iterations > 1 (laf_ops.hip)
-int aff_shape_iterate(affnet_ctx* ctx, const float* A, float* base, const float* lafs, const int32_t* count, int mode, float* lafs_out,
-                      hipStream_t st);
-
-// hand-crafted slot fillers (handcrafted.hip)
-int aff_handcrafted_launch(affnet_ctx* ctx, int kind, const float* patches, const float* lafs, const int32_t* ids, const int32_t* count,
-                           int n_max, const float* h_weights, float* out, float* out_angle, hipStream_t st);
-
-// HardNet with a stage mark between trunk and head (cnn32.hip)
-int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
-                                   int n_max, float* out, float* scratch, hipStream_t st);
-
-// shape stage in steps + row-windowed CNN launches (laf_ops.hip / cnn32.hip): lazy evaluation of the shape CNN
-int aff_shape_filter_begin(affnet_ctx* ctx, hipStream_t st);
-int aff_shape_filter_rows(affnet_ctx* ctx, const float* resp, const float* lafs, const float* A, const int32_t* count, int row_begin, int row_end,
-                          bool lazy, hipStream_t st, bool freeze = false);
-int aff_shape_select(affnet_ctx* ctx, const float* d_resp_in, const float* d_lafs_in, const int32_t* d_ids_in, const float* d_A,
-                     const int32_t* d_count_in, float* d_resp_out, float* d_lafs_out, int32_t* d_ids_out, int32_t* d_count_out, hipStream_t st);
-int aff_cnn_forward_pyr_rows(affnet_ctx* ctx, int kind, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count, int n_max,
-                             float* out, float* scratch, int row_begin, int row_count, const int32_t* skip_cnt, int skip_n, hipStream_t st);
-
-// fused launches of the one-image-per-call latency path (cnn32.hip / laf_ops.hip)
-int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,
-                           float* out, float* scratch, int row_begin, int row_count, bool lazy, int shape_op, hipStream_t st);
-int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const int32_t* ids, const int32_t* count, int n_max, float* out, float* scratch,
-                      hipStream_t st, const DenormSel* denorm);
-void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_ids, float* d_lafs_norm, DenormSel* ds);
-int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
-                            float* d_lafs_norm, hipStream_t st);
-
-int aff_detect_impl(affnet_ctx* ctx, const float* d_responses, float* d_resp, float* d_lafs, int32_t* d_ids, int32_t* d_count, void* stream);
-
-// Detector half for a custom RespNet slot: the caller has built the pyramid (affnet_pyramid_build), evaluated its RespNet on
-// every level and hands over the response pyramid; candidates go to the context's internal list for
-// affnet_describe_detected.
-extern "C" int affnet_detect_image_responses(affnet_ctx* ctx, const float* d_responses, void* stream) {
-    AFF_DEVICE(ctx);
-    if (!ctx || !ctx->ws || !d_responses) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect_image_responses: context not bound or null responses");
+// Common frame of the four detector-half entry points below: stage marks 0 / 1 around the pyramid build (d_img == NULL: the caller
+// has built it), the detector (classic or OnePassSIR; d_responses == NULL: Hessian responses computed here), mark 9.  Candidates
+// go to the context's internal list for affnet_describe_detected.
+static int detect_half(affnet_ctx* ctx, const float* d_img, bool onepass, const float* d_packed_fullconv, const float* d_responses, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     aff_prof_mark(ctx, 0, st);
+    if (d_img) {
+        int rc = affnet_pyramid_build(ctx, d_img, stream);
+        if (rc) return rc;
+    }
     aff_prof_mark(ctx, 1, st);
-    int rc = aff_detect_impl(ctx, d_responses, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->st_det_count, stream);
+    int rc = onepass ? aff_detect_onepass_impl(ctx, d_packed_fullconv, d_responses, st)
+                     : aff_detect_impl(ctx, d_responses, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->st_det_count, stream);
     if (rc) return rc;
     aff_prof_mark(ctx, 9, st);
     return AFFNET_OK;
+}
+
+// Detector half for a custom RespNet slot: the caller has built the pyramid (affnet_pyramid_build), evaluated its RespNet on
+// every level and hands over the response pyramid.
+extern "C" int affnet_detect_image_responses(affnet_ctx* ctx, const float* d_responses, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !ctx->ws || !d_responses) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect_image_responses: context not bound or null responses");
+    return detect_half(ctx, nullptr, false, nullptr, d_responses, stream);
 }
 
 extern "C" int affnet_detect_image(affnet_ctx* ctx, const float* d_img, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !ctx->ws || !d_img) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect_image: context not bound or null image");
-    hipStream_t st = (hipStream_t)stream;
-    aff_prof_mark(ctx, 0, st);
-    int rc = affnet_pyramid_build(ctx, d_img, stream);
-    if (rc) return rc;
-    aff_prof_mark(ctx, 1, st);
-    rc = affnet_detect(ctx, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->st_det_count, stream);
-    if (rc) return rc;
-    aff_prof_mark(ctx, 9, st);
-    return AFFNET_OK;
+    return detect_half(ctx, d_img, false, nullptr, nullptr, stream);
 }
-
-int aff_detect_onepass_impl(affnet_ctx* ctx, const float* d_packed_fullconv, const float* d_responses, hipStream_t st);
 
 // OnePassSIR detector half (OnePassSIR.py:53-115,146): pyramid (when d_img != NULL; NULL = already built with
 // affnet_pyramid_build), dense AffNetFastFullConv map per octave (when d_packed_fullconv != NULL; NULL = the caller wrote the maps
@@ -115,29 +83,13 @@ int aff_detect_onepass_impl(affnet_ctx* ctx, const float* d_packed_fullconv, con
 extern "C" int affnet_detect_image_onepass(affnet_ctx* ctx, const float* d_packed_fullconv, const float* d_img, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !ctx->ws) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect_image_onepass: context not bound");
-    hipStream_t st = (hipStream_t)stream;
-    aff_prof_mark(ctx, 0, st);
-    if (d_img) {
-        int rc = affnet_pyramid_build(ctx, d_img, stream);
-        if (rc) return rc;
-    }
-    aff_prof_mark(ctx, 1, st);
-    int rc = aff_detect_onepass_impl(ctx, d_packed_fullconv, nullptr, st);
-    if (rc) return rc;
-    aff_prof_mark(ctx, 9, st);
-    return AFFNET_OK;
+    return detect_half(ctx, d_img, true, d_packed_fullconv, nullptr, stream);
 }
 
 extern "C" int affnet_detect_image_onepass_responses(affnet_ctx* ctx, const float* d_packed_fullconv, const float* d_responses, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !ctx->ws || !d_responses) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect_image_onepass_responses: context not bound or null responses");
-    hipStream_t st = (hipStream_t)stream;
-    aff_prof_mark(ctx, 0, st);
-    aff_prof_mark(ctx, 1, st);
-    int rc = aff_detect_onepass_impl(ctx, d_packed_fullconv, d_responses, st);
-    if (rc) return rc;
-    aff_prof_mark(ctx, 9, st);
-    return AFFNET_OK;
+    return detect_half(ctx, nullptr, true, d_packed_fullconv, d_responses, stream);
 }
 
 extern "C" int affnet_detected_list(affnet_ctx* ctx, float* d_resp, float* d_lafs, int32_t* d_ids, int32_t* d_count, void* stream) {

@@ -38,12 +38,7 @@ __device__ __forceinline__ void aff_shape_filter_row(const float* __restrict__ r
 
 // Denormalisation (LAF.py:407-417) + pyramid-level choice (LAF.py:450-472, float64 |a - b| argmin like scipy's cdist on 1-D points) + re-normalised frame
 // of ONE row, shared by denorm_level_select_kernel (laf_ops.hip) and OriNet's finish kernel (cnn32.hip), which fuses it behind the rotation.
-struct LevelTable { double sig[AFFNET_MAX_OCTAVES * AFFNET_MAX_LEVELS]; int n_oct, n_lvl; };
-struct DenormSel {           // per-launch constants + outputs (pointers of image 0, rows of image b at b * n_max); out_px == NULL: not fused
-    float* out_px; int32_t* ids; float* lafs_norm;
-    float c_a, c_x, c_y, ps, ca, cx, cy;
-    LevelTable lt;
-};
+// (LevelTable / DenormSel, the constants of a launch: common.h)
 __device__ __forceinline__ void aff_denorm_level_row(float l0, float l1, float l2, float l3, float l4, float l5, float c_a, float c_x, float c_y, float ps,
                                                      const LevelTable& lt, float ca, float cx, float cy, float* __restrict__ P, int32_t* __restrict__ I,
                                                      float* __restrict__ O) {
