@@ -130,6 +130,7 @@ SYMBOLS = {
 DEBUG_SYMBOLS = {
     "affnet_cnn32_debug_timing": (_I, [_P, _P]),
     "affnet_cnn32_debug_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),
+    "affnet_cnn32_debug_winograd_u": (_I, [_P, _I, _P, _I, _P, _P]),
     "affnet_selftest_mfma": (_I, [_P, _P, _P, _P]),
     "affnet_debug_split3_variant": (_I, [_P, _I]),
 }

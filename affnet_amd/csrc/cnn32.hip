@@ -9,9 +9,12 @@
 //   * the patch is sampled from the pyramid (or loaded), standardised (mean / unbiased std + 1e-7, DPP wave reductions)
 //     and stored as a zero-haloed 34 x 34 LDS tile;
 //   * the exact path runs all six convolutions on v_mfma_f32_16x16x4_f32 (exact fp32): conv0 with K = 9 taps padded to 12 and the
-//     accumulators initialised with the bias; the direct layers (AffNet / OriNet conv1..5, HardNet conv2 / conv4) as implicit GEMMs
+//     accumulators initialised with the bias; the direct layers (conv2 / conv4 of every net, AffNet conv1..5, OriNet conv5) as implicit GEMMs
 //     (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4
-//     consecutive channels of one pixel; HardNet's stride-1 conv1 / conv3 / conv5 as Winograd F(2x2, 3x3) (conv3x3_wino_mfma).  The
+//     consecutive channels of one pixel; the stride-1 layers as Winograd F(2x2, 3x3): HardNet's conv1 / conv3 / conv5 (conv3x3_wino_mfma,
+//     U = G g G^T from the blob) and OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on
+//     128 registers; U derived from the blob's taps by wino_derive_u_kernel in front of every launch).  AffNet stays in the direct form:
+//     the shape filter behind it turns on the last bits of its output, and another rounding changes which keypoints come back.  The
 //     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
 //     the activation operands of four k-steps, one ds_write_b128 per tile in the epilogue (bias + ReLU), written IN PLACE
@@ -327,6 +330,7 @@ struct PyrSrc {            // pyramid sampling source (fused sampler)
 struct CnnArgs {
     const float* packed;
     NetOffsets off;
+    const float* wino_u;   // exact OriNet: U = G g G^T of conv1 and conv3, derived from the blob in front of this launch (wino_derive_u_kernel)
     const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
     const float* lafs;     // normalised LAFs when sampling
     const int32_t* ids;    // (octave, level, *) when sampling
@@ -362,6 +366,42 @@ __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, i
     do {                                                                                                 \
         if (STAMPS && a.dbg_time && lane == 0) a.dbg_time[((size_t)pidx * NW + wave) * 32 + (k)] = __builtin_readcyclecounter(); \
     } while (0)
+
+// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32; the AffNet blob has the same shapes and the debug accessor derives it too), [xi][cin/16][kq][cout][4] like NetLayout::w_wino.
+// Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
+// BN-folded fp32 taps into a buffer the context owns, one region per net kind.
+struct Wino16 {
+    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, FLOATS = U1 + U3;     // floats per net
+    static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
+};
+
+// One thread per (cin, cout) pair of conv1 (256) and conv3 (1024): reads its 9 taps [tap][cin/16][kq][cout][4] and writes its 16 transform positions in the
+// same fragment order.  Operation order = the packer's for HardNet (affnet_cnn32_pack_weights; tools/winograd_numerics.py: weight_transform): along x
+// s = g0 + g2; (g0, 0.5 (s + g1), 0.5 (s - g1), g2), then the same along y; one rounding per operation (the library is built with -ffp-contract=off).
+__global__ __launch_bounds__(256) void wino_derive_u_kernel(const float* __restrict__ packed, int w1, int w3, float* __restrict__ U) {
+    int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 256 + 1024) return;
+    const bool l3 = e >= 256;
+    const int n = l3 ? 1024 : 256;
+    const float* src = packed + (l3 ? w3 : w1);
+    float* dst = U + (l3 ? Wino16::U1 : 0);
+    if (l3) e -= 256;
+    float t[3][4];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const float g0 = src[(3 * ky) * n + e], g1 = src[(3 * ky + 1) * n + e], g2 = src[(3 * ky + 2) * n + e];
+        const float s = g0 + g2;
+        t[ky][0] = g0; t[ky][1] = 0.5f * (s + g1); t[ky][2] = 0.5f * (s - g1); t[ky][3] = g2;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float s = t[0][j] + t[2][j];
+        dst[j * n + e] = t[0][j];
+        dst[(4 + j) * n + e] = 0.5f * (s + t[1][j]);
+        dst[(8 + j) * n + e] = 0.5f * (s - t[1][j]);
+        dst[(12 + j) * n + e] = t[2][j];
+    }
+}
 
 template <int CB>
 struct TrunkLds {
@@ -456,12 +496,14 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         a.dbg_time[((size_t)pidx * NW + wave) * 32 + 14] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
         a.dbg_time[((size_t)pidx * NW + wave) * 32 + 15] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
     }
-    // conv0 taps + bias (and for exact AffNet / OriNet the first weight chunk of conv1): requested now, consumed after the input phase
+    // conv0 taps + bias (and for exact AffNet the first weight chunk, for exact OriNet the first U fragments of conv1): requested now, consumed after the input phase
     float w0[3][S::T1N];
     f32x4 bias0[S::T1N];
     conv0_load_w<NW, CB, S::T1M, S::T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
     f32x4 b1[1][S::T1N];
-    if constexpr (S3 == 0 && KIND != AFFNET_NET_HARDNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
+    f32x4 Ur[4];                                                      // exact OriNet: the rolling U register set of conv1 / conv3
+    if constexpr (S3 == 0 && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
+    if constexpr (S3 == 0 && KIND == AFFNET_NET_ORINET) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
 
     // ---- input: load or sample 1024 pixels (PPT per thread), standardise, store padded ----------------
     constexpr int PPT = 1024 / NTHR;                    // input pixels per thread (2 or 1)
@@ -627,76 +669,148 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         CNN_STAMP(12);
         if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
     } else if constexpr (S3 == 0) {
-        // Exact AffNet / OriNet: conv1 .. conv5 in the direct form (AffNet / OriNet set the LAF geometry), conv5 straight into the heads.
+        // Exact AffNet / OriNet.  OriNet: conv1 and conv3 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
+        // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which
+        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet keeps conv1 .. conv5 in the direct form: its output decides the
+        // shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST bits of A for near-isotropic shapes, so any other
+        // rounding changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline configuration).  conv0, conv2, conv4 and conv5 in
+        // the direct form for both, conv5 straight into the heads.
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
-        static_assert(T1M * 8 > S::AREG, "conv1: two A sets of T1M float4 do not fit -> rolling single set (conv3x3_mfma_roll)");
-
-        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-        f32x4 bias1[T1N];
-        {
-            f32x4 acc[T1M][T1N];
-            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
-            CNN_STAMP(19);
-            prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
-            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
-            CNN_STAMP(20);
-            __syncthreads();
-        }
-        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-        CNN_STAMP(2);
-
-        // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
-        f32x4 b2[S::G2][T2N];
-        f32x4 bias2[T2N];
-        {
-            f32x4 acc[T1M][T1N];
-            conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], b1, acc, wave, lane);
-            CNN_STAMP(3);
-            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
-            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-            __syncthreads();
-            CNN_STAMP(21);
-            zero_halo<LayC1, NTHR>(act, CB);
-            store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
-            CNN_STAMP(22);
-            __syncthreads();
-            CNN_STAMP(4);
-        }
-        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-        f32x4 b3[S::G3][T2N];
-        f32x4 bias3[T2N];
-        {
-            f32x4 acc[T2M][T2N];
-            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
-            CNN_STAMP(5);
-            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G3>(a.packed + a.off.w[3], b3, wave, lane);
-            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
-            __syncthreads();
-            zero_halo<LayC2, NTHR>(act, 2 * CB);
-            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
-            __syncthreads();
-            CNN_STAMP(6);
-        }
-        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
+        static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
         f32x4 b4[S::G4][T4N];
         f32x4 bias4[T4N];
-        {
-            f32x4 acc[T2M][T2N];
-            conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, S::G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
-            CNN_STAMP(7);
-            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
-            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-            __syncthreads();
-            zero_halo<LayC3, NTHR>(act, 2 * CB);
-            store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
-            __syncthreads();
-            CNN_STAMP(8);
+        if constexpr (KIND == AFFNET_NET_ORINET) {
+            constexpr int NB1 = Wino16::NB1, NB3 = Wino16::NB3;
+            // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+            {
+                f32x4 acc[T1M][T1N];
+                conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+                CNN_STAMP(19);
+                store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+                CNN_STAMP(20);
+                __syncthreads();
+            }
+            if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+            CNN_STAMP(2);
+
+            // ---- conv1: CB -> CB @32x32, Winograd ------------------------------------------------------------
+            f32x4 b2[S::G2][T2N];
+            f32x4 bias2[T2N];
+            {
+                f32x4 y[NB1][4], bw[NB1];
+                conv3x3_wino_mfma_rows<NW, CB, CB, LayC0, NB1>(act, a.wino_u, Ur, y, wave, lane);
+                CNN_STAMP(3);
+                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+                wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
+                __syncthreads();
+                CNN_STAMP(21);
+                zero_halo<LayC1, NTHR>(act, CB);
+                wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
+                CNN_STAMP(22);
+                __syncthreads();
+                CNN_STAMP(4);
+            }
+            if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
+
+            // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
+            {
+                f32x4 acc[T2M][T2N];
+                conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+                CNN_STAMP(5);
+                wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::U1, Ur, wave, lane);
+                __syncthreads();
+                zero_halo<LayC2, NTHR>(act, 2 * CB);
+                store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+                __syncthreads();
+                CNN_STAMP(6);
+            }
+            if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+            // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
+            {
+                f32x4 y[NB3][4], bw[NB3];
+                conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::U1, Ur, y, wave, lane);
+                CNN_STAMP(7);
+                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+                wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
+                __syncthreads();
+                zero_halo<LayC3, NTHR>(act, 2 * CB);
+                wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
+                __syncthreads();
+                CNN_STAMP(8);
+            }
+            if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
+
+        } else {
+            static_assert(T1M * 8 > S::AREG, "conv1: two A sets of T1M float4 do not fit -> rolling single set (conv3x3_mfma_roll)");
+            // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+            f32x4 bias1[T1N];
+            {
+                f32x4 acc[T1M][T1N];
+                conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+                CNN_STAMP(19);
+                prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
+                store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+                CNN_STAMP(20);
+                __syncthreads();
+            }
+            if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+            CNN_STAMP(2);
+
+            // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
+            f32x4 b2[S::G2][T2N];
+            f32x4 bias2[T2N];
+            {
+                f32x4 acc[T1M][T1N];
+                conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], b1, acc, wave, lane);
+                CNN_STAMP(3);
+                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+                __syncthreads();
+                CNN_STAMP(21);
+                zero_halo<LayC1, NTHR>(act, CB);
+                store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
+                CNN_STAMP(22);
+                __syncthreads();
+                CNN_STAMP(4);
+            }
+            if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
+
+            // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
+            f32x4 b3[S::G3][T2N];
+            f32x4 bias3[T2N];
+            {
+                f32x4 acc[T2M][T2N];
+                conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+                CNN_STAMP(5);
+                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G3>(a.packed + a.off.w[3], b3, wave, lane);
+                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
+                __syncthreads();
+                zero_halo<LayC2, NTHR>(act, 2 * CB);
+                store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+                __syncthreads();
+                CNN_STAMP(6);
+            }
+            if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+            // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
+            {
+                f32x4 acc[T2M][T2N];
+                conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, S::G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
+                CNN_STAMP(7);
+                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+                __syncthreads();
+                zero_halo<LayC3, NTHR>(act, 2 * CB);
+                store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
+                __syncthreads();
+                CNN_STAMP(8);
+            }
+            if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
+
         }
-        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
 
         // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
         f32x4 b5[S::G5][T4N];
@@ -1380,9 +1494,35 @@ static int arith_index(const affnet_ctx* ctx) {
     return ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);
 }
 
+// The context's buffer of derived Winograd weights (Wino16::FLOATS per 16-channel net).  Allocated on first use; affnet_graph_capture_extract calls this
+// before the capture begins (no allocation inside a capture).
+int aff_wino_u_ensure(affnet_ctx* ctx) {
+    if (ctx->wino_u) return AFFNET_OK;
+    AFF_HIP(ctx, hipMalloc((void**)&ctx->wino_u, (size_t)2 * Wino16::FLOATS * sizeof(float)));
+    return AFFNET_OK;
+}
+
+// U of conv1 / conv3 of `packed` (AffNet or OriNet blob) into the context's region of that net, on the launch stream: 1280 threads, 46 KB read, 82 KB written.
+// In front of EVERY exact OriNet trunk launch, so that a blob rewritten in place (load_state_dict into the same device buffer) can never meet
+// stale weights, eagerly or in a replayed graph.
+static int wino_derive_u(affnet_ctx* ctx, int kind, const float* packed, const NetLayout& L, hipStream_t st, const float** u) {
+    const int rc = aff_wino_u_ensure(ctx);
+    if (rc) return rc;
+    float* dst = ctx->wino_u + (size_t)kind * Wino16::FLOATS;
+    hipLaunchKernelGGL(wino_derive_u_kernel, dim3(5), dim3(256), 0, st, packed, (int)L.w_off[1], (int)L.w_off[3], dst);
+    AFF_LAUNCH_CHECK(ctx);
+    *u = dst;
+    return AFFNET_OK;
+}
+
 static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid) {
     CnnArgs a;
     a.packed = c.packed; a.off = to_offsets(L, ctx->arith);            // the split copy of the active mode
+    a.wino_u = nullptr;
+    if (c.kind == AFFNET_NET_ORINET && ctx->arith == AFFNET_ARITH_FP32_MFMA) {
+        const int rc = wino_derive_u(ctx, c.kind, c.packed, L, c.st, &a.wino_u);
+        if (rc) return rc;
+    }
     a.patches = c.patches; a.lafs = c.lafs; a.ids = c.ids; a.count = c.count; a.n_max = c.n_max;
     a.out = (c.dbg_layer < 0) ? c.scratch : c.out;      // trunk kernels: HardNet conv5 tensor / AffNet, OriNet head partials
     a.dbg_layer = c.dbg_layer; a.dbg_out = c.dbg_out; a.dbg_time = ctx->dbg_time;
@@ -1539,6 +1679,16 @@ extern "C" int affnet_cnn32_debug_layer(affnet_ctx* ctx, int net_kind, const flo
     c.kind = net_kind; c.packed = d_packed; c.patches = d_patch; c.n_max = 1; c.out = d_out; c.st = (hipStream_t)stream;
     c.dbg_layer = layer; c.dbg_out = d_out;
     return cnn_launch(ctx, c);
+}
+
+extern "C" int affnet_cnn32_debug_winograd_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 1 && layer != 3))
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_debug_winograd_u: AffNet / OriNet, layer 1 or 3");
+    const float* u;
+    const int rc = wino_derive_u(ctx, net_kind, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
+    if (rc) return rc;
+    return aff_copy_async(ctx, d_out, u + (layer == 3 ? Wino16::U1 : 0), (size_t)(layer == 3 ? Wino16::U3 : Wino16::U1) * sizeof(float), (hipStream_t)stream);
 }
 
 #ifdef AFFNET_PROBES   // libaffnet_hip_probes.so only (include/affnet_hip_probes.h)

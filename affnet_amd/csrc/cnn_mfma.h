@@ -1281,6 +1281,91 @@ __device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const flo
     wino_output(acc, y[0]);
 }
 
+// The same layer for the 16-channel trunks (AffNet / OriNet conv1, conv3), which live on 128 registers per lane (two workgroups per CU): acc[16] + U[16] +
+// V[16] of conv3x3_wino_mfma do not fit.  The output transform is linear in the positions, so a wave walks ONE ROW of four positions xi = 4 i .. 4 i + 3 at a
+// time: row i of V needs two rows of the window (B^T along y: rows (0, 2), (1, 2), (2, 1), (1, 3)), 8 ds_read_b128 and 32 VALU operations; the row's four
+// accumulators run over all K groups (same K order per position as conv3x3_wino_mfma: G ascending, four k-steps each) and are then folded into the y stage of
+// A^T M A - t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3, operation by operation what wino_output does - before the next row starts.  Live: 4 accumulators, 4 U
+// fragments, 4 V fragments, t0 / t1.  Per K group the window rows 1 and 2 are read twice (32 instead of 16 ds_read_b128), the VALU work is the same.
+// U enters holding row 0 / group 0 of pass 0 (wino_prefetch_u_row) and rolls one step ahead in its single register set, as in conv3x3_wino_mfma.
+// Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (cnn32.hip: wino_derive_u_kernel).
+template <int NW, int CIN, int COUT, int H, int NB>
+__device__ __forceinline__ void wino_prefetch_u_row(const float* __restrict__ Wu, f32x4 (&U)[4], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);
+    const int u_lane = wino_u_lane<H, COUT, NB>(wave, 0, lane);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) U[k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0);
+}
+
+template <int NW, int CIN, int COUT, typename LI, int NB>
+__device__ __forceinline__ void conv3x3_wino_mfma_rows(const float* act, const float* __restrict__ Wu, f32x4 (&U)[4], f32x4 (&y)[NB][4], int wave, int lane) {
+    constexpr int H = LI::H, HT = H / 2, NGRP = CIN / 16, NSTEP = NB * 4 * NGRP;
+    static_assert(H % 2 == 0 && (HT * HT) % 16 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "Winograd tiling");
+    static_assert((HT * HT / 16) * (COUT / 16) == NW * NB, "the waves' passes must tile the layer exactly");
+    const int m = lane & 15, kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
+    f32x4 t0[4], t1[4], acc[4];
+#pragma unroll
+    for (int s = 0; s < NSTEP; ++s) {                     // step = (pass q, position row i, K group G), G fastest
+        const int q = s / (4 * NGRP), i = (s / NGRP) % 4, G = s % NGRP;
+        const int sn = s + 1 < NSTEP ? s + 1 : s;         // (the last step re-requests its own weights: unused)
+        const int qn = sn / (4 * NGRP), in = (sn / NGRP) % 4, Gn = sn % NGRP;
+        int ty, tx, cb;
+        wino_tile<H, COUT, NB>(wave, q, m, ty, tx, cb);
+        const int u_next = wino_u_lane<H, COUT, NB>(wave, qn, lane);
+        // window rows of position row i: t[c] = d[ra][c] -/+ d[rb][c]
+        const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
+        unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4);
+        asm("" : "+v"(ab));
+        f32x4 da[4], db[4], V[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
+            V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
+        }
+        if (G == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        __builtin_amdgcn_sched_barrier(0);                // pinned as in conv3x3_wino_mfma: two positions' chains interleave, their U reloads follow
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
+                acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[k + 1], 0, 0, 0);
+            }
+            U[k] = wino_load_u<CIN, COUT>(wrsrc, u_next, 4 * in + k, Gn);
+            U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, u_next, 4 * in + k + 1, Gn);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (G == NGRP - 1) {                               // the row's sums over K are complete: y stage of A^T M A, in wino_output's order
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (i == 0) t0[j][e] = acc[j][e];
+                    else if (i == 1) { t0[j][e] = wadd(t0[j][e], acc[j][e]); t1[j][e] = acc[j][e]; }
+                    else if (i == 2) { t0[j][e] = wadd(t0[j][e], acc[j][e]); t1[j][e] = wsub(t1[j][e], acc[j][e]); }
+                    else t1[j][e] = wsub(t1[j][e], acc[j][e]);
+                }
+            if (i == 3) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    y[q][0][e] = wadd(wadd(t0[0][e], t0[1][e]), t0[2][e]);
+                    y[q][1][e] = wsub(wsub(t0[1][e], t0[2][e]), t0[3][e]);
+                    y[q][2][e] = wadd(wadd(t1[0][e], t1[1][e]), t1[2][e]);
+                    y[q][3][e] = wsub(wsub(t1[1][e], t1[2][e]), t1[3][e]);
+                }
+            }
+        }
+    }
+}
+
 // bias of the lane's four output channels in each pass
 template <int NW, int H, int COUT, int NB>
 __device__ __forceinline__ void wino_bias(const float* __restrict__ bias, f32x4 (&bv)[NB], int wave, int lane) {

@@ -114,7 +114,11 @@ struct affnet_ctx {
     // the whole path captured as one HIP graph (affnet_graph_capture_extract): one launch instead of ~45 for latency-bound callers
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
+    // Winograd weights U = G g G^T of conv1 / conv3 of the exact AffNet / OriNet trunks, derived from the caller's blob in front of every trunk launch
+    // (cnn32.hip: wino_derive_u_kernel); the only device memory a context owns, allocated on first use (aff_wino_u_ensure)
+    float* wino_u = nullptr;
     ~affnet_ctx() {
+        if (wino_u) (void)hipFree(wino_u);
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
         if (graph) (void)hipGraphDestroy(graph);
         for (auto& e : prof_ev) (void)hipEventDestroy(e);
@@ -234,6 +238,8 @@ void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_i
 int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
                             float* d_lafs_norm, hipStream_t st);
 
+// cnn32.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one)
+int aff_wino_u_ensure(affnet_ctx* ctx);
 // cnn32.hip: the fused launches of affnet_describe_detected (AffNet + shape filter on a row window, OriNet + rotation, HardNet with
 // the stage mark between trunk and head)
 int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""CPU mirror of HardNet's Winograd F(2x2, 3x3) layers (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma) and the error it adds.
+"""CPU mirror of the Winograd F(2x2, 3x3) layers (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma for HardNet's conv1 / conv3 / conv5,
+conv3x3_wino_mfma_rows for conv1 / conv3 of OriNet; the AffNet mirror prices the same change for AffNet, which stays direct) and the error they add.
 
 The transforms follow the kernel's operation order one add / multiply at a time in the input's dtype:
     U = G g G^T   along x, then y:  s = g0 + g2;  (g0, 0.5 (s + g1), 0.5 (s - g1), g2)
@@ -10,8 +11,12 @@ summation order changes the last bits, not the size of the error).  BatchNorm is
 weights of the kernel are.
 
     python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32 and Winograd fp32
+    python tools/winograd_numerics.py --net affnet|orinet [--layers 1,3]
+        -> per trunk layer and at the pooled head output: max |x - float64 forward| of direct fp32 and Winograd fp32 (shipped checkpoints,
+           tests/golden/cnn_random_patches.npz and --n smooth seeded patches); OriNet also the error of the angle
 """
 import argparse
+import math
 import os
 import sys
 
@@ -25,6 +30,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle")):
 import affnet_oracle as orc  # noqa: E402
 
 WINO_LAYERS = (1, 3, 5)          # HardNet's stride-1 layers after conv0: conv1, conv3, conv5
+WINO_LAYERS_16 = (1, 3)          # OriNet (and the AffNet mirror): conv1 and conv3 (conv5 feeds the heads from the direct form's accumulators)
 
 
 def _g_axis(g0, g1, g2):
@@ -117,6 +123,52 @@ def hardnet_forward(sd, patches, wino=True, dtype=torch.float32):
     return y / torch.sqrt(torch.sum(y * y, dim=1) + 1e-8).unsqueeze(-1)
 
 
+def trunk16_layers(sd, patches, layers=WINO_LAYERS_16, dtype=torch.float32):
+    """The six post-ReLU trunk tensors of AffNet / OriNet in `dtype`, the layers in `layers` as Winograd (() = all direct)"""
+    x = orc.input_norm(patches.to(dtype))
+    outs = []
+    for li, (w, b, st) in enumerate(folded(sd, dtype)):
+        y = wino_conv3x3(x, w) if li in layers else F.conv2d(x, w, None, stride=st, padding=1)
+        x = F.relu(y + b.view(1, -1, 1, 1))
+        outs.append(x)
+    return outs
+
+
+def head16(sd, y, net, dtype=torch.float32):
+    """Pooled head output: AffNet (n, 3) - the numbers A is built from; OriNet (n, 2) - the vector whose atan2 is the angle"""
+    y = torch.tanh(F.conv2d(y, sd["features.19.weight"].to(dtype), sd["features.19.bias"].to(dtype), padding=1 if net == "orinet" else 0))
+    return F.adaptive_avg_pool2d(y, 1).flatten(1)
+
+
+def errors16(sd, patches, net, layers=WINO_LAYERS_16):
+    """{"direct" | "winograd": {"layers": [6 x max |x - fp64| / max(1, |fp64|max)], "head": max |head - fp64|, "angle": rad (OriNet)}}"""
+    with torch.no_grad():
+        ref = trunk16_layers(sd, patches, (), torch.float64)
+        href = head16(sd, ref[5], net, torch.float64)
+        out = {}
+        for name, ls in (("direct", ()), ("winograd", tuple(layers))):
+            got = trunk16_layers(sd, patches, ls)
+            h = head16(sd, got[5], net)
+            rec = {"layers": [float((g.double() - r).abs().max()) / max(1.0, float(r.abs().max())) for g, r in zip(got, ref)],
+                   "head": float((h.double() - href).abs().max())}
+            if net == "orinet":
+                ang = lambda v: torch.atan2(v[:, 0] + 1e-8, v[:, 1] + 1e-8)
+                d = ang(h).double() - ang(href)
+                rec["angle"] = float(((d + math.pi) % (2 * math.pi) - math.pi).abs().max())
+            out[name] = rec
+    return out
+
+
+def smooth_patches(n, seed=1):
+    """n seeded smooth patches (8 x 8 noise, bilinear to 32 x 32) - closer to image content than white noise"""
+    return F.interpolate(torch.rand(n, 1, 8, 8, generator=torch.Generator().manual_seed(seed)) * 255, size=32, mode="bilinear")
+
+
+def load_net16(net):
+    name = {"affnet": "AffNet", "orinet": "OriNet"}[net]
+    return torch.load(os.path.join(ROOT, "pretrained", name + ".pth"), map_location="cpu", weights_only=False)["state_dict"]
+
+
 def errors(sd, patches):
     """(max, mean) |descriptor - float64 forward| of direct fp32 and of Winograd fp32"""
     with torch.no_grad():
@@ -132,7 +184,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--net", choices=("hardnet", "affnet", "orinet"), default="hardnet")
+    ap.add_argument("--layers", default="1,3", help="Winograd layers of the AffNet / OriNet mirror")
     args = ap.parse_args()
+    if args.net != "hardnet":
+        import numpy as np
+        sd = load_net16(args.net)
+        layers = tuple(int(v) for v in args.layers.split(","))
+        golden = torch.from_numpy(np.load(os.path.join(ROOT, "tests", "golden", "cnn_random_patches.npz"))["patches"]).reshape(-1, 1, 32, 32)
+        print("%s, Winograd in layers %s; max abs error vs float64 (layers: relative to max(1, |ref|max))" % (args.net, layers))
+        for tag, p in (("golden random", golden), ("%d smooth" % args.n, smooth_patches(args.n, args.seed + 1))):
+            e = errors16(sd, p, args.net, layers)
+            for k in ("direct", "winograd"):
+                print("%-14s %-9s layers %s  head %.3g%s" % (tag, k, " ".join("%.2g" % v for v in e[k]["layers"]), e[k]["head"],
+                                                           "  angle %.3g rad" % e[k]["angle"] if "angle" in e[k] else ""))
+        return
     sd = orc.synthetic_hardnet_state(0)
     p = torch.rand(args.n, 1, 32, 32, generator=torch.Generator().manual_seed(args.seed)) * 255
     for name, (mx, mean) in errors(sd, p).items():
