@@ -19,8 +19,9 @@
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
 //     the activation operands of four k-steps, one ds_write_b128 per tile in the epilogue (bias + ReLU), written IN PLACE
 //     over the layer's input after a barrier.  No HBM traffic between layers;
-//   * packed weights [tap][cin/16][kq][cout][4] stream from L2 through a buffer descriptor (one buffer_load_dwordx4 per
-//     lane = the weight operands of four k-steps), software-pipelined one chunk ahead, loads interleaved between the MFMAs;
+//   * packed weights (weights_layout.h: w_tap_index; packed on the host by weights_pack.hip) stream from L2 through a buffer descriptor
+//     (one buffer_load_dwordx4 per lane = the weight operands of four k-steps), software-pipelined one chunk ahead, loads interleaved
+//     between the MFMAs;
 //   * heads: HardNet stores its conv5 tile [pixel][channel] to HBM and an 8192 x 128 split-K MFMA GEMM over all patches
 //     (hardnet_head_kernel + hardnet_finish_kernel: BN bias + L2 norm) follows; AffNet / OriNet reduce their heads' dot
 //     products per wave straight from the conv5 accumulators (head_partials, head_partials_ori_lds) and affnet_finish_kernel /
@@ -37,196 +38,6 @@
 
 #include "cnn_mfma.h"
 #include "shape_filter.h"
-
-extern "C" size_t affnet_cnn32_packed_floats(int net_kind) {
-    if (net_kind < 0 || net_kind > AFFNET_NET_AFFNET_FULLCONV) return 0;
-    return net_layout(net_kind).total;
-}
-
-extern "C" int64_t affnet_cnn32_winograd_offset(int net_kind, int layer) {
-    if (net_kind < 0 || net_kind > AFFNET_NET_AFFNET_FULLCONV || layer < 0 || layer > 5) return -1;
-    const NetLayout L = net_layout(net_kind);
-    return L.w_wino[layer] ? (int64_t)L.w_wino[layer] : -1;
-}
-
-extern "C" int affnet_cnn32_pack_weights(int kind, const float* const* conv_w, const float* const* bn_mean, const float* const* bn_var,
-                                         const float* head_w, const float* head_b, const float* head_bn_mean, const float* head_bn_var,
-                                         float* out) {
-    if (kind < 0 || kind > AFFNET_NET_AFFNET_FULLCONV || !conv_w || !bn_mean || !bn_var || !head_w || !out) return AFFNET_ERR_INVALID;
-    const NetLayout L = net_layout(kind);
-    memset(out, 0, L.total * sizeof(float));
-    for (int i = 0; i < 6; ++i) {
-        const int ci = L.cin[i], co = L.cout[i];
-        for (int n = 0; n < co; ++n) {
-            const float s = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);      // BatchNorm2d(affine=False), eps 1e-5, eval mode
-            out[L.b_off[i] + n] = -bn_mean[i][n] * s;
-            for (int c = 0; c < ci; ++c)
-                for (int t = 0; t < 9; ++t) {
-                    const float w = conv_w[i][((size_t)n * ci + c) * 9 + t] * s;
-                    if (i == 0) out[L.w_off[0] + (size_t)t * co + n] = w;               // [tap (12, rows 9..11 zero)][n]
-                    else                                                                // [tap][G = c/16][kq = (c/4)%4][n][j = c%4]
-                        out[L.w_off[i] + ((((size_t)t * (ci / 16) + c / 16) * 4 + (c / 4) % 4) * co + n) * 4 + c % 4] = w;
-                }
-        }
-    }
-    // Winograd F(2x2, 3x3) copies of HardNet's stride-1 layers: U = G g G^T of the same BN-folded fp32 taps, in conv3x3_wino_mfma's former operation
-    // order (along x: s = g0 + g2; (g0, 0.5 (s + g1), 0.5 (s - g1), g2), then the same along y; one rounding per operation, no contraction), so the
-    // values are bit for bit what the loop used to compute per K group.  [xi = 4 i + j][G = c/16][kq = (c/4)%4][n][c%4]
-    for (int i = 1; i < 6; ++i) {
-        if (!L.w_wino[i]) continue;
-        const int ci = L.cin[i], co = L.cout[i];
-        for (int n = 0; n < co; ++n) {
-            const float sc = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);
-            for (int c = 0; c < ci; ++c) {
-                volatile float t[3][4], U[16];                              // volatile: every intermediate is a rounded fp32 value in memory
-                for (int ky = 0; ky < 3; ++ky) {
-                    const float g0 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky] * sc, g1 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky + 1] * sc;
-                    const float g2 = conv_w[i][((size_t)n * ci + c) * 9 + 3 * ky + 2] * sc;
-                    const float s = g0 + g2;
-                    t[ky][0] = g0; t[ky][1] = 0.5f * (s + g1); t[ky][2] = 0.5f * (s - g1); t[ky][3] = g2;
-                }
-                for (int j = 0; j < 4; ++j) {
-                    const float s = t[0][j] + t[2][j];
-                    U[j] = t[0][j]; U[4 + j] = 0.5f * (s + t[1][j]); U[8 + j] = 0.5f * (s - t[1][j]); U[12 + j] = t[2][j];
-                }
-                for (int xi = 0; xi < 16; ++xi)
-                    out[L.w_wino[i] + ((((size_t)xi * (ci / 16) + c / 16) * 4 + (c / 4) % 4) * co + n) * 4 + c % 4] = U[xi];
-            }
-        }
-    }
-    // split copies for AFFNET_ARITH_FP32_SPLIT3 (conv1 .. conv5 = S3_LAYER_MASK, all three nets): the same BN-folded fp32 weight as three bf16 terms (nearest even,
-    // exact remainders), [tap][cin / 32][term][kq][cout][8]: lane (cout, kq) of the bf16 MFMA's A operand = 8 consecutive input channels
-    for (int i = 1; i < 6; ++i) {
-        if (!L.w_s3[i]) continue;
-        const int ci = L.cin[i], co = L.cout[i];
-        uint16_t* dst = reinterpret_cast<uint16_t*>(out + L.w_s3[i]);
-        auto bf16_rne = [](float x) -> uint32_t { uint32_t u; memcpy(&u, &x, 4); return (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u; };
-        for (int n = 0; n < co; ++n) {
-            const float sc = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);
-            for (int c = 0; c < ci; ++c)
-                for (int t9 = 0; t9 < 9; ++t9) {
-                    float r = conv_w[i][((size_t)n * ci + c) * 9 + t9] * sc;          // the value the fp32 path uses
-                    for (int term = 0; term < 3; ++term) {
-                        const uint32_t hb = bf16_rne(r);
-                        float hf; memcpy(&hf, &hb, 4);
-                        r -= hf;                                                       // exact
-                        if (ci == 16) {                                                // two taps per k = 32 step: [step][term][kq][cout][8]
-                            const int st = t9 / 2, kq = (t9 % 2) * 2 + c / 8, j = c % 8;
-                            dst[((((size_t)st * 3 + term) * 4 + kq) * co + n) * 8 + j] = (uint16_t)(hb >> 16);
-                        } else {
-                            const int G = c / 32, kq = (c % 32) / 8, j = c % 8;
-                            dst[(((((size_t)t9 * (ci / 32) + G) * 3 + term) * 4 + kq) * co + n) * 8 + j] = (uint16_t)(hb >> 16);
-                        }
-                    }
-                }
-        }
-    }
-    // two-term copies for AFFNET_ARITH_FP32_SPLIT2H: 2^e * w as hi = fp16(2^e w), lo = fp16(2^e w - hi) (nearest even), e per layer such that the
-    // largest |w| of the layer lands in [2^13, 2^14) - both terms of every weight down to 2^-15 of the largest then sit in fp16's normal range.
-    // Same fragment order with two terms; 2^-e (what the loop multiplies its sums with) follows the copy.
-    auto f16_bits = [](float x) -> uint16_t { const _Float16 h = (_Float16)x; uint16_t u; memcpy(&u, &h, 2); return u; };
-    auto f16_val = [](uint16_t u) -> float { _Float16 h; memcpy(&h, &u, 2); return (float)h; };
-    for (int i = 1; i < 6; ++i) {
-        if (!L.w_h2[i]) continue;
-        const int ci = L.cin[i], co = L.cout[i];
-        uint16_t* dst = reinterpret_cast<uint16_t*>(out + L.w_h2[i]);
-        float wmax = 0.0f;
-        for (int n = 0; n < co; ++n) {
-            const float sc = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);
-            for (int k = 0; k < ci * 9; ++k) wmax = fmaxf(wmax, fabsf(conv_w[i][(size_t)n * ci * 9 + k] * sc));
-        }
-        const int e = (wmax > 0.0f && std::isfinite(wmax)) ? std::min(100, std::max(-100, 13 - ilogbf(wmax))) : 0;      // (clamped: 2^-e must stay a normal fp32)
-        out[L.w_h2[i] + s3_floats(ci, co, 2)] = ldexpf(1.0f, -e);
-        for (int n = 0; n < co; ++n) {
-            const float sc = 1.0f / sqrtf(bn_var[i][n] + 1e-5f);
-            for (int c = 0; c < ci; ++c)
-                for (int t9 = 0; t9 < 9; ++t9) {
-                    const float w = ldexpf(conv_w[i][((size_t)n * ci + c) * 9 + t9] * sc, e);      // the value the fp32 path uses, times 2^e (exact)
-                    const uint16_t hb = f16_bits(w), lb = f16_bits(w - f16_val(hb));
-                    for (int term = 0; term < 2; ++term) {
-                        const uint16_t v = term ? lb : hb;
-                        if (ci == 16) {
-                            const int st = t9 / 2, kq = (t9 % 2) * 2 + c / 8, j = c % 8;
-                            dst[((((size_t)st * 2 + term) * 4 + kq) * co + n) * 8 + j] = v;
-                        } else {
-                            const int G = c / 32, kq = (c % 32) / 8, j = c % 8;
-                            dst[(((((size_t)t9 * (ci / 32) + G) * 2 + term) * 4 + kq) * co + n) * 8 + j] = v;
-                        }
-                    }
-                }
-        }
-    }
-    if (kind == AFFNET_NET_HARDNET) {
-        if (!head_bn_mean || !head_bn_var) return AFFNET_ERR_INVALID;
-        {
-            uint16_t* hh2 = reinterpret_cast<uint16_t*>(out + L.head_h2);
-            float wmax = 0.0f;
-            for (int n = 0; n < 128; ++n) {
-                const float sc = 1.0f / sqrtf(head_bn_var[n] + 1e-5f);
-                for (int k = 0; k < HEAD_K; ++k) wmax = fmaxf(wmax, fabsf(head_w[(size_t)n * HEAD_K + k] * sc));
-            }
-            const int e = (wmax > 0.0f && std::isfinite(wmax)) ? std::min(100, std::max(-100, 13 - ilogbf(wmax))) : 0;      // (clamped: 2^-e must stay a normal fp32)
-            out[L.head_h2 + (size_t)HEAD_K * 128] = ldexpf(1.0f, -e);
-            for (int n = 0; n < 128; ++n) {
-                const float sc = 1.0f / sqrtf(head_bn_var[n] + 1e-5f);
-                for (int c = 0; c < 128; ++c)
-                    for (int pp = 0; pp < 64; ++pp) {
-                        const size_t k = (size_t)pp * 128 + c;
-                        const float w = ldexpf(head_w[(size_t)n * HEAD_K + c * 64 + pp] * sc, e);
-                        const uint16_t hb = f16_bits(w), lb = f16_bits(w - f16_val(hb));
-                        hh2[(((((k >> 5) * 2 + 0) * 4 + ((k & 31) >> 3)) * 128 + n) << 3) + (k & 7)] = hb;
-                        hh2[(((((k >> 5) * 2 + 1) * 4 + ((k & 31) >> 3)) * 128 + n) << 3) + (k & 7)] = lb;
-                    }
-            }
-        }
-        uint16_t* hs3 = reinterpret_cast<uint16_t*>(out + L.head_s3);
-        auto bf16_rne_h = [](float x) -> uint32_t { uint32_t u; memcpy(&u, &x, 4); return (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u; };
-        for (int n = 0; n < 128; ++n) {
-            const float s = 1.0f / sqrtf(head_bn_var[n] + 1e-5f);
-            out[L.head_b + n] = -head_bn_mean[n] * s;
-            // split copy of the same BN-folded weights (AFFNET_ARITH_FP32_SPLIT3): three bf16 terms, exact remainders, in the B-fragment order
-            // of hardnet_head_s3_kernel: [k / 32][term][kq = (k % 32) / 8][n][k % 8]
-            for (int c = 0; c < 128; ++c)
-                for (int pp = 0; pp < 64; ++pp) {
-                    const size_t k = (size_t)pp * 128 + c;
-                    float r = head_w[(size_t)n * HEAD_K + c * 64 + pp] * s;
-                    for (int term = 0; term < 3; ++term) {
-                        const uint32_t hb = bf16_rne_h(r);
-                        float hf; memcpy(&hf, &hb, 4);
-                        r -= hf;
-                        hs3[(((((k >> 5) * 3 + term) * 4 + ((k & 31) >> 3)) * 128 + n) << 3) + (k & 7)] = (uint16_t)(hb >> 16);
-                    }
-                }
-            // K order of the head GEMM = the trunk kernel's output order k = pixel * 128 + channel; stored interleaved by 4 like
-            // the conv weights, [k/16][(k/4)%4][n][k%4], so that one 16-byte load per lane is the B fragment of 4 MFMA k-steps
-            for (int c = 0; c < 128; ++c)
-                for (int pp = 0; pp < 64; ++pp) {
-                    const size_t k = (size_t)pp * 128 + c;
-                    out[L.head_w + (((k >> 4) * 4 + ((k >> 2) & 3)) * 128 + n) * 4 + (k & 3)] = head_w[(size_t)n * HEAD_K + c * 64 + pp] * s;
-                }
-        }
-    } else if (kind == AFFNET_NET_AFFNET_FULLCONV) {
-        if (!head_b) return AFFNET_ERR_INVALID;
-        // dense 8 x 8 head (architectures.py:652) as the A operand of fullconv_head_kernel's GEMM: rows n = o * 8 + kx (24 of 32
-        // used, the rest stay zero), K = (ky, c): [ky][c / 16][(c / 4) % 4][n][c % 4]
-        for (int o = 0; o < 3; ++o)
-            for (int c = 0; c < 64; ++c)
-                for (int ky = 0; ky < 8; ++ky)
-                    for (int kx = 0; kx < 8; ++kx)
-                        out[L.head_w + ((((size_t)ky * 4 + c / 16) * 4 + (c / 4) % 4) * 32 + o * 8 + kx) * 4 + c % 4] =
-                            head_w[((size_t)o * 64 + c) * 64 + ky * 8 + kx];
-        memcpy(out + L.head_b, head_b, 3 * sizeof(float));
-    } else {
-        const int no = kind == AFFNET_NET_AFFNET ? 3 : 2;
-        if (!head_b) return AFFNET_ERR_INVALID;
-        // [o][pixel p][channel c]: (pixel, 4 consecutive channels) = what one lane of the conv5 epilogue owns (head_partials)
-        for (int o = 0; o < no; ++o)
-            for (int c = 0; c < 64; ++c)
-                for (int pp = 0; pp < 64; ++pp) out[L.head_w + (size_t)o * 4096 + pp * 64 + c] = head_w[((size_t)o * 64 + c) * 64 + pp];
-        memcpy(out + L.head_b, head_b, no * sizeof(float));
-    }
-    return AFFNET_OK;
-}
 
 // AffNet head, first half, straight from the conv5 accumulators (no conv5 tensor in HBM): a lane owns channels c4..c4+3 of pixel p of
 // each of its tiles = one float4 of the head weights [o][pixel][channel]; it forms its share of the 3 outputs (conv 64 -> 3, 8x8 valid,
@@ -367,7 +178,7 @@ __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, i
         if (STAMPS && a.dbg_time && lane == 0) a.dbg_time[((size_t)pidx * NW + wave) * 32 + (k)] = __builtin_readcyclecounter(); \
     } while (0)
 
-// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32; the AffNet blob has the same shapes and the debug accessor derives it too), [xi][cin/16][kq][cout][4] like NetLayout::w_wino.
+// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32; the AffNet blob has the same shapes and the debug accessor derives it too), in w_tap_index order like NetLayout::w_wino.
 // Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
 // BN-folded fp32 taps into a buffer the context owns, one region per net kind.
 struct Wino16 {
@@ -375,32 +186,23 @@ struct Wino16 {
     static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
 };
 
-// One thread per (cin, cout) pair of conv1 (256) and conv3 (1024): reads its 9 taps [tap][cin/16][kq][cout][4] and writes its 16 transform positions in the
-// same fragment order.  Operation order = the packer's for HardNet (affnet_cnn32_pack_weights; tools/winograd_numerics.py: weight_transform): along x
-// s = g0 + g2; (g0, 0.5 (s + g1), 0.5 (s - g1), g2), then the same along y; one rounding per operation (the library is built with -ffp-contract=off).
+// One thread per (cin, cout) pair of conv1 (256) and conv3 (1024), numbered in the fragment order (so that a wave's loads and stores are contiguous): reads its
+// 9 taps and writes its 16 transform positions, both in w_tap_index order; the transform and its operation order are wino_weight_transform's (weights_layout.h).
 __global__ __launch_bounds__(256) void wino_derive_u_kernel(const float* __restrict__ packed, int w1, int w3, float* __restrict__ U) {
     int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= 256 + 1024) return;
     const bool l3 = e >= 256;
-    const int n = l3 ? 1024 : 256;
+    const int ch = l3 ? 32 : 16;                                        // cin == cout
     const float* src = packed + (l3 ? w3 : w1);
     float* dst = U + (l3 ? Wino16::U1 : 0);
     if (l3) e -= 256;
-    float t[3][4];
+    const int n = (e >> 2) % ch, c = (e >> 2) / ch * 4 + (e & 3);       // e == w_tap_index(0, c, n, ch, ch)
+    float g[9], u[16];
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const float g0 = src[(3 * ky) * n + e], g1 = src[(3 * ky + 1) * n + e], g2 = src[(3 * ky + 2) * n + e];
-        const float s = g0 + g2;
-        t[ky][0] = g0; t[ky][1] = 0.5f * (s + g1); t[ky][2] = 0.5f * (s - g1); t[ky][3] = g2;
-    }
+    for (int t = 0; t < 9; ++t) g[t] = src[w_tap_index(t, c, n, ch, ch)];
+    wino_weight_transform(g, u);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float s = t[0][j] + t[2][j];
-        dst[j * n + e] = t[0][j];
-        dst[(4 + j) * n + e] = 0.5f * (s + t[1][j]);
-        dst[(8 + j) * n + e] = 0.5f * (s - t[1][j]);
-        dst[(12 + j) * n + e] = t[2][j];
-    }
+    for (int xi = 0; xi < 16; ++xi) dst[w_tap_index(xi, c, n, ch, ch)] = u[xi];
 }
 
 template <int CB>

@@ -1,11 +1,13 @@
 // Shared MFMA building blocks of the 32x32-patch trunks (cnn32.hip) and the fully-convolutional AffNet (fullconv.hip):
 // LDS activation layouts, weight fragment loads, the software-pipelined implicit-GEMM 3x3 convolution on
-// v_mfma_f32_16x16x4_f32, conv0 on the matrix cores and the tile epilogues.  gfx950 only.
+// v_mfma_f32_16x16x4_f32, conv0 on the matrix cores and the tile epilogues.  gfx950 only.  The packed weight blob these loops read -
+// sections, offsets and element orders - is defined in weights_layout.h (included here) and filled by weights_pack.hip.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
 
 #include "common.h"
+#include "weights_layout.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -61,85 +63,6 @@ typedef Lay<16, 24, 1732> LayC3;   // conv3 out -> conv4 (stride 2, tile = 2 out
 typedef Lay<8, 16, 672> LayC4;     // conv4 out -> conv5 (stride 1, tile = 2 rows)
 typedef Lay<8, 16, 672> LayC5;     // conv5 out -> AffNet / OriNet heads
 #define WP32 34
-#define HEAD_K 8192
-
-// ---- packed weight layout --------------------------------------------------------------------------
-struct NetLayout {
-    int cb;                 // base width: 16 (AffNet/OriNet) or 32 (HardNet)
-    int cin[6], cout[6];
-    size_t w_off[6], b_off[6];
-    size_t head_w, head_b;  // head weights / bias (HardNet: BN-folded [8192][128] + bias[128])
-    size_t w_s3[6];         // AFFNET_ARITH_FP32_SPLIT3 (0 = none): conv weights once more as three bf16 terms, [tap][cin/32][term][kq][cout][8]
-    size_t head_s3;         // HardNet only: the BN-folded head weights as three bf16 terms, [k/32][term][kq][n 128][8]  (k = pixel * 128 + channel)
-    size_t w_h2[6];         // AFFNET_ARITH_FP32_SPLIT2H (0 = none): the same layers as TWO fp16 terms of 2^e * w (e per layer: the largest |w| of the layer lands in
-                            // [2^13, 2^14)), same fragment order with 2 terms, followed by 4 floats whose first is 2^-e (the loop's output scale)
-    size_t head_h2;         // HardNet only: the head weights as two fp16 terms, [k/32][term][kq][n 128][8] + 4 floats (2^-e first)
-    size_t w_wino[6];       // HardNet conv1 / conv3 / conv5 (0 = none): the Winograd-transformed fp32 weights U = G g G^T, [xi = 4 i + j (16)][cin/16][kq][cout][4] - the
-                            // tap layout with 16 transform positions in place of 9 taps.  LAST in the blob: every older offset keeps its value
-    size_t total;
-};
-
-// floats occupied by the split copy of a cin x cout 3x3 layer: 9 taps x (cin / 32) groups x 3 terms x 4 lane groups x cout x 8 bf16 (= 4 floats)
-constexpr size_t s3_floats(int cin, int cout, int terms = 3) { return cin == 16 ? (size_t)5 * terms * 4 * cout * 4      // 16 input channels: two taps per k = 32 step, 9 taps in 5 steps
-                                                                                 : (size_t)9 * (cin / 32) * terms * 4 * cout * 4; }
-#define H2_TAIL 4               // floats behind a two-term copy: [0] = 2^-e, the power of two that undoes the copy's scale (exact)
-#define S3_LAYER_MASK 0x3E      // which layers have a split copy / run on split operands (bit i = conv i): conv1 .. conv5 of HardNet
-
-static inline NetLayout net_layout(int kind) {
-    NetLayout L;
-    L.cb = (kind == AFFNET_NET_HARDNET) ? 32 : 16;
-    const int ch[7] = {1, L.cb, L.cb, 2 * L.cb, 2 * L.cb, 4 * L.cb, 4 * L.cb};
-    size_t off = 0;
-    for (int i = 0; i < 6; ++i) {
-        L.cin[i] = ch[i]; L.cout[i] = ch[i + 1];
-        L.w_off[i] = off; off += (i == 0) ? (size_t)12 * ch[1] : (size_t)9 * ch[i] * ch[i + 1];   // conv0: K = 9 padded to 12
-        L.b_off[i] = off; off += ch[i + 1];
-        off = (off + 3) & ~(size_t)3;
-    }
-    L.head_w = off;
-    if (kind == AFFNET_NET_AFFNET) { off += 3 * 4096; L.head_b = off; off += 4; }
-    else if (kind == AFFNET_NET_AFFNET_FULLCONV) { off += 8 * 64 * 32; L.head_b = off; off += 4; }   // [ky][c / 16][(c / 4) % 4][n = o * 8 + kx (32)][c % 4]
-    else if (kind == AFFNET_NET_ORINET) { off += 2 * 4096; L.head_b = off; off += 4; }
-    else { off += (size_t)HEAD_K * 128; L.head_b = off; off += 128; }
-    for (int i = 0; i < 6; ++i) {
-        L.w_s3[i] = 0;
-        const bool has = (kind == AFFNET_NET_HARDNET && ((S3_LAYER_MASK >> i) & 1)) ||
-                         ((kind == AFFNET_NET_AFFNET || kind == AFFNET_NET_ORINET || kind == AFFNET_NET_AFFNET_FULLCONV) && i >= 1);     // 16-channel trunks: conv1 .. conv5
-        if (has) { L.w_s3[i] = off; off += s3_floats(L.cin[i], L.cout[i]); }
-    }
-    L.head_s3 = 0;
-    if (kind == AFFNET_NET_HARDNET) { L.head_s3 = off; off += (size_t)HEAD_K * 128 * 3 / 2; }
-    for (int i = 0; i < 6; ++i) {
-        L.w_h2[i] = 0;
-        if (L.w_s3[i]) { L.w_h2[i] = off; off += s3_floats(L.cin[i], L.cout[i], 2) + H2_TAIL; }
-    }
-    L.head_h2 = 0;
-    if (kind == AFFNET_NET_HARDNET) { L.head_h2 = off; off += (size_t)HEAD_K * 128 + H2_TAIL; }
-    for (int i = 0; i < 6; ++i) {
-        L.w_wino[i] = 0;
-        if (kind == AFFNET_NET_HARDNET && (i == 1 || i == 3 || i == 5)) { L.w_wino[i] = off; off += (size_t)16 * L.cin[i] * L.cout[i]; }
-    }
-    L.total = off;
-    return L;
-}
-
-struct NetOffsets {        // device-side copy of the offsets (by-value kernel argument)
-    int w[6], b[6], head_w, head_b;
-    int w_s3[6];           // the split copy of the ACTIVE arithmetic mode (three bf16 terms or two fp16 terms)
-    int head_s3;
-    int w_wino[3];         // Winograd-transformed weights of conv1 / conv3 / conv5 (HardNet; 0 = none)
-};
-
-static inline NetOffsets to_offsets(const NetLayout& L, int arith = AFFNET_ARITH_FP32_SPLIT3) {
-    NetOffsets o;
-    const bool h2 = arith == AFFNET_ARITH_FP32_SPLIT2H;
-    for (int i = 0; i < 6; ++i) { o.w[i] = (int)L.w_off[i]; o.b[i] = (int)L.b_off[i]; }
-    o.head_w = (int)L.head_w; o.head_b = (int)L.head_b;
-    for (int i = 0; i < 6; ++i) o.w_s3[i] = (int)(h2 ? L.w_h2[i] : L.w_s3[i]);
-    o.head_s3 = (int)(h2 ? L.head_h2 : L.head_s3);
-    for (int i = 0; i < 3; ++i) o.w_wino[i] = (int)L.w_wino[2 * i + 1];
-    return o;
-}
 
 // ---- device helpers ------------------------------------------------------------------------------
 // Wave-wide sum on the VALU only (DPP row reductions + 4 readlanes).  __shfl_xor compiles to ds_bpermute_b32,

@@ -100,6 +100,17 @@ def test_hardnet_prefix_is_the_old_blob(weights):
         off = (off + n + co + 3) & ~3
 
 
+@pytest.mark.parametrize("state,sha", [(0, "6882f2dcf7bc036b1101dc33e64021f4447bd9c4ac532be332f82f5084941b79"),
+                                       (3, "1079eb2a5c9e38196e295022772c9743531b3ec4d2a830920d56487af746c726")])
+def test_whole_hardnet_blob_is_pinned(state, sha):
+    """Every section of the HardNet blob, the split copies of the head and the Winograd section included, byte for byte what the library
+    packed before the packer became a host-only unit (weights_pack.hip; hashes recorded from that library)."""
+    from affnet_amd import engine
+    import affnet_oracle as orc
+    blob = engine.pack_state_dict(2, orc.synthetic_hardnet_state(state), winograd=True)
+    assert blob.numel() == 5015000 and _sha(blob) == sha
+
+
 def test_hardnet_winograd_sections_are_bitwise_the_mirror(weights):
     """U in the blob == tools/winograd_numerics.py: weight_transform of the BN-folded fp32 taps (the operation order of the loop that used
     to compute it per K group; taps folded with the packer's roundings, packed_taps), bit for bit, in [xi][cin/16][(c/4)%4][cout][c%4]."""

@@ -88,7 +88,7 @@ def folded(sd, dtype):
 
 
 def packed_taps(sd, i):
-    """BN-folded fp32 taps [co][ci][3][3] of trunk layer i with the packer's own roundings (affnet_cnn32_pack_weights:
+    """BN-folded fp32 taps [co][ci][3][3] of trunk layer i with the packer's own roundings (affnet_amd/csrc/weights_pack.hip: fold_bn,
     w * (1.0f / sqrtf(var + 1e-5f)), every operation correctly rounded - numpy's float32 sqrt and divide are; torch's vectorised CPU sqrt is
     an ulp off on a few inputs, which is why `folded` above is not used where bits are compared)"""
     import numpy as np
@@ -101,8 +101,9 @@ def packed_taps(sd, i):
 
 
 def packed_weight_transform(sd):
-    """{layer: U} of HardNet's Winograd layers as the packed blob stores them (NetLayout::w_wino, affnet_cnn32_winograd_offset): the
-    fp32 weight_transform of the BN-folded fp32 taps, flat float32 [xi = 4 i + j (16)][ci / 16][(c / 4) % 4][co][c % 4]"""
+    """{layer: U} of HardNet's Winograd layers as the packed blob stores them (affnet_amd/csrc/weights_layout.h: NetLayout::w_wino,
+    w_tap_index; affnet_cnn32_winograd_offset): the fp32 weight_transform of the BN-folded fp32 taps (the mirror of that header's
+    wino_weight_transform), flat float32 [xi = 4 i + j (16)][ci / 16][(c / 4) % 4][co][c % 4]"""
     out = {}
     for i in WINO_LAYERS:
         U = weight_transform(packed_taps(sd, i))             # [4][4][co][ci]
