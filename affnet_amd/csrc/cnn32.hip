@@ -11,9 +11,11 @@
 //   * the exact path runs all six convolutions on v_mfma_f32_16x16x4_f32 (exact fp32): conv0 with K = 9 taps padded to 12 and the
 //     accumulators initialised with the bias; the direct layers (conv2 / conv4 of every net, AffNet conv1..5, OriNet conv5) as implicit GEMMs
 //     (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4
-//     consecutive channels of one pixel; the stride-1 layers as Winograd F(2x2, 3x3): HardNet's conv1 / conv3 / conv5 (conv3x3_wino_mfma,
-//     U = G g G^T from the blob) and OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on
-//     128 registers; U derived from the blob's taps by wino_derive_u_kernel in front of every launch).  AffNet stays in the direct form:
+//     consecutive channels of one pixel; the stride-1 layers as Winograd F(2x2, 3x3), U = G g G^T: HardNet's conv1 / conv3
+//     (conv3x3_wino_mfma_pair_rows: two channel blocks share one window transform, one row of four transform positions per step, the next
+//     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob;
+//     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
+//     blob's taps by wino_derive_u_kernel in front of every launch).  AffNet stays in the direct form:
 //     the shape filter behind it turns on the last bits of its output, and another rounding changes which keypoints come back.  The
 //     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
@@ -357,22 +359,24 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
 
     // ---- one straight-line body per flow ----------------------------------------------------------------
     if constexpr (S3 == 0 && KIND == AFFNET_NET_HARDNET) {
-        // Exact HardNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (conv3x3_wino_mfma, cnn_mfma.h) - 4/9 of the MFMAs; each wave
-        // runs NB (tile block, channel block) passes of a layer.  The Winograd layers load their transformed weights U from the blob
-        // (NetLayout::w_wino), one K group ahead; the first group of a layer is requested in front of the barrier before it, where the direct-form
-        // layers (conv0, conv2, conv4) request their first weight chunk.  conv5's tensor goes to HBM for the head GEMM.
+        // Exact HardNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (cnn_mfma.h) - 4/9 of the MFMAs; each wave runs NB (tile block,
+        // channel block) passes of a layer, in conv1 / conv3 two at a time on one window transform (conv3x3_wino_mfma_pair_rows).  The Winograd layers
+        // load their transformed weights U from the blob (NetLayout::w_wino), ahead of their use; the first fragments of a layer are requested in front of
+        // the barrier before it, where the direct-form layers (conv0, conv2, conv4) request their first weight chunk.  conv5's tensor goes to HBM for
+        // the head GEMM.
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
 
         // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-        f32x4 Uw[16];                                                 // the rolling U register set of conv1 / conv3 / conv5
+        f32x4 Up[2][4];                                               // the rolling U register set of conv1 / conv3: one position row, both channel blocks of a pair
+        f32x4 Uw[16];                                                 // the rolling U register set of conv5
         {
             f32x4 acc[T1M][T1N];
             conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
             CNN_STAMP(19);
             store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
             CNN_STAMP(20);
-            wino_prefetch_u<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Uw, wave, lane);
+            wino_prefetch_u_pair<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Up, wave, lane);
             __syncthreads();
         }
         if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
@@ -384,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         {
             f32x4 y[NB1][4], bw[NB1];
             __builtin_amdgcn_s_setprio(0);
-            conv3x3_wino_mfma<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Uw, y, wave, lane);
+            conv3x3_wino_mfma_pair_rows<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Up, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(3);
             prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
@@ -407,7 +411,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(5);
-            wino_prefetch_u<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Uw, wave, lane);
+            wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
             __syncthreads();
             zero_halo<LayC2, NTHR>(act, 2 * CB);
             store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
@@ -422,7 +426,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         {
             f32x4 y[NB3][4], bw[NB3];
             __builtin_amdgcn_s_setprio(0);
-            conv3x3_wino_mfma<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Uw, y, wave, lane);
+            conv3x3_wino_mfma_pair_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Up, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(7);
             prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);

@@ -1105,53 +1105,153 @@ __device__ __forceinline__ void wino_output(const f32x4 (&acc)[16], f32x4 (&yq)[
     }
 }
 
-// Pre-activation outputs (no bias) of the NB passes: y[q][2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3 of pixel (2 ty + dy, 2 tx + dx).
-// U enters holding the first K group of pass 0 (wino_prefetch_u) and rolls ONE K group ahead in a single register set: once the four
-// MFMAs of position k have issued, U[k] of the next group (the last group of a pass: the first group of the next pass) is requested into
-// the same registers, so a group's weights travel while the window transform and the other 60 MFMAs run.
+// conv1 / conv3 of the exact HardNet trunk.  Pre-activation outputs (no bias) of the NB passes: y[q][2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3 of
+// pixel (2 ty + dy, 2 tx + dx).  V = B^T d B does not depend on the output channel, and wino_tile gives passes 2 j and 2 j + 1 of a wave the same tile block
+// and the channel blocks cb, cb + 1: the loop runs such a pair as ONE unit - one V against U of both channel blocks (the U address of cb + 1 is cb's plus
+// 256 bytes) - so a window is transformed once per unit and not once per pass.  A unit walks rows as conv3x3_wino_mfma_rows does: a step is (unit, position
+// row i, K group G), G fastest; it takes the two window rows of row i (8 ds_read_b128) and 32 VALU operations for the row's 4 V fragments and issues 2 x 4 x 4
+// MFMAs into acc[2][4]; after the last G the row is folded into t0 / t1 of both channel blocks and after row 3 into y, operation by operation what
+// wino_output does.  Every accumulator (tile, cout, position) receives the MFMAs of the one-pass-at-a-time form in its order (G ascending, four k-steps
+// each, same operands), so the layer's bits do not change.  Rows 1 and 2 of a window are read twice per K group; with half as many windows the LDS reads
+// are as many as before.
+// Pipeline inside the wave: the reads and the transform of step s + 1 sit BETWEEN the 32 MFMAs of step s (sched_group_barrier: one read behind each of
+// the first 8 MFMAs, two VALU behind each of the last 16 - the fp32 MFMA holds the pipe for 32 cycles and leaves the issue port to the VALU,
+// tools/probes/mfma_valu_overlap.hip), in two V register sets Va / Vb that swap by name.  U enters holding step 0 (wino_prefetch_u_pair, requested in front
+// of the barrier before the layer) and rolls one step ahead in its single set: fragment (c, k) of the next step is requested once the MFMAs of position k
+// have issued, 24 MFMAs or more in front of its use.
+template <int CIN, int COUT>
+__device__ __forceinline__ f32x4 wino_load_u_pair(__amdgpu_buffer_rsrc_t r, int u_lane, int c, int k, int G) {
+    return buf_read4(r, u_lane, (k * (CIN / 16) + G) * 16 * COUT * 4 + c * 256);
+}
+template <int NW, int CIN, int COUT, int H, int NB>
+__device__ __forceinline__ void wino_prefetch_u_pair(const float* __restrict__ Wu, f32x4 (&U)[2][4], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);
+    const int u_lane = wino_u_lane<H, COUT, NB>(wave, 0, lane);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) U[c][k] = wino_load_u_pair<CIN, COUT>(r, u_lane, c, k, 0);
+}
+
 template <int NW, int CIN, int COUT, typename LI, int NB>
-__device__ __forceinline__ void conv3x3_wino_mfma(const float* act, const float* __restrict__ Wu, f32x4 (&U)[16], f32x4 (&y)[NB][4], int wave, int lane) {
-    constexpr int H = LI::H, HT = H / 2, NGRP = CIN / 16;
+__device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, const float* __restrict__ Wu, f32x4 (&U)[2][4], f32x4 (&y)[NB][4], int wave, int lane) {
+    constexpr int H = LI::H, HT = H / 2, NGRP = CIN / 16, NSTEP = (NB / 2) * 4 * NGRP;
     static_assert(H % 2 == 0 && (HT * HT) % 16 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "Winograd tiling");
     static_assert((HT * HT / 16) * (COUT / 16) == NW * NB, "the waves' passes must tile the layer exactly");
+    static_assert(NB % 2 == 0 && (COUT / 16) % 2 == 0 && NSTEP % 2 == 0, "passes 2 j and 2 j + 1 must share their tile block");
     const int m = lane & 15, kq = lane >> 4;
     const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
+    f32x4 t0[2][4], t1[2][4], acc[2][4], Va[4], Vb[4];
+    // V fragments of step s: the two window rows of its position row (t[c] = d[ra][c] -/+ d[rb][c], B^T along y), then B^T along x
+    auto window_addr = [&](int s) {
+        const int u = s / (4 * NGRP), G = s % NGRP;
         int ty, tx, cb;
-        wino_tile<H, COUT, NB>(wave, q, m, ty, tx, cb);
-        // top-left cell of the window = output pixel (2 ty - 1, 2 tx - 1), i.e. the halo cell (2 ty, 2 tx) of the padded layout
-        const unsigned a0 = lds_byte_addr(act) + (kq * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4;
-        const int u_lane = wino_u_lane<H, COUT, NB>(wave, q, lane);
-        const int u_next = wino_u_lane<H, COUT, NB>(wave, q + 1 < NB ? q + 1 : q, lane);   // (the layer's last group re-requests its own first group: unused)
-        f32x4 acc[16];
+        wino_tile<H, COUT, NB>(wave, 2 * u, m, ty, tx, cb);
+        unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4);
+        asm("" : "+v"(ab));
+        return ab;
+    };
+    auto read_rows = [&](int s, unsigned ab, f32x4 (&da)[4], f32x4 (&db)[4]) {
+        const int i = (s / NGRP) % 4;
+        const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int G = 0; G < NGRP; ++G) {
-            unsigned ab = a0 + G * 16 * LI::PSG;          // 4 plane groups of PSG floats per K group
-            asm("" : "+v"(ab));
-            f32x4 V[16];
-            wino_window<LI>(ab, V);
-            const bool last = G == NGRP - 1;
-            const int ul = last ? u_next : u_lane, Gn = last ? 0 : G + 1;
-            // the schedule is pinned (sched_barrier): left alone, the compiler issues the MFMAs in the order the transform delivers V (by
-            // channel, all positions), every U register then lives to the end of the group and the 16 loads land in a heap behind the
-            // last MFMA, a few instructions in front of their first use.  Two positions' accumulation chains interleave.
-            __builtin_amdgcn_sched_barrier(0);
+        for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
+    };
+    auto transform = [&](int s, const f32x4 (&da)[4], const f32x4 (&db)[4], f32x4 (&V)[4]) {
+        const int i = (s / NGRP) % 4;
 #pragma unroll
-            for (int k = 0; k < 16; k += 2) {
+        for (int e = 0; e < 4; ++e) {
+            float t[4];
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
-                    acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[k + 1], 0, 0, 0);
+            for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
+            V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
+        }
+    };
+    // one step: the MFMAs of step s on V, with the reads + transform of step s + 1 (into Vn) and the U requests of step s + 1 between them
+    auto step = [&](int s, const f32x4 (&V)[4], f32x4 (&Vn)[4]) {
+        const int u = s / (4 * NGRP), i = (s / NGRP) % 4, G = s % NGRP;
+        const bool more = s + 1 < NSTEP;
+        const int sn = more ? s + 1 : s;                  // (the last step re-requests its own weights: unused)
+        const int un = sn / (4 * NGRP), in = (sn / NGRP) % 4, Gn = sn % NGRP;
+        const int u_next = wino_u_lane<H, COUT, NB>(wave, 2 * un, lane);
+        unsigned abn = 0;
+        if (more) abn = window_addr(sn);
+        if (G == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[c][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 da[4], db[4];
+        if (more) read_rows(sn, abn, da, db);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {              // the two channel blocks' chains of position k interleave
+                acc[0][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[0][k][s4], V[k][s4], acc[0][k], 0, 0, 0);   // U^T x V
+                acc[1][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[1][k][s4], V[k][s4], acc[1][k], 0, 0, 0);
+            }
+            U[0][k] = wino_load_u_pair<CIN, COUT>(wrsrc, u_next, 0, 4 * in + k, Gn);
+            U[1][k] = wino_load_u_pair<CIN, COUT>(wrsrc, u_next, 1, 4 * in + k, Gn);
+        }
+        if (more) {
+            transform(sn, da, db, Vn);
+            // pinned order: MFMAs 1 .. 8 each followed by one row read, U of position 0; MFMAs 9 .. 16, U of position 1; MFMAs 17 .. 32 each followed
+            // by two operations of the transform (the reads have had 8 MFMAs or more to return), U of positions 2 and 3 behind MFMAs 24 and 32
+#pragma unroll
+            for (int l = 0; l < 8; ++l) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int l = 0; l < 8; ++l) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
                 }
-                U[k] = wino_load_u<CIN, COUT>(wrsrc, ul, k, Gn);
-                U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, ul, k + 1, Gn);
-                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
             }
         }
-        wino_output(acc, y[q]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (G == NGRP - 1) {                               // the row's sums over K are complete: y stage of A^T M A, in wino_output's order
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (i == 0) t0[c][j][e] = acc[c][j][e];
+                        else if (i == 1) { t0[c][j][e] = wadd(t0[c][j][e], acc[c][j][e]); t1[c][j][e] = acc[c][j][e]; }
+                        else if (i == 2) { t0[c][j][e] = wadd(t0[c][j][e], acc[c][j][e]); t1[c][j][e] = wsub(t1[c][j][e], acc[c][j][e]); }
+                        else t1[c][j][e] = wsub(t1[c][j][e], acc[c][j][e]);
+                    }
+                if (i == 3) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        y[2 * u + c][0][e] = wadd(wadd(t0[c][0][e], t0[c][1][e]), t0[c][2][e]);
+                        y[2 * u + c][1][e] = wsub(wsub(t0[c][1][e], t0[c][2][e]), t0[c][3][e]);
+                        y[2 * u + c][2][e] = wadd(wadd(t1[c][0][e], t1[c][1][e]), t1[c][2][e]);
+                        y[2 * u + c][3][e] = wsub(wsub(t1[c][1][e], t1[c][2][e]), t1[c][3][e]);
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    {
+        f32x4 da[4], db[4];
+        read_rows(0, window_addr(0), da, db);
+        transform(0, da, db, Va);
+    }
+#pragma unroll
+    for (int s = 0; s < NSTEP; s += 2) {
+        step(s, Va, Vb);
+        step(s + 1, Vb, Va);
     }
 }
 
@@ -1186,7 +1286,7 @@ __device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const flo
         const int Gn = G == NGRP - 1 ? G : G + 1;         // (the last group re-requests itself: unused)
         unsigned vb = v0 + Gn * 16 * 1024;
         asm("" : "+v"(vb));
-        __builtin_amdgcn_sched_barrier(0);                // pinned as in conv3x3_wino_mfma
+        __builtin_amdgcn_sched_barrier(0);                // pinned: two positions' chains interleave, their U and V reloads follow
 #pragma unroll
         for (int k = 0; k < 16; k += 2) {
 #pragma unroll
@@ -1205,12 +1305,12 @@ __device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const flo
 }
 
 // The same layer for the 16-channel trunks (AffNet / OriNet conv1, conv3), which live on 128 registers per lane (two workgroups per CU): acc[16] + U[16] +
-// V[16] of conv3x3_wino_mfma do not fit.  The output transform is linear in the positions, so a wave walks ONE ROW of four positions xi = 4 i .. 4 i + 3 at a
+// V[16] of a whole-window loop do not fit.  The output transform is linear in the positions, so a wave walks ONE ROW of four positions xi = 4 i .. 4 i + 3 at a
 // time: row i of V needs two rows of the window (B^T along y: rows (0, 2), (1, 2), (2, 1), (1, 3)), 8 ds_read_b128 and 32 VALU operations; the row's four
-// accumulators run over all K groups (same K order per position as conv3x3_wino_mfma: G ascending, four k-steps each) and are then folded into the y stage of
+// accumulators run over all K groups (same K order per position as every Winograd loop here: G ascending, four k-steps each) and are then folded into the y stage of
 // A^T M A - t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3, operation by operation what wino_output does - before the next row starts.  Live: 4 accumulators, 4 U
 // fragments, 4 V fragments, t0 / t1.  Per K group the window rows 1 and 2 are read twice (32 instead of 16 ds_read_b128), the VALU work is the same.
-// U enters holding row 0 / group 0 of pass 0 (wino_prefetch_u_row) and rolls one step ahead in its single register set, as in conv3x3_wino_mfma.
+// U enters holding row 0 / group 0 of pass 0 (wino_prefetch_u_row) and rolls one step ahead in its single register set.
 // Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (cnn32.hip: wino_derive_u_kernel).
 template <int NW, int CIN, int COUT, int H, int NB>
 __device__ __forceinline__ void wino_prefetch_u_row(const float* __restrict__ Wu, f32x4 (&U)[4], int wave, int lane) {
@@ -1254,7 +1354,7 @@ __device__ __forceinline__ void conv3x3_wino_mfma_rows(const float* act, const f
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
-        __builtin_amdgcn_sched_barrier(0);                // pinned as in conv3x3_wino_mfma: two positions' chains interleave, their U reloads follow
+        __builtin_amdgcn_sched_barrier(0);                // pinned: two positions' chains interleave, their U reloads follow
 #pragma unroll
         for (int k = 0; k < 4; k += 2) {
 #pragma unroll
