@@ -9,13 +9,14 @@
 //   * the patch is sampled from the pyramid (or loaded), standardised (mean / unbiased std + 1e-7, DPP wave reductions)
 //     and stored as a zero-haloed 34 x 34 LDS tile;
 //   * the exact path runs all six convolutions on v_mfma_f32_16x16x4_f32 (exact fp32): conv0 with K = 9 taps padded to 12 and the
-//     accumulators initialised with the bias; the direct layers (conv2 / conv4 of every net, AffNet conv1..5, OriNet conv5) as implicit GEMMs
+//     accumulators initialised with the bias; the direct layers (conv2 / conv4 of every net, AffNet conv1..5) as implicit GEMMs
 //     (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4
 //     consecutive channels of one pixel; the stride-1 layers as Winograd F(2x2, 3x3), U = G g G^T: HardNet's conv1 / conv3
 //     (conv3x3_wino_mfma_pair_rows: two channel blocks share one window transform, one row of four transform positions per step, the next
 //     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob;
 //     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
-//     blob's taps by wino_derive_u_kernel in front of every launch).  AffNet stays in the direct form:
+//     blob's taps by wino_derive_u_kernel in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
+//     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet stays in the direct form:
 //     the shape filter behind it turns on the last bits of its output, and another rounding changes which keypoints come back.  The
 //     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
@@ -87,6 +88,61 @@ __device__ __forceinline__ void head_partials(const float* __restrict__ hw, cons
 //   out[o][qy][qx] = sum over (ky, kx, c) of  W[o][ky][kx][c] * A[qy + ky - 1][qx + kx - 1][c]      (A = 0 outside the 8 x 8 map)
 // Same products as before, grouped by weight position instead of activation position; same [wave][o * 9 + q] partial layout.
 #define ORI_HP 68        // floats per pixel of the LDS copy (64 channels + 4: consecutive pixels 4 banks apart)
+// The head's two halves for the Winograd conv5 of the exact trunk.  First half: the conv5 output (bias + ReLU) into the zero-haloed 10 x 10 copy -
+// ori_head_zero_halo, and the loop's 2 x 2-pixel fragments through wino5_store_lds (cnn_mfma.h).  Second half: ori_head_reduce, lane-owned weights
+// (ori_head_weights, requested ahead of the barriers) against the nine shifted activations, after a barrier.
+struct OriHeadLane {     // the lane's weight position: pixel n of tiles mg * TM + i, channels c4 .. c4 + 3
+    int mg, n, c4;
+    template <int TM>
+    __device__ __forceinline__ static OriHeadLane of(int wave, int lane) {
+        constexpr int MT = 4, MG = MT / TM;
+        const int mg = wave % MG, ng = wave / MG;
+        const int n = lane & 15, g = lane >> 4;
+        return {mg, n, ng * 16 + 4 * g};
+    }
+};
+template <int TM>
+__device__ __forceinline__ void ori_head_weights(const float* __restrict__ hw, const OriHeadLane& L, f32x4 (&w)[2][TM]) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 2 * 4096);
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) w[o][i] = buf_read4(r, (L.n * 64 + L.c4) * 4, (o * 4096 + (L.mg * TM + i) * 16 * 64) * 4);
+}
+template <int NTHR>
+__device__ __forceinline__ void ori_head_zero_halo(float* act, int tid) {
+    for (int e = tid; e < 36 * 16; e += NTHR) {                          // zero halo of the 10 x 10 grid: 36 pixels x 16 float4
+        const int hp = e >> 4, q4 = e & 15;
+        const int y = hp < 10 ? 0 : (hp < 20 ? 9 : 1 + ((hp - 20) >> 1)), x = hp < 10 ? hp : (hp < 20 ? hp - 10 : ((hp - 20) & 1) * 9);
+        *reinterpret_cast<f32x4*>(&act[(y * 10 + x) * ORI_HP + 4 * q4]) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+template <int TM>
+__device__ __forceinline__ void ori_head_pbase(const OriHeadLane& L, int (&pbase)[TM]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int p = (L.mg * TM + i) * 16 + L.n;
+        pbase[i] = ((p >> 3) * 10 + (p & 7)) * ORI_HP + L.c4;           // (ky, kx) in padded coordinates of tap q = (0, 0)
+    }
+}
+template <int TM>
+__device__ __forceinline__ void ori_head_reduce(const f32x4 (&w)[2][TM], const int (&pbase)[TM], float* __restrict__ part, const float* act, int wave, int lane) {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(&act[pbase[i] + ((q / 3) * 10 + q % 3) * ORI_HP]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { s0 = fmaf(av[j], w[0][i][j], s0); s1 = fmaf(av[j], w[1][i][j], s1); }
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        if (lane == 0) { part[wave * 18 + q] = s0; part[wave * 18 + 9 + q] = s1; }
+    }
+}
+// The direct form's head in one piece (the split-operand OriNet trunks): both halves as above, kept as one body so that those kernels' code does not move.
 template <int TM, int NTHR>
 __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ hw, const f32x4 (&bias)[1], const f32x4 (&acc)[TM][1],
                                                       float* __restrict__ part, float* act, int wave, int lane, int tid) {
@@ -143,7 +199,7 @@ struct PyrSrc {            // pyramid sampling source (fused sampler)
 struct CnnArgs {
     const float* packed;
     NetOffsets off;
-    const float* wino_u;   // exact OriNet: U = G g G^T of conv1 and conv3, derived from the blob in front of this launch (wino_derive_u_kernel)
+    const float* wino_u;   // exact OriNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel)
     const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
     const float* lafs;     // normalised LAFs when sampling
     const int32_t* ids;    // (octave, level, *) when sampling
@@ -180,24 +236,27 @@ __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, i
         if (STAMPS && a.dbg_time && lane == 0) a.dbg_time[((size_t)pidx * NW + wave) * 32 + (k)] = __builtin_readcyclecounter(); \
     } while (0)
 
-// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32; the AffNet blob has the same shapes and the debug accessor derives it too), in w_tap_index order like NetLayout::w_wino.
+// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32, conv5 64 -> 64; the AffNet blob has the same shapes and the debug accessor derives it too), in w_tap_index order like NetLayout::w_wino.
 // Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
 // BN-folded fp32 taps into a buffer the context owns, one region per net kind.
 struct Wino16 {
-    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, FLOATS = U1 + U3;     // floats per net
+    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, U5 = 16 * 64 * 64, FLOATS = U1 + U3 + U5;   // floats per net
+    static constexpr int PAIRS = 16 * 16 + 32 * 32 + 64 * 64;                        // (cin, cout) pairs of the three layers
     static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
+    static constexpr int offset(int layer) { return layer == 1 ? 0 : (layer == 3 ? U1 : U1 + U3); }
+    static constexpr int floats(int layer) { return layer == 1 ? U1 : (layer == 3 ? U3 : U5); }
 };
 
-// One thread per (cin, cout) pair of conv1 (256) and conv3 (1024), numbered in the fragment order (so that a wave's loads and stores are contiguous): reads its
+// One thread per (cin, cout) pair of conv1 (256), conv3 (1024) and conv5 (4096), numbered in the fragment order (so that a wave's loads and stores are contiguous): reads its
 // 9 taps and writes its 16 transform positions, both in w_tap_index order; the transform and its operation order are wino_weight_transform's (weights_layout.h).
-__global__ __launch_bounds__(256) void wino_derive_u_kernel(const float* __restrict__ packed, int w1, int w3, float* __restrict__ U) {
+__global__ __launch_bounds__(256) void wino_derive_u_kernel(const float* __restrict__ packed, int w1, int w3, int w5, float* __restrict__ U) {
     int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= 256 + 1024) return;
-    const bool l3 = e >= 256;
-    const int ch = l3 ? 32 : 16;                                        // cin == cout
-    const float* src = packed + (l3 ? w3 : w1);
-    float* dst = U + (l3 ? Wino16::U1 : 0);
-    if (l3) e -= 256;
+    if (e >= Wino16::PAIRS) return;
+    const int l = e >= 256 + 1024 ? 5 : (e >= 256 ? 3 : 1);
+    const int ch = 8 << ((l + 1) >> 1);                                 // cin == cout: 16, 32, 64
+    const float* src = packed + (l == 5 ? w5 : (l == 3 ? w3 : w1));
+    float* dst = U + Wino16::offset(l);
+    e -= l == 5 ? 256 + 1024 : (l == 3 ? 256 : 0);
     const int n = (e >> 2) % ch, c = (e >> 2) / ch * 4 + (e & 3);       // e == w_tap_index(0, c, n, ch, ch)
     float g[9], u[16];
 #pragma unroll
@@ -305,7 +364,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     f32x4 bias0[S::T1N];
     conv0_load_w<NW, CB, S::T1M, S::T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
     f32x4 b1[1][S::T1N];
-    f32x4 Ur[4];                                                      // exact OriNet: the rolling U register set of conv1 / conv3
+    f32x4 Ur[4];                                                      // exact OriNet: the rolling U register set of conv1 / conv3 / conv5
     if constexpr (S3 == 0 && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
     if constexpr (S3 == 0 && KIND == AFFNET_NET_ORINET) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
 
@@ -475,12 +534,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         CNN_STAMP(12);
         if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
     } else if constexpr (S3 == 0) {
-        // Exact AffNet / OriNet.  OriNet: conv1 and conv3 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
+        // Exact AffNet / OriNet.  OriNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
         // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which
         // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet keeps conv1 .. conv5 in the direct form: its output decides the
         // shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST bits of A for near-isotropic shapes, so any other
-        // rounding changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline configuration).  conv0, conv2, conv4 and conv5 in
-        // the direct form for both, conv5 straight into the heads.
+        // rounding changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline configuration).  conv0, conv2, conv4 (and AffNet's conv5) in
+        // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators, OriNet from its Winograd fragments).
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
         f32x4 b4[S::G4][T4N];
@@ -524,7 +583,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
                 f32x4 acc[T2M][T2N];
                 conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
                 CNN_STAMP(5);
-                wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::U1, Ur, wave, lane);
+                wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::offset(3), Ur, wave, lane);
                 __syncthreads();
                 zero_halo<LayC2, NTHR>(act, 2 * CB);
                 store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
@@ -536,7 +595,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
             {
                 f32x4 y[NB3][4], bw[NB3];
-                conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::U1, Ur, y, wave, lane);
+                conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::offset(3), Ur, y, wave, lane);
                 CNN_STAMP(7);
                 prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
                 prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
@@ -625,8 +684,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             f32x4 acc[T4M][T4N];
             conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
             CNN_STAMP(9);
-            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G5>(a.packed + a.off.w[5], b5, wave, lane);
-            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
+            if constexpr (KIND == AFFNET_NET_ORINET) {
+                wino5_prefetch_u(a.wino_u + Wino16::offset(5), Ur, wave, lane);
+            } else {
+                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G5>(a.packed + a.off.w[5], b5, wave, lane);
+                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[5], bias5, wave, lane);
+            }
             __syncthreads();
             zero_halo<LayC4, NTHR>(act, 4 * CB);
             store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
@@ -635,15 +698,41 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
 
+        if constexpr (KIND == AFFNET_NET_ORINET) {
+            // ---- conv5: 4CB -> 4CB @8x8, Winograd, a wave pair per channel block (conv3x3_wino_mfma_half_rows, wino5_combine); its 2 x 2-pixel fragments go
+            // into the head's 10 x 10 copy (over conv4's output, which is dead by then), then the head's per-wave partial sums ----
+            static_assert(Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL && Wino5::HEAD + 100 * ORI_HP <= Wino5::X,
+                          "conv5: the exchange lies behind conv4's output inside the LDS array, the head copy in front of the exchange");
+            f32x4 acc[2][4], y[2], hw[2][T4M];
+            conv3x3_wino_mfma_half_rows<NW, LayC4>(act, a.wino_u + Wino16::offset(5), Ur, acc, wave, lane);
+            CNN_STAMP(11);
+            const f32x4 bw = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[5] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
+            const OriHeadLane HL = OriHeadLane::of<T4M>(wave, lane);
+            if (!STAMPS || a.dbg_layer < 0) ori_head_weights<T4M>(a.packed + a.off.head_w, HL, hw);
+            wino5_combine(lds, acc, y, wave, lane);
+            if (!STAMPS || a.dbg_layer < 0) {
+                float* copy = lds + Wino5::HEAD;
+                ori_head_zero_halo<NTHR>(copy, tid);
+                wino5_store_lds<10, ORI_HP, 4>(copy + 11 * ORI_HP, bw, y, wave, lane);
+                int pbase[T4M];
+                ori_head_pbase<T4M>(HL, pbase);
+                ori_head_reduce<T4M>(hw, pbase, a.out + pidx * HEAD_PART_ORI, copy, wave, lane);
+                CNN_STAMP(13);
+                return;
+            }
+            __syncthreads();
+            wino5_store_lds<LayC5::WP, 4, LayC5::PSG>(act + (LayC5::WP + 1) * 4, bw, y, wave, lane);   // debug dump only
+            __syncthreads();
+            CNN_STAMP(12);
+            if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
+            return;
+        }
         // ---- conv5: 4CB -> 4CB @8x8, then the head's per-wave partial sums ---------------------------------
         f32x4 acc[T4M][T4N];
         conv3x3_mfma<NW, 4 * CB, 4 * CB, LayC4, 1, T4M, T4N, S::G5>(act, a.packed + a.off.w[5], b5, acc, wave, lane);
         CNN_STAMP(11);
         if (!STAMPS || a.dbg_layer < 0) {
-            if constexpr (KIND == AFFNET_NET_ORINET)   // weights once, shifted activations from LDS
-                head_partials_ori_lds<T4M, NTHR>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_ORI, act, wave, lane, tid);
-            else
-                head_partials<T4M>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_AFF, wave, lane);
+            head_partials<T4M>(a.packed + a.off.head_w, bias5, acc, a.out + pidx * HEAD_PART_AFF, wave, lane);
             CNN_STAMP(13);
             return;
         }
@@ -1308,14 +1397,14 @@ int aff_wino_u_ensure(affnet_ctx* ctx) {
     return AFFNET_OK;
 }
 
-// U of conv1 / conv3 of `packed` (AffNet or OriNet blob) into the context's region of that net, on the launch stream: 1280 threads, 46 KB read, 82 KB written.
+// U of conv1 / conv3 / conv5 of `packed` (AffNet or OriNet blob) into the context's region of that net, on the launch stream: 5376 threads, 194 KB read, 344 KB written.
 // In front of EVERY exact OriNet trunk launch, so that a blob rewritten in place (load_state_dict into the same device buffer) can never meet
 // stale weights, eagerly or in a replayed graph.
 static int wino_derive_u(affnet_ctx* ctx, int kind, const float* packed, const NetLayout& L, hipStream_t st, const float** u) {
     const int rc = aff_wino_u_ensure(ctx);
     if (rc) return rc;
     float* dst = ctx->wino_u + (size_t)kind * Wino16::FLOATS;
-    hipLaunchKernelGGL(wino_derive_u_kernel, dim3(5), dim3(256), 0, st, packed, (int)L.w_off[1], (int)L.w_off[3], dst);
+    hipLaunchKernelGGL(wino_derive_u_kernel, dim3((Wino16::PAIRS + 255) / 256), dim3(256), 0, st, packed, (int)L.w_off[1], (int)L.w_off[3], (int)L.w_off[5], dst);
     AFF_LAUNCH_CHECK(ctx);
     *u = dst;
     return AFFNET_OK;
@@ -1489,12 +1578,12 @@ extern "C" int affnet_cnn32_debug_layer(affnet_ctx* ctx, int net_kind, const flo
 
 extern "C" int affnet_cnn32_debug_winograd_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream) {
     AFF_DEVICE(ctx);
-    if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 1 && layer != 3))
-        return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_debug_winograd_u: AffNet / OriNet, layer 1 or 3");
+    if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 1 && layer != 3 && layer != 5))
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_debug_winograd_u: AffNet / OriNet, layer 1, 3 or 5");
     const float* u;
     const int rc = wino_derive_u(ctx, net_kind, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
     if (rc) return rc;
-    return aff_copy_async(ctx, d_out, u + (layer == 3 ? Wino16::U1 : 0), (size_t)(layer == 3 ? Wino16::U3 : Wino16::U1) * sizeof(float), (hipStream_t)stream);
+    return aff_copy_async(ctx, d_out, u + Wino16::offset(layer), (size_t)Wino16::floats(layer) * sizeof(float), (hipStream_t)stream);
 }
 
 #ifdef AFFNET_PROBES   // libaffnet_hip_probes.so only (include/affnet_hip_probes.h)

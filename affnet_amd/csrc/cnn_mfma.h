@@ -1389,6 +1389,128 @@ __device__ __forceinline__ void conv3x3_wino_mfma_rows(const float* act, const f
     }
 }
 
+// conv5 of the exact OriNet trunk (64 -> 64 @8x8): one block of 16 tiles, four channel blocks, four K groups, 1024 MFMAs = 128 per wave.  Wave w = 2 p + h
+// runs channel block p on the position rows 2 h and 2 h + 1 over all four K groups, as conv3x3_wino_mfma_rows walks its rows: a step is (position row, K
+// group), G fastest (the K order of every Winograd loop here), 8 ds_read_b128 + 32 VALU operations for the row's four V fragments, 16 MFMAs; U rolls one step
+// ahead in its single set and enters holding step 0 (wino5_prefetch_u).  (V is NOT shared through LDS as in HardNet's conv5: V of the layer is 16 positions x 64
+// channels x 16 tiles = 64 KB, which neither fits beside conv4's 43 KB output nor leaves room for the exchange below - sharing would cost three more barriers
+// per patch.)
+// Combine (wino5_combine), in wino_output's operation order: the y stage of A^T M A is t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3 over the position rows m_i.
+// Wave 2 p holds m0, m1 and wave 2 p + 1 holds m2, m3: wave 2 p writes m1 and wave 2 p + 1 writes m2 to its 4 KB slot of Wino5::X, barrier, then wave 2 p forms
+// t0 = (m0 + m1) + m2 and from it output row dy = 0, wave 2 p + 1 forms t1 = (m1 - m2) - m3 and output row dy = 1.  Fixed for every patch and launch, no atomics;
+// the sums are those of wino_output (tools/winograd_numerics.py: wino_conv3x3).  X lies behind conv4's output, which other waves still read when a wave
+// writes its slot, and runs past the activation buffer into the input patch and the reduction slots, both dead since conv0; after the barrier conv4's output is
+// dead and takes the head's copy (Wino5::HEAD), clear of X, which the partner still reads.
+// Result: y[dx] = pre-activation couts 16 p + 4 (lane >> 4) + 0..3 of pixel (2 ty + h, 2 tx + dx), tile (ty, tx) = (m >> 2, m & 3).
+struct Wino5 {                                            // float offsets from the start of the activation buffer
+    static constexpr int X = 16 * LayC4::PSG, X_FLOATS = 8 * 4 * 256;
+    static constexpr int HEAD = 0;
+    static constexpr int U_HALF = 8 * 4 * 16 * 64 * 4;    // bytes of U between positions xi and xi + 8
+};
+__device__ __forceinline__ void wino5_prefetch_u(const float* __restrict__ Wu, f32x4 (&U)[4], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * 64 * 64);
+    const int u_lane = ((lane >> 4) * 64 + (wave >> 1) * 16 + (lane & 15)) * 16 + (wave & 1) * Wino5::U_HALF;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) U[k] = wino_load_u<64, 64>(r, u_lane, k, 0);
+}
+
+template <int NW, typename LI>
+__device__ __forceinline__ void conv3x3_wino_mfma_half_rows(const float* act, const float* __restrict__ Wu, f32x4 (&U)[4], f32x4 (&acc)[2][4], int wave, int lane) {
+    constexpr int CIN = 64, COUT = 64, NGRP = CIN / 16, NSTEP = 2 * NGRP;
+    static_assert(NW == 8 && LI::H == 8, "one tile block; a wave pair per channel block");
+    const int m = lane & 15, kq = lane >> 4, p = wave >> 1;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
+    const int u_lane = (kq * COUT + p * 16 + m) * 16;
+    const unsigned a0 = lds_byte_addr(act) + ((kq * LI::PSG + (2 * (m >> 2) * LI::WP + 2 * (m & 3)) * 4) * 4);
+    auto rows = [&](auto hc) {                            // the loop of the wave's half: position rows 2 H2 and 2 H2 + 1 are compile-time constants
+        constexpr int H2 = decltype(hc)::v;
+#pragma unroll
+        for (int s = 0; s < NSTEP; ++s) {                 // step = (position row i, K group G), G fastest
+            const int il = s / NGRP, i = 2 * H2 + il, G = s % NGRP;
+            const int sn = s + 1 < NSTEP ? s + 1 : s;     // (the last step re-requests its own weights: unused)
+            const int in = 2 * H2 + sn / NGRP, Gn = sn % NGRP;
+            // window rows of position row i: t[c] = d[ra][c] -/+ d[rb][c]
+            const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
+            unsigned ab = a0 + 4 * G * LI::PSG * 4;
+            asm("" : "+v"(ab));
+            f32x4 da[4], db[4], V[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
+                V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
+            }
+            if (G == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[il][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+            __builtin_amdgcn_sched_barrier(0);            // pinned: two positions' chains interleave, their U reloads follow
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) {
+                    acc[il][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[il][k], 0, 0, 0);
+                    acc[il][k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[il][k + 1], 0, 0, 0);
+                }
+                U[k] = wino_load_u<CIN, COUT>(wrsrc, u_lane, 4 * in + k, Gn);
+                U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, u_lane, 4 * in + k + 1, Gn);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    if ((wave & 1) == 0) rows(IntC<0>{}); else rows(IntC<1>{});
+}
+
+// `lds` = the start of the activation buffer
+__device__ __forceinline__ void wino5_combine(float* lds, const f32x4 (&acc)[2][4], f32x4 (&y)[2], int wave, int lane) {
+    const int h = wave & 1;
+    float* xw = lds + Wino5::X + (wave * 4 * 64 + lane) * 4;
+    const float* xr = lds + Wino5::X + ((wave ^ 1) * 4 * 64 + lane) * 4;
+    if (h == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&xw[j * 256]) = acc[1][j];       // m1
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&xw[j * 256]) = acc[0][j];       // m2
+    }
+    __syncthreads();                                      // the partner's row is in place; every wave has finished reading conv4's output
+    f32x4 o[4], t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = *reinterpret_cast<const f32x4*>(&xr[j * 256]);
+    if (h == 0) {                                         // t0 = (m0 + m1) + m2
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[j][e] = wadd(wadd(acc[0][j][e], acc[1][j][e]), o[j][e]);
+    } else {                                              // t1 = (m1 - m2) - m3
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[j][e] = wsub(wsub(o[j][e], acc[0][j][e]), acc[1][j][e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        y[0][e] = wadd(wadd(t[0][e], t[1][e]), t[2][e]);
+        y[1][e] = wsub(wsub(t[1][e], t[2][e]), t[3][e]);
+    }
+}
+
+// + bias, ReLU, store the wave's two pixels x 4 channels per lane: pixel (oy, ox), channel c at dst[(oy * ROW + ox) * PIX + (c / 4) * GRP + c % 4]
+// (a Lay layout: ROW = WP, PIX = 4, GRP = PSG, dst at its pixel (0, 0); the OriNet head copy: ROW = 10, PIX = ORI_HP, GRP = 4)
+template <int ROW, int PIX, int GRP>
+__device__ __forceinline__ void wino5_store_lds(float* dst, f32x4 bias, const f32x4 (&y)[2], int wave, int lane) {
+    const int m = lane & 15, oy = 2 * (m >> 2) + (wave & 1), ox = 2 * (m & 3);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        f32x4 v = y[k] + bias;
+        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        *reinterpret_cast<f32x4*>(&dst[(oy * ROW + ox + k) * PIX + ((wave >> 1) * 4 + (lane >> 4)) * GRP]) = v;
+    }
+}
+
 // bias of the lane's four output channels in each pass
 template <int NW, int H, int COUT, int NB>
 __device__ __forceinline__ void wino_bias(const float* __restrict__ bias, f32x4 (&bv)[NB], int wave, int lane) {

@@ -114,7 +114,7 @@ struct affnet_ctx {
     // the whole path captured as one HIP graph (affnet_graph_capture_extract): one launch instead of ~45 for latency-bound callers
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
-    // Winograd weights U = G g G^T of conv1 / conv3 of the exact AffNet / OriNet trunks, derived from the caller's blob in front of every trunk launch
+    // Winograd weights U = G g G^T of conv1 / conv3 / conv5 of the exact AffNet / OriNet trunks, derived from the caller's blob in front of every trunk launch
     // (cnn32.hip: wino_derive_u_kernel); the only device memory a context owns, allocated on first use (aff_wino_u_ensure)
     float* wino_u = nullptr;
     ~affnet_ctx() {

@@ -24,7 +24,7 @@ extern "C" {
 int affnet_cnn32_debug_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch,
                              int layer, float* d_out, void* stream);
 
-/* Parity aid: derives U = G g G^T of trunk layer `layer` (1 or 3) of the AffNet / OriNet blob d_packed exactly as every exact-fp32 trunk launch of
+/* Parity aid: derives U = G g G^T of trunk layer `layer` (1, 3 or 5) of the AffNet / OriNet blob d_packed exactly as every exact-fp32 trunk launch of
  * these nets does (same kernel, same context buffer) and copies it to d_out: 16 * cin * cout floats, [xi = 4 i + j][cin / 16][(c / 4) % 4][cout][c % 4]. */
 int affnet_cnn32_debug_winograd_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream);
 

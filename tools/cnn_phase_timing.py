@@ -14,10 +14,14 @@ dev = torch.device("cuda:0")
 n = int(os.environ.get("PHASE_PATCHES", "2048"))      # 256 = one workgroup per CU: the phases without a co-resident workgroup
 p = (torch.rand(n, 1, 32, 32) * 255).to(dev)
 A = affnet_amd.AffNetFast(); A.load_state_dict(torch.load(os.path.join(ROOT, "pretrained/AffNet.pth"), map_location="cpu", weights_only=False)["state_dict"]); A.to(dev)
+O = affnet_amd.OriNetFast(); O.load_state_dict(torch.load(os.path.join(ROOT, "pretrained/OriNet.pth"), map_location="cpu", weights_only=False)["state_dict"]); O.to(dev)
 H = affnet_amd.HardNet(); H.load_state_dict(affnet_amd.synthetic_hardnet_state(0)); H.to(dev)
 names = ["input+norm", "conv0", "conv1 mfma", "conv1 store", "conv2 mfma", "conv2 store", "conv3 mfma", "conv3 store",
          "conv4 mfma", "conv4 store", "conv5 mfma", "conv5 store"]
-for net, nm, nw in [(A, "AffNet", 8), (H, "HardNet", 8)]:
+only = os.environ.get("PHASE_NETS")                    # e.g. PHASE_NETS=OriNet: that net's table alone
+for net, nm, nw in [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]:
+    if only and nm not in only.split(","):
+        continue
     net(p); torch.cuda.synchronize()
     st = torch.zeros(n * nw * 32, dtype=torch.int64, device=dev)
     lib.affnet_cnn32_debug_timing(engine.utility_ctx(dev), ptr(st))
@@ -82,5 +86,5 @@ for net, nm, nw in [(A, "AffNet", 8), (H, "HardNet", 8)]:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "HardNet": 78184448.0}[nm]
+    fl = {"AffNet": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """CPU mirror of the Winograd F(2x2, 3x3) layers (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma for HardNet's conv1 / conv3 / conv5,
-conv3x3_wino_mfma_rows for conv1 / conv3 of OriNet; the AffNet mirror prices the same change for AffNet, which stays direct) and the error they add.
+conv3x3_wino_mfma_rows for conv1 / conv3 and conv3x3_wino_mfma_half_rows + wino5_combine for conv5 of OriNet; the AffNet mirror prices the same change for AffNet, which stays direct) and the error they add.
 
 The transforms follow the kernel's operation order one add / multiply at a time in the input's dtype:
     U = G g G^T   along x, then y:  s = g0 + g2;  (g0, 0.5 (s + g1), 0.5 (s - g1), g2)
@@ -11,7 +11,7 @@ summation order changes the last bits, not the size of the error).  BatchNorm is
 weights of the kernel are.
 
     python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32 and Winograd fp32
-    python tools/winograd_numerics.py --net affnet|orinet [--layers 1,3]
+    python tools/winograd_numerics.py --net affnet|orinet [--layers 1,3,5]
         -> per trunk layer and at the pooled head output: max |x - float64 forward| of direct fp32 and Winograd fp32 (shipped checkpoints,
            tests/golden/cnn_random_patches.npz and --n smooth seeded patches); OriNet also the error of the angle
 """
@@ -30,7 +30,8 @@ for _p in (ROOT, os.path.join(ROOT, "oracle")):
 import affnet_oracle as orc  # noqa: E402
 
 WINO_LAYERS = (1, 3, 5)          # HardNet's stride-1 layers after conv0: conv1, conv3, conv5
-WINO_LAYERS_16 = (1, 3)          # OriNet (and the AffNet mirror): conv1 and conv3 (conv5 feeds the heads from the direct form's accumulators)
+WINO_LAYERS_16 = (1, 3, 5)       # OriNet (and the AffNet mirror): conv1, conv3 and conv5.  conv5's two waves per channel block combine their position rows in
+                                 # _at_axis's order - (m0 + m1) + m2 in the wave of rows 0, 1, (m1 - m2) - m3 in the wave of rows 2, 3 (cnn_mfma.h: wino5_combine)
 
 
 def _g_axis(g0, g1, g2):
@@ -186,7 +187,7 @@ def main():
     ap.add_argument("--n", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--net", choices=("hardnet", "affnet", "orinet"), default="hardnet")
-    ap.add_argument("--layers", default="1,3", help="Winograd layers of the AffNet / OriNet mirror")
+    ap.add_argument("--layers", default="1,3,5", help="Winograd layers of the AffNet / OriNet mirror")
     args = ap.parse_args()
     if args.net != "hardnet":
         import numpy as np
