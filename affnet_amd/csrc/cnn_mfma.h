@@ -517,14 +517,19 @@ __device__ __forceinline__ void zero_halo_q(float* act, int tid = threadIdx.x) {
     }
 }
 
+// The epilogues' ReLU and + bias, ReLU of one float4 (the lane's four channels of a pixel)
+__device__ __forceinline__ f32x4 relu4(f32x4 v) {
+    v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+    return v;
+}
+__device__ __forceinline__ f32x4 bias_relu(f32x4 y, f32x4 bias) { return relu4(y + bias); }
+
 // (+ bias,) ReLU, split into three bf16 terms, store ONE pixel tile into a LayQ layout: `cell` = byte offset of the lane's pixel cell
 template <typename LO, int TN, bool ADD_BIAS = true>
 __device__ __forceinline__ void split_store_tile_q(char* base, int cell, int nt0, const f32x4 (&bias)[TN], const f32x4 (&acc)[TN], int g) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        f32x4 v = acc[j];
-        if (ADD_BIAS) v += bias[j];
-        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        const f32x4 v = ADD_BIAS ? bias_relu(acc[j], bias[j]) : relu4(acc[j]);
         const int c0 = (nt0 + j) * 16 + 4 * g;                           // first of this lane's 4 channels
         char* dst = base + (c0 >> 3) * LO::GS + cell + (c0 & 4) * 2;
         split_store4<LO::TERMS, LO::TSTEP>(dst, v);
@@ -980,9 +985,7 @@ __device__ __forceinline__ void store_tiles_lds(float* act, const f32x4 (&bias)[
         const int pbase = ((oy + 1) * LO::WP + ox + 1) * 4;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            f32x4 v = acc[i][j];
-            if (ADD_BIAS) v += bias[j];
-            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            const f32x4 v = ADD_BIAS ? bias_relu(acc[i][j], bias[j]) : relu4(acc[i][j]);
             *reinterpret_cast<f32x4*>(&act[((ng * TN + j) * 4 + g) * LO::PSG + pbase]) = v;
         }
     }
@@ -1000,15 +1003,14 @@ __device__ __forceinline__ void store_tiles_global(float* __restrict__ dst, cons
         const int p = (mg * TM + i) * 16 + n;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            f32x4 v = acc[i][j] + bias[j];
-            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            const f32x4 v = bias_relu(acc[i][j], bias[j]);
             *reinterpret_cast<f32x4*>(dst + p * COUT + (ng * TN + j) * 16 + 4 * g) = v;
         }
     }
 }
 
 
-// ---- Winograd F(2x2, 3x3) on v_mfma_f32_16x16x4_f32 (HardNet's stride-1 layers on the exact path) ----------------------------------
+// ---- Winograd F(2x2, 3x3) on v_mfma_f32_16x16x4_f32 (the stride-1 layers of the exact HardNet and OriNet trunks) -------------------
 // A 2x2 output tile is  Y = A^T [ (G g G^T) (.) (B^T d B) ] A  over its 4x4 input window d: 16 products per (cin, cout) instead of 36,
 // i.e. 16 GEMMs (one per transform position xi = 4 i + j) of [cout x cin] x [cin x tile], 4/9 of the direct form's MFMAs.
 //   B^T d along an axis: (d0 - d2, d1 + d2, d2 - d1, d1 - d3)             (y first, then x)
@@ -1047,10 +1049,11 @@ __device__ __forceinline__ int wino_u_lane(int wave, int q, int lane) {
 }
 
 // U of K group G: one buffer_load_dwordx4 per transform position = the A operand of its four k-steps.  Wu = the packed U = G g G^T
-// [xi][CIN/16][kq][COUT][4] (NetLayout::w_wino), computed once at pack time with the operation order above.
+// [xi][CIN/16][kq][COUT][4] (NetLayout::w_wino), computed once at pack time with the operation order above.  c: channel blocks past the lane's own
+// (256 bytes = 16 couts each; the second block of a pair in conv3x3_wino_mfma_pair_rows)
 template <int CIN, int COUT>
-__device__ __forceinline__ f32x4 wino_load_u(__amdgpu_buffer_rsrc_t r, int u_lane, int k, int G) {
-    return buf_read4(r, u_lane, (k * (CIN / 16) + G) * 16 * COUT * 4);
+__device__ __forceinline__ f32x4 wino_load_u(__amdgpu_buffer_rsrc_t r, int u_lane, int k, int G, int c = 0) {
+    return buf_read4(r, u_lane, (k * (CIN / 16) + G) * 16 * COUT * 4 + c * 256);
 }
 
 // U of the first K group of the wave's first pass: does not depend on the activations, so the kernel requests it BEFORE the barrier in
@@ -1063,7 +1066,33 @@ __device__ __forceinline__ void wino_prefetch_u(const float* __restrict__ Wu, f3
     for (int k = 0; k < 16; ++k) U[k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0);
 }
 
-// V = B^T d B of the 4x4 window at LDS byte address `ab` (16 ds_read_b128: the lane's four interleaved channels), along y, then along x
+// Position row i of V = B^T d B (xi = 4 i .. 4 i + 3) needs two rows of the window: B^T along y is t[c] = d[ra][c] -/+ d[rb][c] over the window rows
+// (ra, rb) = (0, 2), (1, 2), (2, 1), (1, 3), a sum for i == 1 and a difference otherwise.
+__device__ __forceinline__ constexpr int wino_row_a(int i) { return i == 0 ? 0 : (i == 2 ? 2 : 1); }
+__device__ __forceinline__ constexpr int wino_row_b(int i) { return i == 2 ? 1 : (i == 3 ? 3 : 2); }
+
+// The two window rows of position row i at LDS byte address `ab` of the window (8 ds_read_b128: the lane's four interleaved channels)
+template <typename LI>
+__device__ __forceinline__ void wino_read_rows(unsigned ab, int i, f32x4 (&da)[4], f32x4 (&db)[4]) {
+    const int ra = wino_row_a(i), rb = wino_row_b(i);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
+}
+
+// The four V fragments V[0 .. 3] of position row i from its two window rows: B^T along y, then along x (32 VALU operations)
+__device__ __forceinline__ void wino_transform_row(int i, const f32x4 (&da)[4], const f32x4 (&db)[4], f32x4* V) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
+        V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
+    }
+}
+
+// V = B^T d B of the 4x4 window at LDS byte address `ab` (16 ds_read_b128: the lane's four interleaved channels), along y, then along x: the arithmetic of
+// wino_transform_row for all four rows at once, lane by lane (written as four calls it compiles to another instruction order in conv5 of HardNet:
+// profiles/wino_helpers_report.md)
 template <typename LI>
 __device__ __forceinline__ void wino_window(unsigned ab, f32x4 (&V)[16]) {
     f32x4 d[4][4];
@@ -1119,10 +1148,6 @@ __device__ __forceinline__ void wino_output(const f32x4 (&acc)[16], f32x4 (&yq)[
 // tools/probes/mfma_valu_overlap.hip), in two V register sets Va / Vb that swap by name.  U enters holding step 0 (wino_prefetch_u_pair, requested in front
 // of the barrier before the layer) and rolls one step ahead in its single set: fragment (c, k) of the next step is requested once the MFMAs of position k
 // have issued, 24 MFMAs or more in front of its use.
-template <int CIN, int COUT>
-__device__ __forceinline__ f32x4 wino_load_u_pair(__amdgpu_buffer_rsrc_t r, int u_lane, int c, int k, int G) {
-    return buf_read4(r, u_lane, (k * (CIN / 16) + G) * 16 * COUT * 4 + c * 256);
-}
 template <int NW, int CIN, int COUT, int H, int NB>
 __device__ __forceinline__ void wino_prefetch_u_pair(const float* __restrict__ Wu, f32x4 (&U)[2][4], int wave, int lane) {
     const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);
@@ -1130,7 +1155,7 @@ __device__ __forceinline__ void wino_prefetch_u_pair(const float* __restrict__ W
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) U[c][k] = wino_load_u_pair<CIN, COUT>(r, u_lane, c, k, 0);
+        for (int c = 0; c < 2; ++c) U[c][k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0, c);
 }
 
 template <int NW, int CIN, int COUT, typename LI, int NB>
@@ -1142,7 +1167,6 @@ __device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, co
     const int m = lane & 15, kq = lane >> 4;
     const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, 16 * CIN * COUT);
     f32x4 t0[2][4], t1[2][4], acc[2][4], Va[4], Vb[4];
-    // V fragments of step s: the two window rows of its position row (t[c] = d[ra][c] -/+ d[rb][c], B^T along y), then B^T along x
     auto window_addr = [&](int s) {
         const int u = s / (4 * NGRP), G = s % NGRP;
         int ty, tx, cb;
@@ -1150,22 +1174,6 @@ __device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, co
         unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4);
         asm("" : "+v"(ab));
         return ab;
-    };
-    auto read_rows = [&](int s, unsigned ab, f32x4 (&da)[4], f32x4 (&db)[4]) {
-        const int i = (s / NGRP) % 4;
-        const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
-    };
-    auto transform = [&](int s, const f32x4 (&da)[4], const f32x4 (&db)[4], f32x4 (&V)[4]) {
-        const int i = (s / NGRP) % 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float t[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
-            V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
-        }
     };
     // one step: the MFMAs of step s on V, with the reads + transform of step s + 1 (into Vn) and the U requests of step s + 1 between them
     auto step = [&](int s, const f32x4 (&V)[4], f32x4 (&Vn)[4]) {
@@ -1184,7 +1192,7 @@ __device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, co
         }
         __builtin_amdgcn_sched_barrier(0);
         f32x4 da[4], db[4];
-        if (more) read_rows(sn, abn, da, db);
+        if (more) wino_read_rows<LI>(abn, in, da, db);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
 #pragma unroll
@@ -1192,11 +1200,11 @@ __device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, co
                 acc[0][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[0][k][s4], V[k][s4], acc[0][k], 0, 0, 0);   // U^T x V
                 acc[1][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[1][k][s4], V[k][s4], acc[1][k], 0, 0, 0);
             }
-            U[0][k] = wino_load_u_pair<CIN, COUT>(wrsrc, u_next, 0, 4 * in + k, Gn);
-            U[1][k] = wino_load_u_pair<CIN, COUT>(wrsrc, u_next, 1, 4 * in + k, Gn);
+            U[0][k] = wino_load_u<CIN, COUT>(wrsrc, u_next, 4 * in + k, Gn, 0);
+            U[1][k] = wino_load_u<CIN, COUT>(wrsrc, u_next, 4 * in + k, Gn, 1);
         }
         if (more) {
-            transform(sn, da, db, Vn);
+            wino_transform_row(in, da, db, Vn);
             // pinned order: MFMAs 1 .. 8 each followed by one row read, U of position 0; MFMAs 9 .. 16, U of position 1; MFMAs 17 .. 32 each followed
             // by two operations of the transform (the reads have had 8 MFMAs or more to return), U of positions 2 and 3 behind MFMAs 24 and 32
 #pragma unroll
@@ -1245,8 +1253,8 @@ __device__ __forceinline__ void conv3x3_wino_mfma_pair_rows(const float* act, co
     };
     {
         f32x4 da[4], db[4];
-        read_rows(0, window_addr(0), da, db);
-        transform(0, da, db, Va);
+        wino_read_rows<LI>(window_addr(0), 0, da, db);
+        wino_transform_row(0, da, db, Va);
     }
 #pragma unroll
     for (int s = 0; s < NSTEP; s += 2) {
@@ -1336,20 +1344,11 @@ __device__ __forceinline__ void conv3x3_wino_mfma_rows(const float* act, const f
         int ty, tx, cb;
         wino_tile<H, COUT, NB>(wave, q, m, ty, tx, cb);
         const int u_next = wino_u_lane<H, COUT, NB>(wave, qn, lane);
-        // window rows of position row i: t[c] = d[ra][c] -/+ d[rb][c]
-        const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
         unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (2 * ty * LI::WP + 2 * tx) * 4) * 4);
         asm("" : "+v"(ab));
         f32x4 da[4], db[4], V[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float t[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
-            V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
-        }
+        wino_read_rows<LI>(ab, i, da, db);
+        wino_transform_row(i, da, db, V);
         if (G == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1429,20 +1428,11 @@ __device__ __forceinline__ void conv3x3_wino_mfma_half_rows(const float* act, co
             const int il = s / NGRP, i = 2 * H2 + il, G = s % NGRP;
             const int sn = s + 1 < NSTEP ? s + 1 : s;     // (the last step re-requests its own weights: unused)
             const int in = 2 * H2 + sn / NGRP, Gn = sn % NGRP;
-            // window rows of position row i: t[c] = d[ra][c] -/+ d[rb][c]
-            const int ra = i == 0 ? 0 : (i == 2 ? 2 : 1), rb = i == 2 ? 1 : (i == 3 ? 3 : 2);
             unsigned ab = a0 + 4 * G * LI::PSG * 4;
             asm("" : "+v"(ab));
             f32x4 da[4], db[4], V[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { da[c] = lds_read4(ab + (ra * LI::WP + c) * 16); db[c] = lds_read4(ab + (rb * LI::WP + c) * 16); }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) t[c] = i == 1 ? wadd(da[c][e], db[c][e]) : wsub(da[c][e], db[c][e]);
-                V[0][e] = wsub(t[0], t[2]); V[1][e] = wadd(t[1], t[2]); V[2][e] = wsub(t[2], t[1]); V[3][e] = wsub(t[1], t[3]);
-            }
+            wino_read_rows<LI>(ab, i, da, db);
+            wino_transform_row(i, da, db, V);
             if (G == 0) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[il][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1505,8 +1495,7 @@ __device__ __forceinline__ void wino5_store_lds(float* dst, f32x4 bias, const f3
     const int m = lane & 15, oy = 2 * (m >> 2) + (wave & 1), ox = 2 * (m & 3);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        f32x4 v = y[k] + bias;
-        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        const f32x4 v = bias_relu(y[k], bias);
         *reinterpret_cast<f32x4*>(&dst[(oy * ROW + ox + k) * PIX + ((wave >> 1) * 4 + (lane >> 4)) * GRP]) = v;
     }
 }
@@ -1533,8 +1522,7 @@ __device__ __forceinline__ void wino_store_lds(float* act, const f32x4 (&bias)[N
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int oy = 2 * ty + (k >> 1), ox = 2 * tx + (k & 1);
-            f32x4 v = y[q][k] + bias[q];
-            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            const f32x4 v = bias_relu(y[q][k], bias[q]);
             *reinterpret_cast<f32x4*>(&act[(cb * 4 + g) * LO::PSG + ((oy + 1) * LO::WP + ox + 1) * 4]) = v;
         }
     }
@@ -1551,8 +1539,7 @@ __device__ __forceinline__ void wino_store_global(float* __restrict__ dst, const
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int p = (2 * ty + (k >> 1)) * H + 2 * tx + (k & 1);
-            f32x4 v = y[q][k] + bias[q];
-            v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+            const f32x4 v = bias_relu(y[q][k], bias[q]);
             *reinterpret_cast<f32x4*>(dst + p * COUT + cb * 16 + 4 * g) = v;
         }
     }

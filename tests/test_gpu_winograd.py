@@ -1,4 +1,5 @@
-"""HardNet on the exact path runs conv1, conv3 and conv5 as Winograd F(2x2, 3x3) (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma):
+"""HardNet on the exact path runs conv1, conv3 and conv5 as Winograd F(2x2, 3x3) (affnet_amd/csrc/cnn_mfma.h:
+conv3x3_wino_mfma_pair_rows for conv1 / conv3, conv3x3_wino_mfma_shared_v for conv5):
 the descriptors against a float64 forward of the same network, on ragged batch sizes and on degenerate patches, and bit-equal from
 run to run."""
 import os

@@ -1,5 +1,5 @@
 """HardNet's Winograd layers read their transformed weights U = G g G^T from the packed blob and conv5 shares its window transform
-through LDS (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma, conv3x3_wino_mfma_shared_v).  Neither changes a value or the order of a sum,
+through LDS (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma_pair_rows, conv3x3_wino_mfma_shared_v).  Neither changes a value or the order of a sum,
 so the descriptors are BIT-EQUAL to those of the library that computed U in the loop: tests/golden/hardnet_desc_n301.npy was recorded
 on the MI355X from that library (tests/golden/make_golden_hardnet_desc.py says how) for the fixed batch below - 301 patches, ragged,
 with the degenerate patches of tests/test_gpu_winograd.py among them."""
