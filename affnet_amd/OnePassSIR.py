@@ -8,8 +8,9 @@ evaluation per candidate patch.
 * AffNet = any callable image (1,1,h,w) -> (1,4,h,w) (the reference's slot signature, OnePassSIR.py:69): evaluated per octave by this
   mirror, the maps are copied into the workspace and the same detector runs on them.
 
-As in the reference every pyramid octave must be at least 34 px wide / high (LocalNorm2d(33) reflect-pads by 16): construct with
-border >= 15 like the reference's scripts (extract_geom_and_desc_upisup.py:63).  The reference's own default AffNet slot
+Every pyramid octave must be at least 34 px wide / high here (the dense kernels have never run below that; the reference's
+LocalNorm2d(33) reflect-pads by 16 and needs only 17 px): construct with border >= 15 like the reference's scripts
+(extract_geom_and_desc_upisup.py:63).  The reference's own default AffNet slot
 (AffineShapeEstimator, a per-patch module) cannot produce a dense map and fails there as well: AffNet is required here.
 """
 import ctypes as C

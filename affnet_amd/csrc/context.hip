@@ -198,7 +198,7 @@ extern "C" int affnet_ctx_create(affnet_ctx** out, int device, const affnet_conf
         for (int o = 0; o < c.n_octaves; ++o) {
             if (c.oct_h[o] < 34 || c.oct_w[o] < 34) {
                 *out = ctx;
-                return aff_fail(ctx, AFFNET_ERR_INVALID, "onepass: octave %d is %dx%d, LocalNorm2d(33) needs >= 34 px (the reference raises too: use "
+                return aff_fail(ctx, AFFNET_ERR_INVALID, "onepass: octave %d is %dx%d, LocalNorm2d(33) needs >= 34 px in this library (17 in the reference: use "
                                 "border >= 15 like its scripts, so that the pyramid stops earlier)", o, c.oct_w[o], c.oct_h[o]);
             }
             ctx->aff_off[o] = aff; aff += aff_align((size_t)4 * c.oct_h[o] * c.oct_w[o] * sizeof(float)) / sizeof(float);

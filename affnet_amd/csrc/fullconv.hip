@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void nms2d_kernel(const float* __restrict__ in
 int aff_fullconv_launch(affnet_ctx* ctx, const float* packed, const float* img, size_t img_stride, int h, int w, float* out, size_t out_stride,
                         float* scratch, size_t scratch_stride, int B, hipStream_t st) {
     if (h < 34 || w < 34)
-        return aff_fail(ctx, AFFNET_ERR_INVALID, "fullconv: image %dx%d too small (LocalNorm2d(33) reflect-pads by 16; the reference raises as well)", w, h);
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "fullconv: image %dx%d too small (this library requires 34 px per side; the reference's LocalNorm2d(33) needs 17)", w, h);
     const DenseGeom g = dense_geom(h, w);
     if (g.Hf < 1 || g.Wf < 1) return aff_fail(ctx, AFFNET_ERR_INVALID, "fullconv: image %dx%d too small for the 8x8 head", w, h);
     const NetLayout L = net_layout(AFFNET_NET_AFFNET_FULLCONV);

@@ -198,7 +198,7 @@ def fullconv_forward(packed, img, arith=0):
     h, w = img.size(2), img.size(3)
     nbytes = lib.affnet_fullconv_scratch_bytes(h, w)
     if nbytes == 0:
-        raise ValueError("image %dx%d too small for AffNetFastFullConv (LocalNorm2d(33) needs H, W >= 34; the reference raises too)" % (w, h))
+        raise ValueError("image %dx%d too small for AffNetFastFullConv (this library requires H, W >= 34; the reference's LocalNorm2d(33) needs 17)" % (w, h))
     dev = img.device
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     out = torch.empty(1, 4, h, w, dtype=torch.float32, device=dev)
