@@ -23,6 +23,7 @@ from . import _lib, engine
 from ._lib import lib, check, ptr
 from .architectures import _HipPatchNet
 from .HandCraftedModules import AffineShapeEstimator, OrientationDetector, _HipHandCrafted
+from .pytorch_sift import SIFTNet
 
 
 class ScaleSpaceAffinePatchExtractor(nn.Module):
@@ -109,7 +110,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         covers the B images, results get a leading batch dimension and `count` is (B,).  With `det_stream` (a torch.cuda.Stream) the
         pyramid + detector run there and the CNN stages on the current stream, ordered by events, so that
         two extractor objects alternating over a stream of images overlap the latency-bound detector of
-        image i+1 with the MFMA-bound CNN stages of image i.  `input_ready`: None = the detector stream first waits for
+        image i+1 with the MFMA-bound CNN stages of image i.  `desc`: a HardNet (inside the fused call) or a SIFTNet (the geometry is
+        enqueued without a descriptor buffer; level choice and affnet_sift_forward_pyr follow on the current stream, patches sampled
+        from the pyramid, still no host synchronisation).  `input_ready`: None = the detector stream first waits for
         everything enqueued so far on the current stream (safe default: x may still be in flight there); a
         torch.cuda.Event = wait for that event only; False = x is already resident (no wait)."""
         ctx = self._context(x, allow_batch=True)
@@ -124,15 +127,17 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         count = torch.zeros(B, dtype=torch.int32, device=dev)
         dsc = torch.empty(B, F, 128, dtype=torch.float32, device=dev) if desc is not None else None
         nets = self._nets(dev, do_ori, desc)
+        sift = isinstance(desc, SIFTNet)
+        fused_dsc = None if sift else dsc          # the descriptor buffer of the fused C call: HardNet's only
         if self.RespNet is not None:
             rmaps = self._response_pyramid(ctx, img)
             check(lib.affnet_detect_image_responses(ctx.handle, ptr(rmaps), engine.stream_of(dev)), ctx.handle, "affnet_detect_image_responses")
-            rc = lib.affnet_describe_detected(ctx.handle, C.byref(nets), int(bool(do_ori)), ptr(lafs), ptr(resp), ptr(ids), ptr(dsc),
+            rc = lib.affnet_describe_detected(ctx.handle, C.byref(nets), int(bool(do_ori)), ptr(lafs), ptr(resp), ptr(ids), ptr(fused_dsc),
                                               ptr(count), engine.stream_of(dev))
             check(rc, ctx.handle, "affnet_describe_detected")
         elif det_stream is None:
             rc = lib.affnet_extract_features(ctx.handle, C.byref(nets), ptr(img), int(bool(do_ori)), ptr(lafs), ptr(resp), ptr(ids),
-                                             ptr(dsc), ptr(count), engine.stream_of(dev))
+                                             ptr(fused_dsc), ptr(count), engine.stream_of(dev))
             check(rc, ctx.handle, "affnet_extract_features")
         else:
             cur = torch.cuda.current_stream(dev)
@@ -147,11 +152,22 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
             ev = torch.cuda.Event()
             ev.record(det_stream)
             cur.wait_event(ev)
-            rc = lib.affnet_describe_detected(ctx.handle, C.byref(nets), int(bool(do_ori)), ptr(lafs), ptr(resp), ptr(ids), ptr(dsc),
+            rc = lib.affnet_describe_detected(ctx.handle, C.byref(nets), int(bool(do_ori)), ptr(lafs), ptr(resp), ptr(ids), ptr(fused_dsc),
                                               ptr(count), engine.stream_of(dev))
             check(rc, ctx.handle, "affnet_describe_detected")
             self._busy = torch.cuda.Event()
             self._busy.record(cur)
+        if sift:
+            # SparseImgRepresenter.py:181-188 on the device: pyramid level per frame, then SIFT on patches sampled from that level
+            st = engine.stream_of(dev)
+            lvl = torch.empty(B, F, 3, dtype=torch.int32, device=dev)
+            norm = torch.empty(B, F, 2, 3, dtype=torch.float32, device=dev)
+            check(lib.affnet_level_select(ctx.handle, ptr(lafs), ptr(count), F, desc.PS, ptr(lvl), ptr(norm), st), ctx.handle, "affnet_level_select")
+            check(lib.affnet_sift_forward_pyr(ctx.handle, ptr(norm), ptr(lvl), ptr(count), F, ptr(desc.window(dev)), float(desc.clipval), ptr(dsc), st),
+                  ctx.handle, "affnet_sift_forward_pyr")
+            if det_stream is not None:             # the workspace is read until here
+                self._busy = torch.cuda.Event()
+                self._busy.record(torch.cuda.current_stream(dev))
         if B == 1:      # the reference's shapes
             lafs, resp, ids, dsc = lafs[0], resp[0], ids[0], (None if dsc is None else dsc[0])
         # "overflow": (B,) device view of the capacity-overflow flags (non-zero = a fixed-capacity list overflowed and this image's rows are
@@ -170,7 +186,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                 nets.h_orientation_window = C.cast(self.OriNet.window(), C.c_void_p)
             else:
                 nets.d_orinet = self.OriNet.packed_weights(dev).data_ptr()
-        nets.d_hardnet = desc.packed_weights(dev).data_ptr() if desc is not None else None
+        nets.d_hardnet = desc.packed_weights(dev).data_ptr() if desc is not None and not isinstance(desc, SIFTNet) else None
         return nets
 
     def capture(self, x, do_ori=False, desc=None):
@@ -178,6 +194,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         CapturedPath: `.image` is the static input tensor, `.launch(x)` copies x into it and replays the graph with a single launch
         on the current stream (returns the same dict as enqueue()), `.run(x)` adds the count read-back and slicing of run().  For
         callers that process one image at a time (hesaffnet.py:35-60): ~45 kernel launches per image become one."""
+        if isinstance(desc, SIFTNet):
+            raise NotImplementedError("graph capture covers the fused C call (HardNet descriptors or none); the SIFT descriptor follows it "
+                                      "as two more launches - use enqueue() / run()")
         return CapturedPath(self, x, do_ori, desc)
 
     def run_batch(self, x, do_ori=False, desc=None):
@@ -198,7 +217,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
 
     def run(self, x, do_ori=False, desc=None):
         """Fused path.  Returns dict(LAFs px (N,2,3), responses (N,), ids (N,3), descriptors (N,128)|None).
-        `desc`: affnet_amd.HardNet.HardNet or None."""
+        `desc`: affnet_amd.HardNet.HardNet, affnet_amd.pytorch_sift.SIFTNet or None."""
         if x.dim() == 4 and x.size(0) != 1:
             raise ValueError("run() is for a single (1,1,H,W) image; use run_batch() for (B,1,H,W) batches")
         r = self.enqueue(x, do_ori=do_ori, desc=desc)
@@ -382,7 +401,7 @@ class CapturedPath(object):
 def get_geometry_and_descriptors(img, det, desc, do_ori=True):
     """train_OriNet_test_on_graffity.py:293-298.  With native nets this is one fused C call."""
     from .HardNet import HardNet
-    if isinstance(desc, HardNet) and det._native(det.AffNet) and det._native(det.OriNet):
+    if isinstance(desc, (HardNet, SIFTNet)) and det._native(det.AffNet) and det._native(det.OriNet):
         r = det.run(img, do_ori=do_ori, desc=desc)
         return r["LAFs"], r["descriptors"]
     with torch.no_grad():

@@ -7,7 +7,8 @@ from .SparseImgRepresenter import ScaleSpaceAffinePatchExtractor, get_geometry_a
 from .architectures import AffNetFast, OriNetFast, AffNetFastFullConv  # noqa: F401
 from .OnePassSIR import OnePassSIR  # noqa: F401
 from .HardNet import HardNet  # noqa: F401
-from . import LAF, HandCraftedModules, Losses, ReprojectionStuff  # noqa: F401
+from .pytorch_sift import SIFTNet  # noqa: F401
+from . import LAF, HandCraftedModules, Losses, ReprojectionStuff, pytorch_sift  # noqa: F401
 from .synthetic import synthetic_image, synthetic_hardnet_state  # noqa: F401
 
 __version__ = "0.1.0"

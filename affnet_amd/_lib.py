@@ -101,6 +101,9 @@ SYMBOLS = {
     "affnet_level_select": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "affnet_handcrafted_forward": (_I, [_P, _I, _P, _I, _P, _P, _P, _P]),
     "affnet_handcrafted_forward_pyr": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "affnet_sift_host_window": (_I, [_I, C.POINTER(C.c_float)]),
+    "affnet_sift_forward": (_I, [_P, _P, _I, _P, C.c_float, _P, _P]),
+    "affnet_sift_forward_pyr": (_I, [_P, _P, _P, _P, _I, _P, C.c_float, _P, _P]),
     "affnet_match_scratch_bytes": (_SZ, [_I, _I]),
     "affnet_distance_matrix": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "affnet_match_snn": (_I, [_P, _P, _I, _P, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P]),

@@ -8,7 +8,7 @@ set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function $EXTRA_HIPCC_FLAGS"
-FILES="config_fill context pyramid detect laf_ops weights_pack cnn32 pipeline match handcrafted fullconv"
+FILES="config_fill context pyramid detect laf_ops weights_pack cnn32 pipeline match handcrafted sift fullconv"
 OBJ="$HERE/obj"
 OUT="$HERE/../libaffnet_hip.so"
 if [ "$AFFNET_PROBES" = "1" ]; then

@@ -3,10 +3,12 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
-Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000.  The reference's HardNet++.pth is a missing
-blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches)."""
+Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
+missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
+--desc sift: SIFTNet(patch_size=32), the descriptor the reference's test() constructs (train_AffNet_test_on_graffity.py:122) - no
+weights needed; at N = 500 it gives the reference's 79 tentatives / 4 true matches."""
 import os
 import sys
 
@@ -26,6 +28,13 @@ def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
 
 
 def main(argv):
+    desc_kind = "hardnet"
+    if "--desc" in argv:
+        i = argv.index("--desc")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("hardnet", "sift"):
+            sys.exit("--desc takes hardnet or sift")
+        desc_kind = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
     gd = os.path.join(ROOT, "tests", "golden")
     f1, f2, fh = (argv + [None] * 3)[:3]
     f1, f2, fh = f1 or os.path.join(gd, "graf_img1.png"), f2 or os.path.join(gd, "graf_img6.png"), fh or os.path.join(gd, "graf_H1to6p")
@@ -36,14 +45,15 @@ def main(argv):
     O = affnet_amd.OriNetFast(PS=32); O.load_state_dict(ld(os.path.join(ROOT, "pretrained", "OriNet.pth")))
     Hn = affnet_amd.HardNet(); Hn.load_state_dict(ld(argv[4]) if len(argv) > 4 else affnet_amd.synthetic_hardnet_state(0))
     A, O, Hn = A.to(dev), O.to(dev), Hn.to(dev)
+    desc = affnet_amd.SIFTNet(patch_size=32) if desc_kind == "sift" else Hn
     det = affnet_amd.ScaleSpaceAffinePatchExtractor(mrSize=5.192, num_features=n, border=5, num_Baum_iters=1, AffNet=A, OriNet=O).to(dev)
     img1, img2 = load_grayscale_var(f1).to(dev), load_grayscale_var(f2).to(dev)
     H1to2 = torch.from_numpy(np.loadtxt(fh)).float()
     for do_ori, tag in ((True, "graf1-6"), (False, "ori graf1-6")):
         if img1.shape == img2.shape:
-            r1, r2 = det.run_batch(torch.cat([img1, img2], 0), do_ori=do_ori, desc=Hn)
+            r1, r2 = det.run_batch(torch.cat([img1, img2], 0), do_ori=do_ori, desc=desc)
         else:
-            r1, r2 = det.run(img1, do_ori=do_ori, desc=Hn), det.run(img2, do_ori=do_ori, desc=Hn)
+            r1, r2 = det.run(img1, do_ori=do_ori, desc=desc), det.run(img2, do_ori=do_ori, desc=desc)
         t1, t2, _, _ = match_snn(r1["descriptors"], r2["descriptors"], 0.8)
         _, plain, _ = get_GT_correspondence_indexes(r1["LAFs"][t1], r2["LAFs"][t2], H1to2, dist_threshold=6)
         print("Test on %s, %d tentatives %d true matches %s  inl.ratio" % (tag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))

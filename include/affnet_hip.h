@@ -314,6 +314,26 @@ int affnet_handcrafted_forward(affnet_ctx* ctx, int kind, const float* d_patches
 int affnet_handcrafted_forward_pyr(affnet_ctx* ctx, int kind, const float* d_lafs, const int32_t* d_ids, const int32_t* d_count,
                                    int n_max, const float* h_weights, float* d_out, void* stream);
 
+/* ---- SIFT descriptor ------------------------------------------------- */
+
+/* Host helper (no GPU): h_out[32 * 32] = the Gaussian window of SIFTNet(patch_size = 32), CircularGaussKernel(kernlen = 32) of
+ * pytorch_sift.py:31-44 under Python 3 (halfSize = 16.0, sigma^2 = 0.9 * 256, zero where the squared distance is >= 256), evaluated in
+ * double and cast to float.  AFFNET_ERR_INVALID unless patch_size == 32.  The caller uploads it once: the d_window of the calls below. */
+int affnet_sift_host_window(int patch_size, float* h_out);
+/* SIFTNet(patch_size = 32, num_ang_bins = 8, num_spatial_bins = 4, clipval).forward (pytorch_sift.py:69-94) on n 32x32 patches
+ * (d_patches (n,32,32) fp32): centred gradients with replicate padding, magnitude x d_window, soft binning into 8 orientations,
+ * 11 x 11 stride-6 pooling (getPoolingKernel, :19-25) into 4 x 4 cells, L2 norm, clamp to [0, clipval], L2 norm.
+ * d_desc (n,128), index = bin * 16 + cell row * 4 + cell column.  Plain fp32 whatever the context's arithmetic mode; the summation
+ * order is fixed (bit-reproducible, independent of n and of the batch). */
+int affnet_sift_forward(affnet_ctx* ctx, const float* d_patches, int n, const float* d_window, float clipval, float* d_desc, void* stream);
+/* Same, each patch sampled from the pyramid in the workspace along what affnet_level_select(..., ps = 32, ...) produced: normalised
+ * LAFs (B,n_max,2,3) and (octave, level, *) ids (B,n_max,3), rows < d_count[image] (d_count NULL => n_max rows).  d_desc (B,n_max,128);
+ * rows >= d_count[image] are zero.  Bit-identical to affnet_pyr_grid_sample(ps = 32) + affnet_sift_forward on the same frames.
+ * The SIFT path without host synchronisation: affnet_extract_features(d_desc = NULL), affnet_level_select on its pixel LAFs and this
+ * call, on one stream. */
+int affnet_sift_forward_pyr(affnet_ctx* ctx, const float* d_lafs_norm, const int32_t* d_ids, const int32_t* d_count, int n_max,
+                            const float* d_window, float clipval, float* d_desc, void* stream);
+
 /* ---- LAF stages ---------------------------------------------------------------------------- */
 
 /* base_A = A; new_LAF = [A * LAF_2x2 | centre]; keep rows with 1/6 < |l1/(l2+1e-8)| < 6 and
