@@ -1,4 +1,4 @@
-// Shared MFMA building blocks of the 32x32-patch trunks (cnn32.hip) and the fully-convolutional AffNet (fullconv.hip):
+// Shared MFMA building blocks of the 32x32-patch trunks (cnn_trunk.h), their heads (cnn_heads.hip) and the fully-convolutional AffNet (fullconv.hip):
 // LDS activation layouts, weight fragment loads, the software-pipelined implicit-GEMM 3x3 convolution on
 // v_mfma_f32_16x16x4_f32, conv0 on the matrix cores and the tile epilogues.  gfx950 only.  The packed weight blob these loops read -
 // sections, offsets and element orders - is defined in weights_layout.h (included here) and filled by weights_pack.hip.
@@ -1319,7 +1319,7 @@ __device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const flo
 // A^T M A - t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3, operation by operation what wino_output does - before the next row starts.  Live: 4 accumulators, 4 U
 // fragments, 4 V fragments, t0 / t1.  Per K group the window rows 1 and 2 are read twice (32 instead of 16 ds_read_b128), the VALU work is the same.
 // U enters holding row 0 / group 0 of pass 0 (wino_prefetch_u_row) and rolls one step ahead in its single register set.
-// Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (cnn32.hip: wino_derive_u_kernel).
+// Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (cnn_trunk_orinet.hip: wino_derive_u_kernel).
 template <int NW, int CIN, int COUT, int H, int NB>
 __device__ __forceinline__ void wino_prefetch_u_row(const float* __restrict__ Wu, f32x4 (&U)[4], int wave, int lane) {
     const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);

@@ -1,0 +1,11 @@
+// AffNet's six instantiations of cnn32_trunk_kernel (cnn_trunk.h).  (Tried and removed: two AffNet patches per persistent 16-wave workgroup in anti-phase - correct
+// but 8 % slower, the small-tile loops reach 85-90 % of the pipe rate with two waves per SIMD.)
+#include "cnn_trunk.h"
+
+// [exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see cnn_check)
+TrunkKernel aff_trunk_affnet(int arith_index, bool stamps) {
+    static const TrunkKernel k[3][2] = {{cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, false>, cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, true>},
+                                        {cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, false, 3>, cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, true, 3>},
+                                        {cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, false, 2>, cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, true, 2>}};
+    return k[arith_index][stamps];
+}

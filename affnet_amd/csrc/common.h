@@ -10,9 +10,7 @@
 
 #include "../../include/affnet_hip.h"
 #include "../../include/affnet_hip_debug.h"
-#ifdef AFFNET_PROBES
-#include "../../include/affnet_hip_probes.h"
-#endif
+#include "weights_layout.h"
 
 #define AFF_WAVE 64
 
@@ -115,7 +113,7 @@ struct affnet_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     // Winograd weights U = G g G^T of conv1 / conv3 / conv5 of the exact AffNet / OriNet trunks, derived from the caller's blob in front of every trunk launch
-    // (cnn32.hip: wino_derive_u_kernel); the only device memory a context owns, allocated on first use (aff_wino_u_ensure)
+    // (cnn_trunk_orinet.hip: wino_derive_u_kernel); the only device memory a context owns, allocated on first use (aff_wino_u_ensure)
     float* wino_u = nullptr;
     ~affnet_ctx() {
         if (wino_u) (void)hipFree(wino_u);
@@ -198,6 +196,92 @@ struct DenormSel {           // per-launch constants + outputs (pointers of imag
 // ---- internal interface: every function that crosses a file boundary -----------------------------------------------------
 // Each non-static aff_* function of the library is declared HERE, once, under the file that defines it.  The .hip files carry no
 // declarations of their own, so a definition and its callers are compiled against the same prototype.  No default arguments.
+// The plain types and constants that only such prototypes and the kernels behind them share come first.
+
+// the 32x32-patch CNNs: cnn32.hip (host layer), cnn_trunk.h (trunk kernels, instantiated per net in cnn_trunk_*.hip), cnn_heads.hip
+// floats of head partials per patch that an AffNet / OriNet trunk leaves for its finish kernel ([wave][4] / [wave][18])
+#define HEAD_PART_AFF 32
+#define HEAD_PART_ORI 144
+// HardNet head GEMM (cnn_heads.hip): K quarters per patch block, K chunk per LDS slab and its row stride
+#define HEAD_KSPLIT 4
+#define HEAD_KC 128
+#define HEAD_AS (HEAD_KC + 4)    // row stride: 16-byte aligned rows
+
+struct PyrSrc {            // pyramid sampling source (fused sampler)
+    PyrTable t;            // the samplers' level table
+    float base[32];        // affine_grid base coordinates for PS = 32
+};
+
+struct CnnArgs {
+    const float* packed;
+    NetOffsets off;
+    const float* wino_u;   // exact OriNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel)
+    const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
+    const float* lafs;     // normalised LAFs when sampling
+    const int32_t* ids;    // (octave, level, *) when sampling
+    const int32_t* count;
+    int n_max;
+    float* out;            // AffNet/OriNet: (n,2,2); HardNet: trunk output (n,8192)
+    int dbg_layer;         // >= 0: dump activations after this trunk layer of patch 0 and exit
+    int s3_alt;            // tuning variant bits of the split-operand trunks (affnet_debug_split3_variant): bit 0 = the two waves of a SIMD alternate at the higher priority inside the HardNet loops
+    float* dbg_out;
+    unsigned long long* dbg_time;   // != NULL: s_memtime stamps [patch][wave][32] at the phase boundaries (tuning aid)
+    // Row window [row_begin, row_begin + gridDim.x) of every image, and the lazy-evaluation predicate of the fused pipeline: when
+    // skip_cnt != NULL the launch does nothing for an image whose detections are response-sorted (CNT_SEL_MODE == 1) and whose first
+    // pass already produced skip_n survivors of the shape filter (CNT_SURVIVED1) - pipeline.hip, affnet_describe_detected.
+    int row_begin;
+    const int32_t* skip_cnt;
+    int skip_n;
+    // Shape-stage bookkeeping done by thread 0 of workgroup (0, image) of the AffNet trunk launches (each was a 5 us launch of its
+    // own): shape_op 1 = first pass: survivor / evaluation counters = 0; 2 = second (lazy) pass: freeze the first pass's survivor
+    // count (CNT_SURVIVED1) for the predicate of the finish + filter kernel that follows this launch.  The trunk workgroups
+    // themselves test CNT_SURVIVED, which nothing changes while a trunk launch runs.
+    int32_t* shape_cnt;
+    int shape_op;
+};
+// (the split-operand variants are template instantiations: cnn32_trunk_kernel<KIND, NW, STAMPS, S3>, S3 = 3 bf16 terms or 2 fp16 terms; 0 = exact)
+
+// the lazy-evaluation predicate above, for the trunk and finish kernels
+__device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, int image, int which = CNT_SURVIVED1) {
+    if (!skip_cnt) return false;
+    const int32_t* c = skip_cnt + (size_t)image * CNT_TOTAL;
+    return c[CNT_SEL_MODE] == 1 && c[which] >= skip_n;
+}
+
+// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32, conv5 64 -> 64; the AffNet blob has the same shapes and the debug accessor derives it too), in w_tap_index order like NetLayout::w_wino.
+// Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
+// BN-folded fp32 taps into a buffer the context owns, one region per net kind.
+struct Wino16 {
+    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, U5 = 16 * 64 * 64, FLOATS = U1 + U3 + U5;   // floats per net
+    static constexpr int PAIRS = 16 * 16 + 32 * 32 + 64 * 64;                        // (cin, cout) pairs of the three layers
+    static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
+    static constexpr int offset(int layer) { return layer == 1 ? 0 : (layer == 3 ? U1 : U1 + U3); }
+    static constexpr int floats(int layer) { return layer == 1 ? U1 : (layer == 3 ? U3 : U5); }
+};
+
+struct ShapeFuse {           // finish + shape filter in one kernel (pointers of image 0; strides like shape_filter_kernel)
+    const float* resp; const float* lafs; float* key; int32_t* good; int32_t* cnt;
+};
+
+// One CNN call: trunk launch + the net's finish stage.  Callers set the fields they mean by name; the rest keep these defaults.
+struct CnnCall {
+    int kind = -1;                                                   // AFFNET_NET_AFFNET / _ORINET / _HARDNET
+    const float* packed = nullptr;
+    const float* patches = nullptr;                                  // (n,32,32), or NULL: sample from the pyramid with lafs / ids
+    const float* lafs = nullptr; const int32_t* ids = nullptr;
+    const int32_t* count = nullptr; int n_max = 0;
+    float* out = nullptr; float* scratch = nullptr;
+    hipStream_t st = nullptr;
+    int dbg_layer = -1; float* dbg_out = nullptr;                    // layer >= 0: dump this trunk layer of patch 0, no finish stage
+    bool mark_head = false;                                          // stage mark 7 between trunk and head (affnet_describe_detected)
+    int row_begin = 0, row_count = -1;                               // row window of every image; -1 = up to n_max
+    const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
+    const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
+    float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
+};
+
+// kernel of one trunk instantiation, as the per-net getters below return it
+typedef void (*TrunkKernel)(CnnArgs, PyrSrc);
 
 // context.hip
 int aff_fail(affnet_ctx* ctx, int code, const char* fmt, ...);
@@ -238,8 +322,8 @@ void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_i
 int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
                             float* d_lafs_norm, hipStream_t st);
 
-// cnn32.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one)
-int aff_wino_u_ensure(affnet_ctx* ctx);
+// cnn32.hip: 0 = exact fp32, 1 = three bf16 terms, 2 = two fp16 terms: index of the context's arithmetic in the trunk and head kernel tables
+int aff_arith_index(const affnet_ctx* ctx);
 // cnn32.hip: the fused launches of affnet_describe_detected (AffNet + shape filter on a row window, OriNet + rotation, HardNet with
 // the stage mark between trunk and head)
 int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,
@@ -249,7 +333,22 @@ int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const i
 int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
                                    int n_max, float* out, float* scratch, hipStream_t st);
 
-// ---- sampler math shared by laf_ops.hip, handcrafted.hip and cnn32.hip ----------------------------
+// cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip: the net's trunk instantiation [aff_arith_index][phase stamps]
+TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
+TrunkKernel aff_trunk_orinet(int arith_index, bool stamps);
+TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
+// cnn_trunk_orinet.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one); derive U of
+// conv1 / conv3 / conv5 of an AffNet or OriNet blob into the context's region of that net kind, *u = that region
+int aff_wino_u_ensure(affnet_ctx* ctx);
+int aff_wino_derive_u(affnet_ctx* ctx, int kind, const float* packed, const NetLayout& L, hipStream_t st, const float** u);
+
+// cnn_heads.hip: what cnn_launch runs behind a trunk launch: AffNet / OriNet finish kernel on `rows` rows of the window of B images, HardNet
+// head GEMM + finish kernel over all rows
+int aff_finish_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B);
+int aff_finish_orinet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B);
+int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int B);
+
+// ---- sampler math shared by laf_ops.hip, handcrafted.hip and cnn_trunk.h --------------------------
 // LDS-staged footprint of one patch (north_star: "coalesced HBM reads and LDS-staged image tiles"): the affine frame of a PS x PS
 // patch covers an axis-aligned box of the level image; when that box is small its rows are loaded once with coalesced row-segment
 // loads (zeros outside the image = grid_sample's zero padding) and the four bilinear taps of every sample come from LDS.  The

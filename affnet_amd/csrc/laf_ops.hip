@@ -98,7 +98,7 @@ extern "C" int affnet_pyr_grid_sample(affnet_ctx* ctx, const float* d_lafs, cons
 
 // ---- shape compose + filter ------------------------------------------------------------------------
 // Rows [row_begin, row_end) of every image; the other rows keep what they hold (the caller zeroes key / good first).  With the
-// lazy-evaluation predicate (skip_cnt != NULL, see cnn32.hip CnnArgs) the pass does nothing for an image that already has its
+// lazy-evaluation predicate (skip_cnt != NULL, see CnnArgs, common.h) the pass does nothing for an image that already has its
 // skip_n survivors - its remaining candidates were never run through the shape CNN and stay "not good".  Survivors are counted
 // into CNT_SURVIVED here (one atomic per wave); thread 0 of a second pass records how many candidates were evaluated at all.
 __global__ __launch_bounds__(256) void shape_filter_kernel(const float* __restrict__ resp, const float* __restrict__ lafs,
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void shape_filter_kernel(const float* __restri
     bool skip = false;
     if (skip_cnt) {
         const int32_t* c = skip_cnt + (size_t)blockIdx.y * CNT_TOTAL;
-        skip = c[CNT_SEL_MODE] == 1 && c[CNT_SURVIVED1] >= skip_n;      // frozen by the second AffNet trunk launch (cnn32.hip, shape_op == 2)
+        skip = c[CNT_SEL_MODE] == 1 && c[CNT_SURVIVED1] >= skip_n;      // frozen by the second AffNet trunk launch (cnn_trunk.h, shape_op == 2)
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) cnt[CNT_AFF_EVAL] = skip ? min(n, row_begin) : min(n, row_end);
     if (skip || i >= row_end || i >= n) return;
@@ -386,7 +386,7 @@ __global__ void denorm_level_select_kernel(const float* __restrict__ in, float* 
     aff_denorm_level_row(L[0], L[1], L[2], L[3], L[4], L[5], c_a, c_x, c_y, ps, lt, ca, cx, cy, P, ids + 3 * (bi * n_max + i), lafs_norm + 6 * (bi * n_max + i));
 }
 
-// The constants of denorm_level_select_kernel for this context, for a kernel that fuses the step (OriNet's finish kernel, cnn32.hip).
+// The constants of denorm_level_select_kernel for this context, for a kernel that fuses the step (OriNet's finish kernel, cnn_heads.hip).
 void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_ids, float* d_lafs_norm, DenormSel* ds) {
     const affnet_config& c = ctx->cfg;
     ds->lt.n_oct = c.n_octaves; ds->lt.n_lvl = c.levels_per_octave;

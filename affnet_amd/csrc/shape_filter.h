@@ -1,4 +1,4 @@
-// Shape filter of one candidate row, shared by shape_filter_kernel (laf_ops.hip) and the AffNet finish kernel (cnn32.hip) that
+// Shape filter of one candidate row, shared by shape_filter_kernel (laf_ops.hip) and the AffNet finish kernel (cnn_heads.hip) that
 // fuses it: SparseImgRepresenter.py:121-162 (compose), Utils.py:168-175 (batch_eig2x2), LAF.py:98-104 (checkTouchBoundary), op by op.
 #pragma once
 #include "common.h"
@@ -37,7 +37,7 @@ __device__ __forceinline__ void aff_shape_filter_row(const float* __restrict__ r
 }
 
 // Denormalisation (LAF.py:407-417) + pyramid-level choice (LAF.py:450-472, float64 |a - b| argmin like scipy's cdist on 1-D points) + re-normalised frame
-// of ONE row, shared by denorm_level_select_kernel (laf_ops.hip) and OriNet's finish kernel (cnn32.hip), which fuses it behind the rotation.
+// of ONE row, shared by denorm_level_select_kernel (laf_ops.hip) and OriNet's finish kernel (cnn_heads.hip), which fuses it behind the rotation.
 // (LevelTable / DenormSel, the constants of a launch: common.h)
 __device__ __forceinline__ void aff_denorm_level_row(float l0, float l1, float l2, float l3, float l4, float l5, float c_a, float c_x, float c_y, float ps,
                                                      const LevelTable& lt, float ca, float cx, float cy, float* __restrict__ P, int32_t* __restrict__ I,

@@ -1,6 +1,6 @@
 // The packed weight blob (include/affnet_hip.h: affnet_cnn32_packed_floats): its sections and offsets, the element order of every
 // section, and the Winograd weight transform.  The one contract between the host packer (weights_pack.hip) and the kernels
-// (cnn32.hip, cnn_mfma.h, fullconv.hip).  Plain arithmetic, no HIP header: compiles as C++ on the host as well.
+// (cnn32.hip, cnn_trunk.h, cnn_heads.hip, cnn_mfma.h, fullconv.hip).  Plain arithmetic, no HIP header: compiles as C++ on the host as well.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

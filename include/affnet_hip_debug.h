@@ -6,7 +6,7 @@
  * fragment-layout self-test) and for the in-kernel phase stamps of tools/cnn_phase_timing.py / s3_phase_timing.py.  The
  * probe KERNELS of the tuning tools (isolated MFMA loops, counter-calibration streams, split-arithmetic
  * GEMM / rate probes) are not in libaffnet_hip.so at all: include/affnet_hip_probes.h,
- * libaffnet_hip_probes.so (AFFNET_PROBES=1 bash affnet_amd/csrc/build.sh).
+ * libaffnet_hip_probes.so (csrc/debug.hip, split_probe.hip, cnn_probe.hip; AFFNET_PROBES=1 bash affnet_amd/csrc/build.sh).
  */
 #ifndef AFFNET_HIP_DEBUG_H
 #define AFFNET_HIP_DEBUG_H

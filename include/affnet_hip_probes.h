@@ -1,8 +1,8 @@
 /*
  * affnet_hip_probes.h - probe kernels of the tuning / measurement tools under tools/.
  *
- * NOT in libaffnet_hip.so: these entry points exist only in libaffnet_hip_probes.so, the same sources compiled with -DAFFNET_PROBES
- * (`AFFNET_PROBES=1 bash affnet_amd/csrc/build.sh`; __graft_entry__.build() builds it next to the product library so that the tools
+ * NOT in libaffnet_hip.so: these entry points exist only in libaffnet_hip_probes.so = the product objects plus csrc/debug.hip, split_probe.hip
+ * and cnn_probe.hip (`AFFNET_PROBES=1 bash affnet_amd/csrc/build.sh`; __graft_entry__.build() builds it next to the product library so that the tools
  * travel to the GPU box).  The tools select it with AFFNET_HIP_LIB=<path> (affnet_amd/_lib.py).  The shipped library holds product
  * kernels (+ the stamped debug instantiations of affnet_hip_debug.h) only.
  */

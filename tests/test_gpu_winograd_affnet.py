@@ -1,6 +1,6 @@
 """The exact OriNet trunk runs conv1 and conv3 as Winograd F(2x2, 3x3) (affnet_amd/csrc/cnn_mfma.h: conv3x3_wino_mfma_rows); AffNet stays in the
 direct form (the shape filter behind it turns on the last bits of its output).  The transformed weights U = G g G^T are not part of the packed blob:
-a kernel of the library derives them from the blob's BN-folded taps in front of every OriNet trunk launch (affnet_amd/csrc/cnn32.hip:
+a kernel of the library derives them from the blob's BN-folded taps in front of every OriNet trunk launch (affnet_amd/csrc/cnn_trunk_orinet.hip:
 wino_derive_u_kernel) into a buffer the context owns; the debug accessor derives them for an AffNet blob as well (same shapes).  Pinned here: the
 derived U bit for bit for both blobs, the OriNet trunk layer by layer (tests/test_gpu_parity.py covers AffNet and HardNet), that a blob rewritten in place can never meet stale U - eagerly or
 in a replayed graph - and that two runs give the same bits."""

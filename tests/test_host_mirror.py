@@ -197,7 +197,7 @@ def test_design_kernel_figures_match_the_built_objects():
 
 
 def _unpack_trunk(kind, blob):
-    """Rebuilds conv weights / biases from the packed blob (the layout cnn32.hip documents)."""
+    """Rebuilds conv weights / biases from the packed blob (the layout weights_layout.h documents)."""
     cb = 32 if kind == 2 else 16
     ch = [1, cb, cb, 2 * cb, 2 * cb, 4 * cb, 4 * cb]
     off, layers = 0, []
@@ -443,7 +443,7 @@ def test_lds_bank_model_of_the_split_layouts():
     """tools/lds_bank_model.py (service groups and bank rules of MI355X_MICROARCH.md, section LDS) on the layouts the split-operand trunks use: every
     fragment read of the loops is conflict free (4 LDS cycles) except the ONE reader per net and mode the design knowingly leaves with 2-way conflicts
      - conv4 in LayQ, conv3 (HardNet) / conv4 (16-channel nets) in LayR, whose output buffer two readers with opposite group strides
-    share.  A change of a row pitch or group stride in cnn32.hip that breaks this has to show up here (the model mirrors those parameters)."""
+    share.  A change of a row pitch or group stride in cnn_trunk.h that breaks this has to show up here (the model mirrors those parameters)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import lds_bank_model as bm
     got = {name: bm.read_cycles(L, stride, c16) for name, L, stride, c16 in bm.readers()}
@@ -452,7 +452,7 @@ def test_lds_bank_model_of_the_split_layouts():
                     "HardNet fp32_split2h conv3 (stride 1, 16-wide)", "AffNet / OriNet fp32_split2h conv4 (stride 2, 16-wide)"}, got
     assert all(got[k] == 8 for k in slow), got
     # the parameters the model mirrors are the ones in the kernel source
-    src = open(os.path.join(ROOT, "affnet_amd", "csrc", "cnn32.hip")).read()
+    src = open(os.path.join(ROOT, "affnet_amd", "csrc", "cnn_trunk.h")).read()
     for frag in ("LayR<32, 32, 34, CB, 0>", "LayR<32, 32, 34, CB, 16>", "LayR<16, 16, 20, 2 * CB, 16>, LayQ<16, 16, 18, 2 * CB, 0, 3>", "LayR<16, 16, 20, 2 * CB, 0>, LayQ<16, 16, 18, 2 * CB, 0, 3>",
                  "LayR<8, 8, 12, 4 * CB, 0>, LayQ<8, 8, 16, 4 * CB, 128, 3>", "LayQ<16, 32, 34, CB, 0, 3>", "LayQ<16, 32, 34, CB, 16, 3>"):
         assert frag in src, frag

@@ -70,7 +70,7 @@ def write_cycles(L):
 
 
 def readers():
-    """(name, layout, stride, 16-input-channel loop) of every split-operand loop of the trunks (cnn32.hip) - HardNet (CB = 32) and AffNet / OriNet (CB = 16)."""
+    """(name, layout, stride, 16-input-channel loop) of every split-operand loop of the trunks (cnn_trunk.h) - HardNet (CB = 32) and AffNet / OriNet (CB = 16)."""
     out = []
     for cb, net in ((32, "HardNet"), (16, "AffNet / OriNet")):
         c16 = cb == 16
