@@ -562,47 +562,139 @@ def test_foreign_affnet_with_several_baumberg_iterations(amd, nets):
     assert not torch.equal(one(x, do_ori=True)[0], L1), "the iterations must change the frames"
 
 
+def _shape_select_reference(resp, lafs, Amat, N):
+    """SparseImgRepresenter.py:136-156 on caller-supplied rows (CPU tensors; lafs normalised): good = eigenvalue ratio of the shape inside
+    (1/6, 6) and the composed frame inside the image; more than N good rows -> the N largest key = response * good (equal keys: the lower
+    input row first - torch.topk leaves that open, the kernel does not), responses = those keys; otherwise the good rows in input order.
+    Returns (input row per output row, output responses, composed frames, key, smallest distance of a frame corner of any row from the
+    image boundary in float64: a row ON the boundary could round either way in the two fp32 evaluations)."""
+    new = torch.cat([torch.bmm(Amat, lafs[:, :, 0:2]), lafs[:, :, 2:]], dim=2)
+    l1, l2 = orc.eig2x2(Amat)
+    ratio = torch.abs(l1 / (l2 + 1e-8))
+    good = ((ratio < 6.0) & (ratio > (1.0 / 6.0))) & orc.inside_image(new)
+    key = resp * good.float()
+    c = orc.frame_corners(torch.cat([torch.bmm(Amat.double(), lafs[:, :, 0:2].double()), lafs[:, :, 2:].double()], dim=2))
+    margin = float(torch.minimum(c.abs(), (c - 1.0).abs()).min())
+    if 0 < N < int(good.sum()):
+        order = np.lexsort((np.arange(len(key)), -key.numpy().astype(np.float64)))[:N]
+        out = key.numpy()[order]
+    else:
+        order = np.nonzero(good.numpy())[0]
+        out = resp.numpy()[order]
+    return order, out, new.numpy()[order], key.numpy(), margin
+
+
 def test_shape_filter_select_on_caller_supplied_unsorted_rows(amd, nets):
     """the public stage entry affnet_shape_filter_select promises the N largest responses among the rows that pass the shape
     filter for ANY caller-supplied rows.  Its selection kernel has a shortcut for response-sorted rows that used to be taken on the strength
     of a flag the context's LAST detector call left behind: shuffled rows handed to the entry after a sorted detection silently got the
     first N good rows instead of the N best.  The kernel now verifies the order itself.  Reference: SparseImgRepresenter.py:147-156
-    (topk of response * good)."""
+    (topk of response * good), restated on the CPU by _shape_select_reference: every selection below is compared with it, not only with
+    another GPU run.  Two contexts: 450 candidate rows of a synthetic image, and 1500 rows of a planted detection (tests/_planted.py), whose
+    shuffled rows cross the second 1024-row tile of the kernel's general rank path.  Inputs per context: sorted, shuffled, a block of
+    rows sharing one response (equal keys: the input row decides), every response non-positive (the N-th key is not positive and the
+    rejected rows' zero keys compete), and a few positive responses above non-positive ones."""
     import ctypes as C
+    import _planted as pl
     from affnet_amd._lib import lib, ptr, check
     from affnet_amd import engine
     A, O, H = nets
+    st = engine.stream_of(torch.device(DEV))
+
+    def rows_of(ctx):
+        P = ctx.cap_pre
+        resp = torch.empty(P, device=DEV); lafs = torch.empty(P, 2, 3, device=DEV); ids = torch.empty(P, 3, dtype=torch.int32, device=DEV)
+        cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+        check(lib.affnet_detected_list(ctx.handle, ptr(resp), ptr(lafs), ptr(ids), ptr(cnt), st), ctx.handle, "detected_list")
+        return resp, lafs, ids, cnt
+
+    def selector(ctx, Amat, cnt):
+        F = ctx.cap_final
+
+        def select(r, l, i):
+            r2 = torch.empty(F, device=DEV); l2 = torch.empty(F, 2, 3, device=DEV); i2 = torch.empty(F, 3, dtype=torch.int32, device=DEV)
+            c2 = torch.zeros(1, dtype=torch.int32, device=DEV)
+            check(lib.affnet_shape_filter_select(ctx.handle, ptr(r), ptr(l), ptr(i), ptr(Amat), ptr(cnt), ptr(r2), ptr(l2), ptr(i2), ptr(c2), st), ctx.handle,
+                  "shape_filter_select")
+            k = int(c2.item())
+            return r2[:k].clone(), l2[:k].clone(), i2[:k].clone()
+        return select
+
+    def against_reference(tag, select, r, l, i, Amat, N, exact=True):
+        """one selection against the CPU reference; exact = rows and order, else the responses as a multiset and the rows of positive key"""
+        r, l, i = r.contiguous(), l.contiguous(), i.contiguous()
+        rg, lg, ig = select(r, l, i)
+        order, rw, lw, key, margin = _shape_select_reference(r.cpu(), l.cpu(), Amat.cpu(), N)
+        assert margin > 1e-6, "%s: a frame corner lies %.3g from the image boundary - the fixture, not the kernel, is ambiguous" % (tag, margin)
+        assert rg.numel() == len(order), "%s: %d rows, the reference has %d" % (tag, rg.numel(), len(order))
+        rg, lg, ig = rg.cpu().numpy(), lg.cpu().numpy(), ig.cpu().numpy()
+        iw = i.cpu().numpy()[order]
+        if exact:
+            assert np.array_equal(ig, iw), "%s: not the reference's rows in the reference's order" % tag
+            assert np.array_equal(rg, rw), "%s: responses differ" % tag
+            assert np.abs(lg - lw).max() < 1e-6, "%s: composed frames differ by %.3g (normalised units)" % (tag, np.abs(lg - lw).max())
+        else:
+            assert np.array_equal(np.sort(rg), np.sort(rw)), "%s: responses differ from the reference's as a multiset" % tag
+            pos = rw > 0
+            assert np.array_equal(ig[rg > 0], iw[pos]) and np.array_equal(rg[rg > 0], rw[pos]), "%s: the rows of positive key differ" % tag
+        return rg, key[order]
+
+    def variants(tag, ctx, resp, lafs, ids, cnt, Amat, seed, block, min_once):
+        n, N = int(cnt.item()), ctx.cap_final
+        select = selector(ctx, Amat, cnt)
+        rs, ls, is_ = select(resp, lafs, ids)                    # sorted rows: the shortcut applies
+        assert rs.numel() == N and bool((rs[:-1] >= rs[1:]).all())
+        against_reference(tag + " sorted", select, resp, lafs, ids, Amat, N)
+        g = torch.Generator().manual_seed(seed)
+        perm = torch.randperm(n, generator=g).to(DEV)
+        ru, lu, iu = select(resp[perm].contiguous(), lafs[perm].contiguous(), ids[perm].contiguous())
+        # the same SET of rows in the same (descending response) order, whatever order the caller supplied them in
+        assert torch.equal(ru, rs), "%s: shuffled input rows: the selection is not the N largest responses" % tag
+        # (rows whose response occurs once in the selection: equal responses come out in input-row order, which the shuffle changes)
+        _, inv, mult = rs.unique(return_inverse=True, return_counts=True)
+        once = mult[inv] == 1
+        assert int(once.sum()) >= min_once, "%s: only %d of %d selected rows have a response of their own" % (tag, int(once.sum()), N)
+        assert torch.equal(iu[once], is_[once]) and torch.equal(lu[once], ls[once])
+        against_reference(tag + " shuffled", select, resp[perm], lafs[perm], ids[perm], Amat, N)
+        # equal keys: rows block[0] .. block[1] of the sorted list share one response; sorted and shuffled, the lower input row comes first
+        tied = resp.clone()
+        tied[block[0]:block[1]] = resp[block[0]]
+        for name, p in (("sorted", torch.arange(n, device=DEV)), ("shuffled", perm)):
+            rg = against_reference("%s tied block, %s" % (tag, name), select, tied[p], lafs[p], ids[p], Amat, N)[0]
+            assert (rg == float(resp[block[0]])).sum() > 8, "the block of equal keys was meant to be inside the selection"
+        # no positive response at all: descending (the sorted shortcut's test of the N-th key), and shuffled
+        neg = -resp.flip(0)
+        assert bool((neg[:-1] >= neg[1:]).all()) and float(neg.max()) <= 0.0
+        for name, p in (("sorted", torch.arange(n, device=DEV)), ("shuffled", perm)):
+            rg, kw = against_reference("%s non-positive, %s" % (tag, name), select, neg[p], lafs[p], ids[p], Amat, N, exact=False)
+            assert not (kw[N - 1] > 0) and (rg == 0).sum() > 0, "zero keys of rejected rows were meant to compete"
+        # a few positive responses, fewer than N good ones, above non-positive ones: the N-th key is not positive, the positive rows are exact
+        few = torch.cat([resp[:N // 3], -resp[N // 3:].flip(0)])
+        for name, p in (("sorted", torch.arange(n, device=DEV)), ("shuffled", perm)):
+            rg = against_reference("%s few positive, %s" % (tag, name), select, few[p], lafs[p], ids[p], Amat, N, exact=False)[0]
+            assert 0 < (rg > 0).sum() < N
+
+    # a mildly anisotropic shape for every row (an isotropic frame has a zero discriminant in batch_eig2x2, Utils.py:168-175, and the
+    # reference's fallback then rejects it): the eigen-ratio test passes, the boundary test decides
     x = orc.synthetic_image(240, 320, 1).to(DEV)
     det = amd.ScaleSpaceAffinePatchExtractor(mrSize=5.192, num_features=300, border=5, num_Baum_iters=1, AffNet=A, OriNet=O).to(DEV)
     det.run(x, do_ori=False)                                 # leaves the context in "sorted detections" mode (450 candidates > C)
     ctx = det._ctx
-    P, F = ctx.cap_pre, ctx.cap_final
-    st = engine.stream_of(torch.device(DEV))
-    resp = torch.empty(P, device=DEV); lafs = torch.empty(P, 2, 3, device=DEV); ids = torch.empty(P, 3, dtype=torch.int32, device=DEV)
-    cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
-    check(lib.affnet_detected_list(ctx.handle, ptr(resp), ptr(lafs), ptr(ids), ptr(cnt), st), ctx.handle, "detected_list")
-    n = int(cnt.item())
-    assert n == P == 450
-    # a mildly anisotropic shape for every row (an isotropic frame has a zero discriminant in batch_eig2x2, Utils.py:168-175, and the
-    # reference's fallback then rejects it): the eigen-ratio test passes, the boundary test decides
-    Amat = torch.tensor([[1.2, 0.0], [0.1, 0.9]], device=DEV).repeat(P, 1, 1).contiguous()
-
-    def select(r, l, i):
-        r2 = torch.empty(F, device=DEV); l2 = torch.empty(F, 2, 3, device=DEV); i2 = torch.empty(F, 3, dtype=torch.int32, device=DEV)
-        c2 = torch.zeros(1, dtype=torch.int32, device=DEV)
-        check(lib.affnet_shape_filter_select(ctx.handle, ptr(r), ptr(l), ptr(i), ptr(Amat), ptr(cnt), ptr(r2), ptr(l2), ptr(i2), ptr(c2), st), ctx.handle,
-              "shape_filter_select")
-        k = int(c2.item())
-        return r2[:k].clone(), l2[:k].clone(), i2[:k].clone()
-
-    rs, ls, is_ = select(resp, lafs, ids)                    # sorted rows: the shortcut applies
-    assert rs.numel() == F == 300 and bool((rs[:-1] >= rs[1:]).all())
-    g = torch.Generator().manual_seed(11)
-    perm = torch.randperm(n, generator=g).to(DEV)
-    ru, lu, iu = select(resp[perm].contiguous(), lafs[perm].contiguous(), ids[perm].contiguous())
-    # the same SET of rows in the same (descending response) order, whatever order the caller supplied them in
-    assert torch.equal(ru, rs), "shuffled input rows: the selection is not the N largest responses"
-    assert torch.equal(iu, is_) and torch.equal(lu, ls)
+    resp, lafs, ids, cnt = rows_of(ctx)
+    assert int(cnt.item()) == ctx.cap_pre == 450 and ctx.cap_final == 300
+    Amat = torch.tensor([[1.2, 0.0], [0.1, 0.9]], device=DEV).repeat(ctx.cap_pre, 1, 1).contiguous()
+    variants("synthetic 240x320", ctx, resp, lafs, ids, cnt, Amat, 11, (40, 90), min_once=298)        # the 450 candidates hold one pair of equal responses
+    # second context: a planted detection with cap_pre = 1500 > 1024 rows
+    case = pl.single_bucket(192, 256, "digit3")
+    det2 = amd.ScaleSpaceAffinePatchExtractor(mrSize=5.192, num_features=1000, border=5, num_Baum_iters=1, AffNet=A,
+                                              RespNet=pl.planted_fn(case.H, case.W, case.plant, pl.plan_of(case.H, case.W)[1])).to(DEV)
+    det2.enqueue(torch.zeros(1, 1, case.H, case.W, device=DEV))
+    torch.cuda.synchronize()
+    ctx2 = det2._ctx
+    resp, lafs, ids, cnt = rows_of(ctx2)
+    assert int(cnt.item()) == ctx2.cap_pre == 1500 and ctx2.cap_final == 1000
+    Amat = torch.tensor([[1.2, 0.0], [0.1, 0.9]], device=DEV).repeat(ctx2.cap_pre, 1, 1).contiguous()
+    variants("planted 192x256", ctx2, resp, lafs, ids, cnt, Amat, 12, (300, 700), min_once=1)
 
 
 def test_two_stream_pipelining_gives_identical_results(amd, nets):
