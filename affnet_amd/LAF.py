@@ -2,7 +2,8 @@
 
 Only what the hot path and its callers need: extract_patches (:364-372), denormalizeLAFs /
 normalizeLAFs (:407-429), LAFs2ell (:225-240, host, Oxford ellipse text format),
-convertLAFs_to_A23format (:200-223)."""
+convertLAFs_to_A23format (:200-223), and the way back from ellipses: ells2LAFsT (:76-89, device), invSqrt / Ell2LAF / ells2LAFs
+(:11-34,154-183, host)."""
 import numpy as np
 import torch
 
@@ -57,6 +58,70 @@ def LAFs2ellT(LAFs):
         ctx = engine.utility_ctx(lafs.device)
         check(lib.affnet_lafs_to_ellipses(ctx, ptr(lafs), None, n, ptr(out), engine.stream_of(lafs.device)), ctx, "affnet_lafs_to_ellipses")
     return out
+
+
+def ells2LAFsT(ells):
+    """(n,5) cuda Oxford ellipses x y a b c -> (n,2,3) pixel LAFs on the device (LAF.py:76-89: invSqrtTorch :52-74, up-is-up rectification
+    :285-291).  The inverse of LAFs2ellT up to the rotation that the ellipse does not carry."""
+    engine.require_cuda(ells, "ells")
+    ell = ells.contiguous().float()
+    n = ell.size(0)
+    out = torch.zeros(n, 2, 3, dtype=torch.float32, device=ell.device)
+    if n:
+        ctx = engine.utility_ctx(ell.device)
+        check(lib.affnet_ellipses_to_lafs(ctx, ptr(ell), None, n, ptr(out), engine.stream_of(ell.device)), ctx, "affnet_ellipses_to_lafs")
+    return out
+
+
+def invSqrt(a, b, c):
+    """Inverse square root of the symmetric matrix [a b; b c], normalised to unit determinant: (new_a, new_b, new_c).  LAF.py:11-34
+    (scalars or numpy arrays; the arithmetic runs in the inputs' dtype)."""
+    eps = 1e-12
+    mask = (b != 0)
+    r1 = mask * (c - a) / (2. * b + eps)
+    t1 = np.sign(r1) / (np.abs(r1) + np.sqrt(1. + r1 * r1))
+    r = 1.0 / np.sqrt(1. + t1 * t1)
+    t = t1 * r
+    r = r * mask + 1.0 * (1.0 - mask)
+    t = t * mask
+    x = 1. / np.sqrt(r * r * a - 2 * r * t * b + t * t * c)
+    z = 1. / np.sqrt(t * t * a + 2 * r * t * b + r * r * c)
+    d = np.sqrt(x * z)
+    x = x / d
+    z = z / d
+    return r * r * x + t * t * z, -r * t * x + t * r * z, t * t * x + r * r * z
+
+
+def _rectify_up_is_up_np(A):
+    """LAF.py:168-176 (rectifyAffineTransformationUpIsUp_np)."""
+    det = np.sqrt(np.abs(A[0, 0] * A[1, 1] - A[1, 0] * A[0, 1] + 1e-10))
+    b2a2 = np.sqrt(A[0, 1] * A[0, 1] + A[0, 0] * A[0, 0])
+    return np.array([[b2a2 / det, 0.0], [(A[1, 1] * A[0, 1] + A[1, 0] * A[0, 0]) / (b2a2 * det), det / b2a2]])
+
+
+def Ell2LAF(ell):
+    """One Oxford ellipse x y a b c -> (2,3) float64 LAF.  LAF.py:154-166 with two departures, so that the host reader and the device reader
+    (ells2LAFsT, LAF.py:76-89) turn one ellipse file into the same frames: the scale carries ells2LAFsT's + 1e-12 under the root (:83; without
+    it a 100 px ellipse comes out 2.5e-5 larger than on the device), and the rectification is the numpy form of :168-176 (as shipped, :165
+    hands the 2x2 numpy matrix to the batched torch function, which cannot index it)."""
+    A23 = np.zeros((2, 3))
+    A23[0, 2], A23[1, 2] = ell[0], ell[1]
+    a, b, c = ell[2], ell[3], ell[4]
+    sc = np.sqrt(np.sqrt(a * c - b * b + 1e-12))
+    ia, ib, ic = invSqrt(a, b, c)
+    A = np.array([[ia, ib], [ib, ic]]) / sc
+    sc = np.sqrt(A[0, 0] * A[1, 1] - A[1, 0] * A[0, 1])
+    A23[0:2, 0:2] = _rectify_up_is_up_np(A / sc) * sc
+    return A23
+
+
+def ells2LAFs(ells):
+    """(n,5) numpy Oxford ellipses -> (n,2,3) float64 LAFs, row by row (host; LAF.py:178-182)."""
+    ells = np.asarray(ells)
+    LAFs = np.zeros((len(ells), 2, 3))
+    for i in range(len(ells)):
+        LAFs[i, :, :] = Ell2LAF(ells[i, :])
+    return LAFs
 
 
 def convertLAFs_to_A23format(LAFs):

@@ -122,6 +122,40 @@ class OnePassSIR(nn.Module):
         check(lib.affnet_detect_image_onepass_responses(ctx.handle, packed, ptr(rmaps), st), ctx.handle, "affnet_detect_image_onepass_responses")
         self._rmaps = rmaps         # stays alive until the kernels that read it have run
 
+    def _orientation_stage(self, ctx, lafs, ids, cnt, n):
+        """OnePassSIR.py:117-130 on rows < n of `lafs` (normalised, rotated IN PLACE): the OriNet slot on patches cut from the pyramid at
+        ids = (octave, level, *)."""
+        dev, st = lafs.device, engine.stream_of(lafs.device)
+        PS = self.OriNet.PS
+        patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
+        check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(lafs), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle, "affnet_pyr_grid_sample")
+        with torch.no_grad():
+            ang = self.OriNet(patches)
+        if ang.dim() <= 2:          # angles -> rotation matrices (LAF.py:306-311)
+            c, s = torch.cos(ang).view(-1, 1, 1), torch.sin(ang).view(-1, 1, 1)
+            ang = torch.cat([torch.cat([c, s], 2), torch.cat([-s, c], 2)], 1)
+        R = ang.to(dev, torch.float32).contiguous()
+        check(lib.affnet_apply_rotation(ctx.handle, ptr(lafs), ptr(R), ptr(cnt), n, st), ctx.handle, "affnet_apply_rotation")
+
+    def getOrientation(self, LAFs, final_pyr_idxs, final_level_idxs):
+        """OnePassSIR.py:117-130 with the reference's arguments: NORMALISED frames (n,2,3) and their pyramid (octave, level) indices -> the
+        frames rotated by the OriNet slot's answer on their patches, cut from the pyramid of the last forward() / run()."""
+        ctx = self._ctx
+        if ctx is None or self.scale_pyr is None:
+            raise RuntimeError("call forward() / run() first: the pyramid of the last image is reused (stateful like the reference)")
+        if ctx.batch != 1:
+            raise RuntimeError("getOrientation works on the pyramid of a single image")
+        engine.require_cuda(LAFs, "LAFs")
+        dev, n = LAFs.device, LAFs.size(0)
+        lafs = LAFs.float().contiguous().clone()
+        if n == 0:
+            return lafs
+        ids = torch.zeros(n, 3, dtype=torch.int32, device=dev)
+        ids[:, 0] = torch.as_tensor(final_pyr_idxs).to(dev).view(-1).to(torch.int32)
+        ids[:, 1] = torch.as_tensor(final_level_idxs).to(dev).view(-1).to(torch.int32)
+        self._orientation_stage(ctx, lafs, ids, torch.full((1,), n, dtype=torch.int32, device=dev), n)
+        return lafs
+
     def _staged_orientation(self, x, desc):
         """Foreign OriNet slot (OnePassSIR.py:117-130 getOrientation with any callable): detector on the device, the slot called on the
         patch tensor, rotation / denormalisation / descriptors by the stage kernels the fused path is made of."""
@@ -137,16 +171,7 @@ class OnePassSIR(nn.Module):
         check(lib.affnet_detected_list(ctx.handle, ptr(resp), ptr(lafs), ptr(ids), ptr(cnt), st), ctx.handle, "affnet_detected_list")
         ctx.read_counts()
         n = int(cnt.item())
-        PS = self.OriNet.PS
-        patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
-        check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(lafs), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle, "affnet_pyr_grid_sample")
-        with torch.no_grad():
-            ang = self.OriNet(patches)
-        if ang.dim() <= 2:          # angles -> rotation matrices (LAF.py:306-311)
-            c, s = torch.cos(ang).view(-1, 1, 1), torch.sin(ang).view(-1, 1, 1)
-            ang = torch.cat([torch.cat([c, s], 2), torch.cat([-s, c], 2)], 1)
-        R = ang.to(dev, torch.float32).contiguous()
-        check(lib.affnet_apply_rotation(ctx.handle, ptr(lafs), ptr(R), ptr(cnt), n, st), ctx.handle, "affnet_apply_rotation")
+        self._orientation_stage(ctx, lafs, ids, cnt, n)
         out = torch.empty_like(lafs)
         check(lib.affnet_scale_lafs(ctx.handle, ptr(lafs), ptr(out), ptr(cnt), P, x.size(3), x.size(2), 0, st), ctx.handle, "affnet_scale_lafs")
         dsc = None

@@ -51,6 +51,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         self.scale_pyr = self.sigmas = self.pix_dists = None
         self._ctx = None
         self._ctx_key = None
+        self._fctx = self._fctx_key = self._pyr_ctx = None    # context of the caller-supplied-frames path; owner of the published pyramid
         self.last_ids = None       # (N,3) int32 (octave, level-1, pixel) of the detections returned last
         self.max_keep = 16384      # row capacity in threshold mode (num = -1)
         self.raw_div = 4           # raw-maxima list capacity per octave = h*w / raw_div (overflow -> AffnetHipError, never truncation)
@@ -76,6 +77,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         return self._ctx
 
     def _publish_pyramid(self, ctx):
+        self._pyr_ctx = ctx          # the context whose workspace holds the published pyramid (getAffineShape / getOrientation sample from it)
         self.scale_pyr = ctx.pyramid_views()
         self.sigmas = [list(s) for s in ctx.plan.sigmas]
         self.pix_dists = [list(p) for p in ctx.plan.pix_dists]
@@ -159,12 +161,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
             self._busy.record(cur)
         if sift:
             # SparseImgRepresenter.py:181-188 on the device: pyramid level per frame, then SIFT on patches sampled from that level
-            st = engine.stream_of(dev)
-            lvl = torch.empty(B, F, 3, dtype=torch.int32, device=dev)
-            norm = torch.empty(B, F, 2, 3, dtype=torch.float32, device=dev)
-            check(lib.affnet_level_select(ctx.handle, ptr(lafs), ptr(count), F, desc.PS, ptr(lvl), ptr(norm), st), ctx.handle, "affnet_level_select")
-            check(lib.affnet_sift_forward_pyr(ctx.handle, ptr(norm), ptr(lvl), ptr(count), F, ptr(desc.window(dev)), float(desc.clipval), ptr(dsc), st),
-                  ctx.handle, "affnet_sift_forward_pyr")
+            self._sift_follow(ctx, desc, lafs, count, dsc)
             if det_stream is not None:             # the workspace is read until here
                 self._busy = torch.cuda.Event()
                 self._busy.record(torch.cuda.current_stream(dev))
@@ -173,6 +170,17 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         # "overflow": (B,) device view of the capacity-overflow flags (non-zero = a fixed-capacity list overflowed and this image's rows are
         # truncated) - valid once the enqueued work has completed; run() / run_batch() / bench.py check it through affnet_read_counts
         return {"LAFs": lafs, "responses": resp, "ids": ids, "descriptors": dsc, "count": count, "overflow": ctx.counter_view(0), "_img": img}
+
+    @staticmethod
+    def _sift_follow(ctx, desc, lafs, count, dsc):
+        """The SIFT descriptor behind a fused call: level choice of the pixel frames (B,F,2,3) and affnet_sift_forward_pyr into dsc (B,F,128)."""
+        dev, (B, F) = lafs.device, lafs.shape[:2]
+        st = engine.stream_of(dev)
+        lvl = torch.empty(B, F, 3, dtype=torch.int32, device=dev)
+        norm = torch.empty(B, F, 2, 3, dtype=torch.float32, device=dev)
+        check(lib.affnet_level_select(ctx.handle, ptr(lafs), ptr(count), F, desc.PS, ptr(lvl), ptr(norm), st), ctx.handle, "affnet_level_select")
+        check(lib.affnet_sift_forward_pyr(ctx.handle, ptr(norm), ptr(lvl), ptr(count), F, ptr(desc.window(dev)), float(desc.clipval), ptr(dsc), st),
+              ctx.handle, "affnet_sift_forward_pyr")
 
     def _nets(self, dev, do_ori, desc):
         nets = _lib.Nets()
@@ -231,13 +239,199 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         return {"LAFs": r["LAFs"][:n], "responses": r["responses"][:n], "ids": r["ids"][:n],
                 "descriptors": None if dsc is None else dsc[:n]}
 
+    # ---- caller-supplied keypoint frames -----------------------------------------------------------
+    def _frames_context(self, x, n_max):
+        """Context of the frames path: prefilter capacity = n_max rows; the feature budget is self.num when it cuts (0 < num < n_max and a shape
+        stage exists to cut in), otherwise n_max (no cut: affnet_describe_detected needs equal capacities without a shape stage)."""
+        engine.require_cuda(x, "image")
+        if x.dim() != 4 or x.size(1) != 1 or x.size(0) < 1:
+            raise ValueError("expected a (B,1,H,W) image batch")
+        budget = self.num if (0 < self.num < n_max and self.num_Baum_iters > 0) else n_max
+        key = (x.size(0), x.size(2), x.size(3), x.device, n_max, budget, self.mrSize, self.b, self.init_sigma, self.nlevels, self.num_Baum_iters,
+               self.raw_div, self.lazy_shape_rows)
+        if self._fctx is not None and self._fctx_key == key and self._fctx.arith != _lib.arith_code(self.arith):
+            self._fctx.set_arith(self.arith)
+        if self._fctx is None or self._fctx_key != key:
+            self._fctx = engine.Context(x.size(2), x.size(3), x.device, self.nlevels, self.init_sigma, self.b, self.mrSize, float(self.th), budget, n_max,
+                                        self.max_keep, batch=x.size(0), baum_iters=self.num_Baum_iters, raw_div=self.raw_div,
+                                        lazy_shape_rows=self.lazy_shape_rows, arith=self.arith)
+            self._fctx_key = key
+        return self._fctx
+
+    def enqueue_frames(self, x, LAFs, responses=None, counts=None, do_ori=True, desc=None):
+        """Describes keypoint frames of the CALLER on the fused path - affine shape (num_Baum_iters > 0), orientation (do_ori), descriptors
+        (desc: HardNet or SIFTNet) - instead of the Hessian detector's own: the reference's public getAffineShape / getOrientation used as
+        "frames in, descriptors out" (SparseImgRepresenter.py:113-180).  x (B,1,H,W); LAFs (n,2,3) or (B,n_max,2,3) cuda PIXEL frames that
+        describe the whole measurement region (mrSize is not applied again; LAF.ells2LAFsT reads them from Oxford ellipses); responses (n,) /
+        (B,n_max) or None = caller order (row i gets n_max - i); counts (B,) int32 device tensor (or a list of ints) of valid rows per image,
+        None = all.  No host synchronisation.  Returns the same dict as enqueue(); ids[..., 0:2] = the pyramid (octave, level) the first
+        sampling slot read, ids[..., 2] = the source row of every output row.  With num_features < n_max and a shape stage the num_features best
+        survivors of the shape filter are kept, like forward()."""
+        if not (self._native(self.AffNet) and self._native(self.OriNet)):
+            raise NotImplementedError("the fused path needs the native AffNetFast / OriNetFast slots (foreign slots: getAffineShape / getOrientation)")
+        engine.require_cuda(x, "image")
+        engine.require_cuda(LAFs, "LAFs")
+        dev, B = x.device, x.size(0)
+        fr = LAFs.contiguous().float()
+        if fr.dim() == 3:
+            fr = fr.unsqueeze(0)
+        if fr.dim() != 4 or fr.size(0) != B or tuple(fr.shape[2:]) != (2, 3):
+            raise ValueError("LAFs must be (n,2,3) for one image or (B,n_max,2,3) for a (B,1,H,W) batch, got %s" % (tuple(LAFs.shape),))
+        n_max = fr.size(1)
+        if n_max == 0:              # nothing to describe: one padding row that the zero count excludes
+            fr, responses, counts, n_max = torch.zeros(B, 1, 2, 3, dtype=torch.float32, device=dev), None, [0] * B, 1
+        rin = None
+        if responses is not None:
+            engine.require_cuda(responses, "responses")
+            rin = responses.contiguous().float().view(B, n_max)
+        cin = None
+        if counts is not None:
+            cin = counts if isinstance(counts, torch.Tensor) else torch.tensor(list(counts), dtype=torch.int32)
+            cin = cin.to(dev, torch.int32).contiguous().view(B)
+        ctx = self._frames_context(x, n_max)
+        img = x.contiguous().float()
+        F = ctx.cap_final
+        lafs = torch.empty(B, F, 2, 3, dtype=torch.float32, device=dev)
+        resp = torch.empty(B, F, dtype=torch.float32, device=dev)
+        ids = torch.empty(B, F, 3, dtype=torch.int32, device=dev)
+        count = torch.zeros(B, dtype=torch.int32, device=dev)
+        dsc = torch.empty(B, F, 128, dtype=torch.float32, device=dev) if desc is not None else None
+        nets = self._nets(dev, do_ori, desc)
+        sift = isinstance(desc, SIFTNet)
+        rc = lib.affnet_describe_frames(ctx.handle, C.byref(nets), ptr(img), ptr(fr), ptr(rin), ptr(cin), n_max, int(bool(do_ori)), ptr(lafs), ptr(resp),
+                                        ptr(ids), None if sift else ptr(dsc), ptr(count), engine.stream_of(dev))
+        check(rc, ctx.handle, "affnet_describe_frames")
+        if sift:
+            self._sift_follow(ctx, desc, lafs, count, dsc)
+        self._publish_pyramid(ctx)
+        if B == 1:
+            lafs, resp, ids, dsc = lafs[0], resp[0], ids[0], (None if dsc is None else dsc[0])
+        return {"LAFs": lafs, "responses": resp, "ids": ids, "descriptors": dsc, "count": count, "overflow": ctx.counter_view(0), "_img": img,
+                "_frames": (fr, rin, cin)}
+
+    def describe_frames(self, x, LAFs, responses=None, counts=None, do_ori=True, desc=None):
+        """enqueue_frames + the one read-back of the row counts and slicing: a dict(LAFs px (N,2,3), responses, ids, descriptors) for a single
+        image like run(), a list of B such dicts for a batch like run_batch() (images without rows are legal there).  Raises on a non-finite
+        input row (AffnetHipError) and, for a single image, when no row was given (AffnetEmptyError)."""
+        r = self.enqueue_frames(x, LAFs, responses=responses, counts=counts, do_ori=do_ori, desc=desc)
+        ctx = self._fctx
+        dsc = r["descriptors"]
+        if x.size(0) == 1:
+            n = int(ctx.read_counts()[1])
+            self.last_ids = r["ids"][:n]
+            return {"LAFs": r["LAFs"][:n], "responses": r["responses"][:n], "ids": r["ids"][:n], "descriptors": None if dsc is None else dsc[:n]}
+        ctx.read_counts(allow_empty=True)
+        return [{"LAFs": r["LAFs"][b, :n], "responses": r["responses"][b, :n], "ids": r["ids"][b, :n],
+                 "descriptors": None if dsc is None else dsc[b, :n]} for b, n in enumerate(r["count"].cpu().tolist())]
+
+    # ---- the two per-frame stages as the reference's public methods -------------------------------------
+    def _pyramid_ctx(self):
+        ctx = self._pyr_ctx
+        if ctx is None or self.scale_pyr is None:
+            raise RuntimeError("call forward() / run() first: the pyramid of the last image is reused (stateful like the reference)")
+        if ctx.batch != 1:
+            raise RuntimeError("getAffineShape / getOrientation work on the pyramid of a single image")
+        return ctx
+
+    def _shape_stage(self, ctx, resp, lafs, ids, cnt, n):
+        """SparseImgRepresenter.py:113-165 on rows < n of capacity-P arrays (normalised frames, (octave, level, tag) ids, cnt = device row
+        count): the AffNet slot on patches cut from the pyramid, its iterations, shape filter and top-N.  Returns the capacity-F arrays
+        (resp, frames, ids, cnt) and the new row count."""
+        dev, st = lafs.device, engine.stream_of(lafs.device)
+        P, F = ctx.cap_pre, ctx.cap_final
+        PS = self.AffNet.PS
+        patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
+
+        def shape_pass(frames):             # one evaluation of the slot on patches cut along `frames` (P,2,3), rows < n
+            check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(frames), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle,
+                  "affnet_pyr_grid_sample")
+            with torch.no_grad():
+                a = torch.cat([self.AffNet(patches[s:s + 256], {}) for s in range(0, n, 256)], 0)   # Utils.py:37-66
+            full = torch.zeros(P, 2, 2, dtype=torch.float32, device=dev)
+            full[:n] = a.to(dev, torch.float32)
+            return full
+        A = shape_pass(lafs)                # base_A = bmm(A_0, I) = A_0
+        if self.num_Baum_iters > 1:
+            # SparseImgRepresenter.py:127-146: patches re-extracted along [base_A * LAF | centre], base_A = A_i * base_A - the steps
+            # the fused path runs between its shape passes (affnet_shape_iterate), here around a foreign slot
+            frames = torch.empty(P, 2, 3, dtype=torch.float32, device=dev)
+            for _ in range(1, self.num_Baum_iters):
+                check(lib.affnet_shape_iterate(ctx.handle, None, ptr(A), ptr(lafs), ptr(cnt), 0, ptr(frames), st), ctx.handle, "affnet_shape_iterate")
+                Ai = shape_pass(frames)
+                check(lib.affnet_shape_iterate(ctx.handle, ptr(Ai), ptr(A), ptr(lafs), ptr(cnt), 1, ptr(frames), st), ctx.handle, "affnet_shape_iterate")
+        r2 = torch.empty(F, dtype=torch.float32, device=dev)
+        l2 = torch.empty(F, 2, 3, dtype=torch.float32, device=dev)
+        i2 = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        c2 = torch.zeros(1, dtype=torch.int32, device=dev)
+        check(lib.affnet_shape_filter_select(ctx.handle, ptr(resp), ptr(lafs), ptr(ids), ptr(A), ptr(cnt), ptr(r2), ptr(l2),
+                                             ptr(i2), ptr(c2), st), ctx.handle, "affnet_shape_filter_select")
+        return r2, l2, i2, c2, int(c2.item())
+
+    def _orientation_stage(self, ctx, lafs, ids, cnt, n):
+        """SparseImgRepresenter.py:167-180 on rows < n of `lafs` (normalised, rotated IN PLACE): the OriNet slot on patches cut from the pyramid."""
+        dev, st = lafs.device, engine.stream_of(lafs.device)
+        PS = self.OriNet.PS
+        patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
+        if n:
+            check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(lafs), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle,
+                  "affnet_pyr_grid_sample")
+        with torch.no_grad():
+            ang = self.OriNet(patches)
+        if ang.dim() <= 2:   # angles -> rotation matrices (LAF.py:306-311)
+            c, s = torch.cos(ang).view(-1, 1, 1), torch.sin(ang).view(-1, 1, 1)
+            ang = torch.cat([torch.cat([c, s], 2), torch.cat([-s, c], 2)], 1)
+        R = ang.to(dev, torch.float32).contiguous()
+        if n:
+            check(lib.affnet_apply_rotation(ctx.handle, ptr(lafs), ptr(R), ptr(cnt), n, st), ctx.handle, "affnet_apply_rotation")
+
+    @staticmethod
+    def _frame_rows(ctx, LAFs, pyr_idxs, level_idxs, cap):
+        """Caller rows -> the stage kernels' arrays: (cap,2,3) frames, (cap,3) int32 ids = (octave, level, source row), device row count."""
+        engine.require_cuda(LAFs, "LAFs")
+        dev, n = LAFs.device, LAFs.size(0)
+        if n > cap:
+            raise ValueError("%d frames, the context of the last forward() holds %d rows" % (n, cap))
+        lafs = torch.zeros(cap, 2, 3, dtype=torch.float32, device=dev)
+        lafs[:n] = LAFs.float()
+        ids = torch.zeros(cap, 3, dtype=torch.int32, device=dev)
+        ids[:n, 0] = torch.as_tensor(pyr_idxs).to(dev).view(-1).to(torch.int32)
+        ids[:n, 1] = torch.as_tensor(level_idxs).to(dev).view(-1).to(torch.int32)
+        ids[:n, 2] = torch.arange(n, dtype=torch.int32, device=dev)
+        return lafs, ids, torch.full((1,), n, dtype=torch.int32, device=dev), n
+
+    def getAffineShape(self, final_resp, LAFs, final_pyr_idxs, final_level_idxs, num_features=0):
+        """SparseImgRepresenter.py:113-165 with the reference's arguments and return values: responses (n,), NORMALISED frames (n,2,3) and their
+        pyramid (octave, level) indices -> (responses, frames with the estimated shape, octave, level indices) of the survivors of the shape
+        filter, at most num_features of them.  Samples the pyramid of the last forward() / run(); any frames, not only the detector's
+        (at most as many rows as that call's candidate capacity).  num_features must be the extractor's own budget (the context is sized for
+        it).  self.last_ids[:, 2] names the input row of every returned row."""
+        ctx = self._pyramid_ctx()
+        if self.num_Baum_iters <= 0:
+            raise ValueError("getAffineShape needs num_Baum_iters > 0 (the reference's loop body never runs otherwise, SparseImgRepresenter.py:127)")
+        if num_features != self.num and not (num_features <= 0 and self.num <= 0):
+            raise ValueError("num_features = %d: the context of the last forward() is sized for the extractor's own budget (%d)" % (num_features, self.num))
+        lafs, ids, cnt, n = self._frame_rows(ctx, LAFs, final_pyr_idxs, final_level_idxs, ctx.cap_pre)
+        resp = torch.zeros(ctx.cap_pre, dtype=torch.float32, device=lafs.device)
+        resp[:n] = final_resp.to(lafs.device, torch.float32).view(-1)
+        resp, lafs, ids, cnt, n = self._shape_stage(ctx, resp, lafs, ids, cnt, n)
+        self.last_ids = ids[:n]
+        return resp[:n], lafs[:n], ids[:n, 0].long(), ids[:n, 1].long()
+
+    def getOrientation(self, LAFs, final_pyr_idxs, final_level_idxs):
+        """SparseImgRepresenter.py:167-180: NORMALISED frames (n,2,3) and their pyramid (octave, level) indices -> the frames rotated by the
+        OriNet slot's answer on their patches, cut from the pyramid of the last forward() / run()."""
+        ctx = self._pyramid_ctx()
+        lafs, ids, cnt, n = self._frame_rows(ctx, LAFs, final_pyr_idxs, final_level_idxs, LAFs.size(0))
+        self._orientation_stage(ctx, lafs, ids, cnt, n)
+        return lafs
+
     # ------------------------------------------------------------------------------------------
     def _staged(self, x, do_ori):
         """Stage-by-stage path for foreign AffNet / OriNet slots (same kernels, slot called on tensors)."""
         ctx = self._context(x)
         dev, st = x.device, engine.stream_of(x.device)
         img = x.contiguous().float()
-        P, F = ctx.cap_pre, ctx.cap_final
+        P = ctx.cap_pre
         rmaps = None
         if self.RespNet is not None:
             rmaps = self._response_pyramid(ctx, img)
@@ -256,49 +450,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         n = int(cnt.item())
         ctx.read_counts()                   # raises AffnetEmptyError ("no keypoints detected") / on capacity overflow
         if self.num_Baum_iters > 0:
-            PS = self.AffNet.PS
-            patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
-
-            def shape_pass(frames):             # one evaluation of the slot on patches cut along `frames` (P,2,3), rows < n
-                check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(frames), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle,
-                      "affnet_pyr_grid_sample")
-                with torch.no_grad():
-                    a = torch.cat([self.AffNet(patches[s:s + 256], {}) for s in range(0, n, 256)], 0)   # Utils.py:37-66
-                full = torch.zeros(P, 2, 2, dtype=torch.float32, device=dev)
-                full[:n] = a.to(dev, torch.float32)
-                return full
-            A = shape_pass(lafs)                # base_A = bmm(A_0, I) = A_0
-            if self.num_Baum_iters > 1:
-                # SparseImgRepresenter.py:127-146: patches re-extracted along [base_A * LAF | centre], base_A = A_i * base_A - the steps
-                # the fused path runs between its shape passes (affnet_shape_iterate), here around a foreign slot
-                frames = torch.empty(P, 2, 3, dtype=torch.float32, device=dev)
-                for _ in range(1, self.num_Baum_iters):
-                    check(lib.affnet_shape_iterate(ctx.handle, None, ptr(A), ptr(lafs), ptr(cnt), 0, ptr(frames), st), ctx.handle, "affnet_shape_iterate")
-                    Ai = shape_pass(frames)
-                    check(lib.affnet_shape_iterate(ctx.handle, ptr(Ai), ptr(A), ptr(lafs), ptr(cnt), 1, ptr(frames), st), ctx.handle, "affnet_shape_iterate")
-            Afull = A
-            r2 = torch.empty(F, dtype=torch.float32, device=dev)
-            l2 = torch.empty(F, 2, 3, dtype=torch.float32, device=dev)
-            i2 = torch.empty(F, 3, dtype=torch.int32, device=dev)
-            c2 = torch.zeros(1, dtype=torch.int32, device=dev)
-            check(lib.affnet_shape_filter_select(ctx.handle, ptr(resp), ptr(lafs), ptr(ids), ptr(Afull), ptr(cnt), ptr(r2), ptr(l2),
-                                                 ptr(i2), ptr(c2), st), ctx.handle, "affnet_shape_filter_select")
-            n = int(c2.item())
-            resp, lafs, ids, cnt = r2, l2, i2, c2
+            resp, lafs, ids, cnt, n = self._shape_stage(ctx, resp, lafs, ids, cnt, n)
         if do_ori:
-            PS = self.OriNet.PS
-            patches = torch.empty(n, 1, PS, PS, dtype=torch.float32, device=dev)
-            if n:
-                check(lib.affnet_pyr_grid_sample(ctx.handle, ptr(lafs), ptr(ids), ptr(cnt), n, PS, ptr(patches), st), ctx.handle,
-                      "affnet_pyr_grid_sample")
-            with torch.no_grad():
-                ang = self.OriNet(patches)
-            if ang.dim() <= 2:   # angles -> rotation matrices (LAF.py:306-311)
-                c, s = torch.cos(ang).view(-1, 1, 1), torch.sin(ang).view(-1, 1, 1)
-                ang = torch.cat([torch.cat([c, s], 2), torch.cat([-s, c], 2)], 1)
-            R = ang.to(dev, torch.float32).contiguous()
-            if n:
-                check(lib.affnet_apply_rotation(ctx.handle, ptr(lafs), ptr(R), ptr(cnt), n, st), ctx.handle, "affnet_apply_rotation")
+            self._orientation_stage(ctx, lafs, ids, cnt, n)
         out = torch.empty_like(lafs)
         check(lib.affnet_scale_lafs(ctx.handle, ptr(lafs), ptr(out), ptr(cnt), lafs.size(0), x.size(3), x.size(2), 0, st), ctx.handle,
               "affnet_scale_lafs")

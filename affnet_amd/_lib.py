@@ -98,6 +98,7 @@ SYMBOLS = {
     "affnet_apply_rotation": (_I, [_P, _P, _P, _P, _I, _P]),
     "affnet_scale_lafs": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "affnet_lafs_to_ellipses": (_I, [_P, _P, _P, _I, _P, _P]),
+    "affnet_ellipses_to_lafs": (_I, [_P, _P, _P, _I, _P, _P]),
     "affnet_level_select": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "affnet_handcrafted_forward": (_I, [_P, _I, _P, _I, _P, _P, _P, _P]),
     "affnet_handcrafted_forward_pyr": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
@@ -115,6 +116,8 @@ SYMBOLS = {
     "affnet_detect_image_onepass": (_I, [_P, _P, _P, _P]),
     "affnet_detect_image_onepass_responses": (_I, [_P, _P, _P, _P]),
     "affnet_detected_list": (_I, [_P, _P, _P, _P, _P, _P]),
+    "affnet_load_frames": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "affnet_describe_frames": (_I, [_P, C.POINTER(Nets), _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_shape_iterate": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
     "affnet_affmap_offset": (C.c_int64, [_P, _I]),
     "affnet_affmap_image_stride": (C.c_int64, [_P]),

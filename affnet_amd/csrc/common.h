@@ -38,7 +38,11 @@ enum {
     CNT_TOTAL = AFFNET_MAX_OCTAVES + 24 + (AFFNET_MAX_LEVELS - 2) * AFFNET_MAX_OCTAVES + 8 * AFFNET_MAX_OCTAVES
 };
 
-#define SEL_HIST_BINS 2048      // first digit (11 bits) of the global top-k's radix select, histogrammed by many workgroups
+// CNT_OVERFLOW bits of affnet_load_frames (the detector and the shape stage use 1, 2, 4, 8; include/affnet_hip.h, affnet_read_counts)
+#define OVF_FRAMES_COUNT 16        // a device row count above n_max was clamped
+#define OVF_FRAMES_NONFINITE 32    // a row with a non-finite entry was stored as a zero row
+
+#define SEL_HIST_BINS 2048     // first digit (11 bits) of the global top-k's radix select, histogrammed by many workgroups
 
 struct RawMax {            // one 3-D local maximum found by hessian_nms_kernel
     int32_t pix;           // flat pixel index y*w+x in the octave

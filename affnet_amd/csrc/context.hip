@@ -323,6 +323,9 @@ extern "C" int affnet_read_counts(affnet_ctx* ctx, int32_t out[4], void* stream)
     }
     out[0] = host[CNT_DET]; out[1] = host[CNT_SHAPED]; out[2] = host[CNT_OVERFLOW];
     out[3] = raw;
+    if (host[CNT_OVERFLOW] & OVF_FRAMES_NONFINITE)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "load_frames: a caller-supplied frame or response was not finite (stored as a zero row; flag %d)",
+                        host[CNT_OVERFLOW]);
     if (host[CNT_OVERFLOW]) return aff_fail(ctx, AFFNET_ERR_CAPACITY, "a fixed-capacity detector list overflowed (flag %d)", host[CNT_OVERFLOW]);
     if (host[CNT_DET] == 0)
         return aff_fail(ctx, AFFNET_ERR_EMPTY, "no keypoints detected in %d image(s) (the reference raises in torch.cat, SparseImgRepresenter.py:100)", ctx->B);

@@ -353,18 +353,7 @@ __global__ void level_select_kernel(const float* __restrict__ lafs_px, const int
     if (i >= n) return;
     lafs_px += bi * n_max * 6; ids += bi * n_max * 3; lafs_norm += bi * n_max * 6;
     const float* L = lafs_px + 6 * (size_t)i;
-    // get_LAFs_scales (LAF.py:450-451) in fp32, then / PS in fp32, then float64 |a - b| argmin (cdist on 1-D points)
-    const float p1 = L[0] * L[4], p2 = L[1] * L[3];
-    const float sc = sqrtf(fabsf(p1 - p2) + 1e-12f);
-    const double need = (double)(sc / ps);
-    int best = 0;
-    double bd = INFINITY;
-    const int tot = lt.n_oct * lt.n_lvl;
-    for (int k = 0; k < tot; ++k) {
-        const double df = lt.sig[k] - need;
-        const double d = sqrt(df * df);               // scipy cdist 'euclidean' on 1-D points
-        if (d < bd) { bd = d; best = k; }
-    }
+    const int best = aff_level_argmin(L[0], L[1], L[3], L[4], ps, lt);
     ids[3 * i] = best / lt.n_lvl; ids[3 * i + 1] = best % lt.n_lvl; ids[3 * i + 2] = 0;
     float* O = lafs_norm + 6 * (size_t)i;
     O[0] = ca * L[0]; O[1] = ca * L[1]; O[2] = cx * L[2];
@@ -459,6 +448,152 @@ extern "C" int affnet_lafs_to_ellipses(affnet_ctx* ctx, const float* d_lafs, con
     if (!ctx || !d_lafs || !d_out || n_max < 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "lafs_to_ellipses: bad argument");
     if (n_max == 0) return AFFNET_OK;
     hipLaunchKernelGGL(lafs2ell_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, (hipStream_t)stream, d_lafs, d_count, n_max, d_out);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// ---- Oxford ellipse -> LAF on the device ---------------------------------------------------------------------------------
+// Replaces LAF.py:76-89 (ells2LAFsT) + :52-74 (invSqrtTorch) + :285-291 (rectifyAffineTransformationUpIsUp), operation by operation in fp32.
+__global__ void ell2lafs_kernel(const float* __restrict__ ell, const int32_t* __restrict__ d_count, int n_max, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t bi = blockIdx.y;
+    const int n = d_count ? min(d_count[bi], n_max) : n_max;
+    if (i >= n_max) return;
+    float* O = out + 6 * (bi * n_max + i);
+    if (i >= n) { O[0] = O[1] = O[2] = O[3] = O[4] = O[5] = 0.f; return; }
+    const float* E = ell + 5 * (bi * n_max + i);
+    const float a = E[2], b = E[3], c = E[4];
+    const float sc = sqrtf(sqrtf((a * c - b * b) + 1e-12f));
+    // invSqrtTorch: the rotation (r, t) that diagonalises [a b; b c], its eigenvalues to the power -1/2, normalised to unit determinant
+    const float mask = b != 0.0f ? 1.0f : 0.0f;
+    const float r1 = (mask * (c - a)) / (2.0f * b + 1e-12f);
+    const float sg = r1 > 0.0f ? 1.0f : (r1 < 0.0f ? -1.0f : 0.0f);
+    const float t1 = sg / (fabsf(r1) + sqrtf(1.0f + r1 * r1));
+    float r = 1.0f / sqrtf(1.0f + t1 * t1);
+    float t = t1 * r;
+    r = r * mask + 1.0f * (1.0f - mask);
+    t = t * mask;
+    const float rr = r * r, tt = t * t, rt2 = (2.0f * r) * t;
+    float x = 1.0f / sqrtf((rr * a - rt2 * b) + tt * c);
+    float z = 1.0f / sqrtf((tt * a + rt2 * b) + rr * c);
+    const float d = sqrtf(x * z);
+    x = x / d; z = z / d;
+    const float ia = rr * x + tt * z;
+    const float ib = ((-r) * t) * x + (t * r) * z;
+    const float ic = tt * x + rr * z;
+    const float a00 = ia / sc, a01 = ib / sc, a11 = ic / sc;        // A = [[ia, ib], [ib, ic]] / sc
+    const float sc2 = sqrtf(fabsf(a00 * a11 - a01 * a01));
+    const float b00 = a00 / sc2, b01 = a01 / sc2, b11 = a11 / sc2;
+    // rectifyAffineTransformationUpIsUp(A / sc2) * sc2
+    const float det = sqrtf(fabsf((b00 * b11 - b01 * b01) + 1e-10f));
+    const float b2a2 = sqrtf(b01 * b01 + b00 * b00);
+    O[0] = (b2a2 / det) * sc2; O[1] = (0.0f * det) * sc2; O[2] = E[0];
+    O[3] = ((b11 * b01 + b01 * b00) / (b2a2 * det)) * sc2; O[4] = (det / b2a2) * sc2; O[5] = E[1];
+}
+
+extern "C" int affnet_ellipses_to_lafs(affnet_ctx* ctx, const float* d_ell, const int32_t* d_count, int n_max, float* d_lafs, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_ell || !d_lafs || n_max < 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "ellipses_to_lafs: bad argument");
+    if (n_max == 0) return AFFNET_OK;
+    hipLaunchKernelGGL(ell2lafs_kernel, dim3(aff_cdiv(n_max, 256), ctx->B), dim3(256), 0, (hipStream_t)stream, d_ell, d_count, n_max, d_lafs);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// ---- caller-supplied frames -> the context's detection list (affnet_load_frames) ----------------------------------------------
+// Two launches.  frames_begin_kernel (one workgroup per image) leaves the image's counter block as a detector half would: everything 0
+// (raw maxima, candidates, overflow flag, the shape stage's counters), CNT_DET = the clamped row count, CNT_SEL_MODE = 1 ("rows are
+// response-sorted") until frames_rows_kernel finds a row whose response exceeds its predecessor's.
+__global__ __launch_bounds__(256) void frames_begin_kernel(const int32_t* __restrict__ d_count, int n_max, int32_t* __restrict__ cnt,
+                                                           int32_t* __restrict__ det_count) {
+    cnt += (size_t)blockIdx.y * CNT_TOTAL;
+    for (int k = threadIdx.x; k < CNT_TOTAL; k += 256) cnt[k] = 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int given = d_count ? d_count[blockIdx.y] : n_max;
+    const int n = given < 0 ? 0 : (given > n_max ? n_max : given);
+    if (given > n_max) cnt[CNT_OVERFLOW] = OVF_FRAMES_COUNT;
+    cnt[CNT_DET] = n; cnt[CNT_SEL_MODE] = 1;
+    det_count[blockIdx.y] = n;
+}
+
+struct FramesIn {            // caller arrays of image 0 (rows of image b at b * n_max); resp / ids may be NULL
+    const float* lafs; const float* resp; const int32_t* ids;
+    int n_max, normalised;
+};
+
+// Response row i is stored with: the caller's (or n_max - i), 0 for a row with a non-finite entry.
+__device__ __forceinline__ float frames_row_response(const FramesIn& in, size_t bi, int i, bool* finite) {
+    const float* L = in.lafs + 6 * (bi * in.n_max + i);
+    const float r = in.resp ? in.resp[bi * in.n_max + i] : (float)(in.n_max - i);
+    bool ok = isfinite(r);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ok = ok && isfinite(L[k]);
+    *finite = ok;
+    return ok ? r : 0.0f;
+}
+
+// One thread per row of the detection list (capacity cap rows per image): rows < count from the caller's arrays, the rest zero.
+__global__ __launch_bounds__(256) void frames_rows_kernel(FramesIn in, DenormSel ds, const int32_t* __restrict__ det_count, int cap,
+                                                          float* __restrict__ out_resp, float* __restrict__ out_lafs, int32_t* __restrict__ out_ids,
+                                                          int32_t* cnt) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const size_t bi = blockIdx.y;
+    if (i >= cap) return;
+    cnt += bi * CNT_TOTAL;
+    float* O = out_lafs + 6 * (bi * cap + i);
+    int32_t* I = out_ids + 3 * (bi * cap + i);
+    float* R = out_resp + bi * cap + i;
+    if (i >= det_count[bi]) {            // (det_count <= n_max <= cap)
+        *R = 0.0f; O[0] = O[1] = O[2] = O[3] = O[4] = O[5] = 0.f; I[0] = I[1] = I[2] = 0;
+        return;
+    }
+    bool finite;
+    const float r = frames_row_response(in, bi, i, &finite);
+    if (i > 0) {
+        bool pf;
+        const float prev = frames_row_response(in, bi, i - 1, &pf);
+        if (!(r <= prev)) cnt[CNT_SEL_MODE] = 0;       // every writer stores the same value
+    }
+    *R = r;
+    const int32_t* T = in.ids ? in.ids + 3 * (bi * in.n_max + i) : nullptr;
+    if (!finite) {
+        atomicOr(&cnt[CNT_OVERFLOW], OVF_FRAMES_NONFINITE);
+        O[0] = O[1] = O[2] = O[3] = O[4] = O[5] = 0.f;
+        I[0] = T ? T[0] : 0; I[1] = T ? T[1] : 0; I[2] = T ? T[2] : i;
+        return;
+    }
+    const float* L = in.lafs + 6 * (bi * in.n_max + i);
+    const float l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4], l5 = L[5];
+    if (in.normalised) {
+        O[0] = l0; O[1] = l1; O[2] = l2; O[3] = l3; O[4] = l4; O[5] = l5;
+    } else {                             // scale_lafs_kernel, inverse
+        O[0] = ds.ca * l0; O[1] = ds.ca * l1; O[2] = ds.cx * l2; O[3] = ds.ca * l3; O[4] = ds.ca * l4; O[5] = ds.cy * l5;
+    }
+    if (T) { I[0] = T[0]; I[1] = T[1]; I[2] = T[2]; return; }
+    // level of the PIXEL frame (normalised input: denormalised as scale_lafs_kernel does it), like level_select_kernel
+    const bool nm = in.normalised != 0;
+    const int best = aff_level_argmin(nm ? ds.c_a * l0 : l0, nm ? ds.c_a * l1 : l1, nm ? ds.c_a * l3 : l3, nm ? ds.c_a * l4 : l4, ds.ps, ds.lt);
+    I[0] = best / ds.lt.n_lvl; I[1] = best % ds.lt.n_lvl; I[2] = i;
+}
+
+extern "C" int affnet_load_frames(affnet_ctx* ctx, const float* d_lafs, int normalised, const float* d_resp, const int32_t* d_ids,
+                                  const int32_t* d_count, int n_max, int ps, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !ctx->ws || !d_lafs) return aff_fail(ctx, AFFNET_ERR_INVALID, "load_frames: context not bound or null frames");
+    if (n_max < 0 || n_max > ctx->cap_pre)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "load_frames: n_max = %d not in 0..%d (affnet_capacity_prefilter)", n_max, ctx->cap_pre);
+    if (!d_ids && ps < 1) return aff_fail(ctx, AFFNET_ERR_INVALID, "load_frames: patch size %d for the level choice", ps);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(frames_begin_kernel, dim3(1, ctx->B), dim3(256), 0, st, d_count, n_max, ctx->cnt, ctx->st_det_count);
+    AFF_LAUNCH_CHECK(ctx);
+    if (ctx->cap_pre == 0) return AFFNET_OK;
+    FramesIn in;
+    in.lafs = d_lafs; in.resp = d_resp; in.ids = d_ids; in.n_max = n_max; in.normalised = normalised ? 1 : 0;
+    DenormSel ds;
+    aff_denorm_sel_fill(ctx, ps < 1 ? 1 : ps, nullptr, nullptr, nullptr, &ds);
+    hipLaunchKernelGGL(frames_rows_kernel, dim3(aff_cdiv(ctx->cap_pre, 256), ctx->B), dim3(256), 0, st, in, ds, ctx->st_det_count, ctx->cap_pre,
+                       ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->cnt);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

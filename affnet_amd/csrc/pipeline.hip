@@ -232,6 +232,35 @@ extern "C" int affnet_extract_features(affnet_ctx* ctx, const affnet_nets* nets,
     return affnet_describe_detected(ctx, nets, do_ori, d_lafs_px, d_resp, d_ids, d_desc, d_count, stream);
 }
 
+// "Frames in, shapes, orientations and descriptors out" (SparseImgRepresenter.py:113-180 as public methods; the reference's
+// SIFT-AffNet-HardNet notebook): the caller's pixel frames take the detector's place in the internal list, the describe half is unchanged.
+extern "C" int affnet_describe_frames(affnet_ctx* ctx, const affnet_nets* nets, const float* d_img, const float* d_lafs_px, const float* d_resp_in,
+                                      const int32_t* d_count_in, int n_max, int do_ori, float* d_lafs_px_out, float* d_resp, int32_t* d_ids,
+                                      float* d_desc, int32_t* d_count, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !ctx->ws || !nets || !d_lafs_px || !d_lafs_px_out || !d_resp || !d_ids || !d_count)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "describe_frames: context not bound or null argument");
+    if (do_ori && !nets->d_orinet && !nets->h_orientation_window)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "describe_frames: do_ori needs OriNet weights or the OrientationDetector window");
+    if (d_desc && !nets->d_hardnet) return aff_fail(ctx, AFFNET_ERR_INVALID, "describe_frames: descriptors need HardNet weights");
+    hipStream_t st = (hipStream_t)stream;
+    aff_prof_mark(ctx, 0, st);
+    if (d_img) {
+        int rc = affnet_pyramid_build(ctx, d_img, stream);
+        if (rc) return rc;
+    }
+    aff_prof_mark(ctx, 1, st);
+    // patch size of the first slot that samples along these frames: its level choice is the one that matters
+    int ps = 32;
+    if (nets->d_affnet) ps = 32;
+    else if (nets->h_baumberg_window && ctx->cfg.baum_iters > 0) ps = 19;
+    else if (do_ori && !nets->d_orinet) ps = 19;
+    int rc = affnet_load_frames(ctx, d_lafs_px, 0, d_resp_in, nullptr, d_count_in, n_max, ps, stream);
+    if (rc) return rc;
+    aff_prof_mark(ctx, 9, st);
+    return affnet_describe_detected(ctx, nets, do_ori, d_lafs_px_out, d_resp, d_ids, d_desc, d_count, stream);
+}
+
 
 // ---- the whole path as ONE HIP graph ---------------------------------------------------------------------------------
 // affnet_extract_features enqueues ~45 kernels / memsets without ever touching the host, so for a fixed set of buffers it can be

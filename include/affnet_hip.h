@@ -368,6 +368,11 @@ int affnet_scale_lafs(affnet_ctx* ctx, const float* d_in, float* d_out, const in
  * Replaces LAF.py:35-51 (LAFs2ellT) + :106-144 (bsvd2x2).  Rows >= count are zero. */
 int affnet_lafs_to_ellipses(affnet_ctx* ctx, const float* d_lafs, const int32_t* d_count, int n_max, float* d_out, void* stream);
 
+/* The inverse: Oxford ellipses (n,5) = x y a b c -> pixel LAFs (n,2,3) with A = up-is-up rectified ([a b; b c])^-1/2.
+ * Replaces LAF.py:76-89 (ells2LAFsT) + :52-74 (invSqrtTorch) + :285-291 (rectifyAffineTransformationUpIsUp), operation by
+ * operation in fp32.  The centres pass through bit for bit.  Rows >= count are zero (d_count NULL => n_max rows). */
+int affnet_ellipses_to_lafs(affnet_ctx* ctx, const float* d_ell, const int32_t* d_count, int n_max, float* d_lafs, void* stream);
+
 /* Pyramid level for descriptor patches: argmin over (o,l) of |sigma[o][l]*2^o - sqrt|det A|/PS|
  * in float64, first minimum wins; also writes normalised LAFs (by pyr[0][0] size).
  * Replaces LAF.py:450-472 (host scipy cdist round trip) + SparseImgRepresenter.py:181-188.
@@ -459,6 +464,42 @@ int affnet_detect_image_onepass_responses(affnet_ctx* ctx, const float* d_packed
  * NORMALISED LAFs (x mrSize), (octave, level, pixel) ids, row counts.  For callers that run a foreign (Python) OriNet / AffNet /
  * descriptor between the stages (SparseImgRepresenter.py:38-49, OnePassSIR.py:44-47) on exactly the rows the fused path would use. */
 int affnet_detected_list(affnet_ctx* ctx, float* d_resp, float* d_lafs, int32_t* d_ids, int32_t* d_count, void* stream);
+/* Caller-supplied keypoint frames instead of a detector half: fills the context's internal detection list (and the per-image
+ * counters behind affnet_read_counts / affnet_counter_offset) as a detector half leaves them, for B images, without a host
+ * synchronisation.  Follow with affnet_describe_detected; the pyramid must have been built with affnet_pyramid_build.
+ * This is the way in that the reference's public getAffineShape / getOrientation (SparseImgRepresenter.py:113-180) offer: any
+ * frames, not only the Hessian detector's.
+ *   d_lafs  (B,n_max,2,3), n_max <= affnet_capacity_prefilter(ctx) (else AFFNET_ERR_INVALID).  normalised = 0: pixel frames as
+ *           affnet_extract_features returns them - they describe the whole measurement region, mrSize is not applied again; they
+ *           are normalised with affnet_scale_lafs(inverse = 1)'s constants.  normalised = 1: the reference's normalised frames, as
+ *           getAffineShape takes them (what affnet_detected_list returns).
+ *   d_ids   NULL: (octave, level) of every frame by the rule of get_pyramid_and_level_index_for_LAFs (LAF.py:450-472) at patch
+ *           size ps, bit-identical to affnet_level_select (normalised frames are denormalised like affnet_scale_lafs first), and
+ *           column 2 = the source row index i.  Otherwise (B,n_max,3), copied through: columns 0 / 1 are the reference's
+ *           final_pyr_idxs / final_level_idxs (the samplers clamp them to the pyramid), column 2 is an opaque caller tag.  Column 2
+ *           survives the shape stage into affnet_describe_detected's d_ids: every output row names the input row it came from.
+ *   d_resp  NULL: the response of row i is (float)(n_max - i), strictly decreasing: caller order is kept and a top-N keeps the
+ *           first N survivors of the shape filter.  Otherwise (B,n_max).
+ *   d_count NULL: n_max rows in every image.  Otherwise (B); a count above n_max is clamped to n_max (below 0: to 0) and bit 16
+ *           of the overflow flag is set.
+ * The rows are taken as response-sorted (lazy second AffNet pass, prefix selection) only if this call has verified that the
+ * responses of the rows < count are non-increasing; unsorted rows take the general paths with identical results.
+ * A row with a non-finite frame entry or response is stored as an all-zero frame with response 0 and bit 32 of the overflow flag
+ * is set: affnet_read_counts then returns AFFNET_ERR_INVALID.  The results of such a call are unspecified, but no non-finite
+ * coordinate reaches a sampler. */
+int affnet_load_frames(affnet_ctx* ctx, const float* d_lafs, int normalised, const float* d_resp, const int32_t* d_ids,
+                       const int32_t* d_count, int n_max, int ps, void* stream);
+
+/* affnet_pyramid_build (skipped when d_img == NULL: the pyramid of the image is already in the workspace),
+ * affnet_load_frames(d_lafs_px, normalised = 0, ids NULL, ps = the patch size of the first slot that samples: 32 for AffNetFast /
+ * OriNetFast / HardNet, 19 for the hand-crafted windows) and affnet_describe_detected in one call: "frames in, shapes, orientations
+ * and descriptors out" (examples/SIFT-AffNet-HardNet-kornia-matching.ipynb of the reference) with pyramid-level sampling, the
+ * shape filter / top-N and the batch per launch of the fused path.  d_lafs_px (B,n_max,2,3) pixel frames, d_resp_in (B,n_max) or
+ * NULL, d_count_in (B) or NULL as for affnet_load_frames; outputs as for affnet_extract_features, d_ids[..., 2] = source row. */
+int affnet_describe_frames(affnet_ctx* ctx, const affnet_nets* nets, const float* d_img, const float* d_lafs_px, const float* d_resp_in,
+                           const int32_t* d_count_in, int n_max, int do_ori, float* d_lafs_px_out, float* d_resp, int32_t* d_ids,
+                           float* d_desc, int32_t* d_count, void* stream);
+
 /* Float offset (from the workspace base) of the (4, h_o, w_o) affine-shape map of octave o of image 0, and the floats between the
  * maps of consecutive images; -1 / 0 when the context has no OnePassSIR areas. */
 int64_t affnet_affmap_offset(const affnet_ctx* ctx, int octave);
@@ -488,7 +529,10 @@ int affnet_profile_read(affnet_ctx* ctx, double sum_ms[AFFNET_PROFILE_STAGES], i
  * out[0] = rows after detection, out[1] = rows after shape filter, out[2] = capacity-overflow
  * flag, out[3] = raw maxima found (sums / OR over the images of the batch).
  * Returns AFFNET_ERR_CAPACITY when a fixed-capacity device list overflowed (results would be truncated: treat as an
- * error), AFFNET_ERR_EMPTY when no image of the call produced a detection (out[] is still filled), else AFFNET_OK. */
+ * error), AFFNET_ERR_EMPTY when no image of the call produced a detection (out[] is still filled), else AFFNET_OK.
+ * Bits of the flag: 1 raw-maxima list, 2 candidate list, 4 selected list, 8 shape-stage output, 16 a device row count handed to
+ * affnet_load_frames exceeded its n_max (clamped), 32 affnet_load_frames met a non-finite row: that one is the caller's input, not a
+ * capacity, and returns AFFNET_ERR_INVALID. */
 int affnet_read_counts(affnet_ctx* ctx, int32_t out[4], void* stream);
 
 /* The same counters without a host synchronisation: int32 offset (from the workspace base) of a per-image device counter of image 0
