@@ -69,6 +69,9 @@ class OnePassSIR(nn.Module):
         """Whole path without host synchronisation; x (B,1,H,W).  Returns capacity-sized device tensors + the device row counts."""
         if do_ori and not isinstance(self.OriNet, (_HipPatchNet, _HipHandCrafted)):      # before anything is enqueued
             raise NotImplementedError("enqueue() is the no-synchronisation path: a foreign OriNet runs Python between the stages - use run() / forward()")
+        if desc is not None and getattr(desc, "KIND", None) != _lib.NET_HARDNET:      # the fused call reads d_hardnet as a HardNet blob, nothing else
+            raise NotImplementedError("the fused OnePassSIR call describes with HardNet only, got %s (SIFTNet / HardTFeatNet: describe the returned LAFs "
+                                      "through ScaleSpaceAffinePatchExtractor.describe_frames)" % type(desc).__name__)
         ctx = self._context(x)
         dev, st = x.device, engine.stream_of(x.device)
         img = x.contiguous().float()

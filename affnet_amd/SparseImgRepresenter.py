@@ -23,7 +23,10 @@ from . import _lib, engine
 from ._lib import lib, check, ptr
 from .architectures import _HipPatchNet
 from .HandCraftedModules import AffineShapeEstimator, OrientationDetector, _HipHandCrafted
+from .HardNet import HardTFeatNet
 from .pytorch_sift import SIFTNet
+
+_FOLLOW = (SIFTNet, HardTFeatNet)      # descriptors that run behind the fused C call (level choice + their pyramid-form kernel), not inside it
 
 
 class ScaleSpaceAffinePatchExtractor(nn.Module):
@@ -112,9 +115,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         covers the B images, results get a leading batch dimension and `count` is (B,).  With `det_stream` (a torch.cuda.Stream) the
         pyramid + detector run there and the CNN stages on the current stream, ordered by events, so that
         two extractor objects alternating over a stream of images overlap the latency-bound detector of
-        image i+1 with the MFMA-bound CNN stages of image i.  `desc`: a HardNet (inside the fused call) or a SIFTNet (the geometry is
-        enqueued without a descriptor buffer; level choice and affnet_sift_forward_pyr follow on the current stream, patches sampled
-        from the pyramid, still no host synchronisation).  `input_ready`: None = the detector stream first waits for
+        image i+1 with the MFMA-bound CNN stages of image i.  `desc`: a HardNet (inside the fused call), or a SIFTNet / HardTFeatNet (the
+        geometry is enqueued without a descriptor buffer; level choice and affnet_sift_forward_pyr / affnet_tfeat_forward_pyr follow on the
+        current stream, patches sampled from the pyramid, still no host synchronisation; the extractor's `arith` governs the geometry only).  `input_ready`: None = the detector stream first waits for
         everything enqueued so far on the current stream (safe default: x may still be in flight there); a
         torch.cuda.Event = wait for that event only; False = x is already resident (no wait)."""
         ctx = self._context(x, allow_batch=True)
@@ -129,8 +132,10 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         count = torch.zeros(B, dtype=torch.int32, device=dev)
         dsc = torch.empty(B, F, 128, dtype=torch.float32, device=dev) if desc is not None else None
         nets = self._nets(dev, do_ori, desc)
-        sift = isinstance(desc, SIFTNet)
-        fused_dsc = None if sift else dsc          # the descriptor buffer of the fused C call: HardNet's only
+        follow = isinstance(desc, _FOLLOW)
+        if isinstance(desc, HardTFeatNet):
+            desc.check_usable()
+        fused_dsc = None if follow else dsc          # the descriptor buffer of the fused C call: HardNet's only
         if self.RespNet is not None:
             rmaps = self._response_pyramid(ctx, img)
             check(lib.affnet_detect_image_responses(ctx.handle, ptr(rmaps), engine.stream_of(dev)), ctx.handle, "affnet_detect_image_responses")
@@ -159,9 +164,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
             check(rc, ctx.handle, "affnet_describe_detected")
             self._busy = torch.cuda.Event()
             self._busy.record(cur)
-        if sift:
-            # SparseImgRepresenter.py:181-188 on the device: pyramid level per frame, then SIFT on patches sampled from that level
-            self._sift_follow(ctx, desc, lafs, count, dsc)
+        if follow:
+            # SparseImgRepresenter.py:181-188 on the device: pyramid level per frame, then the descriptor on patches sampled from that level
+            self._desc_follow(ctx, desc, lafs, count, dsc)
             if det_stream is not None:             # the workspace is read until here
                 self._busy = torch.cuda.Event()
                 self._busy.record(torch.cuda.current_stream(dev))
@@ -171,14 +176,22 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         # truncated) - valid once the enqueued work has completed; run() / run_batch() / bench.py check it through affnet_read_counts
         return {"LAFs": lafs, "responses": resp, "ids": ids, "descriptors": dsc, "count": count, "overflow": ctx.counter_view(0), "_img": img}
 
-    @staticmethod
-    def _sift_follow(ctx, desc, lafs, count, dsc):
-        """The SIFT descriptor behind a fused call: level choice of the pixel frames (B,F,2,3) and affnet_sift_forward_pyr into dsc (B,F,128)."""
+    def _desc_follow(self, ctx, desc, lafs, count, dsc):
+        """The SIFT / HardTFeat descriptor behind a fused call: level choice of the pixel frames (B,F,2,3) and affnet_sift_forward_pyr /
+        affnet_tfeat_forward_pyr into dsc (B,F,128)."""
         dev, (B, F) = lafs.device, lafs.shape[:2]
         st = engine.stream_of(dev)
         lvl = torch.empty(B, F, 3, dtype=torch.int32, device=dev)
         norm = torch.empty(B, F, 2, 3, dtype=torch.float32, device=dev)
         check(lib.affnet_level_select(ctx.handle, ptr(lafs), ptr(count), F, desc.PS, ptr(lvl), ptr(norm), st), ctx.handle, "affnet_level_select")
+        if isinstance(desc, HardTFeatNet):
+            floats = lib.affnet_tfeat_scratch_floats(B * F)
+            cached = getattr(self, "_tfeat_scratch", None)         # one cached scratch tensor, grown when a larger call comes
+            if cached is None or cached.device != dev or cached.numel() < floats:
+                cached = self._tfeat_scratch = torch.empty(floats, dtype=torch.float32, device=dev)
+            check(lib.affnet_tfeat_forward_pyr(ctx.handle, ptr(desc.packed_weights(dev)), ptr(norm), ptr(lvl), ptr(count), F, ptr(dsc), ptr(cached), st),
+                  ctx.handle, "affnet_tfeat_forward_pyr")
+            return
         check(lib.affnet_sift_forward_pyr(ctx.handle, ptr(norm), ptr(lvl), ptr(count), F, ptr(desc.window(dev)), float(desc.clipval), ptr(dsc), st),
               ctx.handle, "affnet_sift_forward_pyr")
 
@@ -194,7 +207,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                 nets.h_orientation_window = C.cast(self.OriNet.window(), C.c_void_p)
             else:
                 nets.d_orinet = self.OriNet.packed_weights(dev).data_ptr()
-        nets.d_hardnet = desc.packed_weights(dev).data_ptr() if desc is not None and not isinstance(desc, SIFTNet) else None
+        nets.d_hardnet = desc.packed_weights(dev).data_ptr() if desc is not None and not isinstance(desc, _FOLLOW) else None
         return nets
 
     def capture(self, x, do_ori=False, desc=None):
@@ -202,9 +215,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         CapturedPath: `.image` is the static input tensor, `.launch(x)` copies x into it and replays the graph with a single launch
         on the current stream (returns the same dict as enqueue()), `.run(x)` adds the count read-back and slicing of run().  For
         callers that process one image at a time (hesaffnet.py:35-60): ~45 kernel launches per image become one."""
-        if isinstance(desc, SIFTNet):
-            raise NotImplementedError("graph capture covers the fused C call (HardNet descriptors or none); the SIFT descriptor follows it "
-                                      "as two more launches - use enqueue() / run()")
+        if isinstance(desc, _FOLLOW):
+            raise NotImplementedError("graph capture covers the fused C call (HardNet descriptors or none); the SIFT and HardTFeat descriptors "
+                                      "follow it as further launches - use enqueue() / run()")
         return CapturedPath(self, x, do_ori, desc)
 
     def run_batch(self, x, do_ori=False, desc=None):
@@ -225,7 +238,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
 
     def run(self, x, do_ori=False, desc=None):
         """Fused path.  Returns dict(LAFs px (N,2,3), responses (N,), ids (N,3), descriptors (N,128)|None).
-        `desc`: affnet_amd.HardNet.HardNet, affnet_amd.pytorch_sift.SIFTNet or None."""
+        `desc`: affnet_amd.HardNet.HardNet, affnet_amd.HardNet.HardTFeatNet, affnet_amd.pytorch_sift.SIFTNet or None."""
         if x.dim() == 4 and x.size(0) != 1:
             raise ValueError("run() is for a single (1,1,H,W) image; use run_batch() for (B,1,H,W) batches")
         r = self.enqueue(x, do_ori=do_ori, desc=desc)
@@ -260,7 +273,7 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
 
     def enqueue_frames(self, x, LAFs, responses=None, counts=None, do_ori=True, desc=None):
         """Describes keypoint frames of the CALLER on the fused path - affine shape (num_Baum_iters > 0), orientation (do_ori), descriptors
-        (desc: HardNet or SIFTNet) - instead of the Hessian detector's own: the reference's public getAffineShape / getOrientation used as
+        (desc: HardNet, HardTFeatNet or SIFTNet) - instead of the Hessian detector's own: the reference's public getAffineShape / getOrientation used as
         "frames in, descriptors out" (SparseImgRepresenter.py:113-180).  x (B,1,H,W); LAFs (n,2,3) or (B,n_max,2,3) cuda PIXEL frames that
         describe the whole measurement region (mrSize is not applied again; LAF.ells2LAFsT reads them from Oxford ellipses); responses (n,) /
         (B,n_max) or None = caller order (row i gets n_max - i); counts (B,) int32 device tensor (or a list of ints) of valid rows per image,
@@ -297,12 +310,14 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         count = torch.zeros(B, dtype=torch.int32, device=dev)
         dsc = torch.empty(B, F, 128, dtype=torch.float32, device=dev) if desc is not None else None
         nets = self._nets(dev, do_ori, desc)
-        sift = isinstance(desc, SIFTNet)
+        follow = isinstance(desc, _FOLLOW)
+        if isinstance(desc, HardTFeatNet):
+            desc.check_usable()
         rc = lib.affnet_describe_frames(ctx.handle, C.byref(nets), ptr(img), ptr(fr), ptr(rin), ptr(cin), n_max, int(bool(do_ori)), ptr(lafs), ptr(resp),
-                                        ptr(ids), None if sift else ptr(dsc), ptr(count), engine.stream_of(dev))
+                                        ptr(ids), None if follow else ptr(dsc), ptr(count), engine.stream_of(dev))
         check(rc, ctx.handle, "affnet_describe_frames")
-        if sift:
-            self._sift_follow(ctx, desc, lafs, count, dsc)
+        if follow:
+            self._desc_follow(ctx, desc, lafs, count, dsc)
         self._publish_pyramid(ctx)
         if B == 1:
             lafs, resp, ids, dsc = lafs[0], resp[0], ids[0], (None if dsc is None else dsc[0])
@@ -555,7 +570,7 @@ class CapturedPath(object):
 def get_geometry_and_descriptors(img, det, desc, do_ori=True):
     """train_OriNet_test_on_graffity.py:293-298.  With native nets this is one fused C call."""
     from .HardNet import HardNet
-    if isinstance(desc, (HardNet, SIFTNet)) and det._native(det.AffNet) and det._native(det.OriNet):
+    if isinstance(desc, (HardNet,) + _FOLLOW) and det._native(det.AffNet) and det._native(det.OriNet):
         r = det.run(img, do_ori=do_ori, desc=desc)
         return r["LAFs"], r["descriptors"]
     with torch.no_grad():

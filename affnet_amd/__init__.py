@@ -6,7 +6,7 @@ from . import _lib  # noqa: F401  (raises ImportError when libaffnet_hip.so is m
 from .SparseImgRepresenter import ScaleSpaceAffinePatchExtractor, get_geometry_and_descriptors  # noqa: F401
 from .architectures import AffNetFast, OriNetFast, AffNetFastFullConv  # noqa: F401
 from .OnePassSIR import OnePassSIR  # noqa: F401
-from .HardNet import HardNet  # noqa: F401
+from .HardNet import HardNet, HardTFeatNet  # noqa: F401
 from .pytorch_sift import SIFTNet  # noqa: F401
 from . import LAF, HandCraftedModules, Losses, ReprojectionStuff, pytorch_sift  # noqa: F401
 from .synthetic import synthetic_image, synthetic_hardnet_state  # noqa: F401

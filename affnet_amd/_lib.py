@@ -105,6 +105,11 @@ SYMBOLS = {
     "affnet_sift_host_window": (_I, [_I, C.POINTER(C.c_float)]),
     "affnet_sift_forward": (_I, [_P, _P, _I, _P, C.c_float, _P, _P]),
     "affnet_sift_forward_pyr": (_I, [_P, _P, _P, _P, _I, _P, C.c_float, _P, _P]),
+    "affnet_tfeat_packed_floats": (_SZ, []),
+    "affnet_tfeat_pack_weights": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "affnet_tfeat_scratch_floats": (_SZ, [_I]),
+    "affnet_tfeat_forward": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
+    "affnet_tfeat_forward_pyr": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "affnet_match_scratch_bytes": (_SZ, [_I, _I]),
     "affnet_distance_matrix": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "affnet_match_snn": (_I, [_P, _P, _I, _P, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P]),

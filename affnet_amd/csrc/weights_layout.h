@@ -113,6 +113,35 @@ static inline NetOffsets to_offsets(const NetLayout& L, int arith = AFFNET_ARITH
     return o;
 }
 
+// ---- HardTFeat (tfeat.hip): a blob of its own (affnet_tfeat_packed_floats), no BatchNorm to fold ---------------------------------------
+//   conv1 1 -> 32, 7 x 7     [k = ky * 7 + kx (52, rows 49..51 zero)][n]: the B operand of 13 MFMA k-steps;   bias [32]
+//   conv2 32 -> 64, 6 x 6    w_tap_index over 36 taps p = ky * 6 + kx, cin 32, cout 64;                          bias [64]
+//   classifier 64 -> 128, 8 x 8 as a (4096 x 128) GEMM: k = (y * 8 + x) * 64 + c, the order in which the trunk kernel stores conv2's output
+//                            (the reference flattens as c * 64 + y * 8 + x: the packer transposes, callers never see k), in the head
+//                            order [k/16][(k/4)%4][n][k%4];                                                        bias [128]
+#define TFEAT_K1 52             // conv1's K = 49 taps padded to a multiple of the MFMA's 4
+#define TFEAT_HEAD_K 4096       // contraction length of the classifier
+constexpr size_t tfeat_c1_index(int k, int n) { return (size_t)k * 32 + n; }
+constexpr size_t tfeat_c2_index(int p, int c, int n) { return w_tap_index(p, c, n, 32, 64); }
+constexpr size_t tfeat_head_index(int pixel, int c, int n) { return w_tap_index(0, pixel * 64 + c, n, TFEAT_HEAD_K, 128); }
+
+struct TfeatLayout {
+    size_t c1_w, c1_b, c2_w, c2_b, head_w, head_b, total;
+};
+
+static inline TfeatLayout tfeat_layout() {
+    TfeatLayout L;
+    size_t off = 0;
+    L.c1_w = off; off += (size_t)TFEAT_K1 * 32;
+    L.c1_b = off; off += 32;
+    L.c2_w = off; off += (size_t)36 * 32 * 64;
+    L.c2_b = off; off += 64;
+    L.head_w = off; off += (size_t)TFEAT_HEAD_K * 128;
+    L.head_b = off; off += 128;
+    L.total = off;
+    return L;
+}
+
 // ---- Winograd F(2x2, 3x3) weight transform --------------------------------------------------------------
 // U = G g G^T of one 3x3 filter g[ky * 3 + kx] into U[xi = 4 i + j], along x and then along y, one fp32 rounding per operation (the
 // library is built with -ffp-contract=off).  The single definition of the operation order: the packer (HardNet's Winograd section) and

@@ -22,6 +22,29 @@ extern "C" int64_t affnet_cnn32_winograd_offset(int net_kind, int layer) {
     return L.w_wino[layer] ? (int64_t)L.w_wino[layer] : -1;
 }
 
+extern "C" size_t affnet_tfeat_packed_floats(void) { return tfeat_layout().total; }
+
+// HardTFeat: no BatchNorm, so every weight is copied unchanged into the element orders of weights_layout.h (tfeat_c1_index, tfeat_c2_index,
+// tfeat_head_index); conv1's rows 49..51 stay zero.
+extern "C" int affnet_tfeat_pack_weights(const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b, const float* cls_w,
+                                         const float* cls_b, float* h_out) {
+    if (!conv1_w || !conv1_b || !conv2_w || !conv2_b || !cls_w || !cls_b || !h_out) return AFFNET_ERR_INVALID;
+    const TfeatLayout L = tfeat_layout();
+    memset(h_out, 0, L.total * sizeof(float));
+    for (int n = 0; n < 32; ++n)                                // conv1 [n][1][7][7]
+        for (int k = 0; k < 49; ++k) h_out[L.c1_w + tfeat_c1_index(k, n)] = conv1_w[n * 49 + k];
+    memcpy(h_out + L.c1_b, conv1_b, 32 * sizeof(float));
+    for (int n = 0; n < 64; ++n)                                // conv2 [n][c 32][6][6]
+        for (int c = 0; c < 32; ++c)
+            for (int p = 0; p < 36; ++p) h_out[L.c2_w + tfeat_c2_index(p, c, n)] = conv2_w[((size_t)n * 32 + c) * 36 + p];
+    memcpy(h_out + L.c2_b, conv2_b, 64 * sizeof(float));
+    for (int n = 0; n < 128; ++n)                               // classifier [n][c 64][8][8]
+        for (int c = 0; c < 64; ++c)
+            for (int p = 0; p < 64; ++p) h_out[L.head_w + tfeat_head_index(p, c, n)] = cls_w[((size_t)n * 64 + c) * 64 + p];
+    memcpy(h_out + L.head_b, cls_b, 128 * sizeof(float));
+    return AFFNET_OK;
+}
+
 namespace {
 
 // BatchNorm2d(affine=False), eps 1e-5, eval mode, folded into `cout` filters of `k` weights: w * s (one multiply) and the bias -mean * s

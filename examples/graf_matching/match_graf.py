@@ -3,12 +3,15 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
 missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
 --desc sift: SIFTNet(patch_size=32), the descriptor the reference's test() constructs (train_AffNet_test_on_graffity.py:122) - no
-weights needed; at N = 500 it gives the reference's 79 tentatives / 4 true matches."""
+weights needed; at N = 500 it gives the reference's 79 tentatives / 4 true matches.
+--desc tfeat: HardTFeatNet (HardNet.py:30-59), the reference's `--descriptor TFeat`.  --tfeat-weights: a .pth with a `state_dict` (the
+reference's HardTFeat.pth) or one of the fixtures tests/golden/tfeat_weights_{0,1,2}.npz (the three are read together); default: the
+fixtures.  With the trained weights at N = 500 the reference gives 34 tentatives / 5 true matches."""
 import os
 import sys
 
@@ -27,12 +30,31 @@ def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
     return torch.from_numpy(img.astype(np.float32)).view(1, 1, img.shape[0], img.shape[1])
 
 
+def load_tfeat_state(path):
+    """A .pth checkpoint with `state_dict`, or the weight fixtures (any of the three .npz names, or None): the six tensors by their reference names."""
+    if path and path.endswith(".pth"):
+        return torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+    gd = os.path.dirname(os.path.abspath(path)) if path else os.path.join(ROOT, "tests", "golden")
+    parts = [np.load(os.path.join(gd, "tfeat_weights_%d.npz" % i)) for i in range(3)]
+    sd = {k: torch.from_numpy(parts[0][k]) for k in affnet_amd.HardTFeatNet.KEYS[:4]}
+    sd["classifier.1.weight"] = torch.from_numpy(np.concatenate([p["classifier.1.weight.part"] for p in parts], 0))
+    sd["classifier.1.bias"] = torch.from_numpy(parts[2]["classifier.1.bias"])
+    return sd
+
+
 def main(argv):
     desc_kind = "hardnet"
+    tfeat_path = None
+    if "--tfeat-weights" in argv:
+        i = argv.index("--tfeat-weights")
+        if i + 1 >= len(argv):
+            sys.exit("--tfeat-weights takes a path")
+        tfeat_path = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
     if "--desc" in argv:
         i = argv.index("--desc")
-        if i + 1 >= len(argv) or argv[i + 1] not in ("hardnet", "sift"):
-            sys.exit("--desc takes hardnet or sift")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("hardnet", "sift", "tfeat"):
+            sys.exit("--desc takes hardnet, sift or tfeat")
         desc_kind = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
     gd = os.path.join(ROOT, "tests", "golden")
@@ -46,6 +68,10 @@ def main(argv):
     Hn = affnet_amd.HardNet(); Hn.load_state_dict(ld(argv[4]) if len(argv) > 4 else affnet_amd.synthetic_hardnet_state(0))
     A, O, Hn = A.to(dev), O.to(dev), Hn.to(dev)
     desc = affnet_amd.SIFTNet(patch_size=32) if desc_kind == "sift" else Hn
+    if desc_kind == "tfeat":
+        desc = affnet_amd.HardTFeatNet(sm=affnet_amd.SIFTNet(patch_size=32))
+        desc.load_state_dict(load_tfeat_state(tfeat_path))
+        desc = desc.to(dev)
     det = affnet_amd.ScaleSpaceAffinePatchExtractor(mrSize=5.192, num_features=n, border=5, num_Baum_iters=1, AffNet=A, OriNet=O).to(dev)
     img1, img2 = load_grayscale_var(f1).to(dev), load_grayscale_var(f2).to(dev)
     H1to2 = torch.from_numpy(np.loadtxt(fh)).float()

@@ -334,6 +334,32 @@ int affnet_sift_forward(affnet_ctx* ctx, const float* d_patches, int n, const fl
 int affnet_sift_forward_pyr(affnet_ctx* ctx, const float* d_lafs_norm, const int32_t* d_ids, const int32_t* d_count, int n_max,
                             const float* d_window, float clipval, float* d_desc, void* stream);
 
+/* ---- HardTFeat descriptor -------------------------------------------- */
+
+/* HardTFeatNet.forward in eval mode (HardNet.py:30-59): input norm (mean, unbiased std + 1e-7), conv 1 -> 32 7x7 + tanh, max-pool 2x2,
+ * conv 32 -> 64 6x6 + tanh, conv 64 -> 128 8x8 + tanh, x / sqrt(sum x^2 + 1e-8).  Floats of its packed weight blob: */
+size_t affnet_tfeat_packed_floats(void);
+/* Host only (no GPU): the six learned tensors in the reference's shapes - features.0 (32,1,7,7) + (32), features.3 (64,32,6,6) + (64),
+ * classifier.1 (128,64,8,8) + (128) - into h_out[affnet_tfeat_packed_floats()].  The element orders (csrc/weights_layout.h), among them
+ * the classifier's k order, are the packer's and the kernels' contract, not the caller's. */
+int affnet_tfeat_pack_weights(const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b, const float* cls_w,
+                              const float* cls_b, float* h_out);
+/* Floats of device scratch the two calls below need for `rows` rows in all (B * n_max for the pyramid form): conv2's output and the
+ * split-K partial sums of the classifier. */
+size_t affnet_tfeat_scratch_floats(int rows);
+/* Descriptors of d_patches (n_max,32,32) fp32, rows < d_count[0] (d_count NULL => n_max rows); d_desc (n_max,128), rows >= the count are
+ * zero.  d_packed: the uploaded blob.  Exact fp32 on the fp32 matrix cores whatever the context's arithmetic mode; every sum has a fixed
+ * order (no float atomics): a row does not depend on n_max, on the other rows or on its position.  No host synchronisation. */
+int affnet_tfeat_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, const int32_t* d_count, int n_max, float* d_desc,
+                         float* d_scratch, void* stream);
+/* Same, each patch sampled from the pyramid in the workspace along what affnet_level_select(..., ps = 32, ...) produced: normalised
+ * LAFs (B,n_max,2,3) and (octave, level, *) ids (B,n_max,3), rows < d_count[image] (d_count NULL => n_max rows).  d_desc (B,n_max,128);
+ * rows >= d_count[image] are zero.  Bit-identical to affnet_pyr_grid_sample(ps = 32) + affnet_tfeat_forward on the same frames.  Exact
+ * fp32 whatever the context's arithmetic mode.  The HardTFeat path without host synchronisation: affnet_extract_features(d_desc = NULL),
+ * affnet_level_select on its pixel LAFs and this call, on one stream. */
+int affnet_tfeat_forward_pyr(affnet_ctx* ctx, const float* d_packed, const float* d_lafs_norm, const int32_t* d_ids, const int32_t* d_count,
+                             int n_max, float* d_desc, float* d_scratch, void* stream);
+
 /* ---- LAF stages ---------------------------------------------------------------------------- */
 
 /* base_A = A; new_LAF = [A * LAF_2x2 | centre]; keep rows with 1/6 < |l1/(l2+1e-8)| < 6 and
