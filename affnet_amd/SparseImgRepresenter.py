@@ -60,6 +60,11 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         self.raw_div = 4           # raw-maxima list capacity per octave = h*w / raw_div (overflow -> AffnetHipError, never truncation)
         self.lazy_shape_rows = -1  # fused path: AffNet first runs on the 1.2 N best candidates, on the rest only if needed (identical rows);
                                    # 0 = all 1.5 N candidates at once like the reference (affnet_config.lazy_shape_rows)
+        self.shape_form = 1        # fused path, arith "fp32": 1 = AffNet trunk with Winograd conv1 / conv3, the candidates whose filter decision could turn on
+                                   # the last bits of A recomputed by the direct kernel (same counts, ids and responses); 0 = direct kernel on every candidate
+                                   # (affnet_set_shape_form; read at every call, a captured graph keeps its form).  forward() always runs form 0: it
+                                   # equals the staged path and getAffineShape / getOrientation bit for bit, which form 1 does not (A of an unflagged
+                                   # candidate carries the Winograd rounding, <= 4e-6)
 
     # ------------------------------------------------------------------------------------------
     def _context(self, x, allow_batch=False):
@@ -77,6 +82,8 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                                        float(self.th), self.num, pre, self.max_keep, batch=x.size(0), baum_iters=self.num_Baum_iters, raw_div=self.raw_div,
                                        lazy_shape_rows=self.lazy_shape_rows, arith=self.arith)
             self._ctx_key = key
+        if self._ctx.shape_form != int(self.shape_form):
+            self._ctx.set_shape_form(self.shape_form)
         return self._ctx
 
     def _publish_pyramid(self, ctx):
@@ -269,6 +276,8 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                                         self.max_keep, batch=x.size(0), baum_iters=self.num_Baum_iters, raw_div=self.raw_div,
                                         lazy_shape_rows=self.lazy_shape_rows, arith=self.arith)
             self._fctx_key = key
+        if self._fctx.shape_form != int(self.shape_form):
+            self._fctx.set_shape_form(self.shape_form)
         return self._fctx
 
     def enqueue_frames(self, x, LAFs, responses=None, counts=None, do_ori=True, desc=None):
@@ -479,7 +488,13 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         aff_native = self.num_Baum_iters == 0 or self._native(self.AffNet)
         ori_native = (not do_ori) or self._native(self.OriNet)
         if aff_native and ori_native:
-            r = self.run(x, do_ori=do_ori)
+            # forward() is the reference's call and is pinned bit for bit to the staged path and to getAffineShape / getOrientation, which run the
+            # direct AffNet kernel on patch tensors: shape form 0 here, whatever `shape_form` says for run() / run_batch() / enqueue() / capture()
+            form, self.shape_form = self.shape_form, 0
+            try:
+                r = self.run(x, do_ori=do_ori)
+            finally:
+                self.shape_form = form
             return r["LAFs"], r["responses"]
         return self._staged(x, do_ori)
 

@@ -32,6 +32,7 @@ def arith_code(arith):
     if int(arith) not in (ARITH_FP32_MFMA, ARITH_FP32_SPLIT3, ARITH_FP32_SPLIT2H):
         raise ValueError("arith must be AFFNET_ARITH_FP32_MFMA (0), AFFNET_ARITH_FP32_SPLIT3 (1) or AFFNET_ARITH_FP32_SPLIT2H (2)")
     return int(arith)
+SHAPE_FORM_DIRECT, SHAPE_FORM_WINOGRAD = 0, 1                            # include/affnet_hip.h AFFNET_SHAPE_FORM_*
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_EMPTY = 0, -1, -2, -3, -4
 
 
@@ -71,6 +72,8 @@ SYMBOLS = {
     "affnet_version": (C.c_char_p, []),
     "affnet_set_arith": (_I, [_P, _I]),
     "affnet_get_arith": (_I, [_P]),
+    "affnet_set_shape_form": (_I, [_P, _I]),
+    "affnet_get_shape_form": (_I, [_P]),
     "affnet_workspace_bytes": (_SZ, [_P]),
     "affnet_bind_workspace": (_I, [_P, _P, _SZ]),
     "affnet_pyramid_level_offset": (C.c_int64, [_P, _I, _I]),
@@ -152,6 +155,7 @@ PROBE_SYMBOLS = {
     "affnet_split3_gemm": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "affnet_split3_rate": (_I, [_I, _I, _I, _P, _P]),
     "affnet_debug_stream": (_I, [_P, _P, _SZ, _I, _I, _I, _P]),
+    "affnet_probe_shape_offsets": (_I, [_P, C.POINTER(C.c_int64 * 3)]),
 }
 
 

@@ -34,11 +34,12 @@ int aff_arith_index(const affnet_ctx* ctx) {
     return ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);
 }
 
-static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid) {
+// wino: AffNet's Winograd instantiation (exact arithmetic); reeval: the margin rule's flags for the direct AffNet trunk behind it; shape_op: see CnnArgs
+static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, bool wino, const int32_t* reeval, int shape_op) {
     CnnArgs a;
     a.packed = c.packed; a.off = to_offsets(L, ctx->arith);            // the split copy of the active mode
-    a.wino_u = nullptr;
-    if (c.kind == AFFNET_NET_ORINET && ctx->arith == AFFNET_ARITH_FP32_MFMA) {
+    a.wino_u = nullptr; a.reeval = reeval;
+    if ((c.kind == AFFNET_NET_ORINET || wino) && ctx->arith == AFFNET_ARITH_FP32_MFMA) {
         const int rc = aff_wino_derive_u(ctx, c.kind, c.packed, L, c.st, &a.wino_u);
         if (rc) return rc;
     }
@@ -46,14 +47,15 @@ static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, d
     a.out = (c.dbg_layer < 0) ? c.scratch : c.out;      // trunk kernels: HardNet conv5 tensor / AffNet, OriNet head partials
     a.dbg_layer = c.dbg_layer; a.dbg_out = c.dbg_out; a.dbg_time = ctx->dbg_time;
     a.row_begin = c.row_begin; a.skip_cnt = c.skip_cnt; a.skip_n = c.skip_n;
-    a.shape_cnt = (c.fuse && c.shape_op) ? c.fuse->cnt : nullptr; a.shape_op = c.shape_op;
+    a.shape_cnt = (c.fuse && shape_op) ? c.fuse->cnt : nullptr; a.shape_op = shape_op;
     a.s3_alt = ctx->split3_variant;
     PyrSrc ps;
     aff_fill_pyr_src(ctx, &ps);
     // the net's instantiation [exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see cnn_check)
     static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk getter order");
     static TrunkKernel (*const trunk_of[3])(int, bool) = {aff_trunk_affnet, aff_trunk_orinet, aff_trunk_hardnet};
-    hipLaunchKernelGGL(trunk_of[c.kind](aff_arith_index(ctx), a.dbg_time || c.dbg_layer >= 0), grid, dim3(512), 0, c.st, a, ps);
+    const bool stamps = a.dbg_time || c.dbg_layer >= 0;
+    hipLaunchKernelGGL(wino ? aff_trunk_affnet_wino(stamps) : trunk_of[c.kind](aff_arith_index(ctx), stamps), grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -64,8 +66,19 @@ static int cnn_launch(affnet_ctx* ctx, const CnnCall& c) {
     if (rc || rows == 0) return rc;
     const NetLayout L = net_layout(c.kind);
     const int B = c.patches ? 1 : ctx->B;                // patch tensors are single-"image"; pyramid sampling covers the batch
-    rc = trunk_launch(ctx, c, L, dim3(rows, B));
+    // Shape form 1 (CnnCall::wino_reeval; exact AffNet with the fused filter only): Winograd trunk on every row of the window (it does the counter work), the margin
+    // rule on its partials (flags in the unused part of the scratch: 144 floats per row, 32 of them partials), the direct trunk on the flagged rows, which
+    // overwrites their partials, then the finish + filter kernel as ever.  The same window, row counts and lazy predicate for all; nothing here depends on B or rows.
+    const bool form1 = c.wino_reeval && c.kind == AFFNET_NET_AFFNET && c.fuse && c.dbg_layer < 0 && ctx->arith == AFFNET_ARITH_FP32_MFMA;
+    rc = trunk_launch(ctx, c, L, dim3(rows, B), form1, nullptr, c.shape_op);
     if (rc) return rc;
+    if (form1) {
+        int32_t* flags = reinterpret_cast<int32_t*>(c.scratch + (size_t)B * c.n_max * HEAD_PART_AFF);
+        rc = aff_margin_affnet(ctx, c, L, rows, B, flags);
+        if (rc) return rc;
+        rc = trunk_launch(ctx, c, L, dim3(rows, B), false, flags, 0);
+        if (rc) return rc;
+    }
     if (c.dbg_layer < 0 && c.kind != AFFNET_NET_HARDNET) {
         rc = c.kind == AFFNET_NET_AFFNET ? aff_finish_affnet(ctx, c, L, rows, B) : aff_finish_orinet(ctx, c, L, rows, B);
         if (rc) return rc;
@@ -105,6 +118,7 @@ int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* re
     c.row_begin = row_begin; c.row_count = row_count;
     c.skip_cnt = lazy ? ctx->cnt : nullptr; c.skip_n = ctx->cfg.num_features;
     c.fuse = &sf; c.shape_op = shape_op;
+    c.wino_reeval = ctx->shape_form == AFFNET_SHAPE_FORM_WINOGRAD;
     return cnn_launch(ctx, c);
 }
 

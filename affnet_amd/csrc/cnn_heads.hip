@@ -16,6 +16,20 @@
 //            one thread per patch read 144 floats at a 576-byte stride, 5.8x overfetch, 18 us for 2000 patches), the nine tanh
 //            values of each output are added in tap order as before; optionally LAF <- LAF * R in the same kernel
 //            (SparseImgRepresenter.py:173-177).
+// A of one row from its eight per-wave partials: shared by the finish kernel and the margin kernel, so that the margin rule sees the finish kernel's A
+__device__ __forceinline__ f32x4 affnet_head_to_a(const float* __restrict__ part, const float* __restrict__ hb, size_t pidx) {
+    const f32x4* pp = reinterpret_cast<const f32x4*>(part + pidx * HEAD_PART_AFF);
+    f32x4 r[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) r[w] = pp[w];
+    const f32x4 s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    const float x0 = tanhf(s.x + hb[0]), x1 = tanhf(s.y + hb[1]), x2 = tanhf(s.z + hb[2]);
+    const float a00 = 1.0f + x0, a01 = 0.0f * x0, a10 = x1, a11 = 1.0f + x2;
+    const float det = sqrtf(fabsf(a00 * a11 - a10 * a01 + 1e-10f));
+    const float b2a2 = sqrtf(a01 * a01 + a00 * a00);
+    return (f32x4){b2a2 / det, 0.0f * det, (a11 * a01 + a10 * a00) / (b2a2 * det), det / b2a2};
+}
+
 __global__ __launch_bounds__(256) void affnet_finish_kernel(const float* __restrict__ part, const float* __restrict__ hb,
                                                             const int32_t* __restrict__ count, int n_max, float* __restrict__ out, int row_begin,
                                                             int row_end, const int32_t* __restrict__ skip_cnt, int skip_n, ShapeFuse sf) {
@@ -31,22 +45,30 @@ __global__ __launch_bounds__(256) void affnet_finish_kernel(const float* __restr
     }
     if (row >= n || skip) return;
     float* o = out + 4 * pidx;
-    const f32x4* pp = reinterpret_cast<const f32x4*>(part + pidx * HEAD_PART_AFF);
-    f32x4 r[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) r[w] = pp[w];
-    const f32x4 s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    const float x0 = tanhf(s.x + hb[0]), x1 = tanhf(s.y + hb[1]), x2 = tanhf(s.z + hb[2]);
-    const float a00 = 1.0f + x0, a01 = 0.0f * x0, a10 = x1, a11 = 1.0f + x2;
-    const float det = sqrtf(fabsf(a00 * a11 - a10 * a01 + 1e-10f));
-    const float b2a2 = sqrtf(a01 * a01 + a00 * a00);
-    const float o0 = b2a2 / det, o1 = 0.0f * det, o2 = (a11 * a01 + a10 * a00) / (b2a2 * det), o3 = det / b2a2;
+    const f32x4 A = affnet_head_to_a(part, hb, pidx);
+    const float o0 = A.x, o1 = A.y, o2 = A.z, o3 = A.w;
     o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3;
     if (sf.key) {
         const size_t bi = blockIdx.y;
         aff_shape_filter_row(sf.resp + bi * n_max, sf.lafs + bi * n_max * 6, o0, o1, o2, o3, row, sf.key + bi * n_max, sf.good + bi * n_max,
                              sf.cnt + bi * CNT_TOTAL);
     }
+}
+
+// Shape form 1, between the Winograd AffNet trunk and the direct one: one thread per evaluated row of the window applies the margin rule (shape_filter.h) to
+// the row's A and writes the row's flag; flagged rows are counted per image (CNT_AFF_REEVAL; cleared by the first pass's trunk launch).  The rows and the
+// lazy predicate of the finish kernel; the trunk launch in front of this one has frozen CNT_SURVIVED1.
+__global__ __launch_bounds__(256) void affnet_margin_kernel(const float* __restrict__ part, const float* __restrict__ hb, const int32_t* __restrict__ count,
+                                                            int n_max, int row_begin, int row_end, const int32_t* __restrict__ skip_cnt, int skip_n,
+                                                            const float* __restrict__ lafs, int32_t* __restrict__ flags, int32_t* __restrict__ cnt) {
+    const int row = row_begin + blockIdx.x * 256 + threadIdx.x;
+    const int n = min(count ? min(count[blockIdx.y], n_max) : n_max, row_end);
+    if (row >= n || lazy_skip(skip_cnt, skip_n, blockIdx.y)) return;
+    const size_t bi = blockIdx.y, pidx = bi * n_max + row;
+    const f32x4 A = affnet_head_to_a(part, hb, pidx);
+    const bool flag = aff_shape_margin_flag(lafs + bi * n_max * 6, A.x, A.y, A.z, A.w, row);
+    flags[pidx] = flag ? 1 : 0;
+    if (flag) atomicAdd(&cnt[bi * CNT_TOTAL + CNT_AFF_REEVAL], 1);
 }
 
 __global__ __launch_bounds__(256) void orinet_finish_kernel(const float* __restrict__ part, const float* __restrict__ hb,
@@ -316,6 +338,13 @@ int aff_finish_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int
     if (c.fuse) sf = *c.fuse;
     hipLaunchKernelGGL(affnet_finish_kernel, dim3(aff_cdiv(rows, 256), B), dim3(256), 0, c.st, c.scratch, c.packed + L.head_b, c.count, c.n_max, c.out,
                        c.row_begin, c.row_begin + rows, c.skip_cnt, c.skip_n, sf);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+int aff_margin_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B, int32_t* flags) {
+    hipLaunchKernelGGL(affnet_margin_kernel, dim3(aff_cdiv(rows, 256), B), dim3(256), 0, c.st, c.scratch, c.packed + L.head_b, c.count, c.n_max, c.row_begin,
+                       c.row_begin + rows, c.skip_cnt, c.skip_n, c.fuse->lafs, flags, c.fuse->cnt);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

@@ -18,8 +18,9 @@
 //     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob;
 //     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
 //     blob's taps by wino_derive_u_kernel, cnn_trunk_orinet.hip, in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
-//     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet stays in the direct form:
-//     the shape filter behind it turns on the last bits of its output, and another rounding changes which keypoints come back.  The
+//     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet has both forms: the direct one
+//     (S3 = 0) and one with OriNet's Winograd conv1 / conv3 (S3 = 1).  The shape filter behind AffNet turns on the last bits of its output for a few rows, so
+//     the fused shape pass runs the Winograd form on every row and the direct form on the rows a margin rule flags (shape_filter.h, cnn32.hip).  The
 //     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
 //     the activation operands of four k-steps, one ds_write_b128 per tile in the epilogue (bias + ReLU), written IN PLACE
@@ -246,7 +247,7 @@ struct SplitLays {
 };
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
-// 3 / 2 = terms of the split-operand arithmetic.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// 3 / 2 = terms of the split-operand arithmetic, 1 (AffNet only) = exact with conv1 / conv3 as Winograd.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
 // kernel is one straight-line body per flow: exact HardNet (Winograd), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
@@ -256,7 +257,9 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3, "S3 = number of terms of the split arithmetic");
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND == AFFNET_NET_AFFNET), "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3");
+    constexpr bool EXACT = S3 <= 1;                                           // fp32 operands on v_mfma_f32_16x16x4_f32
+    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || S3 == 1;   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -269,11 +272,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     const int prow = blockIdx.x + a.row_begin;
     if (KIND == AFFNET_NET_AFFNET && a.shape_cnt && blockIdx.x == 0 && threadIdx.x == 0) {
         int32_t* c = a.shape_cnt + (size_t)blockIdx.y * CNT_TOTAL;
-        if (a.shape_op == 1) { c[CNT_SURVIVED] = 0; c[CNT_SURVIVED1] = 0; c[CNT_AFF_EVAL] = 0; }
+        if (a.shape_op == 1) { c[CNT_SURVIVED] = 0; c[CNT_SURVIVED1] = 0; c[CNT_AFF_EVAL] = 0; c[CNT_AFF_REEVAL] = 0; }
         else if (a.shape_op == 2) c[CNT_SURVIVED1] = c[CNT_SURVIVED];
     }
     if (prow >= n || lazy_skip(a.skip_cnt, a.skip_n, blockIdx.y, CNT_SURVIVED)) return;
     const size_t pidx = (size_t)blockIdx.y * a.n_max + prow;
+    if (KIND == AFFNET_NET_AFFNET && a.reeval && a.reeval[pidx] == 0) return;      // shape form 1: the margin rule left the Winograd trunk's partials of this row in place
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // Issue priority (HardNet only, one workgroup per CU): the short latency-bound phases (input, conv0, epilogues) run at
     // priority 3, the MFMA loops at 0: +2% (130 -> 133 TFLOP/s).  For AffNet / OriNet (two workgroups per CU) it is
@@ -293,7 +297,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     f32x4 b1[1][S::T1N];
     f32x4 Ur[4];                                                      // exact OriNet: the rolling U register set of conv1 / conv3 / conv5
     if constexpr (S3 == 0 && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
-    if constexpr (S3 == 0 && KIND == AFFNET_NET_ORINET) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
+    if constexpr (WINO13) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
 
     // ---- input: load or sample 1024 pixels (PPT per thread), standardise, store padded ----------------
     constexpr int PPT = 1024 / NTHR;                    // input pixels per thread (2 or 1)
@@ -324,7 +328,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         const int y = e < 34 ? 0 : (e < 68 ? 33 : 1 + ((e - 68) >> 1)), x = e < 34 ? e : (e < 68 ? e - 34 : ((e - 68) & 1) * 33);
         patch[y * WP32 + x] = 0.0f;
     }
-    if constexpr (S3 == 0) zero_halo<LayC0, NTHR>(act, CB);                          // the halo of the flow's conv0 output layout
+    if constexpr (EXACT) zero_halo<LayC0, NTHR>(act, CB);                          // the halo of the flow's conv0 output layout
     else if constexpr (S3 == 2) zero_halo_q<typename SplitLays<CB>::LR0, NTHR>(act);
     else zero_halo_q<typename SplitLays<CB>::LQH, NTHR>(act);
     float sum = 0.f;
@@ -460,18 +464,19 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         __syncthreads();
         CNN_STAMP(12);
         if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
-    } else if constexpr (S3 == 0) {
+    } else if constexpr (EXACT) {
         // Exact AffNet / OriNet.  OriNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
         // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which
-        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet keeps conv1 .. conv5 in the direct form: its output decides the
-        // shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST bits of A for near-isotropic shapes, so any other
-        // rounding changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline configuration).  conv0, conv2, conv4 (and AffNet's conv5) in
+        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 as
+        // OriNet runs them, conv5 direct.  AffNet's output decides the shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST
+        // bits of A for near-isotropic shapes, so another rounding alone changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline
+        // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0, conv2, conv4 (and AffNet's conv5) in
         // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators, OriNet from its Winograd fragments).
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
         f32x4 b4[S::G4][T4N];
         f32x4 bias4[T4N];
-        if constexpr (KIND == AFFNET_NET_ORINET) {
+        if constexpr (WINO13) {
             constexpr int NB1 = Wino16::NB1, NB3 = Wino16::NB3;
             // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
             {

@@ -32,6 +32,7 @@ enum {
     CNT_SURVIVED1,                           // survivors of the first (lazy) shape pass, frozen before the second pass starts
     CNT_SEL_EQ_TOTAL,                        // candidates whose response equals the top-k threshold (ties: taken in key order)
     CNT_SEL_TIE_LO, CNT_SEL_TIE_HI,          // ties at the threshold are taken up to this (octave, level, pixel) key (64 bits, two halves)
+    CNT_AFF_REEVAL,                          // shape form 1: evaluated candidates the margin rule flagged, recomputed by the direct AffNet trunk (both passes)
     CNT_POS0 = AFFNET_MAX_OCTAVES + 24,      // CNT_POS0 + (level-1)*AFFNET_MAX_OCTAVES + o : positive maxima of (octave, level)
     CNT_HYP0 = AFFNET_MAX_OCTAVES + 24 + (AFFNET_MAX_LEVELS - 2) * AFFNET_MAX_OCTAVES,   // CNT_HYP0 + 8 * o + k: positives of (octave o, level,
                                              // hypothesis) k = 0: level 1; 1 + h1: level 2 given level 1 applied (h1); 3 + h1 + 2 h2: level 3
@@ -110,6 +111,7 @@ struct affnet_ctx {
     int prof_calls = 0;
     // tuning aid (include/affnet_hip_debug.h): s_memtime stamp buffer of THIS context's CNN launches, or NULL
     unsigned long long* dbg_time = nullptr;
+    int shape_form = AFFNET_SHAPE_FORM_WINOGRAD;   // fused exact-fp32 shape pass (affnet_set_shape_form): Winograd trunk + direct re-evaluation of the margin rule's rows, or direct only
     int arith = AFFNET_ARITH_FP32_MFMA;   // arithmetic of the CNN contractions (cfg.arith / affnet_set_arith): exact fp32 MFMA or fp32 = 3 x bf16 split operands
     int split3_variant = 0;            // tuning aid (affnet_debug_split3_variant): bit 0 = alternating wave priorities in the split HardNet loops (round 3's
                                        // tile-major loops gained 2.5 % from it, the term-major loops of round 4 lose 1 %: off)
@@ -219,7 +221,8 @@ struct PyrSrc {            // pyramid sampling source (fused sampler)
 struct CnnArgs {
     const float* packed;
     NetOffsets off;
-    const float* wino_u;   // exact OriNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel)
+    const float* wino_u;   // exact OriNet, Winograd AffNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel)
+    const int32_t* reeval; // direct AffNet trunk behind the Winograd one (shape form 1): per-row flags of the margin rule [image * n_max + row], a workgroup whose flag is 0 returns at once; NULL = every row
     const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
     const float* lafs;     // normalised LAFs when sampling
     const int32_t* ids;    // (octave, level, *) when sampling
@@ -281,6 +284,7 @@ struct CnnCall {
     int row_begin = 0, row_count = -1;                               // row window of every image; -1 = up to n_max
     const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
     const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
+    bool wino_reeval = false;                                        // AffNet, exact fp32, fused filter: Winograd trunk, margin rule, direct trunk on the flagged rows (shape form 1)
     float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
 };
 
@@ -339,6 +343,7 @@ int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const f
 
 // cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip: the net's trunk instantiation [aff_arith_index][phase stamps]
 TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
+TrunkKernel aff_trunk_affnet_wino(bool stamps);          // exact fp32 with conv1 / conv3 as Winograd F(2x2, 3x3): the first trunk of shape form 1
 TrunkKernel aff_trunk_orinet(int arith_index, bool stamps);
 TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
 // cnn_trunk_orinet.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one); derive U of
@@ -349,6 +354,8 @@ int aff_wino_derive_u(affnet_ctx* ctx, int kind, const float* packed, const NetL
 // cnn_heads.hip: what cnn_launch runs behind a trunk launch: AffNet / OriNet finish kernel on `rows` rows of the window of B images, HardNet
 // head GEMM + finish kernel over all rows
 int aff_finish_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B);
+// shape form 1: the margin rule (shape_filter.h) on the Winograd trunk's partials of the window's evaluated rows -> flags[image * n_max + row], CNT_AFF_REEVAL
+int aff_margin_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B, int32_t* flags);
 int aff_finish_orinet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B);
 int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int B);
 

@@ -226,6 +226,14 @@ extern "C" int affnet_set_arith(affnet_ctx* ctx, int arith) {
 }
 extern "C" int affnet_get_arith(const affnet_ctx* ctx) { return ctx ? ctx->arith : AFFNET_ERR_INVALID; }
 
+extern "C" int affnet_set_shape_form(affnet_ctx* ctx, int form) {
+    if (!ctx) return AFFNET_ERR_INVALID;
+    if (form != AFFNET_SHAPE_FORM_DIRECT && form != AFFNET_SHAPE_FORM_WINOGRAD) return aff_fail(ctx, AFFNET_ERR_INVALID, "shape form=%d (AFFNET_SHAPE_FORM_*)", form);
+    ctx->shape_form = form;
+    return AFFNET_OK;
+}
+extern "C" int affnet_get_shape_form(const affnet_ctx* ctx) { return ctx ? ctx->shape_form : AFFNET_ERR_INVALID; }
+
 extern "C" size_t affnet_workspace_bytes(const affnet_ctx* ctx) { return ctx ? ctx->ws_bytes : 0; }
 
 extern "C" int affnet_capacity_prefilter(const affnet_ctx* ctx) { return ctx ? ctx->cap_pre : 0; }
@@ -241,11 +249,12 @@ extern "C" int64_t affnet_pyramid_image_stride(const affnet_ctx* ctx) { return c
 
 // int32 offset (from the workspace base) of a per-image device counter of image 0; consecutive images are affnet_counter_stride()
 // int32 apart.  which: 0 = capacity-overflow flag (non-zero: a fixed-capacity list overflowed, results are truncated),
-// 1 = rows after detection, 2 = rows after the shape filter, 3 = candidates the shape CNN was evaluated on (lazy evaluation).  Lets a caller test the flags on the device / read them with its own
+// 1 = rows after detection, 2 = rows after the shape filter, 3 = candidates the shape CNN was evaluated on (lazy evaluation), 4 = candidates the direct
+// AffNet trunk recomputed behind the Winograd one (shape form 1).  Lets a caller test the flags on the device / read them with its own
 // asynchronous copy instead of the synchronising affnet_read_counts.
 extern "C" int64_t affnet_counter_offset(const affnet_ctx* ctx, int which) {
-    if (!ctx || ctx->ws_bytes == 0 || which < 0 || which > 3) return -1;
-    const int idx = which == 0 ? CNT_OVERFLOW : (which == 1 ? CNT_DET : (which == 2 ? CNT_SHAPED : CNT_AFF_EVAL));
+    if (!ctx || ctx->ws_bytes == 0 || which < 0 || which > 4) return -1;
+    const int idx = which == 0 ? CNT_OVERFLOW : (which == 1 ? CNT_DET : (which == 2 ? CNT_SHAPED : (which == 3 ? CNT_AFF_EVAL : CNT_AFF_REEVAL)));
     return (int64_t)(ctx->off_cnt / sizeof(int32_t)) + idx;
 }
 extern "C" int64_t affnet_counter_stride(const affnet_ctx* ctx) { return ctx ? (int64_t)CNT_TOTAL : 0; }

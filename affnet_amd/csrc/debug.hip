@@ -1,4 +1,4 @@
-// Counter-calibration kernels (include/affnet_hip_probes.h): known-byte-count streaming reads / writes / tile loads, so
+// Counter-calibration kernels and the shape-pass read-back of the tests (include/affnet_hip_probes.h): known-byte-count streaming reads / writes / tile loads, so
 // that rocprofv3's FETCH_SIZE / WRITE_SIZE can be turned into bytes for the access widths this library actually uses
 // (MI355X_MICROARCH.md, HBM section: only 16 B/lane streaming reads are calibrated there).  libaffnet_hip_probes.so only, not part of the product path.
 #include "common.h"
@@ -69,4 +69,13 @@ extern "C" int affnet_debug_stream(const void* d_src, void* d_dst, size_t n_byte
         return AFFNET_ERR_INVALID;
     }
     return hipGetLastError() == hipSuccess ? AFFNET_OK : AFFNET_ERR_HIP;
+}
+
+extern "C" int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3]) {
+    if (!ctx || !ctx->ws || !out) return AFFNET_ERR_INVALID;
+    out[0] = (int64_t)(reinterpret_cast<const char*>(ctx->st_A) - ctx->ws) / 4;
+    // cnn32.hip, cnn_launch: the flags lie behind the head partials of all candidates in the CNN scratch
+    out[1] = (int64_t)(reinterpret_cast<const char*>(ctx->st_hard_scratch) - ctx->ws) / 4 + (int64_t)ctx->B * ctx->cap_pre * HEAD_PART_AFF;
+    out[2] = (int64_t)(reinterpret_cast<const char*>(ctx->st_det_lafs) - ctx->ws) / 4;
+    return AFFNET_OK;
 }

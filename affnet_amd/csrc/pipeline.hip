@@ -157,6 +157,16 @@ extern "C" int affnet_describe_detected(affnet_ctx* ctx, const affnet_nets* nets
         rc = aff_shape_select(ctx, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->st_A, det_count, d_resp, ctx->st_lafs_shaped, d_ids,
                               d_count, st);
         if (rc) return rc;
+    } else if (nets->d_affnet && ctx->cfg.baum_iters <= 1 && N > 0) {
+        // all C candidates at once (lazy_shape_rows = 0, or a first pass that would cover them all): the same launches as one pass above, so that the rows do
+        // not depend on lazy_shape_rows in either shape form (affnet_set_shape_form)
+        rc = aff_affnet_filter_rows(ctx, nets->d_affnet, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, det_count, ctx->st_A, ctx->st_hard_scratch,
+                                    0, P, false, 1, st);
+        if (rc) return rc;
+        aff_prof_mark(ctx, 3, st);
+        rc = aff_shape_select(ctx, ctx->st_det_resp, ctx->st_det_lafs, ctx->st_det_ids, ctx->st_A, det_count, d_resp, ctx->st_lafs_shaped, d_ids,
+                              d_count, st);
+        if (rc) return rc;
     } else if (nets->d_affnet || baumberg) {
         rc = shape_pass(ctx->st_det_lafs, ctx->st_A);
         if (rc) return rc;

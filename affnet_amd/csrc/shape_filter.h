@@ -36,6 +36,47 @@ __device__ __forceinline__ void aff_shape_filter_row(const float* __restrict__ r
     if (ok) atomicAdd(&cnt[CNT_SURVIVED], 1);
 }
 
+// Margin rule of the fused shape pass in form 1 (affnet_set_shape_form; cnn32.hip: cnn_launch): the AffNet trunk with Winograd conv1 / conv3 gives the three head
+// outputs another rounding than the direct trunk, assumed |Winograd - direct| <= delta = 4e-6 per head output (7 x the largest difference seen on the candidates
+// of synthetic images, 5.7e-7).  aff_shape_filter_row above takes three kinds of decision on A; a row is CERTAIN - the same decision from either trunk - only if
+// it keeps a margin from each of them, and every other row is flagged and recomputed by the direct trunk:
+//   * d1 > 0.  a01 is exactly 0 and a00 * a11 = 1 up to rounding, so d1 = tr^2 - 4 det is (a00 - a11)^2 computed as the difference of two numbers near 4 (ulp
+//     4.8e-7): its sign is rounding noise while (a00 - a11)^2 is below a few ulp (every flip seen: <= 5.8e-7).  Certain: (a00 - a11)^2 >= 1e-5, which delta moves
+//     by less than 3e-8;
+//   * the four frame corners inside [0, 1]^2.  Certain: every coordinate at least 1e-5 from 0 and from 1 (delta moves a corner by less than 4e-6);
+//   * 1/6 < ratio < 6.  Certain: |ratio - 6| >= 6e-3 and |ratio - 1/6| >= 1e-3 / 6 (1e-3 relative; no candidate came near).
+// Written as "not certain", so that a non-finite value flags its row.  The same expressions as the filter's, on the same inputs: A as the finish kernel forms
+// it from the partials and the row's base frame.  Widen the thresholds with a written reason; never narrow them.
+#define AFF_MARGIN_D1 1e-5f
+#define AFF_MARGIN_CORNER 1e-5f
+#define AFF_MARGIN_RATIO_REL 1e-3f
+__device__ __forceinline__ bool aff_shape_margin_flag(const float* __restrict__ lafs, float a00, float a01, float a10, float a11, int i) {
+    const float* L = lafs + 6 * (size_t)i;
+    const float n00 = fmaf(a01, L[3], a00 * L[0]), n01 = fmaf(a01, L[4], a00 * L[1]);
+    const float n10 = fmaf(a11, L[3], a10 * L[0]), n11 = fmaf(a11, L[4], a10 * L[1]);
+    const float cx = L[2], cy = L[5];
+    const float tr = a00 + a11;
+    const float p1 = a00 * a11, p2 = a10 * a01;
+    const float d1 = tr * tr - 4.0f * (p1 - p2);
+    const float mk = d1 > 0.f ? 1.0f : 0.0f;
+    const float dl = sqrtf(fabsf(d1));
+    const float l1 = mk * (tr + dl) / 2.0f + 1000.0f * (1.0f - mk);
+    const float l2 = mk * (tr - dl) / 2.0f + 0.0001f * (1.0f - mk);
+    const float ratio = fabsf(l1 / (l2 + 1e-8f));
+    const float iso = (a00 - a11) * (a00 - a11);
+    bool certain = iso >= AFF_MARGIN_D1 && fabsf(ratio - 6.0f) >= 6.0f * AFF_MARGIN_RATIO_REL &&
+                   fabsf(ratio - (float)(1.0 / 6.0)) >= AFF_MARGIN_RATIO_REL / 6.0f;
+    const float px[4] = {-1.f, -1.f, 1.f, 1.f}, py[4] = {-1.f, 1.f, -1.f, 1.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float ox = fmaf(cx, 1.0f, fmaf(n01, py[k], n00 * px[k]));
+        const float oy = fmaf(cy, 1.0f, fmaf(n11, py[k], n10 * px[k]));
+        certain = certain && fabsf(ox) >= AFF_MARGIN_CORNER && fabsf(ox - 1.0f) >= AFF_MARGIN_CORNER && fabsf(oy) >= AFF_MARGIN_CORNER &&
+                  fabsf(oy - 1.0f) >= AFF_MARGIN_CORNER;
+    }
+    return !certain;
+}
+
 // Pyramid level of ONE pixel frame with 2x2 part (q0 q1; q3 q4): get_LAFs_scales (LAF.py:450-451) in fp32, then / PS in fp32, then the float64
 // |a - b| argmin over the (octave, level) table (scipy's cdist 'euclidean' on 1-D points), first minimum wins.  Returns octave * n_lvl + level.
 __device__ __forceinline__ int aff_level_argmin(float q0, float q1, float q3, float q4, float ps, const LevelTable& lt) {

@@ -47,6 +47,7 @@ class Context(object):
         self.cfg = self.plan.fill_config(mr_size, threshold, num_features, num_prefilter, max_keep, raw_div=raw_div, batch=self.batch, baum_iters=baum_iters,
                                          onepass=onepass, lazy_shape_rows=lazy_shape_rows, arith=arith)
         self.arith = _lib.arith_code(arith)
+        self.shape_form = _lib.SHAPE_FORM_WINOGRAD             # the library's default (affnet_set_shape_form)
         self.device = device
         self.handle = C.c_void_p()
         idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -63,6 +64,12 @@ class Context(object):
         """Switches the arithmetic of this context's CNN contractions (affnet_set_arith); 'fp32' restores the default bit for bit."""
         self.arith = _lib.arith_code(arith)
         check(lib.affnet_set_arith(self.handle, self.arith), self.handle, "affnet_set_arith")
+
+    def set_shape_form(self, form):
+        """Form of the fused exact-fp32 AffNet shape pass (affnet_set_shape_form): 0 = every candidate by the direct kernel, 1 = Winograd trunk with
+        direct re-evaluation of the rows the margin rule flags (default).  Read when a call is enqueued; a captured graph keeps its form."""
+        check(lib.affnet_set_shape_form(self.handle, int(form)), self.handle, "affnet_set_shape_form")
+        self.shape_form = int(form)
 
     def pyramid_views(self, image=0):
         """scale_pyr[o][l] of image `image` of the batch as (1,1,h,w) views into the workspace
@@ -88,7 +95,7 @@ class Context(object):
 
     def counter_view(self, which=0):
         """(B,) int32 device view of a per-image counter in the workspace (0 = capacity-overflow flag, 1 = rows after detection, 2 = rows
-        after the shape filter): callers of enqueue() can test it on the device or copy it asynchronously - no host synchronisation."""
+        after the shape filter, 3 = candidates AffNet was evaluated on, 4 = candidates the direct AffNet trunk recomputed in shape form 1): callers of enqueue() can test it on the device or copy it asynchronously - no host synchronisation."""
         off, stride = lib.affnet_counter_offset(self.handle, which), lib.affnet_counter_stride(self.handle)
         return self.workspace.view(torch.int32)[off:off + stride * self.batch:stride]
 

@@ -171,6 +171,20 @@ const char* affnet_version(void);
 int affnet_set_arith(affnet_ctx* ctx, int arith);
 int affnet_get_arith(const affnet_ctx* ctx);
 
+/* Form of the fused AffNet shape pass of affnet_describe_detected (exact fp32 arithmetic only; the split-operand modes, OnePassSIR and the
+ * stand-alone affnet_cnn32_forward / _pyr calls always run the direct kernel):
+ *   AFFNET_SHAPE_FORM_DIRECT   : every candidate by the direct-form trunk.
+ *   AFFNET_SHAPE_FORM_WINOGRAD : (default) every candidate by a trunk with conv1 / conv3 as Winograd F(2x2, 3x3); a margin rule then flags the
+ *                                candidates whose shape-filter decision could turn on the last bits of A (about 2 %), and the direct-form trunk
+ *                                recomputes exactly those, so every decision - counts, ids, responses - is the direct form's.  A of an unflagged
+ *                                row differs from the direct form's by at most 4e-6 per head output.
+ * Read when a call is enqueued; a graph captured earlier keeps the form it was captured with.  The number of re-evaluated candidates per image
+ * is counter 4 of affnet_counter_offset. */
+#define AFFNET_SHAPE_FORM_DIRECT 0
+#define AFFNET_SHAPE_FORM_WINOGRAD 1
+int affnet_set_shape_form(affnet_ctx* ctx, int form);
+int affnet_get_shape_form(const affnet_ctx* ctx);
+
 /* Bytes of caller-owned device workspace the context needs (pyramid + detector lists +
  * CNN scratch).  Offsets into it are exposed so the host mirror can present the pyramid as
  * tensors (`scale_pyr`, SparseImgRepresenter.py:55). */
@@ -563,7 +577,8 @@ int affnet_read_counts(affnet_ctx* ctx, int32_t out[4], void* stream);
 
 /* The same counters without a host synchronisation: int32 offset (from the workspace base) of a per-image device counter of image 0
  * and the int32 stride between images.  which: 0 = capacity-overflow flag, 1 = rows after detection, 2 = rows after the shape filter,
- * 3 = candidates the shape CNN was actually evaluated on (cfg->lazy_shape_rows).
+ * 3 = candidates the shape CNN was actually evaluated on (cfg->lazy_shape_rows), 4 = evaluated candidates that the direct-form trunk
+ * recomputed (affnet_set_shape_form; 0 in form AFFNET_SHAPE_FORM_DIRECT).
  * Valid once the enqueued work has completed on the stream; -1 for a context without a workspace layout. */
 int64_t affnet_counter_offset(const affnet_ctx* ctx, int which);
 int64_t affnet_counter_stride(const affnet_ctx* ctx);

@@ -41,6 +41,14 @@ int affnet_debug_stream(const void* d_src, void* d_dst, size_t n_bytes, int widt
 int affnet_split3_gemm(const float* d_A, const float* d_Bt, int M, int N, int K, int mode, float* d_C, void* stream);
 int affnet_split3_rate(int reps, int terms, int n_blocks, float* d_out, void* stream);
 
+/* Read-back of the fused AffNet shape pass (affnet_set_shape_form) for the tests: where a bound context keeps, after affnet_describe_detected, the shape
+ * matrices A of all candidates ([image][capacity_prefilter][4] floats) and the per-candidate flags of the margin rule ([image][capacity_prefilter] int32,
+ * written for the candidates AffNet was evaluated on; form AFFNET_SHAPE_FORM_WINOGRAD only; the orientation and descriptor stages reuse that scratch, so
+ * read them after a call with do_ori = 0 and no descriptors), and the candidates' normalised frames as the detector half
+ * left them ([image][capacity_prefilter][6] floats; a test plants a non-finite frame there, which affnet_load_frames would refuse).  out[0] / out[1] / out[2]:
+ * offsets from the workspace base, in 4-byte units.  Host only; the context may come from libaffnet_hip.so of the same build. */
+int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif
