@@ -156,6 +156,8 @@ PROBE_SYMBOLS = {
     "affnet_split3_rate": (_I, [_I, _I, _I, _P, _P]),
     "affnet_debug_stream": (_I, [_P, _P, _SZ, _I, _I, _I, _P]),
     "affnet_probe_shape_offsets": (_I, [_P, C.POINTER(C.c_int64 * 3)]),
+    "affnet_probe_affnet_wino_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),
+    "affnet_probe_affnet_wino_partials": (_I, [_P, _P, _P, _I, _P, _P]),
 }
 
 

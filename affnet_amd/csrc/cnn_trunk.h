@@ -19,7 +19,7 @@
 //     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
 //     blob's taps by wino_derive_u_kernel, cnn_trunk_orinet.hip, in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
 //     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet has both forms: the direct one
-//     (S3 = 0) and one with OriNet's Winograd conv1 / conv3 (S3 = 1).  The shape filter behind AffNet turns on the last bits of its output for a few rows, so
+//     (S3 = 0) and one with OriNet's Winograd conv1 / conv3 / conv5 and the head straight from conv5's fragments (S3 = 1).  The shape filter behind AffNet turns on the last bits of its output for a few rows, so
 //     the fused shape pass runs the Winograd form on every row and the direct form on the rows a margin rule flags (shape_filter.h, cnn32.hip).  The
 //     split-operand modes (affnet_set_arith) run conv1..5 on bf16 / fp16 terms (conv3x3_mfma_s3q);
 //   * activations live in ONE LDS buffer, channel-interleaved by 4 ((c/4)*PSG + pixel*4 + c%4): one ds_read_b128 per lane =
@@ -30,7 +30,7 @@
 //     between the MFMAs;
 //   * heads: HardNet stores its conv5 tile [pixel][channel] to HBM and an 8192 x 128 split-K MFMA GEMM over all patches
 //     (cnn_heads.hip: hardnet_head_kernel + hardnet_finish_kernel: BN bias + L2 norm) follows; AffNet / OriNet reduce their heads' dot
-//     products per wave straight from the conv5 accumulators (head_partials, head_partials_ori_lds) and affnet_finish_kernel /
+//     products per wave straight from the conv5 accumulators (head_partials, head_partials_wino, head_partials_ori_lds) and affnet_finish_kernel /
 //     orinet_finish_kernel (cnn_heads.hip) combine the eight partials per patch in fixed order (tanh, rectification / atan2).
 // Host side: cnn32.hip; the plain types both sides share (CnnArgs, PyrSrc, Wino16, HEAD_PART_*) are in common.h.
 #pragma once
@@ -73,6 +73,35 @@ __device__ __forceinline__ void head_partials(const float* __restrict__ hw, cons
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) sacc = fmaf(v[i][j], w[o][i][j], sacc);
+        sacc = wave_sum(sacc);
+        if (lane == 0) part[wave * 4 + o] = sacc;
+    }
+}
+
+// The same head from the fragments of the Winograd conv5 (conv3x3_wino_mfma_half_rows + wino5_combine; AffNet shape form 1): lane (m, g) of wave 2 p + h holds
+// y[k] = pre-activation channels 16 p + 4 g .. + 3 of pixel (2 (m >> 2) + h, 2 (m & 3) + k), k = 0, 1 - again one float4 of the head weights per (output, pixel).
+// The weights do not depend on the activations: aff_head_weights_wino requests them in front of the combine's barrier (as ori_head_weights).  No LDS copy and
+// no barrier of its own; lane-local order (pixel k, channel j), wave_sum, then affnet_finish_kernel's order over the waves: fixed for every patch and launch.
+__device__ __forceinline__ void aff_head_weights_wino(const float* __restrict__ hw, f32x4 (&w)[3][2], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 3 * 4096);
+    const int m = lane & 15, c4 = (wave >> 1) * 16 + 4 * (lane >> 4);
+    const int pix = (2 * (m >> 2) + (wave & 1)) * 8 + 2 * (m & 3);
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) w[o][k] = buf_read4(r, (pix * 64 + c4) * 4, (o * 4096 + k * 64) * 4);
+}
+__device__ __forceinline__ void head_partials_wino(const f32x4 (&w)[3][2], f32x4 bias, const f32x4 (&y)[2], float* __restrict__ part, int wave, int lane) {
+    f32x4 v[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) v[k] = bias_relu(y[k], bias);
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        float sacc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sacc = fmaf(v[k][j], w[o][k][j], sacc);
         sacc = wave_sum(sacc);
         if (lane == 0) part[wave * 4 + o] = sacc;
     }
@@ -247,7 +276,7 @@ struct SplitLays {
 };
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
-// 3 / 2 = terms of the split-operand arithmetic, 1 (AffNet only) = exact with conv1 / conv3 as Winograd.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// 3 / 2 = terms of the split-operand arithmetic, 1 (AffNet only) = exact with conv1 / conv3 / conv5 as Winograd.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
 // kernel is one straight-line body per flow: exact HardNet (Winograd), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
@@ -257,9 +286,10 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND == AFFNET_NET_AFFNET), "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3");
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND == AFFNET_NET_AFFNET), "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5");
     constexpr bool EXACT = S3 <= 1;                                           // fp32 operands on v_mfma_f32_16x16x4_f32
     constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || S3 == 1;   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
+    constexpr bool WINO5 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || S3 == 1;    // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -295,7 +325,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     f32x4 bias0[S::T1N];
     conv0_load_w<NW, CB, S::T1M, S::T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
     f32x4 b1[1][S::T1N];
-    f32x4 Ur[4];                                                      // exact OriNet: the rolling U register set of conv1 / conv3 / conv5
+    f32x4 Ur[4];                                                      // exact OriNet, Winograd AffNet: the rolling U register set of conv1 / conv3 / conv5
     if constexpr (S3 == 0 && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
     if constexpr (WINO13) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
 
@@ -467,11 +497,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     } else if constexpr (EXACT) {
         // Exact AffNet / OriNet.  OriNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
         // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which
-        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 as
-        // OriNet runs them, conv5 direct.  AffNet's output decides the shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST
+        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 / conv5 as
+        // OriNet runs them.  AffNet's output decides the shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST
         // bits of A for near-isotropic shapes, so another rounding alone changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline
-        // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0, conv2, conv4 (and AffNet's conv5) in
-        // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators, OriNet from its Winograd fragments).
+        // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0, conv2, conv4 (and the S3 = 0 kernel's conv5) in
+        // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators or, S3 = 1, from the Winograd fragments; OriNet from its Winograd fragments through an LDS copy).
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
         f32x4 b4[S::G4][T4N];
@@ -616,7 +646,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             f32x4 acc[T4M][T4N];
             conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
             CNN_STAMP(9);
-            if constexpr (KIND == AFFNET_NET_ORINET) {
+            if constexpr (WINO5) {
                 wino5_prefetch_u(a.wino_u + Wino16::offset(5), Ur, wave, lane);
             } else {
                 prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G5>(a.packed + a.off.w[5], b5, wave, lane);
@@ -630,11 +660,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
 
+        static_assert(!WINO5 || (Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL),
+                      "Winograd conv5: the exchange lies behind conv4's output inside the LDS array");
         if constexpr (KIND == AFFNET_NET_ORINET) {
             // ---- conv5: 4CB -> 4CB @8x8, Winograd, a wave pair per channel block (conv3x3_wino_mfma_half_rows, wino5_combine); its 2 x 2-pixel fragments go
             // into the head's 10 x 10 copy (over conv4's output, which is dead by then), then the head's per-wave partial sums ----
-            static_assert(Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL && Wino5::HEAD + 100 * ORI_HP <= Wino5::X,
-                          "conv5: the exchange lies behind conv4's output inside the LDS array, the head copy in front of the exchange");
+            static_assert(Wino5::HEAD + 100 * ORI_HP <= Wino5::X, "conv5: the head copy in front of the exchange");
             f32x4 acc[2][4], y[2], hw[2][T4M];
             conv3x3_wino_mfma_half_rows<NW, LayC4>(act, a.wino_u + Wino16::offset(5), Ur, acc, wave, lane);
             CNN_STAMP(11);
@@ -649,6 +680,26 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
                 int pbase[T4M];
                 ori_head_pbase<T4M>(HL, pbase);
                 ori_head_reduce<T4M>(hw, pbase, a.out + pidx * HEAD_PART_ORI, copy, wave, lane);
+                CNN_STAMP(13);
+                return;
+            }
+            __syncthreads();
+            wino5_store_lds<LayC5::WP, 4, LayC5::PSG>(act + (LayC5::WP + 1) * 4, bw, y, wave, lane);   // debug dump only
+            __syncthreads();
+            CNN_STAMP(12);
+            if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
+            return;
+        } else if constexpr (WINO5) {
+            // ---- conv5 of AffNet's Winograd form: the same loop and combine; the head's per-wave partial sums straight from the combined fragments
+            // (head_partials_wino: no LDS copy, no barrier beyond the combine's), its weights requested in front of that barrier ----
+            f32x4 acc[2][4], y[2], hw[3][2];
+            conv3x3_wino_mfma_half_rows<NW, LayC4>(act, a.wino_u + Wino16::offset(5), Ur, acc, wave, lane);
+            CNN_STAMP(11);
+            const f32x4 bw = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[5] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
+            if (!STAMPS || a.dbg_layer < 0) aff_head_weights_wino(a.packed + a.off.head_w, hw, wave, lane);
+            wino5_combine(lds, acc, y, wave, lane);
+            if (!STAMPS || a.dbg_layer < 0) {
+                head_partials_wino(hw, bw, y, a.out + pidx * HEAD_PART_AFF, wave, lane);
                 CNN_STAMP(13);
                 return;
             }

@@ -343,7 +343,7 @@ int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const f
 
 // cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip: the net's trunk instantiation [aff_arith_index][phase stamps]
 TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
-TrunkKernel aff_trunk_affnet_wino(bool stamps);          // exact fp32 with conv1 / conv3 as Winograd F(2x2, 3x3): the first trunk of shape form 1
+TrunkKernel aff_trunk_affnet_wino(bool stamps);          // exact fp32 with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3): the first trunk of shape form 1
 TrunkKernel aff_trunk_orinet(int arith_index, bool stamps);
 TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
 // cnn_trunk_orinet.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one); derive U of

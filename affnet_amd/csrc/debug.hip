@@ -1,4 +1,4 @@
-// Counter-calibration kernels and the shape-pass read-back of the tests (include/affnet_hip_probes.h): known-byte-count streaming reads / writes / tile loads, so
+// Counter-calibration kernels, the shape-pass read-back and the Winograd AffNet layer dump of the tests (include/affnet_hip_probes.h): known-byte-count streaming reads / writes / tile loads, so
 // that rocprofv3's FETCH_SIZE / WRITE_SIZE can be turned into bytes for the access widths this library actually uses
 // (MI355X_MICROARCH.md, HBM section: only 16 B/lane streaming reads are calibrated there).  libaffnet_hip_probes.so only, not part of the product path.
 #include "common.h"
@@ -78,4 +78,35 @@ extern "C" int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3])
     out[1] = (int64_t)(reinterpret_cast<const char*>(ctx->st_hard_scratch) - ctx->ws) / 4 + (int64_t)ctx->B * ctx->cap_pre * HEAD_PART_AFF;
     out[2] = (int64_t)(reinterpret_cast<const char*>(ctx->st_det_lafs) - ctx->ws) / 4;
     return AFFNET_OK;
+}
+
+// The Winograd AffNet trunk (the first trunk of shape form 1) on a patch tensor, which no entry point of the product library runs: U derived in front of the launch
+// as cnn32.hip's trunk_launch does; the stamped instantiation when a layer dump is asked for or the context has a stamp buffer (affnet_cnn32_debug_timing).
+static int probe_affnet_wino(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, int layer, hipStream_t st) {
+    if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino: AFFNET_ARITH_FP32_MFMA only");
+    const NetLayout L = net_layout(AFFNET_NET_AFFNET);
+    CnnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.packed = d_packed; a.off = to_offsets(L, ctx->arith);
+    const int rc = aff_wino_derive_u(ctx, AFFNET_NET_AFFNET, d_packed, L, st, &a.wino_u);
+    if (rc) return rc;
+    a.patches = d_patches; a.n_max = n; a.out = d_out; a.dbg_layer = layer; a.dbg_out = d_out; a.dbg_time = ctx->dbg_time;
+    PyrSrc ps;
+    memset(&ps, 0, sizeof(ps));                          // patch tensors: nothing is sampled
+    hipLaunchKernelGGL(aff_trunk_affnet_wino(layer >= 0 || a.dbg_time), dim3(n, 1), dim3(512), 0, st, a, ps);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+extern "C" int affnet_probe_affnet_wino_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patch || !d_out || net_kind != AFFNET_NET_AFFNET || layer < 0 || layer > 5)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino_layer: AffNet, layer 0 .. 5");
+    return probe_affnet_wino(ctx, d_packed, d_patch, 1, d_out, layer, (hipStream_t)stream);
+}
+
+extern "C" int affnet_probe_affnet_wino_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patches || !d_partials || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino_partials: bad argument");
+    return probe_affnet_wino(ctx, d_packed, d_patches, n, d_partials, -1, (hipStream_t)stream);
 }

@@ -36,7 +36,7 @@ __device__ __forceinline__ void aff_shape_filter_row(const float* __restrict__ r
     if (ok) atomicAdd(&cnt[CNT_SURVIVED], 1);
 }
 
-// Margin rule of the fused shape pass in form 1 (affnet_set_shape_form; cnn32.hip: cnn_launch): the AffNet trunk with Winograd conv1 / conv3 gives the three head
+// Margin rule of the fused shape pass in form 1 (affnet_set_shape_form; cnn32.hip: cnn_launch): the AffNet trunk with Winograd conv1 / conv3 / conv5 gives the three head
 // outputs another rounding than the direct trunk, assumed |Winograd - direct| <= delta = 4e-6 per head output (7 x the largest difference seen on the candidates
 // of synthetic images, 5.7e-7).  aff_shape_filter_row above takes three kinds of decision on A; a row is CERTAIN - the same decision from either trunk - only if
 // it keeps a margin from each of them, and every other row is flagged and recomputed by the direct trunk:

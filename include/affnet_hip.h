@@ -174,7 +174,7 @@ int affnet_get_arith(const affnet_ctx* ctx);
 /* Form of the fused AffNet shape pass of affnet_describe_detected (exact fp32 arithmetic only; the split-operand modes, OnePassSIR and the
  * stand-alone affnet_cnn32_forward / _pyr calls always run the direct kernel):
  *   AFFNET_SHAPE_FORM_DIRECT   : every candidate by the direct-form trunk.
- *   AFFNET_SHAPE_FORM_WINOGRAD : (default) every candidate by a trunk with conv1 / conv3 as Winograd F(2x2, 3x3); a margin rule then flags the
+ *   AFFNET_SHAPE_FORM_WINOGRAD : (default) every candidate by a trunk with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3); a margin rule then flags the
  *                                candidates whose shape-filter decision could turn on the last bits of A (about 2 %), and the direct-form trunk
  *                                recomputes exactly those, so every decision - counts, ids, responses - is the direct form's.  A of an unflagged
  *                                row differs from the direct form's by at most 4e-6 per head output.

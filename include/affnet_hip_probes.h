@@ -49,6 +49,16 @@ int affnet_split3_rate(int reps, int terms, int n_blocks, float* d_out, void* st
  * offsets from the workspace base, in 4-byte units.  Host only; the context may come from libaffnet_hip.so of the same build. */
 int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3]);
 
+/* Layer dump of the Winograd AffNet trunk (conv1 / conv3 / conv5 as F(2x2, 3x3): what shape form AFFNET_SHAPE_FORM_WINOGRAD runs on every candidate), for the
+ * tests: affnet_cnn32_debug_layer's arguments and output (the activations after trunk layer `layer` = 0 .. 5 of the one 32 x 32 patch, [channel][y][x]), which
+ * always answers with the direct trunk for AffNet.  net_kind must be AFFNET_NET_AFFNET, the context in AFFNET_ARITH_FP32_MFMA; it may come from
+ * libaffnet_hip.so of the same build. */
+int affnet_probe_affnet_wino_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+
+/* The same trunk on n <= 65535 patches (n, 32, 32), for tools/cnn_phase_timing.py: leaves the head partials ([patch][8 waves][4] floats) in d_partials, no finish
+ * kernel; writes the phase stamps when the context has a stamp buffer (affnet_cnn32_debug_timing). */
+int affnet_probe_affnet_wino_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

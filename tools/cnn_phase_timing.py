@@ -19,7 +19,27 @@ H = affnet_amd.HardNet(); H.load_state_dict(affnet_amd.synthetic_hardnet_state(0
 names = ["input+norm", "conv0", "conv1 mfma", "conv1 store", "conv2 mfma", "conv2 store", "conv3 mfma", "conv3 store",
          "conv4 mfma", "conv4 store", "conv5 mfma", "conv5 store"]
 only = os.environ.get("PHASE_NETS")                    # e.g. PHASE_NETS=OriNet: that net's table alone
-for net, nm, nw in [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]:
+
+
+class AffNetForm1:
+    """AffNet's Winograd trunk (conv1 / conv3 / conv5 as F(2x2, 3x3)), which the fused shape pass runs on every candidate in shape form 1: the trunk launch alone
+    (head partials, no finish kernel) through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)"""
+    def __call__(self, x):
+        part = torch.empty(x.shape[0] * 32, device=dev)
+        packed = A.packed_weights(dev)
+        for i in range(0, x.shape[0], 65535):
+            m = min(65535, x.shape[0] - i)
+            rc = lib.affnet_probe_affnet_wino_partials(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(part[i * 32:]), None)
+            assert rc == 0, rc
+        return part
+
+
+nets = [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]
+if hasattr(lib, "affnet_probe_affnet_wino_partials"):
+    nets.insert(1, (AffNetForm1(), "AffNet form 1", 8))
+else:
+    print("(no table of AffNet's Winograd trunk: this library has no affnet_probe_affnet_wino_partials - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
+for net, nm, nw in nets:
     if only and nm not in only.split(","):
         continue
     net(p); torch.cuda.synchronize()
@@ -86,5 +106,5 @@ for net, nm, nw in [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

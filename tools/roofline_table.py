@@ -2,7 +2,8 @@
 """Regenerates the bandwidth / FLOP-rate table of DESIGN.md section 4 from tracked files:
     python tools/roofline_table.py profiles/r02_s2          (prefix of *_kernel_stats.csv, *_traffic.json, *_bench_default.json or, since round 6, *_bench_driver_detail.json)
     python tools/roofline_table.py --winograd PREFIX         evidence of a build whose exact HardNet trunk runs conv1 / conv3 / conv5 as Winograd F(2x2, 3x3):
-                                                             that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's
+                                                             that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's;
+                                                             so is AffNet's Winograd trunk of shape form 1, <0, 8, false, 1> (WINO_AFFNET)
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
 FETCH_SIZE / WRITE_SIZE passes scaled by the calibration measured for the kernel's access width (tools/fetch_calib.py), the
 resulting GB/s and its fraction of 8 TB/s; for the CNN kernels the algorithmic FLOP rate against the 157.3 TFLOP/s fp32 MFMA peak.
@@ -21,6 +22,9 @@ FLOP = {"cnn32_trunk_kernel<0": C * 19193856.0, "cnn32_trunk_kernel<1": NKP * 19
 # Exact HardNet trunk with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3): each of the three layers is 2 * 9 * cin * cout * H^2 = 18874368 FLOPs per patch in
 # the direct form and executes 16 / 36 of them on the MFMA (the transforms run on the VALU and are not counted)
 WINO_HARDNET = NKP * (78184448.0 - 2.0 * 8192 * 128 - 3 * 18874368.0 * (1.0 - 16.0 / 36.0))
+# AffNet's Winograd trunk (shape form 1): conv1 / conv3 / conv5 are 4718592 direct FLOPs per patch each and execute 16 / 36 of them.  conv1 .. conv5 together:
+# 11.0 M executed MFMA FLOPs per patch (13.6 M while conv5 was direct: 288 instead of 128 MFMAs per wave), against OriNet's 11.0 M; conv0 and the head as in the direct form
+WINO_AFFNET = 19193856.0 - 3 * 4718592.0 * (1.0 - 16.0 / 36.0)
 
 
 def octave_pixels(h, w, border=5):
@@ -88,9 +92,12 @@ def main(prefix, winograd=False):
             elif key in name:
                 if winograd and key == "cnn32_trunk_kernel<2":
                     fl = WINO_HARDNET
+                wino_aff = winograd and key == "cnn32_trunk_kernel<0" and name.rstrip().endswith(", 1>")
+                if wino_aff:
+                    fl = fl / 19193856.0 * WINO_AFFNET
                 tf = fl * IMGS / (per_call * avg_ns * 1e-9) / 1e12            # all launches of the kernel in one 32-image call
                 algs = "%.1f TFLOP/s = %.1f %% of 157.3" % (tf, 100 * tf / 157.3)
-                if winograd and key == "cnn32_trunk_kernel<2":
+                if (winograd and key == "cnn32_trunk_kernel<2") or wino_aff:
                     algs += " (executed MFMA FLOPs of the Winograd trunk; direct-form equivalent %.1f TFLOP/s)" % (tf * FLOP[key] / fl)
                 if per_call > 1.01:
                     algs += " (over its %.0f launches per call; %.0f patches / image evaluated)" % (per_call, FLOP[key] / 19193856.0)
