@@ -66,6 +66,10 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                                    # equals the staged path and getAffineShape / getOrientation bit for bit, which form 1 does not (A of an unflagged
                                    # candidate carries the Winograd rounding, <= 4e-6)
 
+        self.desc_form = 1         # fused path, arith "fp32": 1 = HardNet trunk with conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2), 0 = in the direct
+                                   # form (affnet_set_desc_form; read at every call, a captured graph keeps its form).  Descriptors differ by rounding only
+                                   # (<= 2e-6); a stand-alone HardNet.forward always runs form 0
+
     # ------------------------------------------------------------------------------------------
     def _context(self, x, allow_batch=False):
         engine.require_cuda(x, "image")
@@ -84,6 +88,8 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
             self._ctx_key = key
         if self._ctx.shape_form != int(self.shape_form):
             self._ctx.set_shape_form(self.shape_form)
+        if self._ctx.desc_form != int(self.desc_form):
+            self._ctx.set_desc_form(self.desc_form)
         return self._ctx
 
     def _publish_pyramid(self, ctx):
@@ -278,6 +284,8 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
             self._fctx_key = key
         if self._fctx.shape_form != int(self.shape_form):
             self._fctx.set_shape_form(self.shape_form)
+        if self._fctx.desc_form != int(self.desc_form):
+            self._fctx.set_desc_form(self.desc_form)
         return self._fctx
 
     def enqueue_frames(self, x, LAFs, responses=None, counts=None, do_ori=True, desc=None):

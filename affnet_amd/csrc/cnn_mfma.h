@@ -6,6 +6,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <utility>
+
 #include "common.h"
 #include "weights_layout.h"
 
@@ -1543,4 +1545,197 @@ __device__ __forceinline__ void wino_store_global(float* __restrict__ dst, const
             *reinterpret_cast<f32x4*>(dst + p * COUT + cb * 16 + 4 * g) = v;
         }
     }
+}
+
+// ---- polyphase Winograd F(2x2, 2x2): the stride-2 layers of the exact HardNet trunk in form 1 (conv2, conv4) ------------------------------
+// A 3x3 stride-2 padding-1 layer over 2x2 output tiles: along an axis the tile's outputs read the 5 input samples d0 .. d4, taps 0 and 2 on d0, d2, d4 (a
+// 2-tap stride-1 filter, run as F(2, 2)) and tap 1 on d1, d3:
+//   input   (d0 - d2, d2, d2 - d4 | d1, d3)                      (y first, then x)
+//   weight  (g0, g0 + g2, g2 | g1, g1)                           (x first, then y; weights_layout.h: poly_weight_transform)
+//   output  ((m0 + m1) + n0, (m1 - m2) + n1)                     (y first, then x)
+// 25 products per (cin, cout, tile) instead of 36: position rows 0 .. 2 (odd window rows x odd columns, 3 positions each, xi = 3 i + j), 3 .. 5 (odd rows x
+// even columns, 2 each, xi = 9 + 2 i + j), 6 .. 7 (even rows x odd columns, xi = 15 + 3 i + j), 8 .. 9 (even x even, xi = 21 + 2 i + j).
+// tools/winograd_numerics.py: poly_conv3x3_s2 mirrors the operation order.
+// The loop is conv3x3_wino_mfma_pair_rows' with rows of 3 or 2 positions: a unit is one block of 16 tiles against NCB channel blocks (2: one V against U of both;
+// 1: conv4, whose eight waves share the one tile block); a step is (unit, position row, K group), G fastest; it reads the one or two window rows of its position
+// row at the 3 or 2 columns of its phase (2 .. 6 ds_read_b128), transforms them (0 .. 20 VALU operations) and issues NP x 4 x NCB MFMAs; after the last G the row's
+// accumulators fold into the y stage (t0 / t1, five columns each).  Every accumulator receives its MFMAs in one fixed order (G ascending, four k-steps each).
+// Pipeline: the reads and the transform of step s + 1 sit between the MFMAs of step s, V in two register sets that swap by name; U lives in two sets as well and
+// rolls TWO steps ahead (a row of 2 positions has as few as 8 MFMAs): the set of step s takes the fragments of step s + 2 as its positions retire.  Both sets enter
+// holding steps 0 and 1 (poly_prefetch_u, requested in front of the barrier before the layer).
+constexpr int poly_row_np(int r) { return (r < 3 || (r >= 6 && r < 8)) ? 3 : 2; }
+constexpr int poly_row_xi0(int r) { return r < 3 ? 3 * r : (r < 6 ? 9 + 2 * (r - 3) : (r < 8 ? 15 + 3 * (r - 6) : 21 + 2 * (r - 8))); }
+constexpr bool poly_row_oddy(int r) { return r < 6; }
+constexpr int poly_row_yi(int r) { return r < 3 ? r : (r < 6 ? r - 3 : (r < 8 ? r - 6 : r - 8)); }
+constexpr int poly_row_ra(int r) { return poly_row_oddy(r) ? (poly_row_yi(r) == 0 ? 0 : 2) : 1 + 2 * poly_row_yi(r); }      // window row read into da
+constexpr int poly_row_rb(int r) { return (poly_row_oddy(r) && poly_row_yi(r) != 1) ? (poly_row_yi(r) == 0 ? 2 : 4) : -1; }   // the row subtracted from it, or none
+constexpr int poly_row_reads(int r) { return poly_row_np(r) * (poly_row_rb(r) >= 0 ? 2 : 1); }
+constexpr int poly_row_valu(int r) { return 4 * ((poly_row_rb(r) >= 0 ? poly_row_np(r) : 0) + (poly_row_np(r) == 3 ? 2 : 0)); }
+
+template <int... I, typename F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(IntC<I>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
+
+// The window rows of position row R at LDS byte address `ab` of the 5x5 window: columns 0, 2, 4 (odd phase) or 1, 3 (even phase)
+template <typename LI, int R>
+__device__ __forceinline__ void poly_read_row(unsigned ab, f32x4 (&da)[3], f32x4 (&db)[3]) {
+    constexpr int NC = poly_row_np(R), C0 = NC == 3 ? 0 : 1, RA = poly_row_ra(R), RB = poly_row_rb(R);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        da[c] = lds_read4(ab + (RA * LI::WP + C0 + 2 * c) * 16);
+        if constexpr (RB >= 0) db[c] = lds_read4(ab + (RB * LI::WP + C0 + 2 * c) * 16);
+    }
+}
+
+// The V fragments of position row R from its window rows: along y (a difference of two rows or one row as it is), then along x
+template <int R>
+__device__ __forceinline__ void poly_transform_row(const f32x4 (&da)[3], const f32x4 (&db)[3], f32x4 (&V)[3]) {
+    constexpr int NC = poly_row_np(R), RB = poly_row_rb(R);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[3];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) t[c] = RB >= 0 ? wsub(da[c][e], db[c][e]) : da[c][e];
+        if constexpr (NC == 3) { V[0][e] = wsub(t[0], t[1]); V[1][e] = t[1]; V[2][e] = wsub(t[1], t[2]); }
+        else { V[0][e] = t[0]; V[1][e] = t[1]; }
+    }
+}
+
+// U of steps 0 and 1 of the wave's first unit
+template <int NW, int CIN, int COUT, int HOUT, int NB, int NCB>
+__device__ __forceinline__ void poly_prefetch_u(const float* __restrict__ Wu, f32x4 (&Ua)[NCB][3], f32x4 (&Ub)[NCB][3], int wave, int lane) {
+    constexpr int NGRP = CIN / 16;
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, POLY_XI * CIN * COUT);
+    const int u_lane = wino_u_lane<HOUT, COUT, NB>(wave, 0, lane);
+    constexpr int R1 = 1 / NGRP, G1 = 1 % NGRP;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c = 0; c < NCB; ++c) {
+            Ua[c][k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0, c);
+            if (k < poly_row_np(R1)) Ub[c][k] = wino_load_u<CIN, COUT>(r, u_lane, poly_row_xi0(R1) + k, G1, c);
+        }
+}
+
+// Pre-activation outputs (no bias) of the NB passes in wino_tile's numbering over the OUTPUT (H = LI::H / 2): y[q][2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3
+// of pixel (2 ty + dy, 2 tx + dx) - what wino_bias / wino_store_lds take.
+template <int NW, int CIN, int COUT, typename LI, int NB, int NCB>
+__device__ __forceinline__ void conv3x3_poly_mfma_rows(const float* act, const float* __restrict__ Wu, f32x4 (&Ua)[NCB][3], f32x4 (&Ub)[NCB][3], f32x4 (&y)[NB][4],
+                                                       int wave, int lane) {
+    constexpr int HOUT = LI::H / 2, HT = HOUT / 2, NGRP = CIN / 16, NSTEP = (NB / NCB) * 10 * NGRP;
+    static_assert(LI::H % 4 == 0 && (HT * HT) % 16 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "polyphase tiling");
+    static_assert((HT * HT / 16) * (COUT / 16) == NW * NB, "the waves' passes must tile the layer exactly");
+    static_assert((NCB == 1 || NCB == 2) && NB % NCB == 0 && (COUT / 16) % NCB == 0 && NSTEP % 2 == 0, "the passes of a unit must share their tile block");
+    const int m = lane & 15, kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, POLY_XI * CIN * COUT);
+    f32x4 t0[NCB][5], t1[NCB][5], acc[NCB][3], Va[3], Vb[3];      // t0 / t1: the y stage, columns 0 .. 2 odd phase, 3 .. 4 even phase
+    auto window_addr = [&](int u, int G) {
+        int ty, tx, cb;
+        wino_tile<HOUT, COUT, NB>(wave, NCB * u, m, ty, tx, cb);
+        unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (4 * ty * LI::WP + 4 * tx) * 4) * 4);
+        asm("" : "+v"(ab));
+        return ab;
+    };
+    // one step: the MFMAs of step S on V, with the reads + transform of step S + 1 (into Vn) and the U requests of step S + 2 (into this step's set) between them
+    auto step = [&](auto sc, const f32x4 (&V)[3], f32x4 (&Vn)[3], f32x4 (&U)[NCB][3]) {
+        constexpr int S = decltype(sc)::v;
+        constexpr int u = S / (10 * NGRP), R = (S / NGRP) % 10, G = S % NGRP;
+        constexpr bool more = S + 1 < NSTEP;
+        constexpr int Sn = more ? S + 1 : S, un = Sn / (10 * NGRP), Rn = (Sn / NGRP) % 10, Gn = Sn % NGRP;
+        constexpr int S2 = S + 2 < NSTEP ? S + 2 : S, u2 = S2 / (10 * NGRP), R2 = (S2 / NGRP) % 10, G2 = S2 % NGRP;   // (the last two steps re-request their own weights: unused)
+        constexpr int NP = poly_row_np(R), NP2 = poly_row_np(R2), XI2 = poly_row_xi0(R2);
+        constexpr int NM = NP * 4 * NCB, NRn = more ? poly_row_reads(Rn) : 0, VPM = NCB == 2 ? 2 : 4, NVM = more ? (poly_row_valu(Rn) + VPM - 1) / VPM : 0;
+        static_assert(NM >= NRn + NVM, "the next step's reads and transform fit between this step's MFMAs");
+        const int u_next = wino_u_lane<HOUT, COUT, NB>(wave, NCB * u2, lane);
+        unsigned abn = 0;
+        if constexpr (more) abn = window_addr(un, Gn);
+        if constexpr (G == 0) {
+#pragma unroll
+            for (int c = 0; c < NCB; ++c)
+#pragma unroll
+                for (int k = 0; k < NP; ++k) acc[c][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 da[3], db[3];
+        if constexpr (more) poly_read_row<LI, Rn>(abn, da, db);
+        if constexpr (NCB == 2) {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) {              // the two channel blocks' chains of position k interleave
+                    acc[0][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[0][k][s4], V[k][s4], acc[0][k], 0, 0, 0);   // U^T x V
+                    acc[1][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[1][k][s4], V[k][s4], acc[1][k], 0, 0, 0);
+                }
+#pragma unroll
+                for (int k2 = k; k2 < (k == NP - 1 ? 3 : k + 1); ++k2)
+                    if (k2 < NP2) {
+                        U[0][k2] = wino_load_u<CIN, COUT>(wrsrc, u_next, XI2 + k2, G2, 0);
+                        U[1][k2] = wino_load_u<CIN, COUT>(wrsrc, u_next, XI2 + k2, G2, 1);
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4)                    // the positions' chains interleave
+#pragma unroll
+                for (int k = 0; k < NP; ++k) acc[0][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[0][k][s4], V[k][s4], acc[0][k], 0, 0, 0);
+#pragma unroll
+            for (int k2 = 0; k2 < NP2; ++k2) U[0][k2] = wino_load_u<CIN, COUT>(wrsrc, u_next, XI2 + k2, G2, 0);
+        }
+        if constexpr (more) poly_transform_row<Rn>(da, db, Vn);
+        // pinned order: the first MFMAs each followed by one row read, the last NVM MFMAs each by VPM operations of the transform (the reads have had the MFMAs
+        // in between to return), the U requests where their registers retire
+#pragma unroll
+        for (int mi = 0; mi < NM; ++mi) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (mi < NRn) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if (mi >= NM - NVM) __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
+            if (NCB == 2 && (mi + 1) % 8 == 0) {
+                const int k = mi / 8;
+                if (k < NP2) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                if (k == NP - 1 && NP2 > NP) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+            }
+            if (NCB == 1 && mi == NM - 1) __builtin_amdgcn_sched_group_barrier(0x020, NP2 == 3 ? 3 : 2, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (G == NGRP - 1) {                         // the row's sums over K are complete: y stage, rows first
+            constexpr int C0 = NP == 3 ? 0 : 3, yi = poly_row_yi(R);
+#pragma unroll
+            for (int c = 0; c < NCB; ++c) {
+#pragma unroll
+                for (int j = 0; j < NP; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (poly_row_oddy(R)) {
+                            if (yi == 0) t0[c][C0 + j][e] = acc[c][j][e];
+                            else if (yi == 1) { t0[c][C0 + j][e] = wadd(t0[c][C0 + j][e], acc[c][j][e]); t1[c][C0 + j][e] = acc[c][j][e]; }
+                            else t1[c][C0 + j][e] = wsub(t1[c][C0 + j][e], acc[c][j][e]);
+                        } else {
+                            if (yi == 0) t0[c][C0 + j][e] = wadd(t0[c][C0 + j][e], acc[c][j][e]);
+                            else t1[c][C0 + j][e] = wadd(t1[c][C0 + j][e], acc[c][j][e]);
+                        }
+                    }
+                if constexpr (R == 9) {                        // ... then columns
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        y[NCB * u + c][0][e] = wadd(wadd(t0[c][0][e], t0[c][1][e]), t0[c][3][e]);
+                        y[NCB * u + c][1][e] = wadd(wsub(t0[c][1][e], t0[c][2][e]), t0[c][4][e]);
+                        y[NCB * u + c][2][e] = wadd(wadd(t1[c][0][e], t1[c][1][e]), t1[c][3][e]);
+                        y[NCB * u + c][3][e] = wadd(wsub(t1[c][1][e], t1[c][2][e]), t1[c][4][e]);
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    {
+        f32x4 da[3], db[3];
+        poly_read_row<LI, 0>(window_addr(0, 0), da, db);
+        poly_transform_row<0>(da, db, Va);
+    }
+    static_for<NSTEP / 2>([&](auto hc) {
+        constexpr int S = 2 * decltype(hc)::v;
+        step(IntC<S>{}, Va, Vb, Ua);
+        step(IntC<S + 1>{}, Vb, Va, Ub);
+    });
 }

@@ -1,5 +1,5 @@
 // Trunk kernel of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet) for gfx950 on the fp32 matrix cores: cnn32_trunk_kernel and its
-// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip, which instantiate one net's six kernels each
+// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip: HardNet form 1), which instantiate one net's six kernels each
 // (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.
 //
 // Replaces architectures.py:204-252 (AffNetFast), :33-82 (OriNetFast), HardNet.py:61-101
@@ -276,8 +276,8 @@ struct SplitLays {
 };
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
-// 3 / 2 = terms of the split-operand arithmetic, 1 (AffNet only) = exact with conv1 / conv3 / conv5 as Winograd.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
-// kernel is one straight-line body per flow: exact HardNet (Winograd), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
+// 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// kernel is one straight-line body per flow: exact HardNet (Winograd), exact HardNet form 1 (Winograd + polyphase), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
 // AffNet / OriNet: 79 KB LDS -> 2 workgroups per CU (4 waves / SIMD, 128 VGPRs); HardNet: 154 KB LDS -> 1 workgroup per
@@ -286,10 +286,12 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND == AFFNET_NET_AFFNET), "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5");
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET),
+                  "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5, exact HardNet with polyphase conv2 / conv4");
     constexpr bool EXACT = S3 <= 1;                                           // fp32 operands on v_mfma_f32_16x16x4_f32
-    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || S3 == 1;   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
-    constexpr bool WINO5 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || S3 == 1;    // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
+    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || (S3 == 1 && KIND == AFFNET_NET_AFFNET);   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
+    constexpr bool WINO5 = WINO13;                                            // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
+    constexpr bool POLY = S3 == 1 && KIND == AFFNET_NET_HARDNET;              // HardNet descriptor form 1: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -471,6 +473,120 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             __syncthreads();
             zero_halo<LayC4, NTHR>(act, 4 * CB);
             store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(10);
+        }
+        if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv5: 4CB -> 4CB @8x8, Winograd; conv5 tensor -> HBM as [pixel][channel], the head GEMM runs over all patches ----
+        f32x4 y[NB5][4], bw[NB5];
+        __builtin_amdgcn_s_setprio(0);
+        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
+        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
+        __builtin_amdgcn_s_setprio(3);
+        CNN_STAMP(11);
+        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
+        if (!STAMPS || a.dbg_layer < 0) {
+            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
+            CNN_STAMP(13);
+            return;
+        }
+        __syncthreads();
+        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
+        __syncthreads();
+        CNN_STAMP(12);
+        if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
+    } else if constexpr (POLY) {
+        // Exact HardNet, descriptor form 1: the flow above with conv2 and conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly_mfma_rows) -
+        // 25/36 of their MFMAs; a wave runs one unit per layer: in conv2 a tile block against a pair of channel blocks, in conv4 the one tile block against its own
+        // channel block.  Their transformed weights come from a.wino_u (Poly32), which poly_derive_u_kernel fills from the blob's taps in front of the launch; the first
+        // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the flow above's.
+        constexpr int T1M = S::T1M, T1N = S::T1N;
+        constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
+        constexpr int NBP2 = (8 * 8 / 16) * (2 * CB / 16) / NW, NBP4 = (4 * 4 / 16) * (4 * CB / 16) / NW;      // polyphase passes per wave: conv2 a pair, conv4 one
+
+        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+        f32x4 Up[2][4];                                               // the rolling U register set of conv1 / conv3: one position row, both channel blocks of a pair
+        f32x4 Uw[16];                                                 // the rolling U register set of conv5
+        {
+            f32x4 acc[T1M][T1N];
+            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+            CNN_STAMP(19);
+            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+            CNN_STAMP(20);
+            wino_prefetch_u_pair<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Up, wave, lane);
+            __syncthreads();
+        }
+        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+        CNN_STAMP(2);
+
+        // ---- conv1: CB -> CB @32x32, Winograd -------------------------------------------------------------
+        f32x4 P2a[2][3], P2b[2][3];                                   // the two rolling U register sets of conv2
+        {
+            f32x4 y[NB1][4], bw[NB1];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_wino_mfma_pair_rows<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Up, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(3);
+            poly_prefetch_u<NW, CB, 2 * CB, 16, NBP2, 2>(a.wino_u + Poly32::offset(2), P2a, P2b, wave, lane);
+            wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
+            __syncthreads();
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
+        }
+        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv2: CB -> 2CB, stride 2 @16x16, polyphase ---------------------------------------------------
+        {
+            f32x4 y[NBP2][4], bw[NBP2];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_poly_mfma_rows<NW, CB, 2 * CB, LayC1, NBP2, 2>(act, a.wino_u + Poly32::offset(2), P2a, P2b, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(5);
+            wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
+            wino_bias<NW, 16, 2 * CB, NBP2>(a.packed + a.off.b[2], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            wino_store_lds<2 * CB, LayC2, NBP2>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
+        }
+        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
+        f32x4 P4a[1][3], P4b[1][3];                                   // the two rolling U register sets of conv4
+        {
+            f32x4 y[NB3][4], bw[NB3];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_wino_mfma_pair_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Up, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(7);
+            poly_prefetch_u<NW, 2 * CB, 4 * CB, 8, NBP4, 1>(a.wino_u + Poly32::offset(4), P4a, P4b, wave, lane);
+            wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        }
+        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv4: 2CB -> 4CB, stride 2 @8x8, polyphase ------------------------------------------------------
+        {
+            f32x4 y[NBP4][4], bw[NBP4];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_poly_mfma_rows<NW, 2 * CB, 4 * CB, LayC3, NBP4, 1>(act, a.wino_u + Poly32::offset(4), P4a, P4b, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(9);
+            wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
+            wino_bias<NW, 8, 4 * CB, NBP4>(a.packed + a.off.b[4], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC4, NTHR>(act, 4 * CB);
+            wino_store_lds<4 * CB, LayC4, NBP4>(act, bw, y, wave, lane);
             __syncthreads();
             CNN_STAMP(10);
         }

@@ -234,6 +234,14 @@ extern "C" int affnet_set_shape_form(affnet_ctx* ctx, int form) {
 }
 extern "C" int affnet_get_shape_form(const affnet_ctx* ctx) { return ctx ? ctx->shape_form : AFFNET_ERR_INVALID; }
 
+extern "C" int affnet_set_desc_form(affnet_ctx* ctx, int form) {
+    if (!ctx) return AFFNET_ERR_INVALID;
+    if (form != AFFNET_DESC_FORM_DIRECT && form != AFFNET_DESC_FORM_POLYPHASE) return aff_fail(ctx, AFFNET_ERR_INVALID, "descriptor form=%d (AFFNET_DESC_FORM_*)", form);
+    ctx->desc_form = form;
+    return AFFNET_OK;
+}
+extern "C" int affnet_get_desc_form(const affnet_ctx* ctx) { return ctx ? ctx->desc_form : AFFNET_ERR_INVALID; }
+
 extern "C" size_t affnet_workspace_bytes(const affnet_ctx* ctx) { return ctx ? ctx->ws_bytes : 0; }
 
 extern "C" int affnet_capacity_prefilter(const affnet_ctx* ctx) { return ctx ? ctx->cap_pre : 0; }

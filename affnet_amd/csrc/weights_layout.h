@@ -157,3 +157,36 @@ AFF_HOST_DEVICE inline void wino_weight_transform(const float g[9], float U[16])
 #pragma unroll
     for (int j = 0; j < 4; ++j) wino_g_axis(t[j], t[4 + j], t[8 + j], U + j, 4);
 }
+
+// ---- polyphase Winograd F(2x2, 2x2) weight transform of a 3x3 stride-2 layer (HardNet form 1: conv2 / conv4) --------------------------
+// Along an axis taps 0 and 2 meet the odd input samples and form a 2-tap stride-1 filter, run as F(2, 2) with the weights (g0, g0 + g2, g2); tap 1 meets
+// the even samples and serves both outputs of a tile as it is: (g0, g0 + g2, g2 | g1, g1), no constant but 1.  U[xi] of one filter g[ky * 3 + kx], along x
+// and then along y, one fp32 rounding per sum; positions xi = 3 i + j (odd rows, odd columns: 9), 9 + 2 i + j (odd rows, even columns: 6),
+// 15 + 3 i + j (even rows, odd columns: 6), 21 + 2 i + j (even / even: 4).  Stored in w_tap_index order over the 25 positions.  The single definition of
+// the operation order: poly_derive_u_kernel (cnn_trunk_hardnet_poly.hip) calls it, tools/winograd_numerics.py: poly_weight_transform mirrors it.
+#define POLY_XI 25
+AFF_HOST_DEVICE inline void poly_weight_transform(const float g[9], float U[POLY_XI]) {
+    float t[3][3];                              // along x, odd phase: t[ky][j]; the even phase is g[3 ky + 1] itself
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) { t[ky][0] = g[3 * ky]; t[ky][1] = g[3 * ky] + g[3 * ky + 2]; t[ky][2] = g[3 * ky + 2]; }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float s = t[0][j] + t[2][j];
+        U[j] = t[0][j]; U[3 + j] = s; U[6 + j] = t[2][j];                        // odd rows, odd columns
+        U[15 + j] = t[1][j]; U[18 + j] = t[1][j];                                // even rows, odd columns
+    }
+    const float se = g[1] + g[7];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        U[9 + j] = g[1]; U[11 + j] = se; U[13 + j] = g[7];                       // odd rows, even columns
+        U[21 + j] = g[4]; U[23 + j] = g[4];                                      // even rows, even columns
+    }
+}
+
+// U of HardNet's conv2 (32 -> 64) and conv4 (64 -> 128), one after the other in the buffer the context owns (205 KB + 819 KB)
+struct Poly32 {
+    static constexpr int U2 = POLY_XI * 32 * 64, U4 = POLY_XI * 64 * 128, FLOATS = U2 + U4;
+    static constexpr int PAIRS = 32 * 64 + 64 * 128;                             // (cin, cout) pairs of the two layers
+    static constexpr int offset(int layer) { return layer == 2 ? 0 : U2; }
+    static constexpr int floats(int layer) { return layer == 2 ? U2 : U4; }
+};

@@ -59,6 +59,17 @@ int affnet_probe_affnet_wino_layer(affnet_ctx* ctx, int net_kind, const float* d
  * kernel; writes the phase stamps when the context has a stamp buffer (affnet_cnn32_debug_timing). */
 int affnet_probe_affnet_wino_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream);
 
+/* The exact HardNet trunk of descriptor form AFFNET_DESC_FORM_POLYPHASE (conv2 / conv4 as polyphase Winograd F(2x2, 2x2)) on patch tensors, which no entry point of
+ * the product library runs (affnet_cnn32_forward always answers with form 0).  The context must be in AFFNET_ARITH_FP32_MFMA; it may come from libaffnet_hip.so of
+ * the same build.
+ *   _layer:   affnet_cnn32_debug_layer's arguments and output for the one 32 x 32 patch (layer 0 .. 5, [channel][y][x]);
+ *   _forward: affnet_cnn32_forward's for n patches (d_out (n, 128) descriptors, d_scratch n * (8192 + 512) floats); writes the phase stamps when the context
+ *             has a stamp buffer (affnet_cnn32_debug_timing);
+ *   _u:       the derived weights of layer 2 (25 x 32 x 64 floats) or 4 (25 x 64 x 128), in the order the kernel reads them. */
+int affnet_probe_hardnet_poly_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+int affnet_probe_hardnet_poly_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
+int affnet_probe_hardnet_poly_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

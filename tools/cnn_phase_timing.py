@@ -34,7 +34,26 @@ class AffNetForm1:
         return part
 
 
+class HardNetForm1:
+    """HardNet's trunk of descriptor form 1 (conv2 / conv4 as polyphase Winograd F(2x2, 2x2)), which the fused calls run by default and HardNet.forward never does:
+    trunk + head on a patch tensor through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)"""
+    def __call__(self, x):
+        out = torch.empty(x.shape[0], 128, device=dev)
+        packed = H.packed_weights(dev)
+        rows = min(x.shape[0], 16384)
+        scratch = torch.empty(rows * (8192 + 512), device=dev)
+        for i in range(0, x.shape[0], rows):
+            m = min(rows, x.shape[0] - i)
+            rc = lib.affnet_probe_hardnet_poly_forward(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(out[i:i + m]), ptr(scratch), None)
+            assert rc == 0, rc
+        return out
+
+
 nets = [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]
+if hasattr(lib, "affnet_probe_hardnet_poly_forward"):
+    nets.append((HardNetForm1(), "HardNet form 1", 8))
+else:
+    print("(no table of HardNet's polyphase trunk: this library has no affnet_probe_hardnet_poly_forward - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 if hasattr(lib, "affnet_probe_affnet_wino_partials"):
     nets.insert(1, (AffNetForm1(), "AffNet form 1", 8))
 else:
@@ -106,5 +125,5 @@ for net, nm, nw in nets:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

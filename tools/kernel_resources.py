@@ -105,6 +105,7 @@ def workgroups_per_cu(k):
 # the kernels DESIGN.md section 4 quotes figures for (substring of the demangled name -> label)
 DESIGN_KERNELS = [
     ("cnn32_trunk_kernel<2, 8, false, 0>", "HardNet trunk, exact fp32 MFMA"),
+    ("cnn32_trunk_kernel<2, 8, false, 1>", "HardNet trunk, exact fp32 MFMA, polyphase Winograd conv2 / conv4 (descriptor form 1)"),
     ("cnn32_trunk_kernel<2, 8, false, 3>", "HardNet trunk, arith fp32_split3"),
     ("cnn32_trunk_kernel<2, 8, false, 2>", "HardNet trunk, arith fp32_split2h"),
     ("cnn32_trunk_kernel<0, 8, false, 0>", "AffNet trunk, exact fp32 MFMA"),

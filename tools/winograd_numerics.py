@@ -78,6 +78,86 @@ def wino_conv3x3(x, w):
     return out
 
 
+# ---- polyphase Winograd F(2x2, 2x2) of the stride-2 layers (HardNet form 1: conv2 / conv4; cnn_mfma.h: conv3x3_poly_mfma_rows) ----------------
+# Along an axis output o of a 3x3 stride-2 padding-1 convolution reads inputs 2 o - 1, 2 o, 2 o + 1: taps 0 and 2 fall on odd samples, tap 1 on an even
+# one.  Over the 5 samples d0 .. d4 of two outputs the odd phase is a 2-tap stride-1 filter (g0, g2) on (d0, d2, d4), run as F(2, 2):
+#     m0 = (d0 - d2) g0,  m1 = d2 (g0 + g2),  m2 = (d2 - d4) g2;   y0 = m0 + m1,  y1 = m1 - m2
+# and the even phase adds n0 = d1 g1 to y0 and n1 = d3 g1 to y1.  An axis index 0 .. 2 is an odd-phase product, 3 .. 4 an even-phase one; the 25 products
+# of a 2x2 output tile are numbered xi = 3 i + j (odd rows, odd columns), 9 + 2 i + j (odd rows, even columns), 15 + 3 i + j (even rows, odd columns),
+# 21 + 2 i + j (even rows, even columns), i / j counting inside the phase.
+def _pg_axis(g0, g1, g2):
+    return [g0, g0 + g2, g2, g1, g1]
+
+
+def _pb_axis(d0, d1, d2, d3, d4):
+    return [d0 - d2, d2, d2 - d4, d1, d3]
+
+
+def _po_axis(m0, m1, m2, n0, n1):
+    return [(m0 + m1) + n0, (m1 - m2) + n1]
+
+
+def poly_xi(iy, ix):
+    """position number of the axis indices (iy, ix), each 0 .. 2 odd phase, 3 .. 4 even phase"""
+    if iy < 3:
+        return 3 * iy + ix if ix < 3 else 9 + 2 * iy + (ix - 3)
+    return 15 + 3 * (iy - 3) + ix if ix < 3 else 21 + 2 * (iy - 3) + (ix - 3)
+
+
+def poly_weight_transform(w):
+    """w [co][ci][3][3] -> U [25][co][ci] (x first, then y): every entry is a tap or a sum of two along each axis"""
+    t = [_pg_axis(w[:, :, ky, 0], w[:, :, ky, 1], w[:, :, ky, 2]) for ky in range(3)]      # t[ky][ix]
+    cols = [_pg_axis(t[0][ix], t[1][ix], t[2][ix]) for ix in range(5)]                       # cols[ix][iy]
+    U = [None] * 25
+    for iy in range(5):
+        for ix in range(5):
+            U[poly_xi(iy, ix)] = cols[ix][iy]
+    return torch.stack(U)
+
+
+def poly_input_transform(x):
+    """x [n][c][H][H] (H a multiple of 4) -> V [25][n][c][H/4][H/4] over the zero-padded 5x5 windows at stride 4 (y first, then x)"""
+    xp = F.pad(x, (1, 1, 1, 1))
+    H = x.shape[-1]
+    d = [[xp[:, :, r:r + H:4, c:c + H:4] for c in range(5)] for r in range(5)]             # d[r][c]: window element (r, c) of every tile
+    t = [_pb_axis(*[d[r][c] for r in range(5)]) for c in range(5)]                           # t[c][iy]
+    V = [None] * 25
+    for iy in range(5):
+        row = _pb_axis(*[t[c][iy] for c in range(5)])
+        for ix in range(5):
+            V[poly_xi(iy, ix)] = row[ix]
+    return torch.stack(V)
+
+
+def poly_conv3x3_s2(x, w):
+    """3x3 convolution, padding 1, stride 2 (no bias) as polyphase F(2x2, 2x2) in the dtype of x / w: [n][ci][H][H] -> [n][co][H/2][H/2]"""
+    n, _, H, _ = x.shape
+    U = poly_weight_transform(w)                            # [25][co][ci]
+    V = poly_input_transform(x)                             # [25][n][ci][H/4][H/4]
+    M = torch.einsum("poc,pncyx->pnoyx", U, V)              # one contraction over ci per position
+    t = [_po_axis(*[M[poly_xi(iy, ix)] for iy in range(5)]) for ix in range(5)]              # t[ix][dy]: rows first ...
+    out = torch.empty(n, w.shape[0], H // 2, H // 2, dtype=x.dtype)
+    for dy in range(2):
+        Y = _po_axis(*[t[ix][dy] for ix in range(5)])                                        # ... then columns
+        for dx in range(2):
+            out[:, :, dy::2, dx::2] = Y[dx]
+    return out
+
+
+def poly_packed_weight_transform(sd, layers=(2, 4)):
+    """{layer: U} of HardNet's stride-2 layers as poly_derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: poly_weight_transform, w_tap_index over 25
+    positions): flat float32 [xi (25)][ci / 16][(c / 4) % 4][co][c % 4] of the BN-folded fp32 taps"""
+    out = {}
+    for i in layers:
+        U = poly_weight_transform(packed_taps(sd, i))        # [25][co][ci]
+        co, ci = U.shape[1:]
+        out[i] = U.reshape(25, co, ci // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+    return out
+
+
+POLY_LAYERS = (2, 4)             # HardNet's stride-2 layers
+
+
 def folded(sd, dtype):
     """BatchNorm (eval, affine=False, eps 1e-5) folded into the six conv layers: [(weight, bias, stride)]"""
     layers = []
@@ -113,11 +193,14 @@ def packed_weight_transform(sd):
     return out
 
 
-def hardnet_forward(sd, patches, wino=True, dtype=torch.float32):
-    """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`"""
+def hardnet_forward(sd, patches, wino=True, dtype=torch.float32, poly=False):
+    """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`, conv2 / conv4 as polyphase F(2x2, 2x2) when `poly`"""
     x = orc.input_norm(patches.to(dtype))
     for li, (w, b, st) in enumerate(folded(sd, dtype)):
-        y = wino_conv3x3(x, w) if (wino and li in WINO_LAYERS) else F.conv2d(x, w, None, stride=st, padding=1)
+        if poly and li in POLY_LAYERS:
+            y = poly_conv3x3_s2(x, w)
+        else:
+            y = wino_conv3x3(x, w) if (wino and li in WINO_LAYERS) else F.conv2d(x, w, None, stride=st, padding=1)
         x = F.relu(y + b.view(1, -1, 1, 1))
     y = F.conv2d(x, sd["features.19.weight"].to(dtype), None)
     y = F.batch_norm(y, sd["features.20.running_mean"].to(dtype), sd["features.20.running_var"].to(dtype), None, None, False, 0.1, 1e-5)
@@ -172,12 +255,12 @@ def load_net16(net):
 
 
 def errors(sd, patches):
-    """(max, mean) |descriptor - float64 forward| of direct fp32 and of Winograd fp32"""
+    """(max, mean) |descriptor - float64 forward| of direct fp32, of Winograd fp32 and of Winograd + polyphase fp32"""
     with torch.no_grad():
         ref = orc.hardnet_forward({k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}, patches.double())
         out = {}
-        for name, wino in (("direct", False), ("winograd", True)):
-            d = (hardnet_forward(sd, patches, wino=wino).double() - ref).abs()
+        for name, wino, poly in (("direct", False, False), ("winograd", True, False), ("polyphase", True, True)):
+            d = (hardnet_forward(sd, patches, wino=wino, poly=poly).double() - ref).abs()
             out[name] = (float(d.max()), float(d.mean()))
     return out
 
