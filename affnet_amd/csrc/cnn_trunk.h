@@ -1,6 +1,7 @@
 // Trunk kernel of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet) for gfx950 on the fp32 matrix cores: cnn32_trunk_kernel and its
 // device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip: HardNet form 1), which instantiate one net's six kernels each
-// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.
+// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1),
+// exact AffNet / OriNet, split HardNet, split AffNet / OriNet.
 //
 // Replaces architectures.py:204-252 (AffNetFast), :33-82 (OriNetFast), HardNet.py:61-101
 // (HardNet) incl. input_norm, eval-mode BatchNorm (folded into weights + bias at pack time),
@@ -56,10 +57,7 @@ __device__ __forceinline__ void head_partials(const float* __restrict__ hw, cons
     const int c4 = ng * 16 + 4 * g;
     f32x4 v[TM];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        v[i] = acc[i][0] + bias[0];
-        v[i].x = fmaxf(v[i].x, 0.0f); v[i].y = fmaxf(v[i].y, 0.0f); v[i].z = fmaxf(v[i].z, 0.0f); v[i].w = fmaxf(v[i].w, 0.0f);
-    }
+    for (int i = 0; i < TM; ++i) v[i] = bias_relu(acc[i][0], bias[0]);
     const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 3 * 4096);
     f32x4 w[3][TM];
 #pragma unroll
@@ -169,7 +167,9 @@ __device__ __forceinline__ void ori_head_reduce(const f32x4 (&w)[2][TM], const i
         if (lane == 0) { part[wave * 18 + q] = s0; part[wave * 18 + 9 + q] = s1; }
     }
 }
-// The direct form's head in one piece (the split-operand OriNet trunks): both halves as above, kept as one body so that those kernels' code does not move.
+// The direct form's head in one piece (the split-operand OriNet trunks): both halves as above.  The halo and the reduction are the pieces above; the lane's weight
+// position, its weight loads and the pbase / interior-store loop are kept as one body so that those kernels' code does not move (with OriHeadLane + ori_head_weights:
+// 11 / 4 of 3568 / 3822 disassembly lines of the two-term / three-term kernel, with ori_head_pbase besides 13 / 6; profiles/trunk_merge_report.md).
 template <int TM, int NTHR>
 __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ hw, const f32x4 (&bias)[1], const f32x4 (&acc)[TM][1],
                                                       float* __restrict__ part, float* act, int wave, int lane, int tid) {
@@ -179,10 +179,7 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
     const int c4 = ng * 16 + 4 * g;
     f32x4 v[TM];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        v[i] = acc[i][0] + bias[0];
-        v[i].x = fmaxf(v[i].x, 0.0f); v[i].y = fmaxf(v[i].y, 0.0f); v[i].z = fmaxf(v[i].z, 0.0f); v[i].w = fmaxf(v[i].w, 0.0f);
-    }
+    for (int i = 0; i < TM; ++i) v[i] = bias_relu(acc[i][0], bias[0]);
     const __amdgpu_buffer_rsrc_t r = weight_rsrc(hw, 2 * 4096);
     f32x4 w[2][TM];
 #pragma unroll
@@ -190,11 +187,7 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
 #pragma unroll
         for (int i = 0; i < TM; ++i) w[o][i] = buf_read4(r, (n * 64 + c4) * 4, (o * 4096 + (mg * TM + i) * 16 * 64) * 4);
     __syncthreads();                                                     // every wave has finished reading the conv5 input from `act`
-    for (int e = tid; e < 36 * 16; e += NTHR) {                          // zero halo of the 10 x 10 grid: 36 pixels x 16 float4
-        const int hp = e >> 4, q4 = e & 15;
-        const int y = hp < 10 ? 0 : (hp < 20 ? 9 : 1 + ((hp - 20) >> 1)), x = hp < 10 ? hp : (hp < 20 ? hp - 10 : ((hp - 20) & 1) * 9);
-        *reinterpret_cast<f32x4*>(&act[(y * 10 + x) * ORI_HP + 4 * q4]) = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+    ori_head_zero_halo<NTHR>(act, tid);
     int pbase[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -202,20 +195,7 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
         pbase[i] = ((p >> 3) * 10 + (p & 7)) * ORI_HP + c4;             // (ky, kx) in padded coordinates of tap q = (0, 0)
         *reinterpret_cast<f32x4*>(&act[pbase[i] + 11 * ORI_HP]) = v[i];  // interior pixel (py + 1, px + 1)
     }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(&act[pbase[i] + ((q / 3) * 10 + q % 3) * ORI_HP]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s0 = fmaf(av[j], w[0][i][j], s0); s1 = fmaf(av[j], w[1][i][j], s1); }
-        }
-        s0 = wave_sum(s0);
-        s1 = wave_sum(s1);
-        if (lane == 0) { part[wave * 18 + q] = s0; part[wave * 18 + 9 + q] = s1; }
-    }
+    ori_head_reduce<TM>(w, pbase, part, act, wave, lane);
 }
 
 #define CNN_STAMP(k)                                                                                     \
@@ -277,7 +257,8 @@ struct SplitLays {
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
 // 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
-// kernel is one straight-line body per flow: exact HardNet (Winograd), exact HardNet form 1 (Winograd + polyphase), exact AffNet / OriNet, split HardNet, split AffNet / OriNet.  Every
+// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1: Winograd, with polyphase conv2 / conv4 in form 1), exact AffNet / OriNet, split HardNet,
+// split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
 // AffNet / OriNet: 79 KB LDS -> 2 workgroups per CU (4 waves / SIMD, 128 VGPRs); HardNet: 154 KB LDS -> 1 workgroup per
@@ -380,128 +361,17 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     CNN_STAMP(1);
 
     // ---- one straight-line body per flow ----------------------------------------------------------------
-    if constexpr (S3 == 0 && KIND == AFFNET_NET_HARDNET) {
-        // Exact HardNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (cnn_mfma.h) - 4/9 of the MFMAs; each wave runs NB (tile block,
+    if constexpr (EXACT && KIND == AFFNET_NET_HARDNET) {
+        // Exact HardNet, both descriptor forms: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3) (cnn_mfma.h) - 4/9 of the MFMAs; each wave runs NB (tile block,
         // channel block) passes of a layer, in conv1 / conv3 two at a time on one window transform (conv3x3_wino_mfma_pair_rows).  The Winograd layers
         // load their transformed weights U from the blob (NetLayout::w_wino), ahead of their use; the first fragments of a layer are requested in front of
-        // the barrier before it, where the direct-form layers (conv0, conv2, conv4) request their first weight chunk.  conv5's tensor goes to HBM for
+        // the barrier before it, where the direct-form layers (conv0; form 0: conv2, conv4) request their first weight chunk.  conv5's tensor goes to HBM for
         // the head GEMM.
-        constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
-        constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
-
-        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-        f32x4 Up[2][4];                                               // the rolling U register set of conv1 / conv3: one position row, both channel blocks of a pair
-        f32x4 Uw[16];                                                 // the rolling U register set of conv5
-        {
-            f32x4 acc[T1M][T1N];
-            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
-            CNN_STAMP(19);
-            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
-            CNN_STAMP(20);
-            wino_prefetch_u_pair<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Up, wave, lane);
-            __syncthreads();
-        }
-        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-        CNN_STAMP(2);
-
-        // ---- conv1: CB -> CB @32x32, Winograd -------------------------------------------------------------
-        f32x4 b2[S::G2][T2N];
-        f32x4 bias2[T2N];
-        {
-            f32x4 y[NB1][4], bw[NB1];
-            __builtin_amdgcn_s_setprio(0);
-            conv3x3_wino_mfma_pair_rows<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Up, y, wave, lane);
-            __builtin_amdgcn_s_setprio(3);
-            CNN_STAMP(3);
-            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
-            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-            wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
-            __syncthreads();
-            CNN_STAMP(21);
-            zero_halo<LayC1, NTHR>(act, CB);
-            wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
-            CNN_STAMP(22);
-            __syncthreads();
-            CNN_STAMP(4);
-        }
-        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-        {
-            f32x4 acc[T2M][T2N];
-            __builtin_amdgcn_s_setprio(0);
-            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
-            __builtin_amdgcn_s_setprio(3);
-            CNN_STAMP(5);
-            wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
-            __syncthreads();
-            zero_halo<LayC2, NTHR>(act, 2 * CB);
-            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
-            __syncthreads();
-            CNN_STAMP(6);
-        }
-        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
-        f32x4 b4[S::G4][T4N];
-        f32x4 bias4[T4N];
-        {
-            f32x4 y[NB3][4], bw[NB3];
-            __builtin_amdgcn_s_setprio(0);
-            conv3x3_wino_mfma_pair_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Up, y, wave, lane);
-            __builtin_amdgcn_s_setprio(3);
-            CNN_STAMP(7);
-            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
-            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-            wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
-            __syncthreads();
-            zero_halo<LayC3, NTHR>(act, 2 * CB);
-            wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
-            __syncthreads();
-            CNN_STAMP(8);
-        }
-        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
-        {
-            f32x4 acc[T4M][T4N];
-            __builtin_amdgcn_s_setprio(0);
-            conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
-            __builtin_amdgcn_s_setprio(3);
-            CNN_STAMP(9);
-            wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
-            __syncthreads();
-            zero_halo<LayC4, NTHR>(act, 4 * CB);
-            store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
-            __syncthreads();
-            CNN_STAMP(10);
-        }
-        if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
-
-        // ---- conv5: 4CB -> 4CB @8x8, Winograd; conv5 tensor -> HBM as [pixel][channel], the head GEMM runs over all patches ----
-        f32x4 y[NB5][4], bw[NB5];
-        __builtin_amdgcn_s_setprio(0);
-        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
-        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
-        __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(11);
-        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
-        if (!STAMPS || a.dbg_layer < 0) {
-            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
-            CNN_STAMP(13);
-            return;
-        }
-        __syncthreads();
-        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
-        __syncthreads();
-        CNN_STAMP(12);
-        if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
-    } else if constexpr (POLY) {
-        // Exact HardNet, descriptor form 1: the flow above with conv2 and conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly_mfma_rows) -
+        // Form 1 (POLY): conv2 and conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly_mfma_rows) -
         // 25/36 of their MFMAs; a wave runs one unit per layer: in conv2 a tile block against a pair of channel blocks, in conv4 the one tile block against its own
         // channel block.  Their transformed weights come from a.wino_u (Poly32), which poly_derive_u_kernel fills from the blob's taps in front of the launch; the first
-        // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the flow above's.
-        constexpr int T1M = S::T1M, T1N = S::T1N;
+        // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the same statements for both forms.
+        constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
         constexpr int NBP2 = (8 * 8 / 16) * (2 * CB / 16) / NW, NBP4 = (4 * 4 / 16) * (4 * CB / 16) / NW;      // polyphase passes per wave: conv2 a pair, conv4 one
 
@@ -521,14 +391,20 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         CNN_STAMP(2);
 
         // ---- conv1: CB -> CB @32x32, Winograd -------------------------------------------------------------
-        f32x4 P2a[2][3], P2b[2][3];                                   // the two rolling U register sets of conv2
+        f32x4 b2[S::G2][T2N];                                         // form 0: conv2's first weight chunk and bias
+        f32x4 bias2[T2N];
+        f32x4 P2a[2][3], P2b[2][3];                                   // form 1: the two rolling U register sets of conv2
         {
             f32x4 y[NB1][4], bw[NB1];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_wino_mfma_pair_rows<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Up, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(3);
-            poly_prefetch_u<NW, CB, 2 * CB, 16, NBP2, 2>(a.wino_u + Poly32::offset(2), P2a, P2b, wave, lane);
+            if constexpr (POLY) poly_prefetch_u<NW, CB, 2 * CB, 16, NBP2, 2>(a.wino_u + Poly32::offset(2), P2a, P2b, wave, lane);
+            else {
+                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            }
             wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
             __syncthreads();
             CNN_STAMP(21);
@@ -540,8 +416,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
 
-        // ---- conv2: CB -> 2CB, stride 2 @16x16, polyphase ---------------------------------------------------
-        {
+        // ---- conv2: CB -> 2CB, stride 2 @16x16; form 1: polyphase --------------------------------------------
+        if constexpr (POLY) {
             f32x4 y[NBP2][4], bw[NBP2];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_poly_mfma_rows<NW, CB, 2 * CB, LayC1, NBP2, 2>(act, a.wino_u + Poly32::offset(2), P2a, P2b, y, wave, lane);
@@ -554,18 +430,36 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             wino_store_lds<2 * CB, LayC2, NBP2>(act, bw, y, wave, lane);
             __syncthreads();
             CNN_STAMP(6);
+        } else {
+            f32x4 acc[T2M][T2N];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(5);
+            wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
         }
         if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
 
         // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
-        f32x4 P4a[1][3], P4b[1][3];                                   // the two rolling U register sets of conv4
+        f32x4 b4[S::G4][T4N];                                         // form 0: conv4's first weight chunk and bias
+        f32x4 bias4[T4N];
+        f32x4 P4a[1][3], P4b[1][3];                                   // form 1: the two rolling U register sets of conv4
         {
             f32x4 y[NB3][4], bw[NB3];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_wino_mfma_pair_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Up, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(7);
-            poly_prefetch_u<NW, 2 * CB, 4 * CB, 8, NBP4, 1>(a.wino_u + Poly32::offset(4), P4a, P4b, wave, lane);
+            if constexpr (POLY) poly_prefetch_u<NW, 2 * CB, 4 * CB, 8, NBP4, 1>(a.wino_u + Poly32::offset(4), P4a, P4b, wave, lane);
+            else {
+                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            }
             wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
             __syncthreads();
             zero_halo<LayC3, NTHR>(act, 2 * CB);
@@ -575,8 +469,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
 
-        // ---- conv4: 2CB -> 4CB, stride 2 @8x8, polyphase ------------------------------------------------------
-        {
+        // ---- conv4: 2CB -> 4CB, stride 2 @8x8; form 1: polyphase ----------------------------------------------
+        if constexpr (POLY) {
             f32x4 y[NBP4][4], bw[NBP4];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_poly_mfma_rows<NW, 2 * CB, 4 * CB, LayC3, NBP4, 1>(act, a.wino_u + Poly32::offset(4), P4a, P4b, y, wave, lane);
@@ -587,6 +481,18 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             __syncthreads();
             zero_halo<LayC4, NTHR>(act, 4 * CB);
             wino_store_lds<4 * CB, LayC4, NBP4>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(10);
+        } else {
+            f32x4 acc[T4M][T4N];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(9);
+            wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC4, NTHR>(act, 4 * CB);
+            store_tiles_lds<4 * CB, LayC4, T4M, T4N>(act, bias4, acc, wave, lane);
             __syncthreads();
             CNN_STAMP(10);
         }
@@ -620,140 +526,103 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators or, S3 = 1, from the Winograd fragments; OriNet from its Winograd fragments through an LDS copy).
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
+        constexpr int NB1 = Wino16::NB1, NB3 = Wino16::NB3;
+        static_assert(WINO13 || T1M * 8 > S::AREG, "conv1: two A sets of T1M float4 do not fit -> rolling single set (conv3x3_mfma_roll)");
         f32x4 b4[S::G4][T4N];
         f32x4 bias4[T4N];
+        f32x4 bias1[T1N];                                             // the direct form's conv1 / conv3 (!WINO13): conv1's bias, conv3's first weight chunk and bias
+        f32x4 b3[S::G3][T2N];
+        f32x4 bias3[T2N];
+        // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
+        {
+            f32x4 acc[T1M][T1N];
+            conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
+            CNN_STAMP(19);
+            if constexpr (!WINO13) prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
+            store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
+            CNN_STAMP(20);
+            __syncthreads();
+        }
+        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+        CNN_STAMP(2);
+
+        // ---- conv1: CB -> CB @32x32, Winograd or direct ------------------------------------------------------
+        f32x4 b2[S::G2][T2N];
+        f32x4 bias2[T2N];
         if constexpr (WINO13) {
-            constexpr int NB1 = Wino16::NB1, NB3 = Wino16::NB3;
-            // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-            {
-                f32x4 acc[T1M][T1N];
-                conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
-                CNN_STAMP(19);
-                store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
-                CNN_STAMP(20);
-                __syncthreads();
-            }
-            if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-            CNN_STAMP(2);
-
-            // ---- conv1: CB -> CB @32x32, Winograd ------------------------------------------------------------
-            f32x4 b2[S::G2][T2N];
-            f32x4 bias2[T2N];
-            {
-                f32x4 y[NB1][4], bw[NB1];
-                conv3x3_wino_mfma_rows<NW, CB, CB, LayC0, NB1>(act, a.wino_u, Ur, y, wave, lane);
-                CNN_STAMP(3);
-                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
-                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-                wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
-                __syncthreads();
-                CNN_STAMP(21);
-                zero_halo<LayC1, NTHR>(act, CB);
-                wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
-                CNN_STAMP(22);
-                __syncthreads();
-                CNN_STAMP(4);
-            }
-            if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
-
-            // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-            {
-                f32x4 acc[T2M][T2N];
-                conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
-                CNN_STAMP(5);
-                wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::offset(3), Ur, wave, lane);
-                __syncthreads();
-                zero_halo<LayC2, NTHR>(act, 2 * CB);
-                store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
-                __syncthreads();
-                CNN_STAMP(6);
-            }
-            if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
-
-            // ---- conv3: 2CB -> 2CB @16x16, Winograd ----------------------------------------------------------
-            {
-                f32x4 y[NB3][4], bw[NB3];
-                conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::offset(3), Ur, y, wave, lane);
-                CNN_STAMP(7);
-                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
-                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-                wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
-                __syncthreads();
-                zero_halo<LayC3, NTHR>(act, 2 * CB);
-                wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
-                __syncthreads();
-                CNN_STAMP(8);
-            }
-            if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
-
+            f32x4 y[NB1][4], bw[NB1];
+            conv3x3_wino_mfma_rows<NW, CB, CB, LayC0, NB1>(act, a.wino_u, Ur, y, wave, lane);
+            CNN_STAMP(3);
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
+            __syncthreads();
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            wino_store_lds<CB, LayC1, NB1>(act, bw, y, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
         } else {
-            static_assert(T1M * 8 > S::AREG, "conv1: two A sets of T1M float4 do not fit -> rolling single set (conv3x3_mfma_roll)");
-            // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
-            f32x4 bias1[T1N];
-            {
-                f32x4 acc[T1M][T1N];
-                conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
-                CNN_STAMP(19);
-                prefetch_bias<NW, 32, T1M, T1N>(a.packed + a.off.b[1], bias1, wave, lane);
-                store_tiles_lds<CB, LayC0, T1M, T1N, false>(act, bias0, acc, wave, lane);
-                CNN_STAMP(20);
-                __syncthreads();
-            }
-            if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-            CNN_STAMP(2);
+            f32x4 acc[T1M][T1N];
+            conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], b1, acc, wave, lane);
+            CNN_STAMP(3);
+            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            __syncthreads();
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
+        }
+        if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
 
-            // ---- conv1: CB -> CB @32x32 --------------------------------------------------------------------
-            f32x4 b2[S::G2][T2N];
-            f32x4 bias2[T2N];
-            {
-                f32x4 acc[T1M][T1N];
-                conv3x3_mfma_roll<NW, CB, CB, LayC0, 1, T1M, T1N>(act, a.packed + a.off.w[1], b1, acc, wave, lane);
-                CNN_STAMP(3);
-                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
-                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
-                __syncthreads();
-                CNN_STAMP(21);
-                zero_halo<LayC1, NTHR>(act, CB);
-                store_tiles_lds<CB, LayC1, T1M, T1N>(act, bias1, acc, wave, lane);
-                CNN_STAMP(22);
-                __syncthreads();
-                CNN_STAMP(4);
-            }
-            if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
-
-            // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-            f32x4 b3[S::G3][T2N];
-            f32x4 bias3[T2N];
-            {
-                f32x4 acc[T2M][T2N];
-                conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
-                CNN_STAMP(5);
+        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
+        {
+            f32x4 acc[T2M][T2N];
+            conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
+            CNN_STAMP(5);
+            if constexpr (WINO13) wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::offset(3), Ur, wave, lane);
+            else {
                 prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G3>(a.packed + a.off.w[3], b3, wave, lane);
                 prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[3], bias3, wave, lane);
-                __syncthreads();
-                zero_halo<LayC2, NTHR>(act, 2 * CB);
-                store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
-                __syncthreads();
-                CNN_STAMP(6);
             }
-            if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
-
-            // ---- conv3: 2CB -> 2CB @16x16 --------------------------------------------------------------------
-            {
-                f32x4 acc[T2M][T2N];
-                conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, S::G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
-                CNN_STAMP(7);
-                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
-                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
-                __syncthreads();
-                zero_halo<LayC3, NTHR>(act, 2 * CB);
-                store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
-                __syncthreads();
-                CNN_STAMP(8);
-            }
-            if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
-
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC2, T2M, T2N>(act, bias2, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
         }
+        if (STAMPS && a.dbg_layer == 2) { dump_planes<2 * CB, LayC2, NTHR>(act, a.dbg_out); return; }
+
+        // ---- conv3: 2CB -> 2CB @16x16, Winograd or direct ----------------------------------------------------
+        if constexpr (WINO13) {
+            f32x4 y[NB3][4], bw[NB3];
+            conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::offset(3), Ur, y, wave, lane);
+            CNN_STAMP(7);
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            wino_store_lds<2 * CB, LayC3, NB3>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        } else {
+            f32x4 acc[T2M][T2N];
+            conv3x3_mfma<NW, 2 * CB, 2 * CB, LayC2, 1, T2M, T2N, S::G3>(act, a.packed + a.off.w[3], b3, acc, wave, lane);
+            CNN_STAMP(7);
+            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            __syncthreads();
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            store_tiles_lds<2 * CB, LayC3, T2M, T2N>(act, bias3, acc, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        }
+        if (STAMPS && a.dbg_layer == 3) { dump_planes<2 * CB, LayC3, NTHR>(act, a.dbg_out); return; }
 
         // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
         f32x4 b5[S::G5][T4N];
@@ -778,44 +647,34 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
 
         static_assert(!WINO5 || (Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL),
                       "Winograd conv5: the exchange lies behind conv4's output inside the LDS array");
-        if constexpr (KIND == AFFNET_NET_ORINET) {
-            // ---- conv5: 4CB -> 4CB @8x8, Winograd, a wave pair per channel block (conv3x3_wino_mfma_half_rows, wino5_combine); its 2 x 2-pixel fragments go
-            // into the head's 10 x 10 copy (over conv4's output, which is dead by then), then the head's per-wave partial sums ----
-            static_assert(Wino5::HEAD + 100 * ORI_HP <= Wino5::X, "conv5: the head copy in front of the exchange");
-            f32x4 acc[2][4], y[2], hw[2][T4M];
+        if constexpr (WINO5) {
+            // ---- conv5: 4CB -> 4CB @8x8, Winograd, a wave pair per channel block (the loop below, then wino5_combine), then the head's per-wave partial sums.
+            // OriNet: the 2 x 2-pixel fragments go into the head's 10 x 10 copy (over conv4's output, which is dead by then).  AffNet's Winograd form: straight from the
+            // combined fragments (head_partials_wino: no LDS copy, no barrier beyond the combine's).  Both request the head's weights in front of the combine's barrier ----
+            constexpr bool ORI = KIND == AFFNET_NET_ORINET;
+            static_assert(T4M == 2, "hw: one weight vector per (output, pixel tile) for OriNet, per (output, fragment pixel) for AffNet");
+            static_assert(!ORI || Wino5::HEAD + 100 * ORI_HP <= Wino5::X, "conv5: the head copy in front of the exchange");
+            f32x4 acc[2][4], y[2], hw[ORI ? 2 : 3][2];
             conv3x3_wino_mfma_half_rows<NW, LayC4>(act, a.wino_u + Wino16::offset(5), Ur, acc, wave, lane);
             CNN_STAMP(11);
             const f32x4 bw = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[5] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
             const OriHeadLane HL = OriHeadLane::of<T4M>(wave, lane);
-            if (!STAMPS || a.dbg_layer < 0) ori_head_weights<T4M>(a.packed + a.off.head_w, HL, hw);
-            wino5_combine(lds, acc, y, wave, lane);
             if (!STAMPS || a.dbg_layer < 0) {
-                float* copy = lds + Wino5::HEAD;
-                ori_head_zero_halo<NTHR>(copy, tid);
-                wino5_store_lds<10, ORI_HP, 4>(copy + 11 * ORI_HP, bw, y, wave, lane);
-                int pbase[T4M];
-                ori_head_pbase<T4M>(HL, pbase);
-                ori_head_reduce<T4M>(hw, pbase, a.out + pidx * HEAD_PART_ORI, copy, wave, lane);
-                CNN_STAMP(13);
-                return;
+                if constexpr (ORI) ori_head_weights<T4M>(a.packed + a.off.head_w, HL, hw);
+                else aff_head_weights_wino(a.packed + a.off.head_w, hw, wave, lane);
             }
-            __syncthreads();
-            wino5_store_lds<LayC5::WP, 4, LayC5::PSG>(act + (LayC5::WP + 1) * 4, bw, y, wave, lane);   // debug dump only
-            __syncthreads();
-            CNN_STAMP(12);
-            if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
-            return;
-        } else if constexpr (WINO5) {
-            // ---- conv5 of AffNet's Winograd form: the same loop and combine; the head's per-wave partial sums straight from the combined fragments
-            // (head_partials_wino: no LDS copy, no barrier beyond the combine's), its weights requested in front of that barrier ----
-            f32x4 acc[2][4], y[2], hw[3][2];
-            conv3x3_wino_mfma_half_rows<NW, LayC4>(act, a.wino_u + Wino16::offset(5), Ur, acc, wave, lane);
-            CNN_STAMP(11);
-            const f32x4 bw = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[5] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
-            if (!STAMPS || a.dbg_layer < 0) aff_head_weights_wino(a.packed + a.off.head_w, hw, wave, lane);
             wino5_combine(lds, acc, y, wave, lane);
             if (!STAMPS || a.dbg_layer < 0) {
-                head_partials_wino(hw, bw, y, a.out + pidx * HEAD_PART_AFF, wave, lane);
+                if constexpr (ORI) {
+                    float* copy = lds + Wino5::HEAD;
+                    ori_head_zero_halo<NTHR>(copy, tid);
+                    wino5_store_lds<10, ORI_HP, 4>(copy + 11 * ORI_HP, bw, y, wave, lane);
+                    int pbase[T4M];
+                    ori_head_pbase<T4M>(HL, pbase);
+                    ori_head_reduce<T4M>(hw, pbase, a.out + pidx * HEAD_PART_ORI, copy, wave, lane);
+                } else {
+                    head_partials_wino(hw, bw, y, a.out + pidx * HEAD_PART_AFF, wave, lane);
+                }
                 CNN_STAMP(13);
                 return;
             }
