@@ -297,7 +297,9 @@ def test_handcrafted_windows_match_the_reference_formula():
 
 
 def test_exact_arithmetic_spec_of_the_blur():
-    """Documents WHY the HIP blur is bit-exact: torch's CPU conv2d == row-major sequential fmaf chain."""
+    """Documents WHY the HIP blur is bit-exact: torch's CPU conv2d == row-major sequential fmaf chain (fma32: the correctly rounded fp32
+    fma of tests/_fp32_chain.py; the float64 form (a * b + c).astype(float32) rounds twice)."""
+    from _fp32_chain import fma32
     x = orc.synthetic_image(40, 56, 5)
     ker, pad = orc.gauss_kernel_2d(1.2262734984654078)
     ref = orc.gaussian_blur(x, 1.2262734984654078)[0, 0].numpy()
@@ -306,7 +308,7 @@ def test_exact_arithmetic_spec_of_the_blur():
     k = ker.shape[0]
     for i in range(k):
         for j in range(k):
-            acc = (xp[i:i + 40, j:j + 56].astype(np.float64) * np.float64(ker[i, j]) + acc.astype(np.float64)).astype(np.float32)
+            acc = fma32(xp[i:i + 40, j:j + 56], ker[i, j], acc)
     assert np.array_equal(acc, ref)
 
 
