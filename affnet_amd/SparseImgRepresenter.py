@@ -66,8 +66,9 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                                    # equals the staged path and getAffineShape / getOrientation bit for bit, which form 1 does not (A of an unflagged
                                    # candidate carries the Winograd rounding, <= 4e-6)
 
-        self.desc_form = 1         # fused path, arith "fp32": 1 = HardNet trunk with conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2), 0 = in the direct
-                                   # form (affnet_set_desc_form; read at every call, a captured graph keeps its form).  Descriptors differ by rounding only
+        self.desc_form = 2         # fused path, arith "fp32": 2 = HardNet trunk with conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) and conv3 as Winograd
+                                   # F(4x4, 3x3), 1 = conv3 as F(2x2, 3x3) as conv1 / conv5 are, 0 = conv2 / conv4 in the direct form besides
+                                   # (affnet_set_desc_form; read at every call, a captured graph keeps its form).  Descriptors differ by rounding only
                                    # (<= 2e-6); a stand-alone HardNet.forward always runs form 0
 
     # ------------------------------------------------------------------------------------------

@@ -43,9 +43,11 @@ static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, d
         const int rc = aff_wino_derive_u(ctx, c.kind, c.packed, L, c.st, &a.wino_u);
         if (rc) return rc;
     }
-    const bool poly = c.poly && c.kind == AFFNET_NET_HARDNET && ctx->arith == AFFNET_ARITH_FP32_MFMA;      // descriptor form 1
+    const bool poly = c.desc_form != AFFNET_DESC_FORM_DIRECT && c.kind == AFFNET_NET_HARDNET && ctx->arith == AFFNET_ARITH_FP32_MFMA;      // descriptor forms 1 / 2
+    const bool f43 = poly && c.desc_form == AFFNET_DESC_FORM_F43;
     if (poly) {
-        const int rc = aff_poly_derive_u(ctx, c.packed, L, c.st, &a.wino_u);
+        int rc = aff_poly_derive_u(ctx, c.packed, L, c.st, &a.wino_u);
+        if (!rc && f43) rc = aff_f43_derive_u(ctx, c.packed, L, c.st);
         if (rc) return rc;
     }
     a.patches = c.patches; a.lafs = c.lafs; a.ids = c.ids; a.count = c.count; a.n_max = c.n_max;
@@ -60,7 +62,7 @@ static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, d
     static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk getter order");
     static TrunkKernel (*const trunk_of[3])(int, bool) = {aff_trunk_affnet, aff_trunk_orinet, aff_trunk_hardnet};
     const bool stamps = a.dbg_time || c.dbg_layer >= 0;
-    hipLaunchKernelGGL(wino ? aff_trunk_affnet_wino(stamps) : (poly ? aff_trunk_hardnet_poly(stamps) : trunk_of[c.kind](aff_arith_index(ctx), stamps)), grid, dim3(512), 0, c.st, a, ps);
+    hipLaunchKernelGGL(wino ? aff_trunk_affnet_wino(stamps) : (poly ? (f43 ? aff_trunk_hardnet_f43(stamps) : aff_trunk_hardnet_poly(stamps)) : trunk_of[c.kind](aff_arith_index(ctx), stamps)), grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -143,17 +145,17 @@ int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const f
     CnnCall c;
     c.kind = AFFNET_NET_HARDNET; c.packed = packed; c.lafs = lafs; c.ids = ids; c.count = count; c.n_max = n_max; c.out = out; c.scratch = scratch; c.st = st;
     c.mark_head = true;
-    // descriptor form 1; a OnePassSIR context keeps form 0: its fused descriptors equal the staged path's, which describes with the stand-alone forward
-    c.poly = ctx->desc_form == AFFNET_DESC_FORM_POLYPHASE && !ctx->cfg.onepass;
+    // descriptor forms 1 / 2; a OnePassSIR context keeps form 0: its fused descriptors equal the staged path's, which describes with the stand-alone forward
+    c.desc_form = ctx->cfg.onepass ? AFFNET_DESC_FORM_DIRECT : ctx->desc_form;
     return cnn_launch(ctx, c);
 }
 
-int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st) {
+int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st, int form) {
     if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "hardnet_poly: AFFNET_ARITH_FP32_MFMA only");
     CnnCall c;
     c.kind = AFFNET_NET_HARDNET; c.packed = packed; c.patches = patches; c.n_max = n; c.out = out; c.scratch = scratch; c.st = st;
     c.dbg_layer = dbg_layer; c.dbg_out = dbg_layer >= 0 ? out : nullptr;
-    c.poly = true;
+    c.desc_form = form;
     return cnn_launch(ctx, c);
 }
 

@@ -1314,6 +1314,187 @@ __device__ __forceinline__ void conv3x3_wino_mfma_shared_v(float* act, const flo
     wino_output(acc, y[0]);
 }
 
+// ---- Winograd F(4x4, 3x3): conv3 of the exact HardNet trunk in descriptor form 2 ----------------------------------------------------------
+// A 4x4 output tile over its 6x6 input window, points 0, +-1, +-2: 36 products per (cin, cout) for 16 outputs, 2.25 per output against F(2x2, 3x3)'s 4.
+//   B^T d along an axis: (4 d0 - 5 d2) + d4;  a = d4 - 4 d2, b = d3 - 4 d1: a + b, a - b;  c = d4 - d2, e = 2 (d3 - d1): c + e, c - e;  (4 d1 - 5 d3) + d5
+//                                                                                                                               (y first, then x)
+//   G g along an axis:   weights_layout.h: f43_g_axis                                                                           (x first, then y)
+//   A^T m along an axis: p = m1 + m2, q = m1 - m2, r = m3 + m4, s = m3 - m4:  (m0 + p) + r,  q + 2 s,  p + 4 r,  q + (8 s + m5)    (x first, then y)
+// tools/winograd_numerics.py: f43_conv3x3 mirrors this operation order in fp32.
+// conv3 (64 -> 64 at 16 x 16) is ONE block of 16 tiles (tile m = (ty, tx) = (m >> 2, m & 3)), four channel blocks and four K groups; the layer runs as conv5's
+// shared-V loop does, with a wave PAIR per channel block: wave w = 2 p + h
+//   * transforms K group p for the position rows 3 h .. 3 h + 2 (xi = 6 i + j): lane (m, kq) reads rows h .. h + 4 of its window for its four interleaved channels
+//     (30 ds_read_b128; the 16 windows of a service group lie 64 bytes and 4 rows apart and meet 4 at a time in the same banks - a 4-way conflict that no numbering of
+//     the tiles removes, since it is the same set of addresses) and forms 18 V fragments; then barrier (the input is consumed), V into LDS as
+//     [G][xi][kq][m][4] (1 KB contiguous per (G, xi): conflict-free both ways; 147 456 bytes over the layer's input), barrier;
+//   * runs the 18 positions of its half against channel block p over the four K groups: 288 MFMAs into 18 accumulators, no VALU in the loop; U (a.wino_u: F43, derived
+//     in front of the launch) and V roll one K group ahead, each in one register set, a position's fragments requested once its MFMAs have issued;
+//   * folds its accumulators along x (f43_at_axis per position row) into t[3][4] and, in f43_combine, along y into its share of the four output rows, exchanges the
+//     other half's share with its partner through LDS (8 KB per wave, fixed order, no atomics) and ends with y[4 dy + c] = pre-activation couts 16 p + 4 (lane >> 4) + 0..3
+//     of pixel (4 ty + 2 h + dy, 4 tx + c).
+// Every accumulator (tile, cout, position) receives its MFMAs in one fixed order (G ascending, four k-steps each).
+struct F43L {                                             // float offsets from the start of the activation buffer
+    static constexpr int V_FLOATS = 4 * F43_XI * 256;     // V of conv3: [G (4)][xi (36)][kq][m][4]
+    static constexpr int X = 0, X_FLOATS = 8 * 8 * 256;   // the exchange slots of f43_combine, over V (dead behind the barrier in front of the combine)
+};
+__device__ __forceinline__ void f43_bt_lo(float d0, float d1, float d2, float d3, float d4, float& v0, float& v1, float& v2) {
+    v0 = (4.0f * d0 - 5.0f * d2) + d4;
+    const float a = d4 - 4.0f * d2, b = d3 - 4.0f * d1;
+    v1 = a + b; v2 = a - b;
+}
+__device__ __forceinline__ void f43_bt_hi(float d1, float d2, float d3, float d4, float d5, float& v3, float& v4, float& v5) {
+    const float c = d4 - d2, e = 2.0f * (d3 - d1);
+    v3 = c + e; v4 = c - e;
+    v5 = (4.0f * d1 - 5.0f * d3) + d5;
+}
+__device__ __forceinline__ void f43_at_axis(float m0, float m1, float m2, float m3, float m4, float m5, float& y0, float& y1, float& y2, float& y3) {
+    const float p = m1 + m2, q = m1 - m2, r = m3 + m4, s = m3 - m4;
+    y0 = (m0 + p) + r; y1 = q + 2.0f * s; y2 = p + 4.0f * r; y3 = q + (8.0f * s + m5);
+}
+
+// V[6 il + j] = position (3 HF + il, j) of B^T d B of the 6x6 window at LDS byte address `ab`, the lane's four interleaved channels: rows HF .. HF + 4 of the window
+// (30 ds_read_b128), along y, then along x.  No MFMA runs beside it, so the arithmetic is plain C (the compiler may pack it)
+template <typename LI, int HF>
+__device__ __forceinline__ void f43_window_half(unsigned ab, f32x4 (&V)[18]) {
+    f32x4 d[5][6];
+#pragma unroll
+    for (int r = 0; r < 5; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) d[r][c] = lds_read4(ab + ((r + HF) * LI::WP + c) * 16);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[3][6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            if constexpr (HF == 0) f43_bt_lo(d[0][c][e], d[1][c][e], d[2][c][e], d[3][c][e], d[4][c][e], t[0][c], t[1][c], t[2][c]);
+            else f43_bt_hi(d[0][c][e], d[1][c][e], d[2][c][e], d[3][c][e], d[4][c][e], t[0][c], t[1][c], t[2][c]);
+        }
+#pragma unroll
+        for (int il = 0; il < 3; ++il) {
+            float v[6];
+            f43_bt_lo(t[il][0], t[il][1], t[il][2], t[il][3], t[il][4], v[0], v[1], v[2]);
+            f43_bt_hi(t[il][1], t[il][2], t[il][3], t[il][4], t[il][5], v[3], v[4], v[5]);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) V[6 * il + j][e] = v[j];
+        }
+    }
+}
+
+// U of K group 0 of the wave's 18 positions: does not depend on the activations, requested in front of the barrier before the layer.  Wu = U of the layer,
+// [xi (36)][CIN/16][kq][COUT][4]
+template <int CIN, int COUT>
+__device__ __forceinline__ int f43_u_lane(int wave, int lane) {
+    return ((lane >> 4) * COUT + (wave >> 1) * 16 + (lane & 15)) * 16 + (wave & 1) * (18 * CIN * COUT * 4);
+}
+template <int CIN, int COUT>
+__device__ __forceinline__ void f43_prefetch_u(const float* __restrict__ Wu, f32x4 (&U)[18], int wave, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, F43_XI * CIN * COUT);
+    const int u_lane = f43_u_lane<CIN, COUT>(wave, lane);
+#pragma unroll
+    for (int k = 0; k < 18; ++k) U[k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0);
+}
+
+// The caller owns F43L::V_FLOATS floats at `act`.  t[il][c] = the wave's position row 3 h + il folded along x (columns c = 0 .. 3 of the tile)
+template <int NW, int CIN, int COUT, typename LI>
+__device__ __forceinline__ void conv3x3_f43_mfma_shared_v(float* act, const float* __restrict__ Wu, f32x4 (&U)[18], f32x4 (&t)[3][4], int wave, int lane) {
+    constexpr int NGRP = CIN / 16;
+    static_assert(NW == 8 && LI::H == 16 && COUT == 16 * (NW / 2) && NGRP == NW / 2, "one block of 16 4x4 tiles; a wave pair per channel block and per K group");
+    const int m = lane & 15, kq = lane >> 4, p = wave >> 1, h = wave & 1;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, F43_XI * CIN * COUT);
+    const int u_lane = f43_u_lane<CIN, COUT>(wave, lane);
+    f32x4 V[18];
+    {
+        const unsigned ab = lds_byte_addr(act) + ((4 * p + kq) * LI::PSG + (4 * (m >> 2) * LI::WP + 4 * (m & 3)) * 4) * 4;
+        if (h == 0) f43_window_half<LI, 0>(ab, V); else f43_window_half<LI, 1>(ab, V);
+    }
+    __syncthreads();                                      // the whole input has been read
+#pragma unroll
+    for (int k = 0; k < 18; ++k) *reinterpret_cast<f32x4*>(&act[((p * F43_XI + 18 * h + k) * 64 + lane) * 4]) = V[k];
+    __syncthreads();
+    const unsigned v0 = lds_byte_addr(act) + (18 * h * 64 + lane) * 16;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) V[k] = lds_read4(v0 + k * 1024);
+    f32x4 acc[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int G = 0; G < NGRP; ++G) {
+        const int Gn = G == NGRP - 1 ? G : G + 1;         // (the last group re-requests itself: unused.  Peeling it so that it requests nothing was measured: the
+                                                          // layer 29.70 k -> 29.37 k ticks, inside the run-to-run noise of the headline; not kept)
+        unsigned vb = v0 + Gn * F43_XI * 1024;
+        asm("" : "+v"(vb));
+        __builtin_amdgcn_sched_barrier(0);                // pinned: two positions' chains interleave, their U and V reloads follow
+#pragma unroll
+        for (int k = 0; k < 18; k += 2) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);
+                acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k + 1][s4], V[k + 1][s4], acc[k + 1], 0, 0, 0);
+            }
+            U[k] = wino_load_u<CIN, COUT>(wrsrc, u_lane, k, Gn);
+            U[k + 1] = wino_load_u<CIN, COUT>(wrsrc, u_lane, k + 1, Gn);
+            V[k] = lds_read4(vb + k * 1024);
+            V[k + 1] = lds_read4(vb + (k + 1) * 1024);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int il = 0; il < 3; ++il)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float yc[4];
+            f43_at_axis(acc[6 * il][e], acc[6 * il + 1][e], acc[6 * il + 2][e], acc[6 * il + 3][e], acc[6 * il + 4][e], acc[6 * il + 5][e], yc[0], yc[1], yc[2], yc[3]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[il][c][e] = yc[c];
+        }
+}
+
+// A^T along y over the wave pair, f43_at_axis's sums: wave 2 p (rows m0, m1, m2 = t[0 .. 2]) forms p, q and m0 + p, wave 2 p + 1 (m3, m4, m5) forms r, 2 s, 4 r and
+// 8 s + m5; wave 2 p sends p and q, wave 2 p + 1 sends r and 2 s (8 fragments each into its 8 KB slot of F43L::X), barrier, and wave 2 p ends with the tile's output
+// rows 0 and 1, wave 2 p + 1 with rows 2 and 3.  The caller has passed a barrier behind the loop (X lies over V) and passes another before anything is stored over X.
+// `lds` = the start of the activation buffer
+__device__ __forceinline__ void f43_combine(float* lds, const f32x4 (&t)[3][4], f32x4 (&y)[8], int wave, int lane) {
+    const int h = wave & 1;
+    float* xw = lds + F43L::X + (wave * 8 * 64 + lane) * 4;
+    const float* xr = lds + F43L::X + ((wave ^ 1) * 8 * 64 + lane) * 4;
+    f32x4 k0[4], k1[4];                                   // what the wave keeps: (m0 + p, q) or (4 r, 8 s + m5)
+    if (h == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f32x4 p = t[1][c] + t[2][c], q = t[1][c] - t[2][c];
+            k0[c] = t[0][c] + p; k1[c] = q;
+            *reinterpret_cast<f32x4*>(&xw[c * 256]) = p;
+            *reinterpret_cast<f32x4*>(&xw[(4 + c) * 256]) = q;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f32x4 r = t[0][c] + t[1][c], s = t[0][c] - t[1][c];
+            k0[c] = 4.0f * r; k1[c] = 8.0f * s + t[2][c];
+            *reinterpret_cast<f32x4*>(&xw[c * 256]) = r;
+            *reinterpret_cast<f32x4*>(&xw[(4 + c) * 256]) = 2.0f * s;
+        }
+    }
+    __syncthreads();                                      // the partner's share is in place
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const f32x4 o0 = *reinterpret_cast<const f32x4*>(&xr[c * 256]), o1 = *reinterpret_cast<const f32x4*>(&xr[(4 + c) * 256]);
+        y[c] = k0[c] + o0;                                // rows 0 / 2: (m0 + p) + r, p + 4 r
+        y[4 + c] = k1[c] + o1;                            // rows 1 / 3: q + 2 s, q + (8 s + m5)
+    }
+}
+
+// + bias, ReLU, store the wave's 2 x 4 pixels x 4 channels per lane into the LDS layout LO (H = 16)
+template <typename LO>
+__device__ __forceinline__ void f43_store_lds(float* act, f32x4 bias, const f32x4 (&y)[8], int wave, int lane) {
+    const int m = lane & 15, oy = 4 * (m >> 2) + 2 * (wave & 1), ox = 4 * (m & 3);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const f32x4 v = bias_relu(y[k], bias);
+        *reinterpret_cast<f32x4*>(&act[((wave >> 1) * 4 + (lane >> 4)) * LO::PSG + ((oy + (k >> 2) + 1) * LO::WP + ox + (k & 3) + 1) * 4]) = v;
+    }
+}
+
 // The same layer for the 16-channel trunks (AffNet / OriNet conv1, conv3), which live on 128 registers per lane (two workgroups per CU): acc[16] + U[16] +
 // V[16] of a whole-window loop do not fit.  The output transform is linear in the positions, so a wave walks ONE ROW of four positions xi = 4 i .. 4 i + 3 at a
 // time: row i of V needs two rows of the window (B^T along y: rows (0, 2), (1, 2), (2, 1), (1, 3)), 8 ds_read_b128 and 32 VALU operations; the row's four

@@ -1,6 +1,6 @@
 // Trunk kernel of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet) for gfx950 on the fp32 matrix cores: cnn32_trunk_kernel and its
-// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip: HardNet form 1), which instantiate one net's six kernels each
-// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1),
+// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip / cnn_trunk_hardnet_f43.hip: HardNet forms 1 / 2), which instantiate one net's six kernels each
+// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1 / 2),
 // exact AffNet / OriNet, split HardNet, split AffNet / OriNet.
 //
 // Replaces architectures.py:204-252 (AffNetFast), :33-82 (OriNetFast), HardNet.py:61-101
@@ -16,7 +16,8 @@
 //     (cnn_mfma.h: conv3x3_mfma) with the WEIGHTS as the MFMA A operand and the ACTIVATIONS as the B operand, so a lane ends up with 4
 //     consecutive channels of one pixel; the stride-1 layers as Winograd F(2x2, 3x3), U = G g G^T: HardNet's conv1 / conv3
 //     (conv3x3_wino_mfma_pair_rows: two channel blocks share one window transform, one row of four transform positions per step, the next
-//     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob;
+//     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob; in descriptor form 2
+//     conv3 as Winograd F(4x4, 3x3) (conv3x3_f43_mfma_shared_v: V shared through LDS, a wave pair per channel block), U derived in front of the launch;
 //     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
 //     blob's taps by wino_derive_u_kernel, cnn_trunk_orinet.hip, in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
 //     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet has both forms: the direct one
@@ -256,8 +257,9 @@ struct SplitLays {
 };
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
-// 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides.  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
-// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1: Winograd, with polyphase conv2 / conv4 in form 1), exact AffNet / OriNet, split HardNet,
+// 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides,
+// 4 = HardNet as 1 with conv3 as Winograd F(4x4, 3x3) (descriptor form 2).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 and conv3 in F(4x4, 3x3) in form 2), exact AffNet / OriNet, split HardNet,
 // split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
@@ -267,12 +269,16 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET),
-                  "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5, exact HardNet with polyphase conv2 / conv4");
-    constexpr bool EXACT = S3 <= 1;                                           // fp32 operands on v_mfma_f32_16x16x4_f32
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET) || (S3 == 4 && KIND == AFFNET_NET_HARDNET),
+                  "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5, exact HardNet with polyphase conv2 / conv4; "
+                  "4 = exact HardNet as 1 with conv3 as Winograd F(4x4, 3x3)");
+    constexpr bool EXACT = S3 <= 1 || S3 == 4;                                // fp32 operands on v_mfma_f32_16x16x4_f32
     constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || (S3 == 1 && KIND == AFFNET_NET_AFFNET);   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
     constexpr bool WINO5 = WINO13;                                            // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
-    constexpr bool POLY = S3 == 1 && KIND == AFFNET_NET_HARDNET;              // HardNet descriptor form 1: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
+    constexpr bool POLY = (S3 == 1 || S3 == 4) && KIND == AFFNET_NET_HARDNET; // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
+    constexpr bool F43_1 = false;                                             // HardNet descriptor form 2, one flag per layer: conv1 as Winograd F(4x4, 3x3) - not built (NOTES.md)
+    constexpr bool F43_3 = S3 == 4 && KIND == AFFNET_NET_HARDNET;             // ... conv3 as Winograd F(4x4, 3x3), V shared through LDS
+    static_assert(!F43_1, "conv1 in F(4x4, 3x3) has no loop yet");
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -371,6 +377,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // 25/36 of their MFMAs; a wave runs one unit per layer: in conv2 a tile block against a pair of channel blocks, in conv4 the one tile block against its own
         // channel block.  Their transformed weights come from a.wino_u (Poly32), which poly_derive_u_kernel fills from the blob's taps in front of the launch; the first
         // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the same statements for both forms.
+        // Form 2 (F43_3) = form 1 with conv3 as Winograd F(4x4, 3x3) (cnn_mfma.h: conv3x3_f43_mfma_shared_v, f43_combine) - 288 instead of 512 MFMAs per wave; its
+        // weights lie behind the polyphase ones at a.wino_u + F43::BASE (f43_derive_u_kernel).  conv1 has a flag of its own (F43_1) and no F(4x4, 3x3) loop yet.
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
         constexpr int NBP2 = (8 * 8 / 16) * (2 * CB / 16) / NW, NBP4 = (4 * 4 / 16) * (4 * CB / 16) / NW;      // polyphase passes per wave: conv2 a pair, conv4 one
@@ -378,6 +386,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
         f32x4 Up[2][4];                                               // the rolling U register set of conv1 / conv3: one position row, both channel blocks of a pair
         f32x4 Uw[16];                                                 // the rolling U register set of conv5
+        f32x4 Uf[18];                                                 // form 2: the rolling U register set of conv3
         {
             f32x4 acc[T1M][T1N];
             conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
@@ -423,7 +432,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             conv3x3_poly_mfma_rows<NW, CB, 2 * CB, LayC1, NBP2, 2>(act, a.wino_u + Poly32::offset(2), P2a, P2b, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(5);
-            wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
+            if constexpr (F43_3) f43_prefetch_u<2 * CB, 2 * CB>(a.wino_u + F43::BASE + F43::offset(3), Uf, wave, lane);
+            else wino_prefetch_u_pair<NW, 2 * CB, 2 * CB, 16, NB3>(a.packed + a.off.w_wino[1], Up, wave, lane);
             wino_bias<NW, 16, 2 * CB, NBP2>(a.packed + a.off.b[2], bw, wave, lane);
             __syncthreads();
             zero_halo<LayC2, NTHR>(act, 2 * CB);
@@ -449,7 +459,25 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         f32x4 b4[S::G4][T4N];                                         // form 0: conv4's first weight chunk and bias
         f32x4 bias4[T4N];
         f32x4 P4a[1][3], P4b[1][3];                                   // form 1: the two rolling U register sets of conv4
-        {
+        if constexpr (F43_3) {
+            // form 2: F(4x4, 3x3), a wave pair per channel block (cnn_mfma.h: conv3x3_f43_mfma_shared_v); stamp 7 sits behind the halves' exchange
+            static_assert(F43L::V_FLOATS <= TrunkLds<CB>::ACT && F43L::X + F43L::X_FLOATS <= F43L::V_FLOATS, "conv3: V of the layer fits the activation buffer");
+            f32x4 tf[3][4], y[8];
+            __builtin_amdgcn_s_setprio(0);
+            conv3x3_f43_mfma_shared_v<NW, 2 * CB, 2 * CB, LayC2>(act, a.wino_u + F43::BASE + F43::offset(3), Uf, tf, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(23);
+            poly_prefetch_u<NW, 2 * CB, 4 * CB, 8, NBP4, 1>(a.wino_u + Poly32::offset(4), P4a, P4b, wave, lane);
+            const f32x4 bf = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[3] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
+            __syncthreads();                                          // every wave has finished reading V
+            f43_combine(act, tf, y, wave, lane);
+            CNN_STAMP(7);
+            __syncthreads();                                          // ... and its partner's exchange slot
+            zero_halo<LayC3, NTHR>(act, 2 * CB);
+            f43_store_lds<LayC3>(act, bf, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(8);
+        } else {
             f32x4 y[NB3][4], bw[NB3];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_wino_mfma_pair_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.packed + a.off.w_wino[1], Up, y, wave, lane);

@@ -22,11 +22,11 @@ __global__ __launch_bounds__(256) void poly_derive_u_kernel(const float* __restr
     for (int xi = 0; xi < POLY_XI; ++xi) dst[w_tap_index(xi, c, n, cin, cout)] = u[xi];
 }
 
-// The context's buffer of derived polyphase weights (Poly32::FLOATS).  Allocated on first use; affnet_graph_capture_extract calls this before the capture begins
-// (no allocation inside a capture).
+// The context's buffer of derived HardNet weights: the polyphase ones (Poly32::FLOATS) and behind them form 2's F(4x4, 3x3) ones (F43::FLOATS at F43::BASE,
+// cnn_trunk_hardnet_f43.hip).  Allocated on first use; affnet_graph_capture_extract calls this before the capture begins (no allocation inside a capture).
 int aff_poly_u_ensure(affnet_ctx* ctx) {
     if (ctx->poly_u) return AFFNET_OK;
-    AFF_HIP(ctx, hipMalloc((void**)&ctx->poly_u, (size_t)Poly32::FLOATS * sizeof(float)));
+    AFF_HIP(ctx, hipMalloc((void**)&ctx->poly_u, (size_t)(Poly32::FLOATS + F43::FLOATS) * sizeof(float)));
     return AFFNET_OK;
 }
 

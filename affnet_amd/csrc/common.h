@@ -123,8 +123,9 @@ struct affnet_ctx {
     float* wino_u = nullptr;
     // Polyphase weights of conv2 / conv4 of the exact HardNet trunk in descriptor form 1 (Poly32), derived the same way (cnn_trunk_hardnet_poly.hip: poly_derive_u_kernel,
     // aff_poly_u_ensure)
+    // ... and behind them, in the same buffer, form 2's F(4x4, 3x3) weights of conv1 / conv3 (F43; cnn_trunk_hardnet_f43.hip: f43_derive_u_kernel)
     float* poly_u = nullptr;
-    int desc_form = AFFNET_DESC_FORM_POLYPHASE;   // fused exact-fp32 HardNet trunk (affnet_set_desc_form): stride-2 layers in the direct form, or as polyphase Winograd F(2x2, 2x2)
+    int desc_form = AFFNET_DESC_FORM_F43;           // fused exact-fp32 HardNet trunk (affnet_set_desc_form): stride-2 layers in the direct form, or as polyphase Winograd F(2x2, 2x2), or that with conv3 as F(4x4, 3x3)
     ~affnet_ctx() {
         if (wino_u) (void)hipFree(wino_u);
         if (poly_u) (void)hipFree(poly_u);
@@ -227,7 +228,8 @@ struct CnnArgs {
     const float* packed;
     NetOffsets off;
     const float* wino_u;   // exact OriNet, Winograd AffNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel);
-                           // HardNet form 1: the polyphase U of conv2 and conv4 (Poly32, poly_derive_u_kernel)
+                           // HardNet form 1: the polyphase U of conv2 and conv4 (Poly32, poly_derive_u_kernel); form 2: behind it at F43::BASE the F(4x4, 3x3) U of
+                           // conv1 / conv3 (F43, f43_derive_u_kernel)
     const int32_t* reeval; // direct AffNet trunk behind the Winograd one (shape form 1): per-row flags of the margin rule [image * n_max + row], a workgroup whose flag is 0 returns at once; NULL = every row
     const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
     const float* lafs;     // normalised LAFs when sampling
@@ -290,7 +292,7 @@ struct CnnCall {
     int row_begin = 0, row_count = -1;                               // row window of every image; -1 = up to n_max
     const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
     const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
-    bool poly = false;                                               // HardNet, exact fp32: conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (descriptor form 1)
+    int desc_form = AFFNET_DESC_FORM_DIRECT;                         // HardNet, exact fp32: AFFNET_DESC_FORM_* - 1: conv2 / conv4 as polyphase Winograd F(2x2, 2x2), 2: conv3 as F(4x4, 3x3) besides
     bool wino_reeval = false;                                        // AffNet, exact fp32, fused filter: Winograd trunk, margin rule, direct trunk on the flagged rows (shape form 1)
     float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
 };
@@ -348,8 +350,9 @@ int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const i
 int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
                                    int n_max, float* out, float* scratch, hipStream_t st);
 
-// cnn32.hip: HardNet on a patch tensor in descriptor form 1, for the probe library (the public patch-tensor calls run form 0); dbg_layer >= 0: layer dump of patch 0
-int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st);
+// cnn32.hip: HardNet on a patch tensor in descriptor form `form` (1 or 2), for the probe library (the public patch-tensor calls run form 0); dbg_layer >= 0: layer dump of patch 0
+int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st,
+                             int form = AFFNET_DESC_FORM_POLYPHASE);
 
 // cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip: the net's trunk instantiation [aff_arith_index][phase stamps]
 TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
@@ -361,6 +364,10 @@ TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
 TrunkKernel aff_trunk_hardnet_poly(bool stamps);
 int aff_poly_u_ensure(affnet_ctx* ctx);
 int aff_poly_derive_u(affnet_ctx* ctx, const float* packed, const NetLayout& L, hipStream_t st, const float** u);
+// cnn_trunk_hardnet_f43.hip: the exact HardNet trunk of descriptor form 2 (form 1 with conv3 as Winograd F(4x4, 3x3)) [phase stamps]; derive the F(4x4, 3x3) weights of
+// conv1 / conv3 of a HardNet blob behind the polyphase ones in the context's buffer (at F43::BASE floats from what aff_poly_derive_u returns)
+TrunkKernel aff_trunk_hardnet_f43(bool stamps);
+int aff_f43_derive_u(affnet_ctx* ctx, const float* packed, const NetLayout& L, hipStream_t st);
 // cnn_trunk_orinet.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one); derive U of
 // conv1 / conv3 / conv5 of an AffNet or OriNet blob into the context's region of that net kind, *u = that region
 int aff_wino_u_ensure(affnet_ctx* ctx);

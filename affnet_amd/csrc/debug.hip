@@ -131,3 +131,23 @@ extern "C" int affnet_probe_hardnet_poly_u(affnet_ctx* ctx, const float* d_packe
     if (rc) return rc;
     return aff_copy_async(ctx, d_out, u + Poly32::offset(layer), (size_t)Poly32::floats(layer) * sizeof(float), (hipStream_t)stream);
 }
+
+extern "C" int affnet_probe_hardnet_f43_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patch || !d_out || layer < 0 || layer > 5) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_f43_layer: layer 0 .. 5");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patch, 1, d_out, nullptr, layer, (hipStream_t)stream, AFFNET_DESC_FORM_F43);
+}
+
+extern "C" int affnet_probe_hardnet_f43_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patches || !d_out || !d_scratch || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_f43_forward: bad argument");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patches, n, d_out, d_scratch, -1, (hipStream_t)stream, AFFNET_DESC_FORM_F43);
+}
+
+extern "C" int affnet_probe_hardnet_f43_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_out || (layer != 1 && layer != 3)) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_f43_u: layer 1 or 3");
+    const int rc = aff_f43_derive_u(ctx, d_packed, net_layout(AFFNET_NET_HARDNET), (hipStream_t)stream);
+    if (rc) return rc;
+    return aff_copy_async(ctx, d_out, ctx->poly_u + F43::BASE + F43::offset(layer), (size_t)F43::floats(layer) * sizeof(float), (hipStream_t)stream);
+}

@@ -190,3 +190,35 @@ struct Poly32 {
     static constexpr int offset(int layer) { return layer == 2 ? 0 : U2; }
     static constexpr int floats(int layer) { return layer == 2 ? U2 : U4; }
 };
+
+// ---- Winograd F(4x4, 3x3) weight transform (HardNet form 2: conv3; conv1 is derived as well) ---------------------------------------------
+// Standard F(4, 3) on the points 0, +-1, +-2.  Along an axis U = G g with G's rows (1/4, 0, 0), (-1/6)(1, 1, 1), (-1/6)(1, -1, 1), (1/24, 1/12, 1/6),
+// (1/24, -1/12, 1/6), (0, 0, 1), in ONE operation order, one fp32 rounding per operation (1/6, 1/12, 1/24 are the nearest floats):
+//   s = g0 + g2;  p = (1/24) g0 + (1/6) g2;  q = (1/12) g1:   (0.25 g0, (-1/6)(s + g1), (-1/6)(s - g1), p + q, p - q, g2)
+// U[xi = 6 i + j] of one filter g[ky * 3 + kx], along x and then along y.  Stored in w_tap_index order over the 36 positions.  The single definition of the
+// operation order: f43_derive_u_kernel (cnn_trunk_hardnet_f43.hip) calls it, tools/winograd_numerics.py: f43_weight_transform mirrors it.
+#define F43_XI 36
+AFF_HOST_DEVICE inline void f43_g_axis(float g0, float g1, float g2, float* o, int stride) {
+    const float c6 = 1.0f / 6.0f, c12 = 1.0f / 12.0f, c24 = 1.0f / 24.0f;
+    const float s = g0 + g2;
+    const float p = c24 * g0 + c6 * g2, q = c12 * g1;
+    o[0] = 0.25f * g0; o[stride] = -c6 * (s + g1); o[2 * stride] = -c6 * (s - g1);
+    o[3 * stride] = p + q; o[4 * stride] = p - q; o[5 * stride] = g2;
+}
+AFF_HOST_DEVICE inline void f43_weight_transform(const float g[9], float U[F43_XI]) {
+    float t[18];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) f43_g_axis(g[3 * ky], g[3 * ky + 1], g[3 * ky + 2], t + 6 * ky, 1);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) f43_g_axis(t[j], t[6 + j], t[12 + j], U + j, 6);
+}
+
+// U of HardNet's conv1 (32 -> 32) and conv3 (64 -> 64) in F(4x4, 3x3), one after the other BEHIND Poly32's floats in the same context-owned buffer (144 KB + 576 KB):
+// the form 2 trunk takes one derived-weights pointer (CnnArgs::wino_u) and finds both families behind it
+struct F43 {
+    static constexpr int U1 = F43_XI * 32 * 32, U3 = F43_XI * 64 * 64, FLOATS = U1 + U3;
+    static constexpr int PAIRS = 32 * 32 + 64 * 64;                              // (cin, cout) pairs of the two layers
+    static constexpr int BASE = Poly32::FLOATS;                                  // float offset of the family in the context's buffer
+    static constexpr int offset(int layer) { return layer == 1 ? 0 : U1; }       // ... of a layer inside the family
+    static constexpr int floats(int layer) { return layer == 1 ? U1 : U3; }
+};

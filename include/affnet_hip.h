@@ -188,11 +188,14 @@ int affnet_get_shape_form(const affnet_ctx* ctx);
 /* Form of the HardNet trunk of the fused calls (affnet_describe_detected and what is built on it; exact fp32 arithmetic only; the split-operand modes, contexts of
  * the OnePassSIR path (cfg.onepass) and the stand-alone affnet_cnn32_forward / _pyr calls always run form 0):
  *   AFFNET_DESC_FORM_DIRECT    : conv2 / conv4 (stride 2) in the direct form.
- *   AFFNET_DESC_FORM_POLYPHASE : (default) conv2 / conv4 as polyphase Winograd F(2x2, 2x2): 25 instead of 36 products per input channel, output channel and 2x2 output
+ *   AFFNET_DESC_FORM_POLYPHASE : conv2 / conv4 as polyphase Winograd F(2x2, 2x2): 25 instead of 36 products per input channel, output channel and 2x2 output
  *                                tile.  Descriptors differ from form 0 by rounding only (both within 1e-6 of a float64 forward); nothing else of a call changes.
+ *   AFFNET_DESC_FORM_F43       : (default) form 1 with conv3 (64 -> 64 at 16 x 16) as Winograd F(4x4, 3x3) instead of F(2x2, 3x3): 36 products per 16 outputs instead of 16
+ *                                per 4.  Descriptors within 1e-6 of a float64 forward as well (about 3x the direct form's rounding); nothing else of a call changes.
  * Read when a call is enqueued; a graph captured earlier keeps the form it was captured with. */
 #define AFFNET_DESC_FORM_DIRECT 0
 #define AFFNET_DESC_FORM_POLYPHASE 1
+#define AFFNET_DESC_FORM_F43 2
 int affnet_set_desc_form(affnet_ctx* ctx, int form);
 int affnet_get_desc_form(const affnet_ctx* ctx);
 

@@ -70,6 +70,12 @@ int affnet_probe_hardnet_poly_layer(affnet_ctx* ctx, const float* d_packed, cons
 int affnet_probe_hardnet_poly_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
 int affnet_probe_hardnet_poly_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream);
 
+/* The same three for descriptor form AFFNET_DESC_FORM_F43 (form 1 with conv3 as Winograd F(4x4, 3x3)); _u: the derived F(4x4, 3x3) weights of layer 1 (36 x 32 x 32
+ * floats; derived, though the trunk runs conv1 as F(2x2, 3x3)) or 3 (36 x 64 x 64), in the order the kernel reads them. */
+int affnet_probe_hardnet_f43_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+int affnet_probe_hardnet_f43_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
+int affnet_probe_hardnet_f43_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,8 +35,11 @@ class AffNetForm1:
 
 
 class HardNetForm1:
-    """HardNet's trunk of descriptor form 1 (conv2 / conv4 as polyphase Winograd F(2x2, 2x2)), which the fused calls run by default and HardNet.forward never does:
-    trunk + head on a patch tensor through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)"""
+    """HardNet's trunk of descriptor form 1 (conv2 / conv4 as polyphase Winograd F(2x2, 2x2)) or 2 (conv3 as F(4x4, 3x3) besides), which the fused calls run and
+    HardNet.forward never does: trunk + head on a patch tensor through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)"""
+    def __init__(self, probe="affnet_probe_hardnet_poly_forward"):
+        self.probe = getattr(lib, probe)
+
     def __call__(self, x):
         out = torch.empty(x.shape[0], 128, device=dev)
         packed = H.packed_weights(dev)
@@ -44,7 +47,7 @@ class HardNetForm1:
         scratch = torch.empty(rows * (8192 + 512), device=dev)
         for i in range(0, x.shape[0], rows):
             m = min(rows, x.shape[0] - i)
-            rc = lib.affnet_probe_hardnet_poly_forward(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(out[i:i + m]), ptr(scratch), None)
+            rc = self.probe(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(out[i:i + m]), ptr(scratch), None)
             assert rc == 0, rc
         return out
 
@@ -52,6 +55,8 @@ class HardNetForm1:
 nets = [(A, "AffNet", 8), (O, "OriNet", 8), (H, "HardNet", 8)]
 if hasattr(lib, "affnet_probe_hardnet_poly_forward"):
     nets.append((HardNetForm1(), "HardNet form 1", 8))
+    if hasattr(lib, "affnet_probe_hardnet_f43_forward"):
+        nets.append((HardNetForm1("affnet_probe_hardnet_f43_forward"), "HardNet form 2", 8))
 else:
     print("(no table of HardNet's polyphase trunk: this library has no affnet_probe_hardnet_poly_forward - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 if hasattr(lib, "affnet_probe_affnet_wino_partials"):
@@ -116,6 +121,9 @@ for net, nm, nw in nets:
     sub = t[:, :, [3, 21, 22, 4]]
     ds = np.diff(sub, axis=2).mean(axis=(0, 1))
     print("  conv1 epilogue: barrier1 %.0f | halo+stores %.0f | barrier2 %.0f" % tuple(ds))
+    if nm == "HardNet form 2":        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
+        ds = np.diff(t[:, :, [6, 23, 7]], axis=2).mean(axis=(0, 1))
+        print("  conv3 F(4x4, 3x3): transform + V through LDS + loop + fold along x %.0f | barrier + exchange of the halves %.0f" % tuple(ds))
     print("  CUs seen %d; mean resident WGs per CU %.2f; median end->next-start gap %.0f ticks (p90 %.0f)" %
           (len(util), np.mean(util), np.median(gaps), np.percentile(gaps, 90)))
     # wall time of the same launch without stamps
@@ -125,5 +133,5 @@ for net, nm, nw in nets:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

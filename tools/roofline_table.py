@@ -4,7 +4,8 @@
     python tools/roofline_table.py --winograd PREFIX         evidence of a build whose exact HardNet trunk runs conv1 / conv3 / conv5 as Winograd F(2x2, 3x3):
                                                              that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's;
                                                              so is AffNet's Winograd trunk of shape form 1, <0, 8, false, 1> (WINO_AFFNET), and HardNet's trunk of descriptor form 1,
-                                                             <2, 8, false, 1>, whose conv2 / conv4 run as polyphase Winograd F(2x2, 2x2) besides (POLY_HARDNET)
+                                                             <2, 8, false, 1>, whose conv2 / conv4 run as polyphase Winograd F(2x2, 2x2) besides (POLY_HARDNET), and of descriptor form 2, <2, 8, false, 4>,
+                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET)
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
 FETCH_SIZE / WRITE_SIZE passes scaled by the calibration measured for the kernel's access width (tools/fetch_calib.py), the
 resulting GB/s and its fraction of 8 TB/s; for the CNN kernels the algorithmic FLOP rate against the 157.3 TFLOP/s fp32 MFMA peak.
@@ -26,6 +27,9 @@ WINO_HARDNET = NKP * (78184448.0 - 2.0 * 8192 * 128 - 3 * 18874368.0 * (1.0 - 16
 # Descriptor form 1, <2, 8, false, 1>: conv2 / conv4 (stride 2; 9437184 direct FLOPs per patch each) as polyphase Winograd F(2x2, 2x2) execute 25 / 36 of them besides:
 # 38.9 instead of 44.6 M executed MFMA FLOPs per patch
 POLY_HARDNET = WINO_HARDNET - NKP * 2 * 9437184.0 * (1.0 - 25.0 / 36.0)
+# Descriptor form 2, <2, 8, false, 4>: conv3 as Winograd F(4x4, 3x3) executes 36 products per 16 outputs = 9 / 36 of the direct form's instead of F(2x2, 3x3)'s 16 / 36:
+# 35.2 instead of 38.9 M executed MFMA FLOPs per patch
+F43_HARDNET = POLY_HARDNET - NKP * 18874368.0 * (16.0 / 36.0 - 9.0 / 36.0)
 # AffNet's Winograd trunk (shape form 1): conv1 / conv3 / conv5 are 4718592 direct FLOPs per patch each and execute 16 / 36 of them.  conv1 .. conv5 together:
 # 11.0 M executed MFMA FLOPs per patch (13.6 M while conv5 was direct: 288 instead of 128 MFMAs per wave), against OriNet's 11.0 M; conv0 and the head as in the direct form
 WINO_AFFNET = 19193856.0 - 3 * 4718592.0 * (1.0 - 16.0 / 36.0)
@@ -95,7 +99,7 @@ def main(prefix, winograd=False):
                                                           100 * prod * tf / 2516.8))
             elif key in name:
                 if winograd and key == "cnn32_trunk_kernel<2":
-                    fl = POLY_HARDNET if name.rstrip().endswith(", 1>") else WINO_HARDNET
+                    fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else WINO_HARDNET)
                 wino_aff = winograd and key == "cnn32_trunk_kernel<0" and name.rstrip().endswith(", 1>")
                 if wino_aff:
                     fl = fl / 19193856.0 * WINO_AFFNET

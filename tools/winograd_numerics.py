@@ -10,7 +10,9 @@ The contraction over input channels is one matmul per transform position (the ke
 summation order changes the last bits, not the size of the error).  BatchNorm is folded into the conv weights and a bias, as the packed
 weights of the kernel are.
 
-    python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32 and Winograd fp32
+HardNet's descriptor forms 1 and 2 have their mirrors further down: polyphase F(2x2, 2x2) for conv2 / conv4 (poly_*), F(4x4, 3x3) for conv3 (f43_*).
+
+    python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32, Winograd fp32, form 1 and form 2
     python tools/winograd_numerics.py --net affnet|orinet [--layers 1,3,5]
         -> per trunk layer and at the pooled head output: max |x - float64 forward| of direct fp32 and Winograd fp32 (shipped checkpoints,
            tests/golden/cnn_random_patches.npz and --n smooth seeded patches); OriNet also the error of the angle
@@ -158,6 +160,81 @@ def poly_packed_weight_transform(sd, layers=(2, 4)):
 POLY_LAYERS = (2, 4)             # HardNet's stride-2 layers
 
 
+# ---- Winograd F(4x4, 3x3), points 0, +-1, +-2 (HardNet form 2: conv3; cnn_mfma.h: conv3x3_f43_mfma_shared_v + f43_combine) ---------------------------
+# Per axis, one rounding per operation, in the kernel's order (cnn_mfma.h: f43_bt_lo / f43_bt_hi / f43_at_axis, weights_layout.h: f43_g_axis):
+#     U = G g:    s = g0 + g2;  p = (1/24) g0 + (1/6) g2;  q = (1/12) g1:   (0.25 g0, (-1/6)(s + g1), (-1/6)(s - g1), p + q, p - q, g2)
+#     V = B^T d:  (4 d0 - 5 d2) + d4;  a = d4 - 4 d2, b = d3 - 4 d1: a + b, a - b;  c = d4 - d2, e = 2 (d3 - d1): c + e, c - e;  (4 d1 - 5 d3) + d5
+#     Y = A^T m:  p = m1 + m2, q = m1 - m2, r = m3 + m4, s = m3 - m4:  (m0 + p) + r,  q + 2 s,  p + 4 r,  q + (8 s + m5)
+# The weights along x, then y; the input along y, then x; the output along x, then y (in the kernel the y stage is split over a wave pair: f43_combine forms these sums).
+def _f43_const(v, like):
+    return torch.tensor(v, dtype=like.dtype)
+
+
+def _f43_g_axis(g0, g1, g2):
+    # the kernel's constants are the floats nearest to 1/6, 1/12, 1/24 (1.0f / 6.0f ...); in float64 the doubles nearest to them
+    c6, c12, c24 = (_f43_const(1.0 / k, g0) for k in (6.0, 12.0, 24.0))
+    s = g0 + g2
+    p = c24 * g0 + c6 * g2
+    q = c12 * g1
+    return [0.25 * g0, (-c6) * (s + g1), (-c6) * (s - g1), p + q, p - q, g2]
+
+
+def _f43_bt_axis(d0, d1, d2, d3, d4, d5):
+    a, b = d4 - 4.0 * d2, d3 - 4.0 * d1
+    c, e = d4 - d2, 2.0 * (d3 - d1)
+    return [(4.0 * d0 - 5.0 * d2) + d4, a + b, a - b, c + e, c - e, (4.0 * d1 - 5.0 * d3) + d5]
+
+
+def _f43_at_axis(m0, m1, m2, m3, m4, m5):
+    p, q, r, s = m1 + m2, m1 - m2, m3 + m4, m3 - m4
+    return [(m0 + p) + r, q + 2.0 * s, p + 4.0 * r, q + (8.0 * s + m5)]
+
+
+def f43_weight_transform(w):
+    """w [co][ci][3][3] -> U [36][co][ci], xi = 6 i + j (x first, then y)"""
+    t = [_f43_g_axis(w[:, :, ky, 0], w[:, :, ky, 1], w[:, :, ky, 2]) for ky in range(3)]   # t[ky][j]
+    cols = [_f43_g_axis(t[0][j], t[1][j], t[2][j]) for j in range(6)]                        # cols[j][i]
+    return torch.stack([cols[j][i] for i in range(6) for j in range(6)])
+
+
+def f43_input_transform(x):
+    """x [n][c][H][H] (H a multiple of 4) -> V [36][n][c][H/4][H/4] over the zero-padded 6x6 windows at stride 4 (y first, then x)"""
+    xp = F.pad(x, (1, 1, 1, 1))
+    H = x.shape[-1]
+    d = [[xp[:, :, r:r + H:4, c:c + H:4] for c in range(6)] for r in range(6)]             # d[r][c]: window element (r, c) of every tile
+    t = [_f43_bt_axis(*[d[r][c] for r in range(6)]) for c in range(6)]                       # t[c][i]
+    return torch.stack([v for i in range(6) for v in _f43_bt_axis(*[t[c][i] for c in range(6)])])
+
+
+def f43_conv3x3(x, w):
+    """3x3 convolution, padding 1, stride 1 (no bias) as F(4x4, 3x3) in the dtype of x / w: [n][ci][H][H] -> [n][co][H][H]"""
+    n, _, H, _ = x.shape
+    U = f43_weight_transform(w)                             # [36][co][ci]
+    V = f43_input_transform(x)                              # [36][n][ci][H/4][H/4]
+    M = torch.einsum("poc,pncyx->pnoyx", U, V)              # one contraction over ci per position
+    t = [_f43_at_axis(*[M[6 * i + j] for j in range(6)]) for i in range(6)]                  # t[i][c]: columns first ...
+    out = torch.empty(n, w.shape[0], H, H, dtype=x.dtype)
+    for c in range(4):
+        Y = _f43_at_axis(*[t[i][c] for i in range(6)])                                       # ... then rows
+        for r in range(4):
+            out[:, :, r::4, c::4] = Y[r]
+    return out
+
+
+def f43_packed_weight_transform(sd, layers=(1, 3)):
+    """{layer: U} of HardNet's conv1 / conv3 as f43_derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: f43_weight_transform, w_tap_index over 36
+    positions): flat float32 [xi (36)][ci / 16][(c / 4) % 4][co][c % 4] of the BN-folded fp32 taps"""
+    out = {}
+    for i in layers:
+        U = f43_weight_transform(packed_taps(sd, i))         # [36][co][ci]
+        co, ci = U.shape[1:]
+        out[i] = U.reshape(36, co, ci // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+    return out
+
+
+F43_LAYERS = (3,)                # the layers HardNet's descriptor form 2 runs as F(4x4, 3x3)
+
+
 def folded(sd, dtype):
     """BatchNorm (eval, affine=False, eps 1e-5) folded into the six conv layers: [(weight, bias, stride)]"""
     layers = []
@@ -193,12 +270,15 @@ def packed_weight_transform(sd):
     return out
 
 
-def hardnet_forward(sd, patches, wino=True, dtype=torch.float32, poly=False):
-    """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`, conv2 / conv4 as polyphase F(2x2, 2x2) when `poly`"""
+def hardnet_forward(sd, patches, wino=True, dtype=torch.float32, poly=False, f43=()):
+    """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`, conv2 / conv4 as polyphase F(2x2, 2x2) when `poly`, the layers in `f43`
+    (of 1, 3; descriptor form 2: F43_LAYERS) as F(4x4, 3x3) instead of F(2x2, 3x3)"""
     x = orc.input_norm(patches.to(dtype))
     for li, (w, b, st) in enumerate(folded(sd, dtype)):
         if poly and li in POLY_LAYERS:
             y = poly_conv3x3_s2(x, w)
+        elif li in f43:
+            y = f43_conv3x3(x, w)
         else:
             y = wino_conv3x3(x, w) if (wino and li in WINO_LAYERS) else F.conv2d(x, w, None, stride=st, padding=1)
         x = F.relu(y + b.view(1, -1, 1, 1))
@@ -255,12 +335,12 @@ def load_net16(net):
 
 
 def errors(sd, patches):
-    """(max, mean) |descriptor - float64 forward| of direct fp32, of Winograd fp32 and of Winograd + polyphase fp32"""
+    """(max, mean) |descriptor - float64 forward| of direct fp32, of Winograd fp32, of Winograd + polyphase fp32 (form 1) and of form 2 (conv3 as F(4x4, 3x3))"""
     with torch.no_grad():
         ref = orc.hardnet_forward({k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}, patches.double())
         out = {}
-        for name, wino, poly in (("direct", False, False), ("winograd", True, False), ("polyphase", True, True)):
-            d = (hardnet_forward(sd, patches, wino=wino, poly=poly).double() - ref).abs()
+        for name, wino, poly, f43 in (("direct", False, False, ()), ("winograd", True, False, ()), ("polyphase", True, True, ()), ("f43", True, True, F43_LAYERS)):
+            d = (hardnet_forward(sd, patches, wino=wino, poly=poly, f43=f43).double() - ref).abs()
             out[name] = (float(d.max()), float(d.mean()))
     return out
 
