@@ -61,9 +61,10 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
         self.lazy_shape_rows = -1  # fused path: AffNet first runs on the 1.2 N best candidates, on the rest only if needed (identical rows);
                                    # 0 = all 1.5 N candidates at once like the reference (affnet_config.lazy_shape_rows)
         self.shape_form = 1        # fused path, arith "fp32": 1 = AffNet trunk with Winograd conv1 / conv3 / conv5, the candidates whose filter decision could turn on
-                                   # the last bits of A recomputed by the direct kernel (same counts, ids and responses); 0 = direct kernel on every candidate
+                                   # the last bits of A recomputed by the direct kernel (same counts, ids and responses); 2 = that trunk with conv2 / conv4 (stride 2)
+                                   # as polyphase Winograd F(2x2, 2x2) besides, same rule and re-evaluation (selectable, not the default); 0 = direct kernel on every candidate
                                    # (affnet_set_shape_form; read at every call, a captured graph keeps its form).  forward() always runs form 0: it
-                                   # equals the staged path and getAffineShape / getOrientation bit for bit, which form 1 does not (A of an unflagged
+                                   # equals the staged path and getAffineShape / getOrientation bit for bit, which forms 1 / 2 do not (A of an unflagged
                                    # candidate carries the Winograd rounding, <= 4e-6)
 
         self.desc_form = 2         # fused path, arith "fp32": 2 = HardNet trunk with conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) and conv3 as Winograd

@@ -32,7 +32,7 @@ def arith_code(arith):
     if int(arith) not in (ARITH_FP32_MFMA, ARITH_FP32_SPLIT3, ARITH_FP32_SPLIT2H):
         raise ValueError("arith must be AFFNET_ARITH_FP32_MFMA (0), AFFNET_ARITH_FP32_SPLIT3 (1) or AFFNET_ARITH_FP32_SPLIT2H (2)")
     return int(arith)
-SHAPE_FORM_DIRECT, SHAPE_FORM_WINOGRAD = 0, 1                            # include/affnet_hip.h AFFNET_SHAPE_FORM_*
+SHAPE_FORM_DIRECT, SHAPE_FORM_WINOGRAD, SHAPE_FORM_POLYPHASE = 0, 1, 2                         # include/affnet_hip.h AFFNET_SHAPE_FORM_*
 DESC_FORM_DIRECT, DESC_FORM_POLYPHASE, DESC_FORM_F43 = 0, 1, 2                             # include/affnet_hip.h AFFNET_DESC_FORM_*
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_EMPTY = 0, -1, -2, -3, -4
 
@@ -161,6 +161,9 @@ PROBE_SYMBOLS = {
     "affnet_probe_shape_offsets": (_I, [_P, C.POINTER(C.c_int64 * 3)]),
     "affnet_probe_affnet_wino_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),
     "affnet_probe_affnet_wino_partials": (_I, [_P, _P, _P, _I, _P, _P]),
+    "affnet_probe_affnet_poly_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),
+    "affnet_probe_affnet_poly_partials": (_I, [_P, _P, _P, _I, _P, _P]),
+    "affnet_probe_trunk16_poly_u": (_I, [_P, _I, _P, _I, _P, _P]),
     "affnet_probe_hardnet_poly_layer": (_I, [_P, _P, _P, _I, _P, _P]),
     "affnet_probe_hardnet_poly_forward": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "affnet_probe_hardnet_poly_u": (_I, [_P, _P, _I, _P, _P]),

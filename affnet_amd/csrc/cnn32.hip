@@ -34,8 +34,8 @@ int aff_arith_index(const affnet_ctx* ctx) {
     return ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);
 }
 
-// wino: AffNet's Winograd instantiation (exact arithmetic); reeval: the margin rule's flags for the direct AffNet trunk behind it; shape_op: see CnnArgs
-static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, bool wino, const int32_t* reeval, int shape_op) {
+// wino: AffNet's Winograd instantiation (exact arithmetic) of shape form 1 or 2, 0 = none; reeval: the margin rule's flags for the direct AffNet trunk behind it; shape_op: see CnnArgs
+static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, int wino, const int32_t* reeval, int shape_op) {
     CnnArgs a;
     a.packed = c.packed; a.off = to_offsets(L, ctx->arith);            // the split copy of the active mode
     a.wino_u = nullptr; a.reeval = reeval;
@@ -62,7 +62,7 @@ static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, d
     static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk getter order");
     static TrunkKernel (*const trunk_of[3])(int, bool) = {aff_trunk_affnet, aff_trunk_orinet, aff_trunk_hardnet};
     const bool stamps = a.dbg_time || c.dbg_layer >= 0;
-    hipLaunchKernelGGL(wino ? aff_trunk_affnet_wino(stamps) : (poly ? (f43 ? aff_trunk_hardnet_f43(stamps) : aff_trunk_hardnet_poly(stamps)) : trunk_of[c.kind](aff_arith_index(ctx), stamps)), grid, dim3(512), 0, c.st, a, ps);
+    hipLaunchKernelGGL(wino == 2 ? aff_trunk_affnet_poly(stamps) : wino ? aff_trunk_affnet_wino(stamps) : (poly ? (f43 ? aff_trunk_hardnet_f43(stamps) : aff_trunk_hardnet_poly(stamps)) : trunk_of[c.kind](aff_arith_index(ctx), stamps)), grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -73,17 +73,17 @@ static int cnn_launch(affnet_ctx* ctx, const CnnCall& c) {
     if (rc || rows == 0) return rc;
     const NetLayout L = net_layout(c.kind);
     const int B = c.patches ? 1 : ctx->B;                // patch tensors are single-"image"; pyramid sampling covers the batch
-    // Shape form 1 (CnnCall::wino_reeval; exact AffNet with the fused filter only): Winograd trunk on every row of the window (it does the counter work), the margin
+    // Shape forms 1 / 2 (CnnCall::wino_reeval; exact AffNet with the fused filter only; form 2 = form 1's trunk with conv2 / conv4 as polyphase Winograd): Winograd trunk on every row of the window (it does the counter work), the margin
     // rule on its partials (flags in the unused part of the scratch: 144 floats per row, 32 of them partials), the direct trunk on the flagged rows, which
     // overwrites their partials, then the finish + filter kernel as ever.  The same window, row counts and lazy predicate for all; nothing here depends on B or rows.
     const bool form1 = c.wino_reeval && c.kind == AFFNET_NET_AFFNET && c.fuse && c.dbg_layer < 0 && ctx->arith == AFFNET_ARITH_FP32_MFMA;
-    rc = trunk_launch(ctx, c, L, dim3(rows, B), form1, nullptr, c.shape_op);
+    rc = trunk_launch(ctx, c, L, dim3(rows, B), form1 ? c.wino_reeval : 0, nullptr, c.shape_op);
     if (rc) return rc;
     if (form1) {
         int32_t* flags = reinterpret_cast<int32_t*>(c.scratch + (size_t)B * c.n_max * HEAD_PART_AFF);
         rc = aff_margin_affnet(ctx, c, L, rows, B, flags);
         if (rc) return rc;
-        rc = trunk_launch(ctx, c, L, dim3(rows, B), false, flags, 0);
+        rc = trunk_launch(ctx, c, L, dim3(rows, B), 0, flags, 0);
         if (rc) return rc;
     }
     if (c.dbg_layer < 0 && c.kind != AFFNET_NET_HARDNET) {
@@ -125,7 +125,7 @@ int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* re
     c.row_begin = row_begin; c.row_count = row_count;
     c.skip_cnt = lazy ? ctx->cnt : nullptr; c.skip_n = ctx->cfg.num_features;
     c.fuse = &sf; c.shape_op = shape_op;
-    c.wino_reeval = ctx->shape_form == AFFNET_SHAPE_FORM_WINOGRAD;
+    c.wino_reeval = ctx->shape_form;      // AFFNET_SHAPE_FORM_*: 0 = direct only
     return cnn_launch(ctx, c);
 }
 

@@ -1920,3 +1920,114 @@ __device__ __forceinline__ void conv3x3_poly_mfma_rows(const float* act, const f
         step(IntC<S + 1>{}, Vb, Va, Ub);
     });
 }
+
+// ---- the same polyphase form for the 16-channel trunks (AffNet shape form 2, exact OriNet: conv2 16 -> 32 @16x16, conv4 32 -> 64 @8x8) -------------------------
+// These kernels live on 128 registers per lane (two workgroups per CU), so the loop follows conv3x3_wino_mfma_rows' discipline and not conv3x3_poly_mfma_rows': ONE U
+// V register set and small U sets, a step = one position row (3 or 2 positions) of ONE K group: the row's 2 .. 6 ds_read_b128 (requested under the row before), 0 .. 20
+// VALU operations, then 3 or 2 x 4 MFMAs (the positions' chains interleave) and the row's fold into the y stage (t0 / t1, five columns each:
+// poly_row_*, poly_read_row and poly_transform_row above, the fold and its order as in conv3x3_poly_mfma_rows).  Both layers give every wave exactly ten steps = 100 MFMAs
+// (the direct form: 144):
+//   conv2: 64 output tiles = 4 tile blocks x 2 channel blocks = one (tile block, channel block) unit per wave (wino_tile's numbering, NB = 1), CIN = 16 = one K group;
+//   conv4: one tile block x 4 channel blocks x 2 K groups: wave 2 p + h runs channel block p on K group h and folds its own partial rows into a PARTIAL y; the pair adds
+//          the two partial y in the fixed order K group 0 + K group 1 through LDS (poly16_combine), each wave finishing one output row of its tiles.
+// U lives in TWO sets of three fragments and rolls two rows ahead, as in conv3x3_poly_mfma_rows and for its reason: a row has 8 or 12 MFMAs, 256 .. 384 cycles of
+// the pipe, less than an L2 load takes - with one set one row ahead the ten steps ran at the load's latency (measured: conv2 9.2 k ticks against the direct form's 10.1 k).
+// Both sets enter holding rows 0 and 1 (poly16_prefetch_u, requested in front of the barrier before the layer).  Wu = the layer's 25 positions, [xi][CIN/16][kq][COUT][4], derived on
+// the device from the blob's taps (cnn_trunk_orinet.hip: wino_derive_u_kernel; poly_weight_transform).  tools/winograd_numerics.py: poly16_conv2 / poly16_conv4 mirror the order.
+template <int CIN, int COUT>
+__device__ __forceinline__ int poly16_u_lane(int cb, int G, int lane) {
+    return ((lane >> 4) * COUT + cb * 16 + (lane & 15)) * 16 + G * (16 * COUT * 4);
+}
+template <int CIN, int COUT>
+__device__ __forceinline__ void poly16_prefetch_u(const float* __restrict__ Wu, f32x4 (&Ua)[3], f32x4 (&Ub)[3], int cb, int G, int lane) {
+    const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, POLY_XI * CIN * COUT);
+    const int u_lane = poly16_u_lane<CIN, COUT>(cb, G, lane);
+    static_assert(poly_row_np(0) == 3 && poly_row_np(1) == 3, "rows 0 and 1 fill both sets");
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Ua[k] = wino_load_u<CIN, COUT>(r, u_lane, k, 0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Ub[k] = wino_load_u<CIN, COUT>(r, u_lane, poly_row_xi0(1) + k, 0);
+}
+
+// Pre-activation outputs (no bias) of tile (ty, tx) of lane m = lane & 15 over K group G of the input: y[2 dy + dx] = couts 16 cb + 4 (lane >> 4) + 0..3 of pixel
+// (2 ty + dy, 2 tx + dx).  cb and G are uniform over the wave.
+template <int CIN, int COUT, typename LI>
+__device__ __forceinline__ void conv3x3_poly16_mfma_rows(const float* act, const float* __restrict__ Wu, f32x4 (&Ua)[3], f32x4 (&Ub)[3], f32x4 (&y)[4], int ty, int tx, int cb, int G,
+                                                         int lane) {
+    static_assert(LI::H % 4 == 0 && COUT % 16 == 0 && CIN % 16 == 0, "polyphase tiling");
+    const int kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(Wu, POLY_XI * CIN * COUT);
+    const int u_lane = poly16_u_lane<CIN, COUT>(cb, G, lane);
+    unsigned ab = lds_byte_addr(act) + (((4 * G + kq) * LI::PSG + (4 * ty * LI::WP + 4 * tx) * 4) * 4);
+    asm("" : "+v"(ab));
+    f32x4 t0[5], t1[5], acc[3], da[3], db[3], V[3];       // t0 / t1: the y stage, columns 0 .. 2 odd phase, 3 .. 4 even phase
+    poly_read_row<LI, 0>(ab, da, db);
+    poly_transform_row<0>(da, db, V);
+    // one step: the reads of row R + 1, the MFMAs of row R on V and the set U, the requests of row R + 2 into that set, the fold of row R, the transform of row R + 1 into V
+    auto step = [&](auto rc, f32x4 (&U)[3]) {
+        constexpr int R = decltype(rc)::v, R2 = R + 2 < 10 ? R + 2 : R;
+        constexpr int NP = poly_row_np(R), NP2 = R + 2 < 10 ? poly_row_np(R2) : 0, XI2 = poly_row_xi0(R2);
+#pragma unroll
+        for (int k = 0; k < NP; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        __builtin_amdgcn_sched_barrier(0);                // pinned: the positions' chains interleave, the U requests and the next row's reads follow
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+            for (int k = 0; k < NP; ++k) acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[k][s4], V[k][s4], acc[k], 0, 0, 0);   // U^T x V
+#pragma unroll
+        for (int k = 0; k < NP2; ++k) U[k] = wino_load_u<CIN, COUT>(wrsrc, u_lane, XI2 + k, 0);
+        if constexpr (R < 9) poly_read_row<LI, (R < 9 ? R + 1 : R)>(ab, da, db);      // in flight under the fold
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int C0 = NP == 3 ? 0 : 3, yi = poly_row_yi(R);        // the row's sums over the wave's K group are complete: y stage, rows first
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (poly_row_oddy(R)) {
+                    if (yi == 0) t0[C0 + j][e] = acc[j][e];
+                    else if (yi == 1) { t0[C0 + j][e] = wadd(t0[C0 + j][e], acc[j][e]); t1[C0 + j][e] = acc[j][e]; }
+                    else t1[C0 + j][e] = wsub(t1[C0 + j][e], acc[j][e]);
+                } else {
+                    if (yi == 0) t0[C0 + j][e] = wadd(t0[C0 + j][e], acc[j][e]);
+                    else t1[C0 + j][e] = wadd(t1[C0 + j][e], acc[j][e]);
+                }
+            }
+        if constexpr (R == 9) {                           // ... then columns
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                y[0][e] = wadd(wadd(t0[0][e], t0[1][e]), t0[3][e]);
+                y[1][e] = wadd(wsub(t0[1][e], t0[2][e]), t0[4][e]);
+                y[2][e] = wadd(wadd(t1[0][e], t1[1][e]), t1[3][e]);
+                y[3][e] = wadd(wsub(t1[1][e], t1[2][e]), t1[4][e]);
+            }
+        }
+        if constexpr (R < 9) poly_transform_row<(R < 9 ? R + 1 : R)>(da, db, V);
+    };
+    static_for<5>([&](auto hc) {
+        constexpr int R = 2 * decltype(hc)::v;
+        step(IntC<R>{}, Ua);
+        step(IntC<R + 1>{}, Ub);
+    });
+}
+
+// conv4's pair sum.  Wave 2 p + h holds the partial y of K group h; wave 2 p keeps output row dy = 0 of its tiles and hands y[2], y[3] over, wave 2 p + 1 keeps dy = 1 and
+// hands y[0], y[1] over: 2 KB per wave at Poly16::X, behind conv3's output, which other waves still read when a wave writes its slot.  After the barrier every wave forms
+// yo[dx] = (K group 0) + (K group 1) of its row: fixed for every patch and launch, no atomics.  conv4's output (16 plane groups of LayC4) ends in front of X, so the stores
+// that follow need no second barrier against the partner's slot reads.  `lds` = the start of the activation buffer.
+struct Poly16 {                                           // float offsets from the start of the activation buffer
+    static constexpr int X = 8 * LayC3::PSG, X_FLOATS = 8 * 2 * 256;
+};
+__device__ __forceinline__ void poly16_combine(float* lds, const f32x4 (&y)[4], f32x4 (&yo)[2], int wave, int lane) {
+    const int h = wave & 1;
+    float* xw = lds + Poly16::X + (wave * 2 * 64 + lane) * 4;
+    const float* xr = lds + Poly16::X + ((wave ^ 1) * 2 * 64 + lane) * 4;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) *reinterpret_cast<f32x4*>(&xw[k * 256]) = h == 0 ? y[2 + k] : y[k];
+    __syncthreads();                                      // the partner's half is in place; every wave has finished reading conv3's output
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const f32x4 o = *reinterpret_cast<const f32x4*>(&xr[k * 256]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) yo[k][e] = h == 0 ? wadd(y[k][e], o[e]) : wadd(o[e], y[2 + k][e]);
+    }
+}

@@ -199,6 +199,10 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
     ori_head_reduce<TM>(w, pbase, part, act, wave, lane);
 }
 
+// The one exact OriNet instantiation runs conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly16_mfma_rows).  A constant of the build, no run-time switch: the fused
+// and the staged path both run this kernel and are pinned to each other bit for bit.
+constexpr bool ORINET_POLY16 = true;
+
 #define CNN_STAMP(k)                                                                                     \
     do {                                                                                                 \
         if (STAMPS && a.dbg_time && lane == 0) a.dbg_time[((size_t)pidx * NW + wave) * 32 + (k)] = __builtin_readcyclecounter(); \
@@ -258,7 +262,7 @@ struct SplitLays {
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
 // 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides,
-// 4 = HardNet as 1 with conv3 as Winograd F(4x4, 3x3) (descriptor form 2).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// 4 = HardNet as 1 with conv3 as Winograd F(4x4, 3x3) (descriptor form 2), 5 = AffNet as 1 with conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (shape form 2).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
 // kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 and conv3 in F(4x4, 3x3) in form 2), exact AffNet / OriNet, split HardNet,
 // split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
@@ -269,12 +273,13 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET) || (S3 == 4 && KIND == AFFNET_NET_HARDNET),
+    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET) || (S3 == 4 && KIND == AFFNET_NET_HARDNET) || (S3 == 5 && KIND == AFFNET_NET_AFFNET),
                   "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5, exact HardNet with polyphase conv2 / conv4; "
-                  "4 = exact HardNet as 1 with conv3 as Winograd F(4x4, 3x3)");
-    constexpr bool EXACT = S3 <= 1 || S3 == 4;                                // fp32 operands on v_mfma_f32_16x16x4_f32
-    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || (S3 == 1 && KIND == AFFNET_NET_AFFNET);   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
+                  "4 = exact HardNet as 1 with conv3 as Winograd F(4x4, 3x3); 5 = exact AffNet as 1 with polyphase conv2 / conv4");
+    constexpr bool EXACT = S3 <= 1 || S3 == 4 || S3 == 5;                     // fp32 operands on v_mfma_f32_16x16x4_f32
+    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || ((S3 == 1 || S3 == 5) && KIND == AFFNET_NET_AFFNET);   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
     constexpr bool WINO5 = WINO13;                                            // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
+    constexpr bool POLY16 = (S3 == 0 && KIND == AFFNET_NET_ORINET && ORINET_POLY16) || (S3 == 5 && KIND == AFFNET_NET_AFFNET);   // 16-channel trunks: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) on 128 registers
     constexpr bool POLY = (S3 == 1 || S3 == 4) && KIND == AFFNET_NET_HARDNET; // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
     constexpr bool F43_1 = false;                                             // HardNet descriptor form 2, one flag per layer: conv1 as Winograd F(4x4, 3x3) - not built (NOTES.md)
     constexpr bool F43_3 = S3 == 4 && KIND == AFFNET_NET_HARDNET;             // ... conv3 as Winograd F(4x4, 3x3), V shared through LDS
@@ -550,8 +555,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 / conv5 as
         // OriNet runs them.  AffNet's output decides the shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST
         // bits of A for near-isotropic shapes, so another rounding alone changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline
-        // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0, conv2, conv4 (and the S3 = 0 kernel's conv5) in
-        // the direct form for both; conv5 straight into the heads (AffNet from the direct form's accumulators or, S3 = 1, from the Winograd fragments; OriNet from its Winograd fragments through an LDS copy).
+        // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0 (and the S3 = 0 kernel's conv5) in the direct form; conv2 / conv4
+        // (stride 2) direct as well, or - POLY16: the exact OriNet kernel and AffNet's S3 = 5 - as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly16_mfma_rows; U behind the
+        // Winograd sections of a.wino_u); conv5 straight into the heads (AffNet from the direct form's accumulators or, S3 = 1, from the Winograd fragments; OriNet from its Winograd fragments through an LDS copy).
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         static_assert(NW == 8 && CB == 16, "Wino16 describes the 16-channel trunks on 8 waves");
         constexpr int NB1 = Wino16::NB1, NB3 = Wino16::NB3;
@@ -561,6 +567,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         f32x4 bias1[T1N];                                             // the direct form's conv1 / conv3 (!WINO13): conv1's bias, conv3's first weight chunk and bias
         f32x4 b3[S::G3][T2N];
         f32x4 bias3[T2N];
+        f32x4 Upa[3], Upb[3];                                         // POLY16: the two rolling U register sets of conv2 / conv4
+        static_assert(!POLY16 || WINO13, "the polyphase stride-2 layers sit between the Winograd stride-1 layers");
         // ---- conv0: 1 -> CB, K = 9 (padded to 12), MFMA; reads `patch`, writes `act`: no barrier in between ----
         {
             f32x4 acc[T1M][T1N];
@@ -581,8 +589,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             f32x4 y[NB1][4], bw[NB1];
             conv3x3_wino_mfma_rows<NW, CB, CB, LayC0, NB1>(act, a.wino_u, Ur, y, wave, lane);
             CNN_STAMP(3);
-            prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
-            prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            if constexpr (POLY16) poly16_prefetch_u<CB, 2 * CB>(a.wino_u + Wino16::offset(2), Upa, Upb, wave & 1, 0, lane);
+            else {
+                prefetch_b0<NW, 2 * CB, 16, T2M, T2N, S::G2>(a.packed + a.off.w[2], b2, wave, lane);
+                prefetch_bias<NW, 16, T2M, T2N>(a.packed + a.off.b[2], bias2, wave, lane);
+            }
             wino_bias<NW, 32, CB, NB1>(a.packed + a.off.b[1], bw, wave, lane);
             __syncthreads();
             CNN_STAMP(21);
@@ -607,8 +618,22 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 1) { dump_planes<CB, LayC1, NTHR>(act, a.dbg_out); return; }
 
-        // ---- conv2: CB -> 2CB, stride 2 @16x16 -----------------------------------------------------------
-        {
+        // ---- conv2: CB -> 2CB, stride 2 @16x16; POLY16: polyphase, one (tile block, channel block) unit per wave --------
+        if constexpr (POLY16) {
+            f32x4 y[1][4], bw[1];
+            int ty, tx, cb;
+            wino_tile<16, 2 * CB, 1>(wave, 0, lane & 15, ty, tx, cb);
+            static_assert((16 / 2) * (16 / 2) / 16 * (2 * CB / 16) == NW, "conv2: one unit per wave");
+            conv3x3_poly16_mfma_rows<CB, 2 * CB, LayC1>(act, a.wino_u + Wino16::offset(2), Upa, Upb, y[0], ty, tx, cb, 0, lane);
+            CNN_STAMP(5);
+            wino_prefetch_u_row<NW, 2 * CB, 2 * CB, 16, NB3>(a.wino_u + Wino16::offset(3), Ur, wave, lane);
+            wino_bias<NW, 16, 2 * CB, 1>(a.packed + a.off.b[2], bw, wave, lane);
+            __syncthreads();
+            zero_halo<LayC2, NTHR>(act, 2 * CB);
+            wino_store_lds<2 * CB, LayC2, 1>(act, bw, y, wave, lane);
+            __syncthreads();
+            CNN_STAMP(6);
+        } else {
             f32x4 acc[T2M][T2N];
             conv3x3_mfma<NW, CB, 2 * CB, LayC1, 2, T2M, T2N, S::G2>(act, a.packed + a.off.w[2], b2, acc, wave, lane);
             CNN_STAMP(5);
@@ -630,8 +655,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             f32x4 y[NB3][4], bw[NB3];
             conv3x3_wino_mfma_rows<NW, 2 * CB, 2 * CB, LayC2, NB3>(act, a.wino_u + Wino16::offset(3), Ur, y, wave, lane);
             CNN_STAMP(7);
-            prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
-            prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            if constexpr (POLY16) poly16_prefetch_u<2 * CB, 4 * CB>(a.wino_u + Wino16::offset(4), Upa, Upb, wave >> 1, wave & 1, lane);
+            else {
+                prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G4>(a.packed + a.off.w[4], b4, wave, lane);
+                prefetch_bias<NW, 8, T4M, T4N>(a.packed + a.off.b[4], bias4, wave, lane);
+            }
             wino_bias<NW, 16, 2 * CB, NB3>(a.packed + a.off.b[3], bw, wave, lane);
             __syncthreads();
             zero_halo<LayC3, NTHR>(act, 2 * CB);
@@ -655,7 +683,22 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // ---- conv4: 2CB -> 4CB, stride 2 @8x8 --------------------------------------------------------------
         f32x4 b5[S::G5][T4N];
         f32x4 bias5[T4N];
-        {
+        if constexpr (POLY16) {
+            // POLY16: polyphase; wave 2 p + h runs channel block p on K group h, the pair adds its partial y through LDS (cnn_mfma.h: poly16_combine); stamp 9 sits behind the exchange
+            static_assert(Poly16::X >= (2 * CB / 4) * LayC3::PSG && Poly16::X + Poly16::X_FLOATS <= TrunkLds<CB>::TOTAL && (4 * CB / 4) * LayC4::PSG <= Poly16::X,
+                          "polyphase conv4: the exchange lies behind conv3's output inside the LDS array, and conv4's output in front of the exchange");
+            f32x4 y[4], yo[2];
+            conv3x3_poly16_mfma_rows<2 * CB, 4 * CB, LayC3>(act, a.wino_u + Wino16::offset(4), Upa, Upb, y, (lane & 15) >> 2, lane & 3, wave >> 1, wave & 1, lane);
+            CNN_STAMP(24);
+            wino5_prefetch_u(a.wino_u + Wino16::offset(5), Ur, wave, lane);
+            const f32x4 bw = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[4] + (wave >> 1) * 16 + 4 * (lane >> 4)]);
+            poly16_combine(lds, y, yo, wave, lane);
+            CNN_STAMP(9);
+            zero_halo<LayC4, NTHR>(act, 4 * CB);
+            wino5_store_lds<LayC4::WP, 4, LayC4::PSG>(act + (LayC4::WP + 1) * 4, bw, yo, wave, lane);
+            __syncthreads();
+            CNN_STAMP(10);
+        } else {
             f32x4 acc[T4M][T4N];
             conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
             CNN_STAMP(9);

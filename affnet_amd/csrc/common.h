@@ -111,7 +111,7 @@ struct affnet_ctx {
     int prof_calls = 0;
     // tuning aid (include/affnet_hip_debug.h): s_memtime stamp buffer of THIS context's CNN launches, or NULL
     unsigned long long* dbg_time = nullptr;
-    int shape_form = AFFNET_SHAPE_FORM_WINOGRAD;   // fused exact-fp32 shape pass (affnet_set_shape_form): Winograd trunk + direct re-evaluation of the margin rule's rows, or direct only
+    int shape_form = AFFNET_SHAPE_FORM_WINOGRAD;   // fused exact-fp32 shape pass (affnet_set_shape_form): Winograd trunk (form 2, selectable: with polyphase conv2 / conv4) + direct re-evaluation of the margin rule's rows, or direct only
     int arith = AFFNET_ARITH_FP32_MFMA;   // arithmetic of the CNN contractions (cfg.arith / affnet_set_arith): exact fp32 MFMA or fp32 = 3 x bf16 split operands
     int split3_variant = 0;            // tuning aid (affnet_debug_split3_variant): bit 0 = alternating wave priorities in the split HardNet loops (round 3's
                                        // tile-major loops gained 2.5 % from it, the term-major loops of round 4 lose 1 %: off)
@@ -267,11 +267,18 @@ __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, i
 // Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
 // BN-folded fp32 taps into a buffer the context owns, one region per net kind.
 struct Wino16 {
-    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, U5 = 16 * 64 * 64, FLOATS = U1 + U3 + U5;   // floats per net
+    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, U5 = 16 * 64 * 64;
     static constexpr int PAIRS = 16 * 16 + 32 * 32 + 64 * 64;                        // (cin, cout) pairs of the three layers
+    // ... and behind them the 25 polyphase positions (weights_layout.h: poly_weight_transform) of the stride-2 layers conv2 16 -> 32 and conv4 32 -> 64 (51 KB + 205 KB), for
+    // AffNet's shape form 2 and the exact OriNet trunk; appended, so that the Winograd sections stay where they were
+    static constexpr int P2 = 25 * 16 * 32, P4 = 25 * 32 * 64;
+    static constexpr int PAIRS_POLY = 16 * 32 + 32 * 64;
+    static constexpr int FLOATS = U1 + U3 + U5 + P2 + P4;                            // floats per net
     static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
-    static constexpr int offset(int layer) { return layer == 1 ? 0 : (layer == 3 ? U1 : U1 + U3); }
-    static constexpr int floats(int layer) { return layer == 1 ? U1 : (layer == 3 ? U3 : U5); }
+    static constexpr int offset(int layer) {
+        return layer == 1 ? 0 : (layer == 3 ? U1 : (layer == 5 ? U1 + U3 : (layer == 2 ? U1 + U3 + U5 : U1 + U3 + U5 + P2)));
+    }
+    static constexpr int floats(int layer) { return layer == 1 ? U1 : (layer == 3 ? U3 : (layer == 5 ? U5 : (layer == 2 ? P2 : P4))); }
 };
 
 struct ShapeFuse {           // finish + shape filter in one kernel (pointers of image 0; strides like shape_filter_kernel)
@@ -293,7 +300,7 @@ struct CnnCall {
     const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
     const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
     int desc_form = AFFNET_DESC_FORM_DIRECT;                         // HardNet, exact fp32: AFFNET_DESC_FORM_* - 1: conv2 / conv4 as polyphase Winograd F(2x2, 2x2), 2: conv3 as F(4x4, 3x3) besides
-    bool wino_reeval = false;                                        // AffNet, exact fp32, fused filter: Winograd trunk, margin rule, direct trunk on the flagged rows (shape form 1)
+    int wino_reeval = 0;                                             // AffNet, exact fp32, fused filter: 1 / 2 = Winograd trunk of that shape form, margin rule, direct trunk on the flagged rows; 0 = direct only
     float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
 };
 
@@ -359,6 +366,8 @@ TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
 TrunkKernel aff_trunk_affnet_wino(bool stamps);          // exact fp32 with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3): the first trunk of shape form 1
 TrunkKernel aff_trunk_orinet(int arith_index, bool stamps);
 TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
+// cnn_trunk_affnet_poly.hip: the Winograd AffNet trunk with conv2 / conv4 as polyphase Winograd F(2x2, 2x2): the first trunk of shape form 2 [phase stamps]
+TrunkKernel aff_trunk_affnet_poly(bool stamps);
 // cnn_trunk_hardnet_poly.hip: the exact HardNet trunk with conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (descriptor form 1) [phase stamps], and the same pair as above
 // for the polyphase weights of conv2 / conv4 of a HardNet blob
 TrunkKernel aff_trunk_hardnet_poly(bool stamps);

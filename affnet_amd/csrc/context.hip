@@ -228,7 +228,7 @@ extern "C" int affnet_get_arith(const affnet_ctx* ctx) { return ctx ? ctx->arith
 
 extern "C" int affnet_set_shape_form(affnet_ctx* ctx, int form) {
     if (!ctx) return AFFNET_ERR_INVALID;
-    if (form != AFFNET_SHAPE_FORM_DIRECT && form != AFFNET_SHAPE_FORM_WINOGRAD) return aff_fail(ctx, AFFNET_ERR_INVALID, "shape form=%d (AFFNET_SHAPE_FORM_*)", form);
+    if (form != AFFNET_SHAPE_FORM_DIRECT && form != AFFNET_SHAPE_FORM_WINOGRAD && form != AFFNET_SHAPE_FORM_POLYPHASE) return aff_fail(ctx, AFFNET_ERR_INVALID, "shape form=%d (AFFNET_SHAPE_FORM_*)", form);
     ctx->shape_form = form;
     return AFFNET_OK;
 }

@@ -82,7 +82,8 @@ extern "C" int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3])
 
 // The Winograd AffNet trunk (the first trunk of shape form 1) on a patch tensor, which no entry point of the product library runs: U derived in front of the launch
 // as cnn32.hip's trunk_launch does; the stamped instantiation when a layer dump is asked for or the context has a stamp buffer (affnet_cnn32_debug_timing).
-static int probe_affnet_wino(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, int layer, hipStream_t st) {
+// poly: the first trunk of shape form 2 (conv2 / conv4 polyphase) instead.
+static int probe_affnet_wino(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, int layer, hipStream_t st, bool poly = false) {
     if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino: AFFNET_ARITH_FP32_MFMA only");
     const NetLayout L = net_layout(AFFNET_NET_AFFNET);
     CnnArgs a;
@@ -93,7 +94,7 @@ static int probe_affnet_wino(affnet_ctx* ctx, const float* d_packed, const float
     a.patches = d_patches; a.n_max = n; a.out = d_out; a.dbg_layer = layer; a.dbg_out = d_out; a.dbg_time = ctx->dbg_time;
     PyrSrc ps;
     memset(&ps, 0, sizeof(ps));                          // patch tensors: nothing is sampled
-    hipLaunchKernelGGL(aff_trunk_affnet_wino(layer >= 0 || a.dbg_time), dim3(n, 1), dim3(512), 0, st, a, ps);
+    hipLaunchKernelGGL(poly ? aff_trunk_affnet_poly(layer >= 0 || a.dbg_time) : aff_trunk_affnet_wino(layer >= 0 || a.dbg_time), dim3(n, 1), dim3(512), 0, st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -109,6 +110,29 @@ extern "C" int affnet_probe_affnet_wino_partials(affnet_ctx* ctx, const float* d
     AFF_DEVICE(ctx);
     if (!ctx || !d_packed || !d_patches || !d_partials || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino_partials: bad argument");
     return probe_affnet_wino(ctx, d_packed, d_patches, n, d_partials, -1, (hipStream_t)stream);
+}
+
+extern "C" int affnet_probe_affnet_poly_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patch || !d_out || net_kind != AFFNET_NET_AFFNET || layer < 0 || layer > 5)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_poly_layer: AffNet, layer 0 .. 5");
+    return probe_affnet_wino(ctx, d_packed, d_patch, 1, d_out, layer, (hipStream_t)stream, true);
+}
+
+extern "C" int affnet_probe_affnet_poly_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patches || !d_partials || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_poly_partials: bad argument");
+    return probe_affnet_wino(ctx, d_packed, d_patches, n, d_partials, -1, (hipStream_t)stream, true);
+}
+
+extern "C" int affnet_probe_trunk16_poly_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 2 && layer != 4))
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_trunk16_poly_u: AffNet / OriNet, layer 2 or 4");
+    const float* u;
+    const int rc = aff_wino_derive_u(ctx, net_kind, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
+    if (rc) return rc;
+    return aff_copy_async(ctx, d_out, u + Wino16::offset(layer), (size_t)Wino16::floats(layer) * sizeof(float), (hipStream_t)stream);
 }
 
 extern "C" int affnet_probe_hardnet_poly_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {

@@ -68,7 +68,7 @@ class Context(object):
 
     def set_shape_form(self, form):
         """Form of the fused exact-fp32 AffNet shape pass (affnet_set_shape_form): 0 = every candidate by the direct kernel, 1 = Winograd trunk with
-        direct re-evaluation of the rows the margin rule flags (default).  Read when a call is enqueued; a captured graph keeps its form."""
+        direct re-evaluation of the rows the margin rule flags (default), 2 = form 1 with conv2 / conv4 of that trunk as polyphase Winograd.  Read when a call is enqueued; a captured graph keeps its form."""
         check(lib.affnet_set_shape_form(self.handle, int(form)), self.handle, "affnet_set_shape_form")
         self.shape_form = int(form)
 

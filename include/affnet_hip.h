@@ -178,10 +178,15 @@ int affnet_get_arith(const affnet_ctx* ctx);
  *                                candidates whose shape-filter decision could turn on the last bits of A (about 2 %), and the direct-form trunk
  *                                recomputes exactly those, so every decision - counts, ids, responses - is the direct form's.  A of an unflagged
  *                                row differs from the direct form's by at most 4e-6 per head output.
+ *   AFFNET_SHAPE_FORM_POLYPHASE: form 1 with the stride-2 layers conv2 / conv4 of that first trunk as polyphase Winograd F(2x2, 2x2) (25 instead of 36
+ *                                products per 2x2 output tile, no constant but 1); the same margin rule, thresholds and re-evaluation, so every decision is
+ *                                again the direct form's and A of an unflagged row stays within the same 4e-6.  Not the default: its rounding of A moves one
+ *                                LAF row of the 1024 x 768 golden comparison past 1e-3 px.
  * Read when a call is enqueued; a graph captured earlier keeps the form it was captured with.  The number of re-evaluated candidates per image
  * is counter 4 of affnet_counter_offset. */
 #define AFFNET_SHAPE_FORM_DIRECT 0
 #define AFFNET_SHAPE_FORM_WINOGRAD 1
+#define AFFNET_SHAPE_FORM_POLYPHASE 2
 int affnet_set_shape_form(affnet_ctx* ctx, int form);
 int affnet_get_shape_form(const affnet_ctx* ctx);
 

@@ -43,7 +43,7 @@ int affnet_split3_rate(int reps, int terms, int n_blocks, float* d_out, void* st
 
 /* Read-back of the fused AffNet shape pass (affnet_set_shape_form) for the tests: where a bound context keeps, after affnet_describe_detected, the shape
  * matrices A of all candidates ([image][capacity_prefilter][4] floats) and the per-candidate flags of the margin rule ([image][capacity_prefilter] int32,
- * written for the candidates AffNet was evaluated on; form AFFNET_SHAPE_FORM_WINOGRAD only; the orientation and descriptor stages reuse that scratch, so
+ * written for the candidates AffNet was evaluated on; forms AFFNET_SHAPE_FORM_WINOGRAD and _POLYPHASE only; the orientation and descriptor stages reuse that scratch, so
  * read them after a call with do_ori = 0 and no descriptors), and the candidates' normalised frames as the detector half
  * left them ([image][capacity_prefilter][6] floats; a test plants a non-finite frame there, which affnet_load_frames would refuse).  out[0] / out[1] / out[2]:
  * offsets from the workspace base, in 4-byte units.  Host only; the context may come from libaffnet_hip.so of the same build. */
@@ -58,6 +58,13 @@ int affnet_probe_affnet_wino_layer(affnet_ctx* ctx, int net_kind, const float* d
 /* The same trunk on n <= 65535 patches (n, 32, 32), for tools/cnn_phase_timing.py: leaves the head partials ([patch][8 waves][4] floats) in d_partials, no finish
  * kernel; writes the phase stamps when the context has a stamp buffer (affnet_cnn32_debug_timing). */
 int affnet_probe_affnet_wino_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream);
+
+/* The same two for the first trunk of shape form AFFNET_SHAPE_FORM_POLYPHASE (the Winograd AffNet trunk with conv2 / conv4 as polyphase Winograd F(2x2, 2x2)), and
+ * _u: the derived polyphase weights of layer 2 (25 x 16 x 32 floats) or 4 (25 x 32 x 64) of an AffNet or OriNet blob, in the order the kernels read them (the exact
+ * OriNet trunk, which affnet_cnn32_forward / affnet_cnn32_debug_layer run, reads the same sections of its own blob). */
+int affnet_probe_affnet_poly_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+int affnet_probe_affnet_poly_partials(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_partials, void* stream);
+int affnet_probe_trunk16_poly_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream);
 
 /* The exact HardNet trunk of descriptor form AFFNET_DESC_FORM_POLYPHASE (conv2 / conv4 as polyphase Winograd F(2x2, 2x2)) on patch tensors, which no entry point of
  * the product library runs (affnet_cnn32_forward always answers with form 0).  The context must be in AFFNET_ARITH_FP32_MFMA; it may come from libaffnet_hip.so of

@@ -23,13 +23,17 @@ only = os.environ.get("PHASE_NETS")                    # e.g. PHASE_NETS=OriNet:
 
 class AffNetForm1:
     """AffNet's Winograd trunk (conv1 / conv3 / conv5 as F(2x2, 3x3)), which the fused shape pass runs on every candidate in shape form 1: the trunk launch alone
-    (head partials, no finish kernel) through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)"""
+    (head partials, no finish kernel) through the probe library (AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so).  probe = affnet_probe_affnet_poly_partials: the
+    trunk of shape form 2 instead (conv2 / conv4 as polyphase Winograd F(2x2, 2x2) besides)"""
+    def __init__(self, probe="affnet_probe_affnet_wino_partials"):
+        self.probe = getattr(lib, probe)
+
     def __call__(self, x):
         part = torch.empty(x.shape[0] * 32, device=dev)
         packed = A.packed_weights(dev)
         for i in range(0, x.shape[0], 65535):
             m = min(65535, x.shape[0] - i)
-            rc = lib.affnet_probe_affnet_wino_partials(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(part[i * 32:]), None)
+            rc = self.probe(engine.utility_ctx(dev), ptr(packed), ptr(x[i:i + m]), m, ptr(part[i * 32:]), None)
             assert rc == 0, rc
         return part
 
@@ -61,6 +65,8 @@ else:
     print("(no table of HardNet's polyphase trunk: this library has no affnet_probe_hardnet_poly_forward - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 if hasattr(lib, "affnet_probe_affnet_wino_partials"):
     nets.insert(1, (AffNetForm1(), "AffNet form 1", 8))
+    if hasattr(lib, "affnet_probe_affnet_poly_partials"):
+        nets.insert(2, (AffNetForm1("affnet_probe_affnet_poly_partials"), "AffNet form 2", 8))
 else:
     print("(no table of AffNet's Winograd trunk: this library has no affnet_probe_affnet_wino_partials - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 for net, nm, nw in nets:
@@ -124,6 +130,9 @@ for net, nm, nw in nets:
     if nm == "HardNet form 2":        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
         ds = np.diff(t[:, :, [6, 23, 7]], axis=2).mean(axis=(0, 1))
         print("  conv3 F(4x4, 3x3): transform + V through LDS + loop + fold along x %.0f | barrier + exchange of the halves %.0f" % tuple(ds))
+    if nm in ("AffNet form 2", "OriNet") and t[:, :, 24].min() > 0:        # polyphase conv4: "conv4 mfma" = stamp 8 -> 9 spans the loop and the pair's exchange
+        ds = np.diff(t[:, :, [8, 24, 9]], axis=2).mean(axis=(0, 1))
+        print("  conv4 polyphase: loop %.0f | exchange of the K groups' partial y (one barrier) %.0f" % tuple(ds))
     print("  CUs seen %d; mean resident WGs per CU %.2f; median end->next-start gap %.0f ticks (p90 %.0f)" %
           (len(util), np.mean(util), np.median(gaps), np.percentile(gaps, 90)))
     # wall time of the same launch without stamps
@@ -133,5 +142,5 @@ for net, nm, nw in nets:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "AffNet form 2": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

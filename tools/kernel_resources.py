@@ -111,6 +111,7 @@ DESIGN_KERNELS = [
     ("cnn32_trunk_kernel<2, 8, false, 2>", "HardNet trunk, arith fp32_split2h"),
     ("cnn32_trunk_kernel<0, 8, false, 0>", "AffNet trunk, exact fp32 MFMA"),
     ("cnn32_trunk_kernel<0, 8, false, 1>", "AffNet trunk, exact fp32 MFMA, Winograd conv1 / conv3 / conv5 (shape form 1)"),
+    ("cnn32_trunk_kernel<0, 8, false, 5>", "AffNet trunk, exact fp32 MFMA, form 1 with polyphase Winograd conv2 / conv4 (shape form 2)"),
     ("cnn32_trunk_kernel<0, 8, false, 3>", "AffNet trunk, arith fp32_split3"),
     ("cnn32_trunk_kernel<0, 8, false, 2>", "AffNet trunk, arith fp32_split2h"),
     ("cnn32_trunk_kernel<1, 8, false, 0>", "OriNet trunk, exact fp32 MFMA"),

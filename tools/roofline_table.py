@@ -5,7 +5,9 @@
                                                              that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's;
                                                              so is AffNet's Winograd trunk of shape form 1, <0, 8, false, 1> (WINO_AFFNET), and HardNet's trunk of descriptor form 1,
                                                              <2, 8, false, 1>, whose conv2 / conv4 run as polyphase Winograd F(2x2, 2x2) besides (POLY_HARDNET), and of descriptor form 2, <2, 8, false, 4>,
-                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET)
+                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET); AffNet's trunk of shape form 2, <0, 8, false, 5>, whose
+                                                             conv2 / conv4 run as polyphase Winograd besides (POLY_AFFNET), and - in evidence of a build that has that kernel - the
+                                                             exact OriNet trunk, which runs the same five forms (POLY_ORINET)
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
 FETCH_SIZE / WRITE_SIZE passes scaled by the calibration measured for the kernel's access width (tools/fetch_calib.py), the
 resulting GB/s and its fraction of 8 TB/s; for the CNN kernels the algorithmic FLOP rate against the 157.3 TFLOP/s fp32 MFMA peak.
@@ -33,6 +35,10 @@ F43_HARDNET = POLY_HARDNET - NKP * 18874368.0 * (16.0 / 36.0 - 9.0 / 36.0)
 # AffNet's Winograd trunk (shape form 1): conv1 / conv3 / conv5 are 4718592 direct FLOPs per patch each and execute 16 / 36 of them.  conv1 .. conv5 together:
 # 11.0 M executed MFMA FLOPs per patch (13.6 M while conv5 was direct: 288 instead of 128 MFMAs per wave), against OriNet's 11.0 M; conv0 and the head as in the direct form
 WINO_AFFNET = 19193856.0 - 3 * 4718592.0 * (1.0 - 16.0 / 36.0)
+# Shape form 2, <0, 8, false, 5>: conv2 / conv4 (stride 2; 2359296 direct FLOPs per patch each) as polyphase Winograd F(2x2, 2x2) execute 25 / 36 of them besides (100 instead
+# of 144 MFMAs per wave and layer): 9.6 instead of 11.0 M executed MFMA FLOPs per patch over conv1 .. conv5.  The exact OriNet trunk of such a build runs the same five forms
+POLY_AFFNET = WINO_AFFNET - 2 * 2359296.0 * (1.0 - 25.0 / 36.0)
+POLY_ORINET = 19316736.0 - 3 * 4718592.0 * (1.0 - 16.0 / 36.0) - 2 * 2359296.0 * (1.0 - 25.0 / 36.0)
 
 
 def octave_pixels(h, w, border=5):
@@ -100,9 +106,13 @@ def main(prefix, winograd=False):
             elif key in name:
                 if winograd and key == "cnn32_trunk_kernel<2":
                     fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else WINO_HARDNET)
-                wino_aff = winograd and key == "cnn32_trunk_kernel<0" and name.rstrip().endswith(", 1>")
-                if wino_aff:
-                    fl = fl / 19193856.0 * WINO_AFFNET
+                poly16_build = any("cnn32_trunk_kernel<0, 8, false, 5>" in k for k in stats)
+                wino_aff = winograd and ((key == "cnn32_trunk_kernel<0" and (name.rstrip().endswith(", 1>") or name.rstrip().endswith(", 5>"))) or
+                                         (key == "cnn32_trunk_kernel<1" and poly16_build))
+                if wino_aff and key == "cnn32_trunk_kernel<1":
+                    fl = fl / 19316736.0 * POLY_ORINET
+                elif wino_aff:
+                    fl = fl / 19193856.0 * (POLY_AFFNET if name.rstrip().endswith(", 5>") else WINO_AFFNET)
                 tf = fl * IMGS / (per_call * avg_ns * 1e-9) / 1e12            # all launches of the kernel in one 32-image call
                 algs = "%.1f TFLOP/s = %.1f %% of 157.3" % (tf, 100 * tf / 157.3)
                 if (winograd and key == "cnn32_trunk_kernel<2") or wino_aff:

@@ -160,6 +160,30 @@ def poly_packed_weight_transform(sd, layers=(2, 4)):
 POLY_LAYERS = (2, 4)             # HardNet's stride-2 layers
 
 
+# ---- the same form in the 16-channel trunks (AffNet shape form 2, exact OriNet; cnn_mfma.h: conv3x3_poly16_mfma_rows, poly16_combine) -------------------------
+# conv2 (16 -> 32 @32x32 -> 16x16) has ONE K group of 16 input channels: a wave runs the ten position rows of its (tile block, channel block) unit and folds them as
+# poly_conv3x3_s2 does.  conv4 (32 -> 64 @16x16 -> 8x8) has two K groups and a wave pair per channel block: each wave runs the ten position rows over ITS 16 input
+# channels and folds them into a partial y, and the pair adds the partial y in the order K group 0 + K group 1.
+def poly16_conv2(x, w):
+    assert x.shape[1] == 16
+    return poly_conv3x3_s2(x, w)
+
+
+def poly16_conv4(x, w):
+    assert x.shape[1] == 32
+    return poly_conv3x3_s2(x[:, :16], w[:, :16]) + poly_conv3x3_s2(x[:, 16:], w[:, 16:])
+
+
+def poly16_conv(li, x, w):
+    return poly16_conv2(x, w) if li == 2 else poly16_conv4(x, w)
+
+
+def poly16_packed_weight_transform(sd, layers=(2, 4)):
+    """{layer: U} of the stride-2 layers of an AffNet / OriNet state dict as wino_derive_u_kernel leaves them behind the Winograd sections (Wino16::offset(2 / 4)):
+    the layout of poly_packed_weight_transform, 25 x 16 x 32 and 25 x 32 x 64 floats"""
+    return poly_packed_weight_transform(sd, layers)
+
+
 # ---- Winograd F(4x4, 3x3), points 0, +-1, +-2 (HardNet form 2: conv3; cnn_mfma.h: conv3x3_f43_mfma_shared_v + f43_combine) ---------------------------
 # Per axis, one rounding per operation, in the kernel's order (cnn_mfma.h: f43_bt_lo / f43_bt_hi / f43_at_axis, weights_layout.h: f43_g_axis):
 #     U = G g:    s = g0 + g2;  p = (1/24) g0 + (1/6) g2;  q = (1/12) g1:   (0.25 g0, (-1/6)(s + g1), (-1/6)(s - g1), p + q, p - q, g2)
@@ -288,12 +312,16 @@ def hardnet_forward(sd, patches, wino=True, dtype=torch.float32, poly=False, f43
     return y / torch.sqrt(torch.sum(y * y, dim=1) + 1e-8).unsqueeze(-1)
 
 
-def trunk16_layers(sd, patches, layers=WINO_LAYERS_16, dtype=torch.float32):
-    """The six post-ReLU trunk tensors of AffNet / OriNet in `dtype`, the layers in `layers` as Winograd (() = all direct)"""
+def trunk16_layers(sd, patches, layers=WINO_LAYERS_16, dtype=torch.float32, poly=()):
+    """The six post-ReLU trunk tensors of AffNet / OriNet in `dtype`, the layers in `layers` as Winograd (() = all direct), those in `poly` (of 2, 4) as polyphase
+    F(2x2, 2x2) in the 16-channel kernels' order (AffNet shape form 2 and the exact OriNet trunk: POLY_LAYERS)"""
     x = orc.input_norm(patches.to(dtype))
     outs = []
     for li, (w, b, st) in enumerate(folded(sd, dtype)):
-        y = wino_conv3x3(x, w) if li in layers else F.conv2d(x, w, None, stride=st, padding=1)
+        if li in poly:
+            y = poly16_conv(li, x, w)
+        else:
+            y = wino_conv3x3(x, w) if li in layers else F.conv2d(x, w, None, stride=st, padding=1)
         x = F.relu(y + b.view(1, -1, 1, 1))
         outs.append(x)
     return outs
@@ -306,13 +334,13 @@ def head16(sd, y, net, dtype=torch.float32):
 
 
 def errors16(sd, patches, net, layers=WINO_LAYERS_16):
-    """{"direct" | "winograd": {"layers": [6 x max |x - fp64| / max(1, |fp64|max)], "head": max |head - fp64|, "angle": rad (OriNet)}}"""
+    """{"direct" | "winograd" | "polyphase" (Winograd + conv2 / conv4 polyphase): {"layers": [6 x max |x - fp64| / max(1, |fp64|max)], "head": max |head - fp64|, "angle": rad (OriNet)}}"""
     with torch.no_grad():
         ref = trunk16_layers(sd, patches, (), torch.float64)
         href = head16(sd, ref[5], net, torch.float64)
         out = {}
-        for name, ls in (("direct", ()), ("winograd", tuple(layers))):
-            got = trunk16_layers(sd, patches, ls)
+        for name, ls, pl in (("direct", (), ()), ("winograd", tuple(layers), ()), ("polyphase", tuple(layers), POLY_LAYERS)):
+            got = trunk16_layers(sd, patches, ls, poly=pl)
             h = head16(sd, got[5], net)
             rec = {"layers": [float((g.double() - r).abs().max()) / max(1.0, float(r.abs().max())) for g, r in zip(got, ref)],
                    "head": float((h.double() - href).abs().max())}
@@ -360,7 +388,7 @@ def main():
         print("%s, Winograd in layers %s; max abs error vs float64 (layers: relative to max(1, |ref|max))" % (args.net, layers))
         for tag, p in (("golden random", golden), ("%d smooth" % args.n, smooth_patches(args.n, args.seed + 1))):
             e = errors16(sd, p, args.net, layers)
-            for k in ("direct", "winograd"):
+            for k in ("direct", "winograd", "polyphase"):
                 print("%-14s %-9s layers %s  head %.3g%s" % (tag, k, " ".join("%.2g" % v for v in e[k]["layers"]), e[k]["head"],
                                                            "  angle %.3g rad" % e[k]["angle"] if "angle" in e[k] else ""))
         return
