@@ -3,7 +3,7 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
 missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
@@ -11,7 +11,11 @@ missing blob; without a checkpoint the seeded synthetic HardNet is used, whose d
 weights needed; at N = 500 it gives the reference's 79 tentatives / 4 true matches.
 --desc tfeat: HardTFeatNet (HardNet.py:30-59), the reference's `--descriptor TFeat`.  --tfeat-weights: a .pth with a `state_dict` (the
 reference's HardTFeat.pth) or one of the fixtures tests/golden/tfeat_weights_{0,1,2}.npz (the three are read together); default: the
-fixtures.  With the trained weights at N = 500 the reference gives 34 tentatives / 5 true matches."""
+fixtures.  With the trained weights at N = 500 the reference gives 34 tentatives / 5 true matches.
+--verify: matching and geometric verification WITHOUT the ground truth in one device chain (match_and_verify: every tentative's pair of affine
+frames is an affine hypothesis, all scored against all, the best refined as a homography); a second line per run gives the inlier count, how
+many of the inliers the ground-truth homography confirms (the same 6 px centre rule) and how far the recovered H moves the image corners from
+where the file's H puts them."""
 import os
 import sys
 
@@ -22,7 +26,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import affnet_amd  # noqa: E402
-from affnet_amd.ReprojectionStuff import match_snn, get_GT_correspondence_indexes  # noqa: E402
+from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, get_GT_correspondence_indexes  # noqa: E402
 
 
 def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
@@ -45,6 +49,8 @@ def load_tfeat_state(path):
 def main(argv):
     desc_kind = "hardnet"
     tfeat_path = None
+    verify = "--verify" in argv
+    argv = [a for a in argv if a != "--verify"]
     if "--tfeat-weights" in argv:
         i = argv.index("--tfeat-weights")
         if i + 1 >= len(argv):
@@ -83,6 +89,16 @@ def main(argv):
         t1, t2, _, _ = match_snn(r1["descriptors"], r2["descriptors"], 0.8)
         _, plain, _ = get_GT_correspondence_indexes(r1["LAFs"][t1], r2["LAFs"][t2], H1to2, dist_threshold=6)
         print("Test on %s, %d tentatives %d true matches %s  inl.ratio" % (tag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))
+        if verify:
+            v1, v2, H, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0)
+            assert torch.equal(v1, t1) and torch.equal(v2, t2)
+            _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)
+            h, w = img1.shape[2], img1.shape[3]
+            c = torch.tensor([[0.0, 0.0, 1.0], [w, 0.0, 1.0], [w, h, 1.0], [0.0, h, 1.0]], dtype=torch.float64)
+            a, b = c @ H.cpu().T, c @ H1to2.double().T
+            err = ((a[:, :2] / a[:, 2:] - b[:, :2] / b[:, 2:]) ** 2).sum(1).sqrt().max().item()
+            print("Verified on %s, %d inliers of %d tentatives (best hypothesis %d, flags %d), %d of them true matches, corner error vs H1to2 %.1f px"
+                  % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), err))
 
 
 if __name__ == "__main__":

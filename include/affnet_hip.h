@@ -467,6 +467,46 @@ int affnet_reproject_lafs(affnet_ctx* ctx, const float* d_lafs, int n, const flo
 int affnet_centre_nn(affnet_ctx* ctx, const float* d_query_lafs, int nq, const float* d_ref_lafs, int nr, float* d_min_dist,
                      int32_t* d_idx, void* stream);
 
+/* ---- spatial verification of tentative matches from their affine frames ------------------------ */
+
+/* One tentative match of two local affine frames fixes an affine map F2 F1^-1 (spatial matching, Philbin et al. 2007): T tentatives are
+ * T hypotheses, every one is scored against all T matches, the best one is refined by least-squares refits on its inliers.
+ * Deterministic, bounded work, no host synchronisation; all buffers are the caller's.
+ *
+ * Common inputs: d_lafs1 (n1,2,3), d_lafs2 (n2,2,3) pixel frames; d_tent (t_max,2) int32 as affnet_match_snn writes it; d_count one
+ * int32 on the device or NULL (= t_max rows are valid) - rows at or beyond the count are neither read nor written in any output;
+ * inl_th pixels; d_scratch affnet_verify_scratch_bytes(t_max) bytes, 16-byte aligned.
+ *
+ * Scoring (fp32): hypothesis h = tent[h] = (i, j), M = L2 L1^-1 through det L1.  h is invalid - scores 0, is never chosen - when
+ * !(|det| > 1e-12), when one of its twelve numbers is not finite or when an index is outside [0,n1) / [0,n2) (tested before any load).
+ * Match t is an inlier of h when | M (c1_t - c1_h) - (c2_t - c2_h) |^2 <= inl_th^2 and t has valid indices and finite centres.
+ * d_counts (t_max) int32 = inliers per hypothesis (>= 1 for a valid one: it counts itself). */
+#define AFFNET_VERIFY_AFFINE 0
+#define AFFNET_VERIFY_HOMOGRAPHY 1
+#define AFFNET_VERIFY_TILE 128    /* hypotheses per workgroup of the scoring kernel */
+#define AFFNET_VERIFY_CHUNK 128   /* matches per chunk of the scoring kernel        */
+
+/* Host only. */
+size_t affnet_verify_scratch_bytes(int t_max);
+
+/* The scoring stage alone: d_counts, and d_best int32[2] = {smallest h with the largest count, that count}, {-1, 0} when no hypothesis
+ * is valid. */
+int affnet_verify_score(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                        const int32_t* d_count, int t_max, float inl_th, int32_t* d_counts, int32_t* d_best, void* d_scratch,
+                        void* stream);
+
+/* Score + select + local optimisation in fp64: lo_iters (0..8) times { stop with flag 2 below 4 (homography) / 3 (affine) pairs in the
+ * mask; Hartley-normalise the masked pairs; fit (homography: inhomogeneous DLT with h33 = 1, 8 x 8 normal equations; affine: 6
+ * parameters), a pivot below 1e-12 x the largest diagonal entry or coincident points stop with flag 4; denormalise to H[2][2] = 1; new
+ * mask = transfer error | pi(H p1) - p2 |^2 <= inl_th^2 with w > 0 }, keeping the model with the largest mask (ties: the earliest).
+ * Model 0 is the affine hypothesis itself with its fp32 inlier set.
+ * model: AFFNET_VERIFY_AFFINE / _HOMOGRAPHY.  Outputs: d_counts (t_max); d_model double[9] row-major; d_inlier (t_max) uint8;
+ * d_summary int32[4] = {best, counts[best], final inlier count, flags}, flags 1 = no valid hypothesis (best = -1, identity model),
+ * 2 = too few inliers to refit, 4 = degenerate system.  t_max == 0 is valid and gives {-1, 0, 0, 1}. */
+int affnet_verify_matches(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                          const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters, int32_t* d_counts, double* d_model,
+                          uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

@@ -120,6 +120,9 @@ DESIGN_KERNELS = [
     ("hardnet_head_kernel<64>", "HardNet head GEMM (64-patch tiles), exact"),
     ("hardnet_head_s3_kernel<64, 3>", "HardNet head GEMM (64-patch tiles), arith fp32_split3"),
     ("hardnet_head_s3_kernel<64, 2>", "HardNet head GEMM (64-patch tiles), arith fp32_split2h"),
+    ("rowmin_dist_kernel<128>", "SNN matching: MFMA distance tiles with a running row minimum"),
+    ("spv_score_kernel", "spatial verification: T x T scoring of the affine-frame hypotheses"),
+    ("spv_lo_kernel", "spatial verification: fp64 local optimisation, one workgroup"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
     ("blur2d_kernel<13, 4>", "Gaussian blur 13 x 13, 64 x 64 tiles"),
     ("blur2d_pair_kernel<15, 9, 4>", "paired blur 15 x 15 / 9 x 9"),
