@@ -1,6 +1,7 @@
 """Homography reprojection of LAFs and ground-truth correspondences with the reference's names
 (ReprojectionStuff.py:23-40,126-137), plus the SNN matcher of train_AffNet_test_on_graffity.py:292-300 as one call, and the geometric
-verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify)."""
+verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify), and both for many image pairs per device call (pair_table,
+enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank)."""
 import ctypes as C
 
 import numpy as np
@@ -158,3 +159,103 @@ def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8
     host = torch.cat([cnt, summary]).cpu().tolist()          # the one read-back
     k = host[0]
     return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), _verify_info(counts[:k], host[1:])
+
+
+# ---- many image pairs in one device call (csrc/match.hip affnet_match_snn_many, csrc/spatial.hip affnet_verify_matches_many) ---------------------
+
+def pair_table(counts1, counts2, pairs):
+    """Host helper: the (P,4) int32 table {row1, n1, row2, n2} of the *_many calls for `pairs` = [(a, b), ...], image a of side 1 against image b
+    of side 2, where image i of a side owns counts[i] consecutive rows of that side's concatenated buffers.
+    Returns (table, n1_max, n2_max).  ValueError on an image index out of range (or a negative count)."""
+    c1, c2 = [int(c) for c in counts1], [int(c) for c in counts2]
+    if any(c < 0 for c in c1 + c2):
+        raise ValueError("pair_table: negative row count")
+    off1 = np.concatenate([[0], np.cumsum(c1, dtype=np.int64)])
+    off2 = np.concatenate([[0], np.cumsum(c2, dtype=np.int64)])
+    if max(off1[-1], off2[-1]) > 0x7fffffff:
+        raise ValueError("pair_table: more than 2^31 - 1 rows on one side")
+    table = np.zeros((len(pairs), 4), np.int32)
+    for p, (a, b) in enumerate(pairs):
+        a, b = int(a), int(b)
+        if not (0 <= a < len(c1) and 0 <= b < len(c2)):
+            raise ValueError("pair_table: pair %d = (%d, %d) with %d / %d images" % (p, a, b, len(c1), len(c2)))
+        table[p] = (off1[a], c1[a], off2[b], c2[b])
+    return table, int(table[:, 1].max()) if len(pairs) else 0, int(table[:, 3].max()) if len(pairs) else 0
+
+
+def _many_buf(dev, dtype, *shape):
+    """Zero-filled device tensor of `shape` whose storage is never empty (the boundary refuses NULL)."""
+    n = int(np.prod(shape))
+    return torch.zeros(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
+
+
+def enqueue_match_and_verify_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
+    """match_and_verify for P image pairs in one chain of launches on the current stream, no synchronisation.  desc1 (rows1,128) / LAFs1 (rows1,2,3)
+    hold the images of side 1 back to back, counts1[i] rows for image i; side 2 likewise (it may be the same tensors); pairs = [(a, b), ...] image
+    indices into the two sides.  Returns capacity-sized device tensors, cap = the largest n1 of a pair: (tent (P,cap,2) int32 with indices local to
+    the pair's images, count (P,) int32, H (P,3,3) float64, inliers (P,cap) uint8, counts (P,cap) int32, summary (P,4) int32); per pair, rows below
+    count[p] are what match_and_verify gives for that pair, bit for bit, rows at or beyond it are zero."""
+    for t, name in ((desc1, "desc1"), (LAFs1, "LAFs1"), (desc2, "desc2"), (LAFs2, "LAFs2")):
+        engine.require_cuda(t, name)
+    a, b = desc1.contiguous().float(), desc2.contiguous().float()
+    l1, l2 = LAFs1.contiguous().float(), LAFs2.contiguous().float()
+    rows1, rows2, dev = a.size(0), b.size(0), a.device
+    if l1.size(0) != rows1 or l2.size(0) != rows2:
+        raise ValueError("enqueue_match_and_verify_many: one LAF per descriptor row (%d / %d frames for %d / %d descriptors)" % (l1.size(0), l2.size(0), rows1, rows2))
+    if sum(int(c) for c in counts1) != rows1 or sum(int(c) for c in counts2) != rows2:
+        raise ValueError("enqueue_match_and_verify_many: the counts do not add up to the rows of the buffers")
+    table, cap, n2_max = pair_table(counts1, counts2, pairs)
+    P = table.shape[0]
+    tent, cnt = _many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P)
+    H, inl = _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap)
+    counts, summary = _many_buf(dev, torch.int32, P, cap), _many_buf(dev, torch.int32, P, 4)
+    if P == 0:
+        return tent, cnt, H, inl, counts, summary
+    d_pairs = torch.from_numpy(table).to(dev)
+    md, md2, idx = _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.int32, P, cap)
+    scratch = torch.empty(max(lib.affnet_match_many_scratch_bytes(P, cap, n2_max), lib.affnet_verify_many_scratch_bytes(P, cap)), dtype=torch.uint8, device=dev)
+    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty side: never read, but the boundary refuses NULL
+    ctx, st = engine.utility_ctx(dev), engine.stream_of(dev)
+    rc = lib.affnet_match_snn_many(ctx, ptr(a if rows1 else one), rows1, ptr(b if rows2 else one), rows2, a.size(1), ptr(d_pairs), P, cap, n2_max,
+                                   float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt), ptr(scratch), st)
+    check(rc, ctx, "affnet_match_snn_many")
+    rc = lib.affnet_verify_matches_many(ctx, ptr(l1 if rows1 else one), rows1, ptr(l2 if rows2 else one), rows2, ptr(d_pairs), P, ptr(tent), ptr(cnt), cap,
+                                        float(inl_th), _verify_model(model), int(lo_iters), ptr(counts), ptr(H), ptr(inl), ptr(summary), ptr(scratch), st)
+    check(rc, ctx, "affnet_verify_matches_many")
+    return tent, cnt, H, inl, counts, summary
+
+
+def match_and_verify_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
+    """match_and_verify for every pair (a, b) of `pairs`, image indices into the lists descs / LAFs (one (n_i,128) / (n_i,2,3) device tensor per
+    image; both sides of a pair come from the same lists), as one device call chain and ONE read-back.
+    Returns a list of P tuples (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), each what match_and_verify returns for that pair."""
+    if len(descs) != len(LAFs):
+        raise ValueError("match_and_verify_many: one LAF tensor per descriptor tensor")
+    for t in list(descs) + list(LAFs):
+        engine.require_cuda(t, "descs / LAFs")
+    if not len(descs):
+        if len(pairs):
+            raise ValueError("match_and_verify_many: pairs of an empty image list")
+        return []
+    counts = [int(d.size(0)) for d in descs]
+    if any(int(l.size(0)) != c for l, c in zip(LAFs, counts)):
+        raise ValueError("match_and_verify_many: one LAF per descriptor row")
+    D = torch.cat([d.contiguous().float() for d in descs], 0)
+    L = torch.cat([l.contiguous().float().reshape(-1, 2, 3) for l in LAFs], 0)
+    tent, cnt, H, inl, hyp_counts, summary = enqueue_match_and_verify_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model, lo_iters)
+    host = torch.cat([cnt.view(-1, 1), summary], 1).cpu().tolist()          # the one read-back
+    out = []
+    for p, row in enumerate(host):
+        k = row[0]
+        out.append((tent[p, :k, 0].long(), tent[p, :k, 1].long(), H[p], inl[p, :k].bool(), _verify_info(hyp_counts[p, :k], row[1:])))
+    return out
+
+
+def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
+    """Re-ranks `shortlist` (image indices into descs / LAFs) by the number of spatially verified inliers against image `query`, all pairs in one
+    device call.  Returns (order, num_inliers): the shortlist sorted by descending inlier count, ties in shortlist order, and the counts in that order."""
+    shortlist = [int(s) for s in shortlist]
+    res = match_and_verify_many(descs, LAFs, [(int(query), s) for s in shortlist], SNN_threshold, inl_th, model, lo_iters)
+    n = [r[4]["num_inliers"] for r in res]
+    rank = sorted(range(len(shortlist)), key=lambda i: -n[i])          # sorted() is stable: ties keep the shortlist's order
+    return [shortlist[i] for i in rank], [n[i] for i in rank]

@@ -189,6 +189,15 @@ struct AffZeroSegs {
 static inline size_t aff_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int aff_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// One row {row1, n1, row2, n2} of the pair table of the *_many calls (include/affnet_hip.h), tested against the buffers' row counts and the
+// launch's caps before anything is loaded through it.  false: out of range (the row's fields are then not to be used).
+struct AffPairRow { int row1, n1, row2, n2; };
+__device__ __forceinline__ bool aff_pair_row(const int32_t* __restrict__ pairs, int p, int rows1, int rows2, int n1_max, int n2_max, AffPairRow& r) {
+    r.row1 = pairs[4 * (size_t)p]; r.n1 = pairs[4 * (size_t)p + 1]; r.row2 = pairs[4 * (size_t)p + 2]; r.n2 = pairs[4 * (size_t)p + 3];
+    return r.row1 >= 0 && r.n1 >= 0 && r.row2 >= 0 && r.n2 >= 0 && (long long)r.row1 + r.n1 <= rows1 && (long long)r.row2 + r.n2 <= rows2 &&
+           r.n1 <= n1_max && r.n2 <= n2_max;
+}
+
 // Level pointers of the pyramid of image 0 in the workspace (+ img_stride floats per further image of the batch).
 struct PyrTable {
     const float* lvl[AFFNET_MAX_OCTAVES][AFFNET_MAX_LEVELS];

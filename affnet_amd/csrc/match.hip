@@ -10,15 +10,18 @@
 // The reference finds the "second nearest" by overwriting the COLUMNS of all nearest neighbours with 100000
 // (dist_matrix[:, idxs_in_2] = 100000) and taking the row minimum again: the same kernel runs a second time with a
 // per-column `used` mask, so the quirk (a column masked for every row, not only for its own) is reproduced.
+// affnet_match_snn_many runs the same stages for P image pairs per launch (the pair index on a grid dimension, the segments from a device table).
 #include <math.h>
 
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
+// The bodies below are the kernels of one image pair; every __global__ kernel of this file, single-pair or batched (pair index on a grid
+// dimension, further down), only chooses the pointers and the workgroup index `blk` they run on.
+__device__ __forceinline__ void sqnorm_body(const float* __restrict__ x, int n, int dim, float* __restrict__ out, int blk) {
     // one wavefront per row; torch.sum(a * a, dim=1)
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
     float s = 0.f;
     for (int k = lane; k < dim; k += 64) { const float v = x[(size_t)row * dim + k]; s = fmaf(v, v, s); }
@@ -27,20 +30,33 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x
     if (lane == 0) out[row] = s;
 }
 
+__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
+    sqnorm_body(x, n, dim, out, blockIdx.x);
+}
+
 // Workgroup = 4 wavefronts = 64 rows of `a`; wave w owns rows 16w..16w+15 and walks all columns of `b` in tiles of 16.
 // MFMA roles: A operand = a rows (lane (m, kq) holds a[row m][16 t + 4 kq + j]), B operand = b rows (columns of the
 // distance matrix); the K order is permuted identically on both sides, which a dot product does not see.
 // Result tile: lane (n = l & 15, g = l >> 4) holds D[row 4 g + r][col n], r = 0..3.
-template <int DIM>
-__global__ __launch_bounds__(256) void rowmin_dist_kernel(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
-                                                          const float* __restrict__ a_sq, const float* __restrict__ b_sq,
-                                                          const uint8_t* __restrict__ used, float* __restrict__ out_min,
-                                                          int32_t* __restrict__ out_idx, float* __restrict__ out_full) {
+//
+// STAGE (the batched kernel): the four waves of a workgroup want the same 16 columns of `b`, so the workgroup loads each tile once (every thread
+// DIM / 64 float4, the next tile's in flight during the MFMAs of this one), keeps it in one of two LDS buffers `s_b` (ROWMIN_BS floats per column:
+// the 16-byte skew spreads the 16 columns over the banks) and every wave takes its B fragments from there.  The fragments hold the same values
+// in the same lanes, so nothing after the load differs.  One barrier per tile, which every wave of the workgroup must reach: a wave whose 16 rows
+// lie behind n1 computes on clamped rows like the tail lanes of a partial wave and writes nothing.
+#define ROWMIN_BS(DIM) ((DIM) + 4)
+template <int DIM, bool STAGE>
+__device__ __forceinline__ void rowmin_dist_body(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
+                                                 const float* __restrict__ a_sq, const float* __restrict__ b_sq,
+                                                 const uint8_t* __restrict__ used, float* __restrict__ out_min,
+                                                 int32_t* __restrict__ out_idx, float* __restrict__ out_full, int blk, float* s_b) {
     constexpr int NG = DIM / 16;
+    constexpr int BS = ROWMIN_BS(DIM), Q = DIM / 4, NPRE = 16 * Q / 256;      // float4 per column, float4 per thread and tile
+    static_assert(!STAGE || (16 * Q) % 256 == 0, "the staged tile is loaded by 256 threads in whole rounds");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int m = lane & 15, kq = lane >> 4;
-    const int row0 = blockIdx.x * 64 + wave * 16;
-    if (row0 >= n1) return;
+    const int row0 = blk * 64 + wave * 16;
+    if (STAGE ? blk * 64 >= n1 : row0 >= n1) return;      // STAGE: uniform over the workgroup
     f32x4 fa[NG];
     {
         const int r = min(row0 + m, n1 - 1);
@@ -52,19 +68,56 @@ __global__ __launch_bounds__(256) void rowmin_dist_kernel(const float* __restric
     for (int r = 0; r < 4; ++r) asq[r] = a_sq[min(row0 + 4 * kq + r, n1 - 1)];
     float best[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
     int bidx[4] = {0, 0, 0, 0};
+    f32x4 pre[STAGE ? NPRE : 1];
+    // tile at column c0 -> registers (columns clamped like the fragment loads of the direct form); registers -> LDS buffer `buf`
+    auto tile_fetch = [&](int c0) {
+#pragma unroll
+        for (int j = 0; j < NPRE; ++j) {
+            const int e = (int)threadIdx.x + 256 * j;
+            pre[j] = *reinterpret_cast<const f32x4*>(&b[(size_t)min(c0 + e / Q, n2 - 1) * DIM + 4 * (e % Q)]);
+        }
+    };
+    auto tile_store = [&](int buf) {
+#pragma unroll
+        for (int j = 0; j < NPRE; ++j) {
+            const int e = (int)threadIdx.x + 256 * j;
+            *reinterpret_cast<f32x4*>(&s_b[buf * 16 * BS + (e / Q) * BS + 4 * (e % Q)]) = pre[j];
+        }
+    };
+    if (STAGE) {
+        tile_fetch(0);
+        tile_store(0);
+        __syncthreads();
+    }
     for (int c0 = 0; c0 < n2; c0 += 16) {
         const int col = c0 + m;
         const int cc = min(col, n2 - 1);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         f32x4 fb[NG];
+        const int buf = (c0 >> 4) & 1;
+        const bool more = c0 + 16 < n2;
+        float bsq = 0.f;
+        bool masked = false;
+        if (STAGE) {
+            if (more) tile_fetch(c0 + 16);
+            // in front of the MFMAs here: the two loads complete under them, and no branch (the null test of `used`) stands between the last
+            // MFMA and the accumulator reads - with one there, a build of this form read acc[3] too early on the NULL path (NOTES.md)
+            bsq = b_sq[cc];
+            masked = used && used[cc];
 #pragma unroll
-        for (int t = 0; t < NG; ++t) fb[t] = *reinterpret_cast<const f32x4*>(&b[(size_t)cc * DIM + 16 * t + 4 * kq]);
+            for (int t = 0; t < NG; ++t) fb[t] = *reinterpret_cast<const f32x4*>(&s_b[buf * 16 * BS + m * BS + 16 * t + 4 * kq]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < NG; ++t) fb[t] = *reinterpret_cast<const f32x4*>(&b[(size_t)cc * DIM + 16 * t + 4 * kq]);
+        }
 #pragma unroll
         for (int t = 0; t < NG; ++t)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t][j], fb[t][j], acc, 0, 0, 0);
-        const float bsq = b_sq[cc];
-        const bool masked = used && used[cc];
+        if (!STAGE) {
+            bsq = b_sq[cc];
+            masked = used && used[cc];
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             // Losses.py:12-13: sqrt((d1_sq + d2_sq) - 2.0 * a.b + eps)
@@ -74,6 +127,10 @@ __global__ __launch_bounds__(256) void rowmin_dist_kernel(const float* __restric
             // is sticky, as in torch.min
             if (col < n2 && (d < best[r] || (d != d && best[r] == best[r]))) { best[r] = d; bidx[r] = col; }
             if (out_full && col < n2 && row0 + 4 * kq + r < n1) out_full[(size_t)(row0 + 4 * kq + r) * n2 + col] = d;
+        }
+        if (STAGE) {        // the other buffer was last read one tile ago, in front of that tile's barrier
+            if (more) tile_store(buf ^ 1);
+            __syncthreads();
         }
     }
     // minimum over the 16 column lanes (same g): butterfly inside each row of 16 lanes, ties -> smaller column
@@ -93,15 +150,24 @@ __global__ __launch_bounds__(256) void rowmin_dist_kernel(const float* __restric
     }
 }
 
-__global__ void mark_used_kernel(const int32_t* __restrict__ idx, int n1, uint8_t* __restrict__ used) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+template <int DIM>
+__global__ __launch_bounds__(256) void rowmin_dist_kernel(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
+                                                          const float* __restrict__ a_sq, const float* __restrict__ b_sq,
+                                                          const uint8_t* __restrict__ used, float* __restrict__ out_min,
+                                                          int32_t* __restrict__ out_idx, float* __restrict__ out_full) {
+    rowmin_dist_body<DIM, false>(a, n1, b, n2, a_sq, b_sq, used, out_min, out_idx, out_full, blockIdx.x, nullptr);
+}
+
+__device__ __forceinline__ void mark_used_body(const int32_t* __restrict__ idx, int n1, uint8_t* __restrict__ used, int blk) {
+    const int i = blk * blockDim.x + threadIdx.x;
     if (i < n1) used[idx[i]] = 1;
 }
 
+__global__ void mark_used_kernel(const int32_t* __restrict__ idx, int n1, uint8_t* __restrict__ used) { mark_used_body(idx, n1, used, blockIdx.x); }
+
 // One workgroup: ratio test + order-preserving compaction of the tentative matches (train_AffNet_test_on_graffity.py:296-300).
-__global__ __launch_bounds__(1024) void snn_select_kernel(const float* __restrict__ min1, const float* __restrict__ min2,
-                                                          const int32_t* __restrict__ idx, int n1, float thr, int32_t* __restrict__ tent,
-                                                          int32_t* __restrict__ count) {
+__device__ __forceinline__ void snn_select_body(const float* __restrict__ min1, const float* __restrict__ min2, const int32_t* __restrict__ idx, int n1,
+                                                float thr, int32_t* __restrict__ tent, int32_t* __restrict__ count) {
     __shared__ int s_wave[16];
     __shared__ int s_base;
     if (threadIdx.x == 0) s_base = 0;
@@ -125,6 +191,12 @@ __global__ __launch_bounds__(1024) void snn_select_kernel(const float* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) *count = s_base;
+}
+
+__global__ __launch_bounds__(1024) void snn_select_kernel(const float* __restrict__ min1, const float* __restrict__ min2,
+                                                          const int32_t* __restrict__ idx, int n1, float thr, int32_t* __restrict__ tent,
+                                                          int32_t* __restrict__ count) {
+    snn_select_body(min1, min2, idx, n1, thr, tent, count);
 }
 
 extern "C" int affnet_match_snn(affnet_ctx* ctx, const float* d_desc1, int n1, const float* d_desc2, int n2, int dim, float snn_threshold,
@@ -174,6 +246,110 @@ extern "C" int affnet_distance_matrix(affnet_ctx* ctx, const float* d_desc1, int
 
 extern "C" size_t affnet_match_scratch_bytes(int n1, int n2) {
     return (size_t)(n1 + n2) * sizeof(float) + aff_align((size_t)n2, 16) + (size_t)n1 * sizeof(int32_t) + 64;
+}
+
+// ---- many pairs in one call: the pair index on a grid dimension of every stage -------------------------------------------------------------
+// One pair fills an eighth of the part at best (cdiv(2000, 64) = 32 workgroups of the row-minimum kernel on 256 CUs, one workgroup for the
+// selection); P independent pairs are P x that in the same six launches.  Every kernel reads its row of the pair table, tests it (aff_pair_row)
+// and then runs the single-pair body above on the pair's segments, so a pair's outputs are the single-pair call's bit for bit.  Workgroups past
+// the pair's own n1 leave through the body's own test, uniformly.
+struct SnnMany {
+    const float* desc1; int rows1;
+    const float* desc2; int rows2;
+    const int32_t* pairs;
+    int n1_max, n2_max;
+    float* a_sq; float* b_sq;          // scratch: (P, n1_max), (P, n2_max)
+    uint8_t* used; int used_pitch;     // scratch: (P, used_pitch)
+};
+
+// false: the row is out of range, or the pair is empty - nothing to do either way (d_count was cleared)
+__device__ __forceinline__ bool snn_many_row(const SnnMany& m, int p, AffPairRow& r) {
+    return aff_pair_row(m.pairs, p, m.rows1, m.rows2, m.n1_max, m.n2_max, r) && r.n1 > 0 && r.n2 > 0;
+}
+
+// grid (rows / 4, P, side)
+__global__ __launch_bounds__(256) void sqnorm_many_kernel(SnnMany m, int dim) {
+    const int p = blockIdx.y;
+    AffPairRow r;
+    if (!snn_many_row(m, p, r)) return;
+    if (blockIdx.z == 0) sqnorm_body(m.desc1 + (size_t)r.row1 * dim, r.n1, dim, m.a_sq + (size_t)p * m.n1_max, blockIdx.x);
+    else sqnorm_body(m.desc2 + (size_t)r.row2 * dim, r.n2, dim, m.b_sq + (size_t)p * m.n2_max, blockIdx.x);
+}
+
+// grid (n1_max / 64, P); masked != 0: the second pass, over the columns that are nobody's nearest neighbour in THIS pair
+template <int DIM>
+__global__ __launch_bounds__(256) void rowmin_many_kernel(SnnMany m, int masked, float* __restrict__ out_min, int32_t* __restrict__ out_idx) {
+    __shared__ __attribute__((aligned(16))) float s_b[2 * 16 * ROWMIN_BS(DIM)];
+    const int p = blockIdx.y;
+    AffPairRow r;
+    if (!snn_many_row(m, p, r)) return;
+    rowmin_dist_body<DIM, true>(m.desc1 + (size_t)r.row1 * DIM, r.n1, m.desc2 + (size_t)r.row2 * DIM, r.n2, m.a_sq + (size_t)p * m.n1_max,
+                          m.b_sq + (size_t)p * m.n2_max, masked ? m.used + (size_t)p * m.used_pitch : (const uint8_t*)nullptr,
+                          out_min + (size_t)p * m.n1_max, out_idx + (size_t)p * m.n1_max, (float*)nullptr, blockIdx.x, s_b);
+}
+
+// grid (n1_max / 256, P)
+__global__ __launch_bounds__(256) void mark_used_many_kernel(SnnMany m, const int32_t* __restrict__ idx) {
+    const int p = blockIdx.y;
+    AffPairRow r;
+    if (!snn_many_row(m, p, r)) return;
+    mark_used_body(idx + (size_t)p * m.n1_max, r.n1, m.used + (size_t)p * m.used_pitch, blockIdx.x);
+}
+
+// grid (P)
+__global__ __launch_bounds__(1024) void snn_select_many_kernel(SnnMany m, const float* __restrict__ min1, const float* __restrict__ min2,
+                                                               const int32_t* __restrict__ idx, float thr, int32_t* __restrict__ tent,
+                                                               int32_t* __restrict__ count) {
+    const int p = blockIdx.x;
+    AffPairRow r;
+    if (!snn_many_row(m, p, r)) return;
+    const size_t o = (size_t)p * m.n1_max;
+    snn_select_body(min1 + o, min2 + o, idx + o, r.n1, thr, tent + 2 * o, count + p);
+}
+
+// scratch: a_sq float (P, n1_max) | b_sq float (P, n2_max) | used uint8 (P, align16(n2_max)) | second-pass argmin int32 (P, n1_max)
+extern "C" size_t affnet_match_many_scratch_bytes(int n_pairs, int n1_max, int n2_max) {
+    const size_t P = n_pairs > 0 ? (size_t)n_pairs : 0, a = n1_max > 0 ? (size_t)n1_max : 0, b = n2_max > 0 ? (size_t)n2_max : 0;
+    return P * ((a + b) * sizeof(float) + aff_align(b, 16) + a * sizeof(int32_t)) + 64;
+}
+
+extern "C" int affnet_match_snn_many(affnet_ctx* ctx, const float* d_desc1, int rows1, const float* d_desc2, int rows2, int dim, const int32_t* d_pairs,
+                                     int n_pairs, int n1_max, int n2_max, float snn_threshold, float* d_min_dist, int32_t* d_idx, float* d_min2_dist,
+                                     int32_t* d_tent, int32_t* d_count, void* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_desc1 || !d_desc2 || !d_pairs || !d_min_dist || !d_idx || !d_min2_dist || !d_tent || !d_count || !d_scratch || rows1 < 0 || rows2 < 0 ||
+        n_pairs < 0 || n1_max < 0 || n2_max < 0)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "match_snn_many: bad argument");
+    if (dim != 128) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_snn_many: descriptor length %d (only 128 is built)", dim);
+    if (n_pairs > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_snn_many: %d pairs (at most 65535 per call)", n_pairs);
+    if (n_pairs == 0) return AFFNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t P = (size_t)n_pairs;
+    SnnMany m;
+    m.desc1 = d_desc1; m.rows1 = rows1; m.desc2 = d_desc2; m.rows2 = rows2; m.pairs = d_pairs; m.n1_max = n1_max; m.n2_max = n2_max;
+    m.a_sq = (float*)d_scratch;
+    m.b_sq = m.a_sq + P * n1_max;
+    m.used = (uint8_t*)(m.b_sq + P * n2_max);
+    m.used_pitch = (int)aff_align((size_t)n2_max, 16);
+    int32_t* idx2 = (int32_t*)(m.used + P * m.used_pitch);
+    const bool work = n1_max > 0 && n2_max > 0;     // otherwise every pair is empty or out of range
+    {
+        AffZeroSegs z;
+        z.add(d_count, P * sizeof(int32_t));
+        if (work) z.add(m.used, P * m.used_pitch);
+        int zrc = aff_zero_multi_async(ctx, z, st);
+        if (zrc) return zrc;
+    }
+    if (!work) return AFFNET_OK;
+    const unsigned gp = (unsigned)n_pairs;
+    hipLaunchKernelGGL(sqnorm_many_kernel, dim3(aff_cdiv(n1_max > n2_max ? n1_max : n2_max, 4), gp, 2), dim3(256), 0, st, m, dim);
+    hipLaunchKernelGGL(rowmin_many_kernel<128>, dim3(aff_cdiv(n1_max, 64), gp), dim3(256), 0, st, m, 0, d_min_dist, d_idx);
+    hipLaunchKernelGGL(mark_used_many_kernel, dim3(aff_cdiv(n1_max, 256), gp), dim3(256), 0, st, m, (const int32_t*)d_idx);
+    hipLaunchKernelGGL(rowmin_many_kernel<128>, dim3(aff_cdiv(n1_max, 64), gp), dim3(256), 0, st, m, 1, d_min2_dist, idx2);
+    hipLaunchKernelGGL(snn_select_many_kernel, dim3(gp), dim3(1024), 0, st, m, (const float*)d_min_dist, (const float*)d_min2_dist, (const int32_t*)d_idx,
+                       snn_threshold, d_tent, d_count);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
 }
 
 // ---- homography reprojection of LAFs + nearest reprojected centre ---------------------------------------------

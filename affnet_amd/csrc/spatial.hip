@@ -18,6 +18,9 @@
 //                      eliminated by one thread on a matrix held in LDS (a per-thread runtime-indexed array would live in scratch).
 //
 // The row count comes from a device pointer (what affnet_match_snn writes), rows at or beyond it are neither read nor written.
+//
+// affnet_verify_matches_many (end of the file) runs the same four stages for P image pairs per launch: spv_many_*_kernel take the pair index from
+// the grid, find the pair's segments in a device table and call the bodies of the kernels above.
 #include <math.h>
 
 #include "common.h"
@@ -53,8 +56,10 @@ __device__ __forceinline__ bool spv_inlier(const float4 m, const float4 ph, cons
     return (u * u + v * v) <= th2;
 }
 
-__global__ __launch_bounds__(256) void spv_prep_kernel(SpvIn in, float4* __restrict__ pts, float4* __restrict__ hyp, int32_t* __restrict__ counts) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+// The *_body functions are the kernels of one image pair; the __global__ kernels, single-pair here and batched at the end of the file (pair index on
+// a grid dimension), only choose the pointers and the workgroup indices they run on.
+__device__ __forceinline__ void spv_prep_body(const SpvIn& in, float4* __restrict__ pts, float4* __restrict__ hyp, int32_t* __restrict__ counts, int blk) {
+    const int t = blk * 256 + threadIdx.x;
     if (t >= spv_rows(in.count, in.t_max)) return;
     const float qn = __builtin_nanf("");
     float4 p = make_float4(qn, qn, qn, qn), m = p;
@@ -76,11 +81,15 @@ __global__ __launch_bounds__(256) void spv_prep_kernel(SpvIn in, float4* __restr
     pts[t] = p; hyp[t] = m; counts[t] = 0;
 }
 
-__global__ __launch_bounds__(SPV_HT) void spv_score_kernel(const float4* __restrict__ pts, const float4* __restrict__ hyp, const int32_t* __restrict__ count,
-                                                           int t_max, float th2, int32_t* __restrict__ counts) {
+__global__ __launch_bounds__(256) void spv_prep_kernel(SpvIn in, float4* __restrict__ pts, float4* __restrict__ hyp, int32_t* __restrict__ counts) {
+    spv_prep_body(in, pts, hyp, counts, blockIdx.x);
+}
+
+__device__ __forceinline__ void spv_score_body(const float4* __restrict__ pts, const float4* __restrict__ hyp, const int32_t* __restrict__ count, int t_max,
+                                               float th2, int32_t* __restrict__ counts, int blk_h, int blk_t) {
     __shared__ float4 s_pt[SPV_MC];
     const int rows = spv_rows(count, t_max);
-    const int h0 = blockIdx.x * SPV_HT, t0 = blockIdx.y * SPV_MC;
+    const int h0 = blk_h * SPV_HT, t0 = blk_t * SPV_MC;
     if (h0 >= rows || t0 >= rows) return;                     // uniform over the workgroup
     const int nt = min(SPV_MC, rows - t0);
     for (int k = threadIdx.x; k < nt; k += SPV_HT) s_pt[k] = pts[t0 + k];
@@ -93,9 +102,13 @@ __global__ __launch_bounds__(SPV_HT) void spv_score_kernel(const float4* __restr
     if (c) atomicAdd(&counts[h], c);
 }
 
+__global__ __launch_bounds__(SPV_HT) void spv_score_kernel(const float4* __restrict__ pts, const float4* __restrict__ hyp, const int32_t* __restrict__ count,
+                                                           int t_max, float th2, int32_t* __restrict__ counts) {
+    spv_score_body(pts, hyp, count, t_max, th2, counts, blockIdx.x, blockIdx.y);
+}
+
 // best[0] = smallest h with the largest count, best[1] = that count; {-1, 0} when no hypothesis has an inlier (no valid hypothesis, or no rows)
-__global__ __launch_bounds__(256) void spv_select_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max,
-                                                         int32_t* __restrict__ best) {
+__device__ __forceinline__ void spv_select_body(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max, int32_t* __restrict__ best) {
     __shared__ int s_c[4], s_i[4];
     const int rows = spv_rows(count, t_max);
     int bc = 0, bi = 0x7fffffff;
@@ -116,6 +129,11 @@ __global__ __launch_bounds__(256) void spv_select_kernel(const int32_t* __restri
         best[0] = bc > 0 ? bi : -1;
         best[1] = bc > 0 ? bc : 0;
     }
+}
+
+__global__ __launch_bounds__(256) void spv_select_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max,
+                                                         int32_t* __restrict__ best) {
+    spv_select_body(counts, count, t_max, best);
 }
 
 // ---- local optimisation ---------------------------------------------------------------------------------------------------------------
@@ -180,7 +198,7 @@ __device__ __forceinline__ void spv_mul3_lds(const double* A, const double* B, d
         for (int c = 0; c < 3; ++c) Cm[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
 }
 
-__global__ __launch_bounds__(SPV_LO_THREADS) void spv_lo_kernel(SpvLo a) {
+__device__ __forceinline__ void spv_lo_body(const SpvLo& a) {
     __shared__ double s_part[4 * SPV_NSUM], s_sum[SPV_NSUM];
     __shared__ double s_A[8 * 9];
     __shared__ double s_m[4][9];           // 0: candidate model, 1: kept model, 2 / 3: denormalisation factors
@@ -348,6 +366,8 @@ __global__ __launch_bounds__(SPV_LO_THREADS) void spv_lo_kernel(SpvLo a) {
     if (tid == 0) { a.summary[0] = best; a.summary[1] = a.best[1]; a.summary[2] = n_best; a.summary[3] = flags; }
 }
 
+__global__ __launch_bounds__(SPV_LO_THREADS) void spv_lo_kernel(SpvLo a) { spv_lo_body(a); }
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 // scratch: pts float4 [t_max] | hyp float4 [t_max] | best int32 [2] (+ pad to 16) | current mask uint8 [t_max]
 extern "C" size_t affnet_verify_scratch_bytes(int t_max) {
@@ -408,6 +428,115 @@ extern "C" int affnet_verify_matches(affnet_ctx* ctx, const float* d_lafs1, int 
     lo.in = in; lo.pts = pts; lo.hyp = hyp; lo.best = best; lo.th = inl_th; lo.model = model; lo.lo_iters = lo_iters; lo.cur = cur;
     lo.model_out = d_model; lo.inlier = d_inlier; lo.summary = d_summary;
     hipLaunchKernelGGL(spv_lo_kernel, dim3(1), dim3(SPV_LO_THREADS), 0, st, lo);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// ---- many pairs in one call: the pair index on a grid dimension of every stage --------------------------------------------------------------
+// A shortlist of P image pairs is P independent verifications: P x the workgroups of the scoring kernel and P concurrent local optimisations in
+// the four launches of one pair.  Every kernel reads its row of the pair table, tests it (aff_pair_row, before any load through it), builds the
+// pair's SpvIn from the segments and runs the single-pair body above: per pair the outputs are affnet_verify_matches' bit for bit.
+// The tentative lists are (P, t_max, 2) as affnet_match_snn_many writes them with n1_max = t_max, which is this call's cap on n1; n2 has none.
+struct SpvMany {
+    const float* lafs1; int rows1;
+    const float* lafs2; int rows2;
+    const int32_t* pairs;
+    const int32_t* tent;       // (P, t_max, 2)
+    const int32_t* count;      // (P) or NULL
+    int t_max;
+    float4* pts; float4* hyp;  // scratch: (P, t_max) each
+    int32_t* best;             // scratch: (P, 4), {index, count} of the pair in the first two
+};
+
+// false: pair row out of range
+__device__ __forceinline__ bool spv_many_in(const SpvMany& m, int p, SpvIn& in) {
+    AffPairRow r;
+    if (!aff_pair_row(m.pairs, p, m.rows1, m.rows2, m.t_max, 0x7fffffff, r)) return false;
+    in.lafs1 = m.lafs1 + 6 * (size_t)r.row1; in.n1 = r.n1;
+    in.lafs2 = m.lafs2 + 6 * (size_t)r.row2; in.n2 = r.n2;
+    in.tent = m.tent + 2 * (size_t)p * m.t_max;
+    in.count = m.count ? m.count + p : nullptr;
+    in.t_max = m.t_max;
+    return true;
+}
+
+// grid (t_max / 256, P)
+__global__ __launch_bounds__(256) void spv_many_prep_kernel(SpvMany m, int32_t* __restrict__ counts) {
+    const int p = blockIdx.y;
+    SpvIn in;
+    if (!spv_many_in(m, p, in)) return;
+    const size_t o = (size_t)p * m.t_max;
+    spv_prep_body(in, m.pts + o, m.hyp + o, counts + o, blockIdx.x);
+}
+
+// grid (t_max / SPV_HT, t_max / SPV_MC, P)
+__global__ __launch_bounds__(SPV_HT) void spv_many_score_kernel(SpvMany m, float th2, int32_t* __restrict__ counts) {
+    const int p = blockIdx.z;
+    SpvIn in;
+    if (!spv_many_in(m, p, in)) return;
+    const size_t o = (size_t)p * m.t_max;
+    spv_score_body(m.pts + o, m.hyp + o, in.count, m.t_max, th2, counts + o, blockIdx.x, blockIdx.y);
+}
+
+// grid (P); an out-of-range pair has no rows
+__global__ __launch_bounds__(256) void spv_many_select_kernel(SpvMany m, const int32_t* __restrict__ counts) {
+    const int p = blockIdx.x;
+    SpvIn in;
+    if (!spv_many_in(m, p, in)) return;
+    spv_select_body(counts + (size_t)p * m.t_max, in.count, m.t_max, m.best + 4 * (size_t)p);
+}
+
+// grid (P)
+__global__ __launch_bounds__(SPV_LO_THREADS) void spv_many_lo_kernel(SpvMany m, float th, int model, int lo_iters, uint8_t* __restrict__ cur, int cur_pitch,
+                                                                     double* __restrict__ model_out, uint8_t* __restrict__ inlier, int32_t* __restrict__ summary) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    SpvLo a;
+    if (!spv_many_in(m, p, a.in)) {        // identity, nothing of the mask, flags 1 | 8
+        if (tid < 9) model_out[9 * (size_t)p + tid] = (tid % 4 == 0) ? 1.0 : 0.0;
+        if (tid == 0) { int32_t* s = summary + 4 * (size_t)p; s[0] = -1; s[1] = 0; s[2] = 0; s[3] = 1 | AFFNET_VERIFY_FLAG_PAIR_RANGE; }
+        return;
+    }
+    const size_t o = (size_t)p * m.t_max;
+    a.pts = m.pts + o; a.hyp = m.hyp + o; a.best = m.best + 4 * (size_t)p;
+    a.th = th; a.model = model; a.lo_iters = lo_iters;
+    a.cur = cur + (size_t)p * cur_pitch;
+    a.model_out = model_out + 9 * (size_t)p; a.inlier = inlier + o; a.summary = summary + 4 * (size_t)p;
+    spv_lo_body(a);
+}
+
+// scratch: pts float4 (P, t_max) | hyp float4 (P, t_max) | best int32 (P, 4) | current mask uint8 (P, align16(t_max))
+extern "C" size_t affnet_verify_many_scratch_bytes(int n_pairs, int t_max) {
+    const size_t P = n_pairs > 0 ? (size_t)n_pairs : 0, t = t_max > 0 ? (size_t)t_max : 0;
+    return P * (2 * t * sizeof(float4) + 16 + aff_align(t, 16)) + 64;
+}
+
+extern "C" int affnet_verify_matches_many(affnet_ctx* ctx, const float* d_lafs1, int rows1, const float* d_lafs2, int rows2, const int32_t* d_pairs, int n_pairs,
+                                          const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters, int32_t* d_counts,
+                                          double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    { int rc = spv_check(ctx, "verify_matches_many", d_lafs1, rows1, d_lafs2, rows2, d_tent, t_max, inl_th, d_counts, d_scratch); if (rc) return rc; }
+    if (!d_pairs || !d_model || !d_inlier || !d_summary || n_pairs < 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "verify_matches_many: bad argument");
+    if (n_pairs > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "verify_matches_many: %d pairs (at most 65535 per call)", n_pairs);
+    if (model != AFFNET_VERIFY_AFFINE && model != AFFNET_VERIFY_HOMOGRAPHY)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "verify_matches_many: model %d (0 = affine, 1 = homography)", model);
+    if (lo_iters < 0 || lo_iters > 8) return aff_fail(ctx, AFFNET_ERR_INVALID, "verify_matches_many: lo_iters %d outside 0..8", lo_iters);
+    if (n_pairs == 0) return AFFNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t P = (size_t)n_pairs;
+    const unsigned gp = (unsigned)n_pairs;
+    SpvMany m;
+    m.lafs1 = d_lafs1; m.rows1 = rows1; m.lafs2 = d_lafs2; m.rows2 = rows2; m.pairs = d_pairs; m.tent = d_tent; m.count = d_count; m.t_max = t_max;
+    m.pts = (float4*)d_scratch;
+    m.hyp = m.pts + P * t_max;
+    m.best = (int32_t*)(m.hyp + P * t_max);
+    uint8_t* cur = (uint8_t*)(m.best + 4 * P);
+    if (t_max > 0) {
+        hipLaunchKernelGGL(spv_many_prep_kernel, dim3(aff_cdiv(t_max, 256), gp), dim3(256), 0, st, m, d_counts);
+        hipLaunchKernelGGL(spv_many_score_kernel, dim3(aff_cdiv(t_max, SPV_HT), aff_cdiv(t_max, SPV_MC), gp), dim3(SPV_HT), 0, st, m, inl_th * inl_th, d_counts);
+    }
+    hipLaunchKernelGGL(spv_many_select_kernel, dim3(gp), dim3(256), 0, st, m, (const int32_t*)d_counts);
+    hipLaunchKernelGGL(spv_many_lo_kernel, dim3(gp), dim3(SPV_LO_THREADS), 0, st, m, inl_th, model, lo_iters, cur, (int)aff_align((size_t)t_max, 16), d_model,
+                       d_inlier, d_summary);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

@@ -507,6 +507,42 @@ int affnet_verify_matches(affnet_ctx* ctx, const float* d_lafs1, int n1, const f
                           const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters, int32_t* d_counts, double* d_model,
                           uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
 
+/* ---- many image pairs in one call (shortlist re-ranking: one query against K images, all pairs of a small set) ---- */
+
+/* P pairs per call, the pair index on a grid dimension of every kernel: P x the workgroups of one pair per launch, the same number of
+ * launches as for one pair.  All descriptors of side 1 lie in one (rows1,128) buffer, their frames in one (rows1,2,3) buffer; side 2 is
+ * laid out the same way and may be the same buffers.  d_pairs (P,4) int32 on the device = {row1, n1, row2, n2} per pair: the pair's
+ * segments are rows [row1, row1 + n1) of side 1 and [row2, row2 + n2) of side 2.  The host passes only caps (n1_max, n2_max, t_max), so
+ * no grid size needs a read-back.
+ *
+ * Every kernel tests its table row BEFORE any load through it.  A row is out of range when a field is negative, row1 + n1 > rows1,
+ * row2 + n2 > rows2, n1 > n1_max or n2 > n2_max: nothing is read or written through such a row, its count is 0 and its summary
+ * {-1, 0, 0, 1 | AFFNET_VERIFY_FLAG_PAIR_RANGE} with the identity model.  n1 == 0 or n2 == 0 is a valid empty pair (count 0, summary {-1, 0, 0, 1}).
+ *
+ * Per row and per hypothesis the kernels run the device code of the single-pair calls (the same functions): every output of pair p is,
+ * bit for bit, what affnet_match_snn / affnet_verify_matches write for that pair's segments, with indices LOCAL to the segments.
+ * Outputs are pair-major with the caps as row pitch; rows at or beyond a pair's n1 / count are neither read nor written.
+ * n_pairs == 0 is valid and launches nothing; n_pairs <= 65535.  No allocation, no synchronisation, all work on `stream`. */
+#define AFFNET_VERIFY_FLAG_PAIR_RANGE 8   /* d_summary[3] flag 8: pair row out of range (the single-pair calls never set it) */
+
+/* Host only.  Bytes of d_scratch of affnet_match_snn_many. */
+size_t affnet_match_many_scratch_bytes(int n_pairs, int n1_max, int n2_max);
+
+/* affnet_match_snn per pair.  d_min_dist, d_idx, d_min2_dist (P,n1_max); d_tent (P,n1_max,2); d_count (P).  dim must be 128. */
+int affnet_match_snn_many(affnet_ctx* ctx, const float* d_desc1, int rows1, const float* d_desc2, int rows2, int dim, const int32_t* d_pairs,
+                          int n_pairs, int n1_max, int n2_max, float snn_threshold, float* d_min_dist, int32_t* d_idx, float* d_min2_dist,
+                          int32_t* d_tent, int32_t* d_count, void* d_scratch, void* stream);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_verify_matches_many. */
+size_t affnet_verify_many_scratch_bytes(int n_pairs, int t_max);
+
+/* affnet_verify_matches per pair.  d_tent (P,t_max,2) as affnet_match_snn_many writes it with n1_max = t_max (so a row with n1 > t_max is
+ * out of range here as it is there; there is no cap on n2); d_count (P) or NULL (= t_max rows are valid in every pair).
+ * d_counts (P,t_max); d_model (P,9) double; d_inlier (P,t_max) uint8; d_summary (P,4). */
+int affnet_verify_matches_many(affnet_ctx* ctx, const float* d_lafs1, int rows1, const float* d_lafs2, int rows2, const int32_t* d_pairs,
+                               int n_pairs, const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters,
+                               int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

@@ -123,6 +123,9 @@ DESIGN_KERNELS = [
     ("rowmin_dist_kernel<128>", "SNN matching: MFMA distance tiles with a running row minimum"),
     ("spv_score_kernel", "spatial verification: T x T scoring of the affine-frame hypotheses"),
     ("spv_lo_kernel", "spatial verification: fp64 local optimisation, one workgroup"),
+    ("rowmin_many_kernel<128>", "SNN matching of many pairs per call: the same row-minimum body, pair index on the grid"),
+    ("spv_many_score_kernel", "spatial verification of many pairs per call: the same scoring body, pair index on the grid"),
+    ("spv_many_lo_kernel", "spatial verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
     ("blur2d_kernel<13, 4>", "Gaussian blur 13 x 13, 64 x 64 tiles"),
     ("blur2d_pair_kernel<15, 9, 4>", "paired blur 15 x 15 / 9 x 9"),
