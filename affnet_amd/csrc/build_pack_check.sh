@@ -1,6 +1,6 @@
 #!/bin/bash
-# Developer check for a CPU machine: the weight packer (weights_pack.hip, compiled as plain C++) and pack_check.cpp under the address and
-# undefined-behaviour sanitizers, built into build/pack_check next to this script and run.  No GPU, no HIP runtime.
+# Developer check for a CPU machine: the weight packer (weights_pack.hip, compiled as plain C++), the derived-weights tables and routine of
+# weights_layout.h, and pack_check.cpp under the address and undefined-behaviour sanitizers, built into build/pack_check next to this script and run.  No GPU, no HIP runtime.
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 CXX="${CXX:-/opt/rocm/lib/llvm/bin/clang++}"

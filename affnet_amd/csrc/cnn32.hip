@@ -1,5 +1,5 @@
 // Host layer of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet): argument checks, the trunk launch and every entry point built on it.
-// Every entry point fills a CnnCall and cnn_launch runs cnn_check -> trunk_launch -> aff_finish_affnet / aff_finish_orinet / aff_hardnet_head.
+// Every entry point fills a CnnCall and cnn_launch runs cnn_check -> aff_trunk_launch -> aff_finish_affnet / aff_finish_orinet / aff_hardnet_head.
 // No device code here: the trunk kernels are cnn_trunk.h, instantiated per net in cnn_trunk_affnet.hip / _orinet.hip / _hardnet.hip (design:
 // DESIGN.md section 4 and the head of cnn_trunk.h); the finish and head kernels with their launchers are cnn_heads.hip.  CnnCall, CnnArgs and the
 // prototypes that cross files are in common.h.
@@ -30,26 +30,32 @@ static int cnn_check(affnet_ctx* ctx, const CnnCall& c, int* rows) {
     return AFFNET_OK;
 }
 
-int aff_arith_index(const affnet_ctx* ctx) {
-    return ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);
+// The built instantiations, by (net, trunk form): the unit that holds each (the units are separate for the inliner's sake, see their heads)
+TrunkKernel aff_trunk_kernel(int kind, int form, bool stamps) {
+    typedef TrunkKernel (*Unit)(int, bool);
+    static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2 && TRUNK_EXACT == 0 && TRUNK_WINO == 1 && TRUNK_SPLIT2 == 2 && TRUNK_SPLIT3 == 3 &&
+                  TRUNK_WINO_F43 == 4 && TRUNK_WINO_POLY == 5 && TRUNK_FORMS == 6, "order of the table");
+    static const Unit unit[3][TRUNK_FORMS] = {{aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, nullptr, aff_trunk_affnet_poly},
+                                              {aff_trunk_orinet, nullptr, aff_trunk_orinet, aff_trunk_orinet, nullptr, nullptr},
+                                              {aff_trunk_hardnet, aff_trunk_hardnet_poly, aff_trunk_hardnet, aff_trunk_hardnet, aff_trunk_hardnet_f43, nullptr}};
+    if (kind < 0 || kind > 2 || form < 0 || form >= TRUNK_FORMS || !unit[kind][form]) return nullptr;
+    return unit[kind][form](form, stamps);
 }
 
-// wino: AffNet's Winograd instantiation (exact arithmetic) of shape form 1 or 2, 0 = none; reeval: the margin rule's flags for the direct AffNet trunk behind it; shape_op: see CnnArgs
-static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, int wino, const int32_t* reeval, int shape_op) {
+int aff_trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, int wino, const int32_t* reeval, int shape_op) {
+    // the trunk form, once: the split forms follow the context's arithmetic; exact AffNet runs the Winograd form asked for (wino = shape form 1 / 2), exact HardNet the call's descriptor form
+    int form = TRUNK_EXACT;
+    if (ctx->arith != AFFNET_ARITH_FP32_MFMA) form = ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? TRUNK_SPLIT2 : TRUNK_SPLIT3;
+    else if (c.kind == AFFNET_NET_AFFNET && wino) form = wino == 2 ? TRUNK_WINO_POLY : TRUNK_WINO;
+    else if (c.kind == AFFNET_NET_HARDNET && c.desc_form != AFFNET_DESC_FORM_DIRECT) form = c.desc_form == AFFNET_DESC_FORM_F43 ? TRUNK_WINO_F43 : TRUNK_WINO;
+    const bool stamps = ctx->dbg_time || c.dbg_layer >= 0;             // the stamped instantiation: dbg_time or a layer dump (exact mode only, see cnn_check)
+    const TrunkKernel kernel = aff_trunk_kernel(c.kind, form, stamps);
+    if (!kernel) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: no trunk kernel of net %d in form %d is built", c.kind, form);
     CnnArgs a;
     a.packed = c.packed; a.off = to_offsets(L, ctx->arith);            // the split copy of the active mode
-    a.wino_u = nullptr; a.reeval = reeval;
-    if ((c.kind == AFFNET_NET_ORINET || wino) && ctx->arith == AFFNET_ARITH_FP32_MFMA) {
-        const int rc = aff_wino_derive_u(ctx, c.kind, c.packed, L, c.st, &a.wino_u);
-        if (rc) return rc;
-    }
-    const bool poly = c.desc_form != AFFNET_DESC_FORM_DIRECT && c.kind == AFFNET_NET_HARDNET && ctx->arith == AFFNET_ARITH_FP32_MFMA;      // descriptor forms 1 / 2
-    const bool f43 = poly && c.desc_form == AFFNET_DESC_FORM_F43;
-    if (poly) {
-        int rc = aff_poly_derive_u(ctx, c.packed, L, c.st, &a.wino_u);
-        if (!rc && f43) rc = aff_f43_derive_u(ctx, c.packed, L, c.st);
-        if (rc) return rc;
-    }
+    a.reeval = reeval;
+    const int rc = aff_derive_u(ctx, c.kind, form, c.packed, L, c.st, &a.wino_u);
+    if (rc) return rc;
     a.patches = c.patches; a.lafs = c.lafs; a.ids = c.ids; a.count = c.count; a.n_max = c.n_max;
     a.out = (c.dbg_layer < 0) ? c.scratch : c.out;      // trunk kernels: HardNet conv5 tensor / AffNet, OriNet head partials
     a.dbg_layer = c.dbg_layer; a.dbg_out = c.dbg_out; a.dbg_time = ctx->dbg_time;
@@ -58,11 +64,7 @@ static int trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, d
     a.s3_alt = ctx->split3_variant;
     PyrSrc ps;
     aff_fill_pyr_src(ctx, &ps);
-    // the net's instantiation [exact, three bf16 terms, two fp16 terms][phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see cnn_check)
-    static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2, "trunk getter order");
-    static TrunkKernel (*const trunk_of[3])(int, bool) = {aff_trunk_affnet, aff_trunk_orinet, aff_trunk_hardnet};
-    const bool stamps = a.dbg_time || c.dbg_layer >= 0;
-    hipLaunchKernelGGL(wino == 2 ? aff_trunk_affnet_poly(stamps) : wino ? aff_trunk_affnet_wino(stamps) : (poly ? (f43 ? aff_trunk_hardnet_f43(stamps) : aff_trunk_hardnet_poly(stamps)) : trunk_of[c.kind](aff_arith_index(ctx), stamps)), grid, dim3(512), 0, c.st, a, ps);
+    hipLaunchKernelGGL(kernel, grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -77,13 +79,13 @@ static int cnn_launch(affnet_ctx* ctx, const CnnCall& c) {
     // rule on its partials (flags in the unused part of the scratch: 144 floats per row, 32 of them partials), the direct trunk on the flagged rows, which
     // overwrites their partials, then the finish + filter kernel as ever.  The same window, row counts and lazy predicate for all; nothing here depends on B or rows.
     const bool form1 = c.wino_reeval && c.kind == AFFNET_NET_AFFNET && c.fuse && c.dbg_layer < 0 && ctx->arith == AFFNET_ARITH_FP32_MFMA;
-    rc = trunk_launch(ctx, c, L, dim3(rows, B), form1 ? c.wino_reeval : 0, nullptr, c.shape_op);
+    rc = aff_trunk_launch(ctx, c, L, dim3(rows, B), form1 ? c.wino_reeval : 0, nullptr, c.shape_op);
     if (rc) return rc;
     if (form1) {
         int32_t* flags = reinterpret_cast<int32_t*>(c.scratch + (size_t)B * c.n_max * HEAD_PART_AFF);
         rc = aff_margin_affnet(ctx, c, L, rows, B, flags);
         if (rc) return rc;
-        rc = trunk_launch(ctx, c, L, dim3(rows, B), 0, flags, 0);
+        rc = aff_trunk_launch(ctx, c, L, dim3(rows, B), 0, flags, 0);
         if (rc) return rc;
     }
     if (c.dbg_layer < 0 && c.kind != AFFNET_NET_HARDNET) {
@@ -186,7 +188,7 @@ extern "C" int affnet_cnn32_debug_winograd_u(affnet_ctx* ctx, int net_kind, cons
     if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 1 && layer != 3 && layer != 5))
         return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32_debug_winograd_u: AffNet / OriNet, layer 1, 3 or 5");
     const float* u;
-    const int rc = aff_wino_derive_u(ctx, net_kind, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
+    const int rc = aff_derive_u(ctx, net_kind, net_kind == AFFNET_NET_AFFNET ? TRUNK_WINO : TRUNK_EXACT, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
     if (rc) return rc;
     return aff_copy_async(ctx, d_out, u + Wino16::offset(layer), (size_t)Wino16::floats(layer) * sizeof(float), (hipStream_t)stream);
 }

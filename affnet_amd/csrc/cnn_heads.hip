@@ -371,7 +371,7 @@ int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int 
         {hardnet_head_kernel<64>, hardnet_head_kernel<32>, hardnet_head_kernel<16>},
         {hardnet_head_s3_kernel<64, 3>, hardnet_head_s3_kernel<32, 3>, hardnet_head_s3_kernel<16, 3>},
         {hardnet_head_s3_kernel<64, 2>, hardnet_head_s3_kernel<32, 2>, hardnet_head_s3_kernel<16, 2>}};
-    const int ai = aff_arith_index(ctx);
+    const int ai = ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? 2 : (ctx->arith == AFFNET_ARITH_FP32_SPLIT3 ? 1 : 0);      // exact fp32, three bf16 terms, two fp16 terms
     const float* hw = c.packed + (ai == 2 ? L.head_h2 : (ai == 1 ? L.head_s3 : L.head_w));
     hipLaunchKernelGGL(heads[ai][mp == 64 ? 0 : (mp == 32 ? 1 : 2)], dim3(aff_cdiv(n_max, mp), HEAD_KSPLIT, B), dim3(256), 0, c.st, c.scratch, hw, c.count,
                        n_max, partial);

@@ -1502,7 +1502,7 @@ __device__ __forceinline__ void f43_store_lds(float* act, f32x4 bias, const f32x
 // A^T M A - t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3, operation by operation what wino_output does - before the next row starts.  Live: 4 accumulators, 4 U
 // fragments, 4 V fragments, t0 / t1.  Per K group the window rows 1 and 2 are read twice (32 instead of 16 ds_read_b128), the VALU work is the same.
 // U enters holding row 0 / group 0 of pass 0 (wino_prefetch_u_row) and rolls one step ahead in its single register set.
-// Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (cnn_trunk_orinet.hip: wino_derive_u_kernel).
+// Wu = U of the layer, [xi][CIN/16][kq][COUT][4], derived on the device from the blob's taps (derive_u.hip: derive_u_kernel).
 template <int NW, int CIN, int COUT, int H, int NB>
 __device__ __forceinline__ void wino_prefetch_u_row(const float* __restrict__ Wu, f32x4 (&U)[4], int wave, int lane) {
     const __amdgpu_buffer_rsrc_t r = weight_rsrc(Wu, 16 * CIN * COUT);
@@ -1933,7 +1933,7 @@ __device__ __forceinline__ void conv3x3_poly_mfma_rows(const float* act, const f
 // U lives in TWO sets of three fragments and rolls two rows ahead, as in conv3x3_poly_mfma_rows and for its reason: a row has 8 or 12 MFMAs, 256 .. 384 cycles of
 // the pipe, less than an L2 load takes - with one set one row ahead the ten steps ran at the load's latency (measured: conv2 9.2 k ticks against the direct form's 10.1 k).
 // Both sets enter holding rows 0 and 1 (poly16_prefetch_u, requested in front of the barrier before the layer).  Wu = the layer's 25 positions, [xi][CIN/16][kq][COUT][4], derived on
-// the device from the blob's taps (cnn_trunk_orinet.hip: wino_derive_u_kernel; poly_weight_transform).  tools/winograd_numerics.py: poly16_conv2 / poly16_conv4 mirror the order.
+// the device from the blob's taps (derive_u.hip: derive_u_kernel; poly_weight_transform).  tools/winograd_numerics.py: poly16_conv2 / poly16_conv4 mirror the order.
 template <int CIN, int COUT>
 __device__ __forceinline__ int poly16_u_lane(int cb, int G, int lane) {
     return ((lane >> 4) * COUT + cb * 16 + (lane & 15)) * 16 + G * (16 * COUT * 4);

@@ -19,7 +19,7 @@
 //     step's reads and transform between this step's MFMAs) and conv5 (conv3x3_wino_mfma_shared_v: V shared through LDS), U from the blob; in descriptor form 2
 //     conv3 as Winograd F(4x4, 3x3) (conv3x3_f43_mfma_shared_v: V shared through LDS, a wave pair per channel block), U derived in front of the launch;
 //     OriNet's conv1 / conv3 (conv3x3_wino_mfma_rows, one row of four transform positions at a time on 128 registers; U derived from the
-//     blob's taps by wino_derive_u_kernel, cnn_trunk_orinet.hip, in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
+//     blob's taps by derive_u_kernel, derive_u.hip, in front of every launch) and conv5 (conv3x3_wino_mfma_half_rows: a wave pair per channel block, two position rows
 //     each, one row exchanged through LDS in a fixed order, 2x2-pixel fragments straight into the head's LDS copy).  AffNet has both forms: the direct one
 //     (S3 = 0) and one with OriNet's Winograd conv1 / conv3 / conv5 and the head straight from conv5's fragments (S3 = 1).  The shape filter behind AffNet turns on the last bits of its output for a few rows, so
 //     the fused shape pass runs the Winograd form on every row and the direct form on the rows a margin rule flags (shape_filter.h, cnn32.hip).  The
@@ -34,7 +34,7 @@
 //     (cnn_heads.hip: hardnet_head_kernel + hardnet_finish_kernel: BN bias + L2 norm) follows; AffNet / OriNet reduce their heads' dot
 //     products per wave straight from the conv5 accumulators (head_partials, head_partials_wino, head_partials_ori_lds) and affnet_finish_kernel /
 //     orinet_finish_kernel (cnn_heads.hip) combine the eight partials per patch in fixed order (tanh, rectification / atan2).
-// Host side: cnn32.hip; the plain types both sides share (CnnArgs, PyrSrc, Wino16, HEAD_PART_*) are in common.h.
+// Host side: cnn32.hip; the plain types both sides share (CnnArgs, PyrSrc, TRUNK_*, HEAD_PART_*) are in common.h, the derived weights' layouts (Wino16, Poly32, F43) in weights_layout.h.
 #pragma once
 #include <math.h>
 
@@ -199,10 +199,6 @@ __device__ __forceinline__ void head_partials_ori_lds(const float* __restrict__ 
     ori_head_reduce<TM>(w, pbase, part, act, wave, lane);
 }
 
-// The one exact OriNet instantiation runs conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly16_mfma_rows).  A constant of the build, no run-time switch: the fused
-// and the staged path both run this kernel and are pinned to each other bit for bit.
-constexpr bool ORINET_POLY16 = true;
-
 #define CNN_STAMP(k)                                                                                     \
     do {                                                                                                 \
         if (STAMPS && a.dbg_time && lane == 0) a.dbg_time[((size_t)pidx * NW + wave) * 32 + (k)] = __builtin_readcyclecounter(); \
@@ -234,6 +230,20 @@ struct TrunkShape {
     static constexpr int G4 = pick_groups(2 * CB, T4M, T4N, 32, AREG), G5 = pick_groups(4 * CB, T4M, T4N, 32, AREG);
 };
 
+// What trunk form S3 (TRUNK_*, common.h) of net KIND runs in which way: the one place that reads the form's value.  The one exact OriNet instantiation has the Winograd
+// and the polyphase layers (no run-time switch: the fused and the staged path both run this kernel and are pinned to each other bit for bit).
+template <int KIND, int S3>
+struct TrunkTraits {
+    static_assert(S3 == TRUNK_EXACT || S3 == TRUNK_SPLIT2 || S3 == TRUNK_SPLIT3 || (S3 == TRUNK_WINO && KIND != AFFNET_NET_ORINET) ||
+                  (S3 == TRUNK_WINO_F43 && KIND == AFFNET_NET_HARDNET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET), "no such trunk form of this net (common.h: TRUNK_*)");
+    static constexpr bool EXACT = S3 != TRUNK_SPLIT2 && S3 != TRUNK_SPLIT3;     // fp32 operands on v_mfma_f32_16x16x4_f32
+    // 16-channel trunks: conv1 / conv3 / conv5 as Winograd F(2x2, 3x3) on 128 registers (conv5: a wave pair per channel block); conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
+    static constexpr bool WINO13 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || ((S3 == TRUNK_WINO || S3 == TRUNK_WINO_POLY) && KIND == AFFNET_NET_AFFNET);
+    static constexpr bool POLY16 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET);
+    // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2); form 2: conv3 as Winograd F(4x4, 3x3), V shared through LDS (conv1 in F(4x4, 3x3) has no loop yet: NOTES.md)
+    static constexpr bool POLY = (S3 == TRUNK_WINO || S3 == TRUNK_WINO_F43) && KIND == AFFNET_NET_HARDNET, F43_3 = S3 == TRUNK_WINO_F43 && KIND == AFFNET_NET_HARDNET;
+};
+
 template <int C, typename L, int NTHR>
 __device__ __forceinline__ void dump_planes(const float* act, float* dst) {
     constexpr int H = L::H;
@@ -260,9 +270,8 @@ struct SplitLays {
     static_assert(LQH::BYTES <= TrunkLds<CB>::ACT * 4 && LQH2::BYTES <= TrunkLds<CB>::ACT * 4, "pre-split layouts must fit the activation buffer");
 };
 
-// One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = 0 exact,
-// 3 / 2 = terms of the split-operand arithmetic, 1 = exact, AffNet with conv1 / conv3 / conv5 as Winograd, HardNet with conv2 / conv4 as polyphase Winograd besides,
-// 4 = HardNet as 1 with conv3 as Winograd F(4x4, 3x3) (descriptor form 2), 5 = AffNet as 1 with conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (shape form 2).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
+// One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = the trunk form (TRUNK_*, common.h;
+// TrunkTraits above says what each does - for the split-operand forms the value is the number of terms).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
 // kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 and conv3 in F(4x4, 3x3) in form 2), exact AffNet / OriNet, split HardNet,
 // split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
@@ -273,17 +282,8 @@ struct SplitLays {
 // of affnet_cnn32_debug_layer exist only there (26 stamp sites = 26 predicated stores + branches in every wave otherwise).
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
-    static_assert(S3 == 0 || S3 == 2 || S3 == 3 || (S3 == 1 && KIND != AFFNET_NET_ORINET) || (S3 == 4 && KIND == AFFNET_NET_HARDNET) || (S3 == 5 && KIND == AFFNET_NET_AFFNET),
-                  "S3 = number of terms of the split arithmetic; 1 = exact AffNet with Winograd conv1 / conv3 / conv5, exact HardNet with polyphase conv2 / conv4; "
-                  "4 = exact HardNet as 1 with conv3 as Winograd F(4x4, 3x3); 5 = exact AffNet as 1 with polyphase conv2 / conv4");
-    constexpr bool EXACT = S3 <= 1 || S3 == 4 || S3 == 5;                     // fp32 operands on v_mfma_f32_16x16x4_f32
-    constexpr bool WINO13 = (S3 == 0 && KIND == AFFNET_NET_ORINET) || ((S3 == 1 || S3 == 5) && KIND == AFFNET_NET_AFFNET);   // conv1 / conv3 as Winograd F(2x2, 3x3) on 128 registers
-    constexpr bool WINO5 = WINO13;                                            // conv5 as Winograd F(2x2, 3x3), a wave pair per channel block
-    constexpr bool POLY16 = (S3 == 0 && KIND == AFFNET_NET_ORINET && ORINET_POLY16) || (S3 == 5 && KIND == AFFNET_NET_AFFNET);   // 16-channel trunks: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) on 128 registers
-    constexpr bool POLY = (S3 == 1 || S3 == 4) && KIND == AFFNET_NET_HARDNET; // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
-    constexpr bool F43_1 = false;                                             // HardNet descriptor form 2, one flag per layer: conv1 as Winograd F(4x4, 3x3) - not built (NOTES.md)
-    constexpr bool F43_3 = S3 == 4 && KIND == AFFNET_NET_HARDNET;             // ... conv3 as Winograd F(4x4, 3x3), V shared through LDS
-    static_assert(!F43_1, "conv1 in F(4x4, 3x3) has no loop yet");
+    using F = TrunkTraits<KIND, S3>;
+    constexpr bool EXACT = F::EXACT, WINO13 = F::WINO13, POLY16 = F::POLY16, POLY = F::POLY, F43_3 = F::F43_3;
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     conv0_load_w<NW, CB, S::T1M, S::T1N>(a.packed + a.off.w[0], a.packed + a.off.b[0], w0, bias0, wave, lane);
     f32x4 b1[1][S::T1N];
     f32x4 Ur[4];                                                      // exact OriNet, Winograd AffNet: the rolling U register set of conv1 / conv3 / conv5
-    if constexpr (S3 == 0 && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
+    if constexpr (S3 == TRUNK_EXACT && KIND == AFFNET_NET_AFFNET) prefetch_b0<NW, CB, 32, S::T1M, S::T1N, 1>(a.packed + a.off.w[1], b1, wave, lane);
     if constexpr (WINO13) wino_prefetch_u_row<NW, CB, CB, 32, Wino16::NB1>(a.wino_u, Ur, wave, lane);
 
     // ---- input: load or sample 1024 pixels (PPT per thread), standardise, store padded ----------------
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         patch[y * WP32 + x] = 0.0f;
     }
     if constexpr (EXACT) zero_halo<LayC0, NTHR>(act, CB);                          // the halo of the flow's conv0 output layout
-    else if constexpr (S3 == 2) zero_halo_q<typename SplitLays<CB>::LR0, NTHR>(act);
+    else if constexpr (S3 == TRUNK_SPLIT2) zero_halo_q<typename SplitLays<CB>::LR0, NTHR>(act);
     else zero_halo_q<typename SplitLays<CB>::LQH, NTHR>(act);
     float sum = 0.f;
 #pragma unroll
@@ -380,10 +380,10 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // the head GEMM.
         // Form 1 (POLY): conv2 and conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly_mfma_rows) -
         // 25/36 of their MFMAs; a wave runs one unit per layer: in conv2 a tile block against a pair of channel blocks, in conv4 the one tile block against its own
-        // channel block.  Their transformed weights come from a.wino_u (Poly32), which poly_derive_u_kernel fills from the blob's taps in front of the launch; the first
+        // channel block.  Their transformed weights come from a.wino_u (Poly32), which derive_u_kernel fills from the blob's taps in front of the launch; the first
         // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the same statements for both forms.
         // Form 2 (F43_3) = form 1 with conv3 as Winograd F(4x4, 3x3) (cnn_mfma.h: conv3x3_f43_mfma_shared_v, f43_combine) - 288 instead of 512 MFMAs per wave; its
-        // weights lie behind the polyphase ones at a.wino_u + F43::BASE (f43_derive_u_kernel).  conv1 has a flag of its own (F43_1) and no F(4x4, 3x3) loop yet.
+        // weights lie behind the polyphase ones at a.wino_u + F43::BASE.  conv1 has no F(4x4, 3x3) loop yet (NOTES.md); its U is derived all the same.
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
         constexpr int NBP2 = (8 * 8 / 16) * (2 * CB / 16) / NW, NBP4 = (4 * 4 / 16) * (4 * CB / 16) / NW;      // polyphase passes per wave: conv2 a pair, conv4 one
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
     } else if constexpr (EXACT) {
         // Exact AffNet / OriNet.  OriNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
         // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which
-        // wino_derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 / conv5 as
+        // derive_u_kernel fills from the blob's taps in front of every launch.  AffNet, S3 = 0: conv1 .. conv5 in the direct form; S3 = 1: conv1 / conv3 / conv5 as
         // OriNet runs them.  AffNet's output decides the shape filter, whose eigenvalue test (shape_filter.h: d1 = tr^2 - 4 det > 0) turns on the LAST
         // bits of A for near-isotropic shapes, so another rounding alone changes which keypoints a call returns (measured: 124 of 128 000 ids at the headline
         // configuration): the rows where it could are recomputed by the S3 = 0 kernel (a.reeval).  conv0 (and the S3 = 0 kernel's conv5) in the direct form; conv2 / conv4
@@ -702,7 +702,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             f32x4 acc[T4M][T4N];
             conv3x3_mfma<NW, 2 * CB, 4 * CB, LayC3, 2, T4M, T4N, S::G4>(act, a.packed + a.off.w[4], b4, acc, wave, lane);
             CNN_STAMP(9);
-            if constexpr (WINO5) {
+            if constexpr (WINO13) {
                 wino5_prefetch_u(a.wino_u + Wino16::offset(5), Ur, wave, lane);
             } else {
                 prefetch_b0<NW, 4 * CB, 8, T4M, T4N, S::G5>(a.packed + a.off.w[5], b5, wave, lane);
@@ -716,9 +716,9 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         }
         if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
 
-        static_assert(!WINO5 || (Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL),
+        static_assert(!WINO13 || (Wino5::X >= 16 * LayC4::PSG && Wino5::X + Wino5::X_FLOATS <= TrunkLds<CB>::TOTAL),
                       "Winograd conv5: the exchange lies behind conv4's output inside the LDS array");
-        if constexpr (WINO5) {
+        if constexpr (WINO13) {
             // ---- conv5: 4CB -> 4CB @8x8, Winograd, a wave pair per channel block (the loop below, then wino5_combine), then the head's per-wave partial sums.
             // OriNet: the 2 x 2-pixel fragments go into the head's 10 x 10 copy (over conv4's output, which is dead by then).  AffNet's Winograd form: straight from the
             // combined fragments (head_partials_wino: no LDS copy, no barrier beyond the combine's).  Both request the head's weights in front of the combine's barrier ----
@@ -1060,4 +1060,12 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             head_partials<T4M>(a.packed + a.off.head_w, bias5s, acc5, a.out + pidx * HEAD_PART_AFF, wave, lane_h);
         CNN_STAMP(13);
     }
+}
+
+// The getter of a cnn_trunk_*.hip unit: instantiates net KIND in FORMS..., product and stamped, and returns the one asked for; NULL for a form that is not among them
+template <int KIND, int... FORMS>
+TrunkKernel trunk_unit(int form, bool stamps) {
+    TrunkKernel k = nullptr;
+    ((form == FORMS ? (void)(k = !stamps ? cnn32_trunk_kernel<KIND, 8, false, FORMS> : cnn32_trunk_kernel<KIND, 8, true, FORMS>) : (void)0), ...);
+    return k;
 }

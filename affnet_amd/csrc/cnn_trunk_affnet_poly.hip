@@ -1,10 +1,8 @@
-// The first AffNet trunk of shape form 2 (affnet_set_shape_form): cnn32_trunk_kernel<AffNet, 8, *, 5> (cnn_trunk.h) - the Winograd trunk of form 1 (conv1 / conv3 / conv5 as
+// The first AffNet trunk of shape form 2 (affnet_set_shape_form): cnn32_trunk_kernel<AffNet, 8, *, TRUNK_WINO_POLY> (cnn_trunk.h) - the Winograd trunk of form 1 (conv1 / conv3 / conv5 as
 // F(2x2, 3x3), the head from conv5's fragments) with conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (cnn_mfma.h: conv3x3_poly16_mfma_rows); U of all five layers from
-// aff_wino_derive_u.  A unit of its own, as the HardNet forms are: compiled next to the kernels of cnn_trunk_affnet.hip it would change their code, and form 1's layer 4 is
+// aff_derive_u.  A unit of its own, as the HardNet forms are: compiled next to the kernels of cnn_trunk_affnet.hip it would change their code, and form 1's layer 4 is
 // pinned bit for bit.
 #include "cnn_trunk.h"
 
-// [phase stamps]; stamps = dbg_time or a layer dump
-TrunkKernel aff_trunk_affnet_poly(bool stamps) {
-    return stamps ? cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, true, 5> : cnn32_trunk_kernel<AFFNET_NET_AFFNET, 8, false, 5>;
-}
+// by trunk form [phase stamps]; stamps = dbg_time or a layer dump (exact mode only, see cnn_check).
+TrunkKernel aff_trunk_affnet_poly(int form, bool stamps) { return trunk_unit<AFFNET_NET_AFFNET, TRUNK_WINO_POLY>(form, stamps); }

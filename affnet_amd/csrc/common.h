@@ -118,17 +118,12 @@ struct affnet_ctx {
     // the whole path captured as one HIP graph (affnet_graph_capture_extract): one launch instead of ~45 for latency-bound callers
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
-    // Winograd weights U = G g G^T of conv1 / conv3 / conv5 of the exact AffNet / OriNet trunks, derived from the caller's blob in front of every trunk launch
-    // (cnn_trunk_orinet.hip: wino_derive_u_kernel); the only device memory a context owns, allocated on first use (aff_wino_u_ensure)
-    float* wino_u = nullptr;
-    // Polyphase weights of conv2 / conv4 of the exact HardNet trunk in descriptor form 1 (Poly32), derived the same way (cnn_trunk_hardnet_poly.hip: poly_derive_u_kernel,
-    // aff_poly_u_ensure)
-    // ... and behind them, in the same buffer, form 2's F(4x4, 3x3) weights of conv1 / conv3 (F43; cnn_trunk_hardnet_f43.hip: f43_derive_u_kernel)
-    float* poly_u = nullptr;
+    // The transformed weights that are no blob sections (weights_layout.h: DerivedU, a region per net), derived from the caller's blob in front of every trunk launch that
+    // reads them (derive_u.hip: aff_derive_u); the only device memory a context owns, allocated on first use (aff_derived_u_ensure)
+    float* derived_u = nullptr;
     int desc_form = AFFNET_DESC_FORM_F43;           // fused exact-fp32 HardNet trunk (affnet_set_desc_form): stride-2 layers in the direct form, or as polyphase Winograd F(2x2, 2x2), or that with conv3 as F(4x4, 3x3)
     ~affnet_ctx() {
-        if (wino_u) (void)hipFree(wino_u);
-        if (poly_u) (void)hipFree(poly_u);
+        if (derived_u) (void)hipFree(derived_u);
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
         if (graph) (void)hipGraphDestroy(graph);
         for (auto& e : prof_ev) (void)hipEventDestroy(e);
@@ -236,9 +231,9 @@ struct PyrSrc {            // pyramid sampling source (fused sampler)
 struct CnnArgs {
     const float* packed;
     NetOffsets off;
-    const float* wino_u;   // exact OriNet, Winograd AffNet: U = G g G^T of conv1, conv3 and conv5, derived from the blob in front of this launch (wino_derive_u_kernel);
-                           // HardNet form 1: the polyphase U of conv2 and conv4 (Poly32, poly_derive_u_kernel); form 2: behind it at F43::BASE the F(4x4, 3x3) U of
-                           // conv1 / conv3 (F43, f43_derive_u_kernel)
+    const float* wino_u;   // the net's region of derived weights (aff_derive_u in front of this launch), NULL for a form that reads none.  Exact OriNet, Winograd AffNet:
+                           // Wino16 (U = G g G^T of conv1, conv3 and conv5, the polyphase U of conv2 and conv4 behind them); HardNet form 1: Poly32 (the polyphase U of
+                           // conv2 and conv4); form 2: behind it at F43::BASE the F(4x4, 3x3) U of conv1 / conv3 (F43)
     const int32_t* reeval; // direct AffNet trunk behind the Winograd one (shape form 1): per-row flags of the margin rule [image * n_max + row], a workgroup whose flag is 0 returns at once; NULL = every row
     const float* patches;  // (n,32,32) or NULL -> sample from the pyramid
     const float* lafs;     // normalised LAFs when sampling
@@ -263,7 +258,15 @@ struct CnnArgs {
     int32_t* shape_cnt;
     int shape_op;
 };
-// (the split-operand variants are template instantiations: cnn32_trunk_kernel<KIND, NW, STAMPS, S3>, S3 = 3 bf16 terms or 2 fp16 terms; 0 = exact)
+
+// Forms of a trunk: the values of cnn32_trunk_kernel<KIND, NW, STAMPS, S3>'s last template argument, part of the kernels' names.  What a (net, form) pair runs: TrunkTraits (cnn_trunk.h); which pairs are built: aff_trunk_kernel (cnn32.hip).
+constexpr int TRUNK_EXACT = 0;       // exact fp32.  AffNet: every layer direct; OriNet: conv1 / conv3 / conv5 Winograd F(2x2, 3x3), conv2 / conv4 polyphase; HardNet: descriptor form 0
+constexpr int TRUNK_WINO = 1;        // exact fp32.  AffNet: conv1 / conv3 / conv5 Winograd (shape form 1); HardNet: TRUNK_EXACT with conv2 / conv4 polyphase (descriptor form 1)
+constexpr int TRUNK_SPLIT2 = 2;      // two fp16 terms per operand (AFFNET_ARITH_FP32_SPLIT2H); the value is the number of terms
+constexpr int TRUNK_SPLIT3 = 3;      // three bf16 terms per operand (AFFNET_ARITH_FP32_SPLIT3); the value is the number of terms
+constexpr int TRUNK_WINO_F43 = 4;    // exact fp32, HardNet: TRUNK_WINO with conv3 as Winograd F(4x4, 3x3) (descriptor form 2)
+constexpr int TRUNK_WINO_POLY = 5;   // exact fp32, AffNet: TRUNK_WINO with conv2 / conv4 polyphase (shape form 2)
+constexpr int TRUNK_FORMS = 6;
 
 // the lazy-evaluation predicate above, for the trunk and finish kernels
 __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, int image, int which = CNT_SURVIVED1) {
@@ -271,24 +274,6 @@ __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, i
     const int32_t* c = skip_cnt + (size_t)image * CNT_TOTAL;
     return c[CNT_SEL_MODE] == 1 && c[which] >= skip_n;
 }
-
-// U = G g G^T of the Winograd layers of the exact OriNet trunk (conv1 16 -> 16, conv3 32 -> 32, conv5 64 -> 64; the AffNet blob has the same shapes and the debug accessor derives it too), in w_tap_index order like NetLayout::w_wino.
-// Not part of the blob (its size and hash are pinned, and a blob packed by an older library stays valid): derived on the device from the blob's
-// BN-folded fp32 taps into a buffer the context owns, one region per net kind.
-struct Wino16 {
-    static constexpr int U1 = 16 * 16 * 16, U3 = 16 * 32 * 32, U5 = 16 * 64 * 64;
-    static constexpr int PAIRS = 16 * 16 + 32 * 32 + 64 * 64;                        // (cin, cout) pairs of the three layers
-    // ... and behind them the 25 polyphase positions (weights_layout.h: poly_weight_transform) of the stride-2 layers conv2 16 -> 32 and conv4 32 -> 64 (51 KB + 205 KB), for
-    // AffNet's shape form 2 and the exact OriNet trunk; appended, so that the Winograd sections stay where they were
-    static constexpr int P2 = 25 * 16 * 32, P4 = 25 * 32 * 64;
-    static constexpr int PAIRS_POLY = 16 * 32 + 32 * 64;
-    static constexpr int FLOATS = U1 + U3 + U5 + P2 + P4;                            // floats per net
-    static constexpr int NB1 = 2, NB3 = 1;                                           // (tile block, channel block) passes per wave: 16 x 1 / 8, 4 x 2 / 8
-    static constexpr int offset(int layer) {
-        return layer == 1 ? 0 : (layer == 3 ? U1 : (layer == 5 ? U1 + U3 : (layer == 2 ? U1 + U3 + U5 : U1 + U3 + U5 + P2)));
-    }
-    static constexpr int floats(int layer) { return layer == 1 ? U1 : (layer == 3 ? U3 : (layer == 5 ? U5 : (layer == 2 ? P2 : P4))); }
-};
 
 struct ShapeFuse {           // finish + shape filter in one kernel (pointers of image 0; strides like shape_filter_kernel)
     const float* resp; const float* lafs; float* key; int32_t* good; int32_t* cnt;
@@ -313,7 +298,7 @@ struct CnnCall {
     float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
 };
 
-// kernel of one trunk instantiation, as the per-net getters below return it
+// kernel of one trunk instantiation
 typedef void (*TrunkKernel)(CnnArgs, PyrSrc);
 
 // context.hip
@@ -355,8 +340,6 @@ void aff_denorm_sel_fill(affnet_ctx* ctx, int ps, float* d_lafs_px, int32_t* d_i
 int aff_denorm_level_select(affnet_ctx* ctx, const float* d_lafs_norm_in, float* d_lafs_px, const int32_t* d_count, int n_max, int ps, int32_t* d_ids,
                             float* d_lafs_norm, hipStream_t st);
 
-// cnn32.hip: 0 = exact fp32, 1 = three bf16 terms, 2 = two fp16 terms: index of the context's arithmetic in the trunk and head kernel tables
-int aff_arith_index(const affnet_ctx* ctx);
 // cnn32.hip: the fused launches of affnet_describe_detected (AffNet + shape filter on a row window, OriNet + rotation, HardNet with
 // the stage mark between trunk and head)
 int aff_affnet_filter_rows(affnet_ctx* ctx, const float* packed, const float* resp, const float* lafs, const int32_t* ids, const int32_t* count,
@@ -369,27 +352,18 @@ int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const f
 // cnn32.hip: HardNet on a patch tensor in descriptor form `form` (1 or 2), for the probe library (the public patch-tensor calls run form 0); dbg_layer >= 0: layer dump of patch 0
 int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st,
                              int form = AFFNET_DESC_FORM_POLYPHASE);
+// cnn32.hip: the instantiation of net `kind` in trunk form `form` (TRUNK_*) [phase stamps]; NULL for a pair that is not built
+TrunkKernel aff_trunk_kernel(int kind, int form, bool stamps);
+// cnn32.hip: one trunk launch of `c` on `grid` = (rows, images), derived weights in front.  wino: AffNet's Winograd instantiation of shape form 1 / 2, 0 = none; reeval: the margin rule's flags for the direct AffNet trunk behind it; shape_op: see CnnArgs
+int aff_trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3 grid, int wino, const int32_t* reeval, int shape_op);
 
-// cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip: the net's trunk instantiation [aff_arith_index][phase stamps]
-TrunkKernel aff_trunk_affnet(int arith_index, bool stamps);
-TrunkKernel aff_trunk_affnet_wino(bool stamps);          // exact fp32 with conv1 / conv3 / conv5 as Winograd F(2x2, 3x3): the first trunk of shape form 1
-TrunkKernel aff_trunk_orinet(int arith_index, bool stamps);
-TrunkKernel aff_trunk_hardnet(int arith_index, bool stamps);
-// cnn_trunk_affnet_poly.hip: the Winograd AffNet trunk with conv2 / conv4 as polyphase Winograd F(2x2, 2x2): the first trunk of shape form 2 [phase stamps]
-TrunkKernel aff_trunk_affnet_poly(bool stamps);
-// cnn_trunk_hardnet_poly.hip: the exact HardNet trunk with conv2 / conv4 as polyphase Winograd F(2x2, 2x2) (descriptor form 1) [phase stamps], and the same pair as above
-// for the polyphase weights of conv2 / conv4 of a HardNet blob
-TrunkKernel aff_trunk_hardnet_poly(bool stamps);
-int aff_poly_u_ensure(affnet_ctx* ctx);
-int aff_poly_derive_u(affnet_ctx* ctx, const float* packed, const NetLayout& L, hipStream_t st, const float** u);
-// cnn_trunk_hardnet_f43.hip: the exact HardNet trunk of descriptor form 2 (form 1 with conv3 as Winograd F(4x4, 3x3)) [phase stamps]; derive the F(4x4, 3x3) weights of
-// conv1 / conv3 of a HardNet blob behind the polyphase ones in the context's buffer (at F43::BASE floats from what aff_poly_derive_u returns)
-TrunkKernel aff_trunk_hardnet_f43(bool stamps);
-int aff_f43_derive_u(affnet_ctx* ctx, const float* packed, const NetLayout& L, hipStream_t st);
-// cnn_trunk_orinet.hip: allocate the context's derived-weights buffer (before a stream capture begins: no allocation inside one); derive U of
-// conv1 / conv3 / conv5 of an AffNet or OriNet blob into the context's region of that net kind, *u = that region
-int aff_wino_u_ensure(affnet_ctx* ctx);
-int aff_wino_derive_u(affnet_ctx* ctx, int kind, const float* packed, const NetLayout& L, hipStream_t st, const float** u);
+// cnn_trunk_*.hip: the unit's instantiations, by trunk form [phase stamps]; NULL for a form the unit does not build.  Called by aff_trunk_kernel only.
+TrunkKernel aff_trunk_affnet(int form, bool stamps), aff_trunk_affnet_poly(int form, bool stamps), aff_trunk_orinet(int form, bool stamps);
+TrunkKernel aff_trunk_hardnet(int form, bool stamps), aff_trunk_hardnet_poly(int form, bool stamps), aff_trunk_hardnet_f43(int form, bool stamps);
+// derive_u.hip: allocate the context's buffer of derived weights (before a stream capture begins: no allocation inside one)
+int aff_derived_u_ensure(affnet_ctx* ctx);
+// derive_u.hip: derive what trunk form `form` of net `kind` reads from `packed` into that net's region of the context's buffer; *region = it (CnnArgs::wino_u), or NULL and no launch for a form that reads none
+int aff_derive_u(affnet_ctx* ctx, int kind, int form, const float* packed, const NetLayout& L, hipStream_t st, const float** region);
 
 // cnn_heads.hip: what cnn_launch runs behind a trunk launch: AffNet / OriNet finish kernel on `rows` rows of the window of B images, HardNet
 // head GEMM + finish kernel over all rows

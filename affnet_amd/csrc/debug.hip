@@ -80,23 +80,16 @@ extern "C" int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3])
     return AFFNET_OK;
 }
 
-// The Winograd AffNet trunk (the first trunk of shape form 1) on a patch tensor, which no entry point of the product library runs: U derived in front of the launch
-// as cnn32.hip's trunk_launch does; the stamped instantiation when a layer dump is asked for or the context has a stamp buffer (affnet_cnn32_debug_timing).
+// The Winograd AffNet trunk (the first trunk of shape form 1) on a patch tensor, which no entry point of the product library runs: cnn32.hip's trunk launch (U derived in
+// front of it; the stamped instantiation when a layer dump is asked for or the context has a stamp buffer, affnet_cnn32_debug_timing) without a finish stage.
 // poly: the first trunk of shape form 2 (conv2 / conv4 polyphase) instead.
 static int probe_affnet_wino(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, int layer, hipStream_t st, bool poly = false) {
     if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_affnet_wino: AFFNET_ARITH_FP32_MFMA only");
-    const NetLayout L = net_layout(AFFNET_NET_AFFNET);
-    CnnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.packed = d_packed; a.off = to_offsets(L, ctx->arith);
-    const int rc = aff_wino_derive_u(ctx, AFFNET_NET_AFFNET, d_packed, L, st, &a.wino_u);
-    if (rc) return rc;
-    a.patches = d_patches; a.n_max = n; a.out = d_out; a.dbg_layer = layer; a.dbg_out = d_out; a.dbg_time = ctx->dbg_time;
-    PyrSrc ps;
-    memset(&ps, 0, sizeof(ps));                          // patch tensors: nothing is sampled
-    hipLaunchKernelGGL(poly ? aff_trunk_affnet_poly(layer >= 0 || a.dbg_time) : aff_trunk_affnet_wino(layer >= 0 || a.dbg_time), dim3(n, 1), dim3(512), 0, st, a, ps);
-    AFF_LAUNCH_CHECK(ctx);
-    return AFFNET_OK;
+    CnnCall c;
+    c.kind = AFFNET_NET_AFFNET; c.packed = d_packed; c.patches = d_patches; c.n_max = n; c.st = st;
+    c.out = d_out; c.scratch = d_out;                    // a layer dump or the head partials
+    c.dbg_layer = layer; c.dbg_out = d_out;
+    return aff_trunk_launch(ctx, c, net_layout(AFFNET_NET_AFFNET), dim3(n, 1), poly ? 2 : 1, nullptr, 0);
 }
 
 extern "C" int affnet_probe_affnet_wino_layer(affnet_ctx* ctx, int net_kind, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
@@ -125,14 +118,19 @@ extern "C" int affnet_probe_affnet_poly_partials(affnet_ctx* ctx, const float* d
     return probe_affnet_wino(ctx, d_packed, d_patches, n, d_partials, -1, (hipStream_t)stream, true);
 }
 
+// `floats` derived weights at `offset` of the region that trunk form `form` of net `kind` reads, derived from d_packed on the stream and copied to d_out
+static int probe_derived_u(affnet_ctx* ctx, int kind, int form, const float* d_packed, int offset, int floats, float* d_out, void* stream) {
+    const float* u;
+    const int rc = aff_derive_u(ctx, kind, form, d_packed, net_layout(kind), (hipStream_t)stream, &u);
+    if (rc) return rc;
+    return aff_copy_async(ctx, d_out, u + offset, (size_t)floats * sizeof(float), (hipStream_t)stream);
+}
+
 extern "C" int affnet_probe_trunk16_poly_u(affnet_ctx* ctx, int net_kind, const float* d_packed, int layer, float* d_out, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !d_packed || !d_out || (net_kind != AFFNET_NET_AFFNET && net_kind != AFFNET_NET_ORINET) || (layer != 2 && layer != 4))
         return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_trunk16_poly_u: AffNet / OriNet, layer 2 or 4");
-    const float* u;
-    const int rc = aff_wino_derive_u(ctx, net_kind, d_packed, net_layout(net_kind), (hipStream_t)stream, &u);
-    if (rc) return rc;
-    return aff_copy_async(ctx, d_out, u + Wino16::offset(layer), (size_t)Wino16::floats(layer) * sizeof(float), (hipStream_t)stream);
+    return probe_derived_u(ctx, net_kind, net_kind == AFFNET_NET_AFFNET ? TRUNK_WINO_POLY : TRUNK_EXACT, d_packed, Wino16::offset(layer), Wino16::floats(layer), d_out, stream);
 }
 
 extern "C" int affnet_probe_hardnet_poly_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
@@ -150,10 +148,7 @@ extern "C" int affnet_probe_hardnet_poly_forward(affnet_ctx* ctx, const float* d
 extern "C" int affnet_probe_hardnet_poly_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !d_packed || !d_out || (layer != 2 && layer != 4)) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_poly_u: layer 2 or 4");
-    const float* u;
-    const int rc = aff_poly_derive_u(ctx, d_packed, net_layout(AFFNET_NET_HARDNET), (hipStream_t)stream, &u);
-    if (rc) return rc;
-    return aff_copy_async(ctx, d_out, u + Poly32::offset(layer), (size_t)Poly32::floats(layer) * sizeof(float), (hipStream_t)stream);
+    return probe_derived_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO, d_packed, Poly32::offset(layer), Poly32::floats(layer), d_out, stream);
 }
 
 extern "C" int affnet_probe_hardnet_f43_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
@@ -171,7 +166,5 @@ extern "C" int affnet_probe_hardnet_f43_forward(affnet_ctx* ctx, const float* d_
 extern "C" int affnet_probe_hardnet_f43_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream) {
     AFF_DEVICE(ctx);
     if (!ctx || !d_packed || !d_out || (layer != 1 && layer != 3)) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_f43_u: layer 1 or 3");
-    const int rc = aff_f43_derive_u(ctx, d_packed, net_layout(AFFNET_NET_HARDNET), (hipStream_t)stream);
-    if (rc) return rc;
-    return aff_copy_async(ctx, d_out, ctx->poly_u + F43::BASE + F43::offset(layer), (size_t)F43::floats(layer) * sizeof(float), (hipStream_t)stream);
+    return probe_derived_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO_F43, d_packed, F43::BASE + F43::offset(layer), F43::floats(layer), d_out, stream);
 }

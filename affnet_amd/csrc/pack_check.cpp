@@ -1,13 +1,15 @@
-// Stand-alone host check of the weight packer (weights_pack.hip compiled as C++) under the address and undefined-behaviour sanitizers:
-// build_pack_check.sh builds and runs it.  No GPU, no HIP runtime.  Every array has exactly the size the boundary documents (new
-// float[exact]), so an over-read or over-write by a single element is reported.
+// Stand-alone host check of the weight packer (weights_pack.hip compiled as C++) and of the derived-weights tables and routine (weights_layout.h: derive_u_pair, the host
+// side of derive_u_kernel) under the address and undefined-behaviour sanitizers: build_pack_check.sh builds and runs it.  No GPU, no HIP runtime.  Every array has exactly
+// the size the boundary documents (new float[exact]), so an over-read or over-write by a single element is reported.
 #include <math.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <initializer_list>
 #include <memory>
 
 #include "../../include/affnet_hip.h"
+#include "weights_layout.h"
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "pack_check: line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
 
@@ -93,8 +95,64 @@ static int check_kind(int kind) {
     return 0;
 }
 
+// ---- derived weights.  The layouts the trunk kernels read, as numbers: a table that moved a section fails here before it produces valid floats in the wrong place.
+static_assert(Wino16::offset(1) == 0 && Wino16::offset(3) == 4096 && Wino16::offset(5) == 20480 && Wino16::offset(2) == 86016 && Wino16::offset(4) == 98816 && Wino16::FLOATS == 150016 && Wino16::PAIRS == 7936, "Wino16");
+static_assert(Poly32::offset(2) == 0 && Poly32::offset(4) == 51200 && Poly32::FLOATS == 256000 && Poly32::PAIRS == 10240, "Poly32");
+static_assert(F43::BASE == 256000 && F43::offset(1) == 0 && F43::offset(3) == 36864 && F43::FLOATS == 184320 && F43::PAIRS == 5120, "F43");
+
+// Table t of a `kind` blob: derive_u_pair for every pair index into a destination of exactly want_floats floats; every float is written by the pair that owns it and by
+// no other, and holds the family's transform of the 9 taps that plain (layer, tap, cin, cout) indexing finds in the blob.
+static int check_derived(const char* name, int kind, const DerivedTable& t, int want_sections, size_t want_floats) {
+    const NetLayout L = net_layout(kind); const NetOffsets off = to_offsets(L);
+    CHECK(L.total == affnet_cnn32_packed_floats(kind) && t.n == want_sections && t.n <= DERIVED_MAX && (size_t)t.floats == want_floats && t.pairs % 256 == 0);
+    const std::unique_ptr<float[]> blob = filled(L.total, 0.2f, 0.f), U(new float[want_floats]), want(new float[want_floats]);
+    const std::unique_ptr<unsigned char[]> owned(new unsigned char[want_floats]());
+    const float sentinel = -12345.f;                     // no transform of taps in [-0.1, 0.1) comes near it
+    for (size_t i = 0; i < want_floats; ++i) U[i] = sentinel;
+    size_t pairs = 0, floats = 0;
+    for (int i = 0; i < t.n; ++i) {
+        const DerivedSection& s = t.s[i];
+        const int xi = s.family == DERIVED_WINO ? 16 : s.family == DERIVED_POLY ? 25 : 36;
+        CHECK(s.layer >= 1 && s.layer <= 5 && s.cin == L.cin[s.layer] && s.cout == L.cout[s.layer] && (size_t)s.pair0 == pairs && s.family >= 0 && s.family <= DERIVED_F43);
+        for (int c = 0; c < s.cin; ++c)
+            for (int n = 0; n < s.cout; ++n, ++pairs) {
+                float g[9], u[36];
+                for (int tap = 0; tap < 9; ++tap) g[tap] = blob[L.w_off[s.layer] + w_tap_index(tap, c, n, s.cin, s.cout)];
+                if (s.family == DERIVED_WINO) wino_weight_transform(g, u);
+                else if (s.family == DERIVED_POLY) poly_weight_transform(g, u);
+                else f43_weight_transform(g, u);
+                const size_t e = s.pair0 + w_tap_index(0, c, n, s.cin, s.cout);        // distinct per pair, as the pair's floats are
+                CHECK(e < (size_t)t.pairs);
+                for (int p = 0; p < xi; ++p, ++floats) {  // the floats of this pair: nobody's yet, untouched so far
+                    const size_t d = s.dst + w_tap_index(p, c, n, s.cin, s.cout);
+                    CHECK(d < want_floats && !owned[d] && U[d] == sentinel);
+                    owned[d] = 1; want[d] = u[p];
+                }
+                derive_u_pair(t, (int)e, blob.get(), off.w, U.get());
+            }
+    }
+    for (int e = t.pairs; e < t.pairs + 256; ++e) derive_u_pair(t, e, blob.get(), off.w, U.get());      // threads past the last pair: nothing
+    // every pair index was called, every float has its one owner (distinct, and as many as there are) and holds that pair's value: no other pair touched it
+    CHECK(pairs == (size_t)t.pairs && floats == want_floats && memcmp(U.get(), want.get(), want_floats * sizeof(float)) == 0);
+    printf("derived %s: %d sections, %d pairs, %zu floats: every float written once, by its own pair, with its transform\n", name, t.n, t.pairs, want_floats);
+    return 0;
+}
+
+// the regions of the context's buffer: disjoint, back to back in this order, and together the buffer; form 2's one launch fills the last two
+static int check_regions() {
+    const size_t t16 = derived_trunk16().floats, poly = derived_hardnet_poly().floats, f43 = derived_hardnet_f43().floats;
+    CHECK(DerivedU::AFFNET == 0 && DerivedU::ORINET == t16 && DerivedU::HARDNET == 2 * t16 && DerivedU::HARDNET_F43 == 2 * t16 + poly && DerivedU::FLOATS == 2 * t16 + poly + f43);
+    CHECK(DerivedU::region(AFFNET_NET_AFFNET) == DerivedU::AFFNET && DerivedU::region(AFFNET_NET_ORINET) == DerivedU::ORINET && DerivedU::region(AFFNET_NET_HARDNET) == DerivedU::HARDNET);
+    CHECK(derived_hardnet_form2().floats == poly + f43);
+    return 0;
+}
+
 int main() {
     for (int kind = 0; kind <= AFFNET_NET_AFFNET_FULLCONV; ++kind)
         if (check_kind(kind)) return 1;
+    if (check_derived("AffNet", AFFNET_NET_AFFNET, derived_trunk16(), 5, 150016) || check_derived("OriNet", AFFNET_NET_ORINET, derived_trunk16(), 5, 150016) ||
+        check_derived("HardNet polyphase", AFFNET_NET_HARDNET, derived_hardnet_poly(), 2, 256000) || check_derived("HardNet F(4x4, 3x3)", AFFNET_NET_HARDNET, derived_hardnet_f43(), 2, 184320) ||
+        check_derived("HardNet form 2", AFFNET_NET_HARDNET, derived_hardnet_form2(), 4, 256000 + 184320) || check_regions())
+        return 1;
     return 0;
 }

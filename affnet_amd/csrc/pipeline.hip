@@ -285,8 +285,7 @@ extern "C" int affnet_graph_capture_extract(affnet_ctx* ctx, const affnet_nets* 
     if (ctx->prof_on) return aff_fail(ctx, AFFNET_ERR_INVALID, "graph_capture: switch stage profiling off first (its events are per call)");
     if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
     if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
-    { const int rcu = aff_wino_u_ensure(ctx); if (rcu) return rcu; }
-    { const int rcu = aff_poly_u_ensure(ctx); if (rcu) return rcu; }
+    { const int rcu = aff_derived_u_ensure(ctx); if (rcu) return rcu; }
     AFF_HIP(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     const int rc = affnet_extract_features(ctx, nets, d_img, do_ori, d_lafs_px, d_resp, d_ids, d_desc, d_count, stream);
     hipGraph_t g = nullptr;

@@ -145,7 +145,7 @@ static inline TfeatLayout tfeat_layout() {
 // ---- Winograd F(2x2, 3x3) weight transform --------------------------------------------------------------
 // U = G g G^T of one 3x3 filter g[ky * 3 + kx] into U[xi = 4 i + j], along x and then along y, one fp32 rounding per operation (the
 // library is built with -ffp-contract=off).  The single definition of the operation order: the packer (HardNet's Winograd section) and
-// wino_derive_u_kernel (OriNet) call it, tools/winograd_numerics.py: weight_transform mirrors it and the tests compare the two bit for bit.
+// derive_u_pair (below) call it, tools/winograd_numerics.py: weight_transform mirrors it and the tests compare the two bit for bit.
 AFF_HOST_DEVICE inline void wino_g_axis(float g0, float g1, float g2, float* o, int stride) {
     const float s = g0 + g2;
     o[0] = g0; o[stride] = 0.5f * (s + g1); o[2 * stride] = 0.5f * (s - g1); o[3 * stride] = g2;
@@ -163,7 +163,7 @@ AFF_HOST_DEVICE inline void wino_weight_transform(const float g[9], float U[16])
 // the even samples and serves both outputs of a tile as it is: (g0, g0 + g2, g2 | g1, g1), no constant but 1.  U[xi] of one filter g[ky * 3 + kx], along x
 // and then along y, one fp32 rounding per sum; positions xi = 3 i + j (odd rows, odd columns: 9), 9 + 2 i + j (odd rows, even columns: 6),
 // 15 + 3 i + j (even rows, odd columns: 6), 21 + 2 i + j (even / even: 4).  Stored in w_tap_index order over the 25 positions.  The single definition of
-// the operation order: poly_derive_u_kernel (cnn_trunk_hardnet_poly.hip) calls it, tools/winograd_numerics.py: poly_weight_transform mirrors it.
+// the operation order: derive_u_pair (below) calls it, tools/winograd_numerics.py: poly_weight_transform mirrors it.
 #define POLY_XI 25
 AFF_HOST_DEVICE inline void poly_weight_transform(const float g[9], float U[POLY_XI]) {
     float t[3][3];                              // along x, odd phase: t[ky][j]; the even phase is g[3 ky + 1] itself
@@ -183,20 +183,12 @@ AFF_HOST_DEVICE inline void poly_weight_transform(const float g[9], float U[POLY
     }
 }
 
-// U of HardNet's conv2 (32 -> 64) and conv4 (64 -> 128), one after the other in the buffer the context owns (205 KB + 819 KB)
-struct Poly32 {
-    static constexpr int U2 = POLY_XI * 32 * 64, U4 = POLY_XI * 64 * 128, FLOATS = U2 + U4;
-    static constexpr int PAIRS = 32 * 64 + 64 * 128;                             // (cin, cout) pairs of the two layers
-    static constexpr int offset(int layer) { return layer == 2 ? 0 : U2; }
-    static constexpr int floats(int layer) { return layer == 2 ? U2 : U4; }
-};
-
 // ---- Winograd F(4x4, 3x3) weight transform (HardNet form 2: conv3; conv1 is derived as well) ---------------------------------------------
 // Standard F(4, 3) on the points 0, +-1, +-2.  Along an axis U = G g with G's rows (1/4, 0, 0), (-1/6)(1, 1, 1), (-1/6)(1, -1, 1), (1/24, 1/12, 1/6),
 // (1/24, -1/12, 1/6), (0, 0, 1), in ONE operation order, one fp32 rounding per operation (1/6, 1/12, 1/24 are the nearest floats):
 //   s = g0 + g2;  p = (1/24) g0 + (1/6) g2;  q = (1/12) g1:   (0.25 g0, (-1/6)(s + g1), (-1/6)(s - g1), p + q, p - q, g2)
 // U[xi = 6 i + j] of one filter g[ky * 3 + kx], along x and then along y.  Stored in w_tap_index order over the 36 positions.  The single definition of the
-// operation order: f43_derive_u_kernel (cnn_trunk_hardnet_f43.hip) calls it, tools/winograd_numerics.py: f43_weight_transform mirrors it.
+// operation order: derive_u_pair (below) calls it, tools/winograd_numerics.py: f43_weight_transform mirrors it.
 #define F43_XI 36
 AFF_HOST_DEVICE inline void f43_g_axis(float g0, float g1, float g2, float* o, int stride) {
     const float c6 = 1.0f / 6.0f, c12 = 1.0f / 12.0f, c24 = 1.0f / 24.0f;
@@ -213,12 +205,105 @@ AFF_HOST_DEVICE inline void f43_weight_transform(const float g[9], float U[F43_X
     for (int j = 0; j < 6; ++j) f43_g_axis(t[j], t[6 + j], t[12 + j], U + j, 6);
 }
 
-// U of HardNet's conv1 (32 -> 32) and conv3 (64 -> 64) in F(4x4, 3x3), one after the other BEHIND Poly32's floats in the same context-owned buffer (144 KB + 576 KB):
-// the form 2 trunk takes one derived-weights pointer (CnnArgs::wino_u) and finds both families behind it
-struct F43 {
-    static constexpr int U1 = F43_XI * 32 * 32, U3 = F43_XI * 64 * 64, FLOATS = U1 + U3;
-    static constexpr int PAIRS = 32 * 32 + 64 * 64;                              // (cin, cout) pairs of the two layers
-    static constexpr int BASE = Poly32::FLOATS;                                  // float offset of the family in the context's buffer
-    static constexpr int offset(int layer) { return layer == 1 ? 0 : U1; }       // ... of a layer inside the family
-    static constexpr int floats(int layer) { return layer == 1 ? U1 : U3; }
+// ---- derived weights: sections, tables, the derivation routine --------------------------------------------------------------------------
+// Transformed weights that are NOT blob sections (the blobs' sizes and hashes are pinned, and a blob packed by an older library stays valid): derived on the device from
+// the blob's BN-folded fp32 taps into the one buffer a context owns (DerivedU below), in front of every trunk launch that reads them (derive_u.hip).  A section = U of one
+// layer in one family, that family's positions in w_tap_index order.  Everything about a section is in its table row; Wino16 / Poly32 / F43 are views of the tables.
+enum { DERIVED_WINO = 0, DERIVED_POLY = 1, DERIVED_F43 = 2 };   // Winograd F(2x2, 3x3): 16 positions; polyphase F(2x2, 2x2): POLY_XI; Winograd F(4x4, 3x3): F43_XI
+constexpr int derived_xi(int family) { return family == DERIVED_WINO ? 16 : (family == DERIVED_POLY ? POLY_XI : F43_XI); }
+struct DerivedSection {
+    int layer, cin, cout;       // source: conv `layer` of the blob (9 taps in w_tap_index order at NetOffsets::w[layer]), cin -> cout
+    int family;                 // DERIVED_*
+    int pair0;                  // first pair of the section = first thread of a launch; pair0 + w_tap_index(0, c, n, cin, cout) is pair (c, n): the fragment order, contiguous per wave
+    int dst;                    // float offset of the section from the table's base
 };
+constexpr int derived_floats(const DerivedSection& s) { return derived_xi(s.family) * s.cin * s.cout; }
+#define DERIVED_MAX 5
+struct DerivedTable {           // by-value kernel argument
+    int n, pairs, floats;       // sections; pairs (= threads) of all sections; floats from the base to the end of the last section
+    DerivedSection s[DERIVED_MAX];
+};
+// `t` with one more section behind its last: conv `layer` of a trunk of base width cb (NetLayout's channel counts) in `family`
+constexpr DerivedTable derived_add(DerivedTable t, int cb, int layer, int family) {
+    const DerivedSection s = {layer, cb << ((layer - 1) / 2), cb << (layer / 2), family, t.pairs, t.floats};
+    t.s[t.n++] = s; t.pairs += s.cin * s.cout; t.floats += derived_floats(s);
+    return t;
+}
+// A 16-channel net (AffNet, OriNet): conv1 / conv3 / conv5 in Winograd F(2x2, 3x3), behind them (appended later) the stride-2 layers conv2 / conv4 as polyphase Winograd.  600 KB.
+constexpr DerivedTable derived_trunk16() {
+    return derived_add(derived_add(derived_add(derived_add(derived_add(DerivedTable{}, 16, 1, DERIVED_WINO), 16, 3, DERIVED_WINO), 16, 5, DERIVED_WINO), 16, 2, DERIVED_POLY), 16, 4, DERIVED_POLY);
+}
+// HardNet descriptor form 1: conv2 / conv4 as polyphase Winograd (205 KB + 819 KB)
+constexpr DerivedTable derived_hardnet_poly() { return derived_add(derived_add(DerivedTable{}, 32, 2, DERIVED_POLY), 32, 4, DERIVED_POLY); }
+// HardNet's conv1 / conv3 in Winograd F(4x4, 3x3) (144 KB + 576 KB; conv1's has no loop yet, NOTES.md) ...
+constexpr DerivedTable derived_hardnet_f43() { return derived_add(derived_add(DerivedTable{}, 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }
+// ... and what descriptor form 2 reads: those directly BEHIND form 1's polyphase sections - its trunk takes one derived-weights pointer (CnnArgs::wino_u) and finds both there
+constexpr DerivedTable derived_hardnet_form2() { return derived_add(derived_add(derived_hardnet_poly(), 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }
+// the section of conv `layer` (layer -1: not in the table)
+constexpr DerivedSection derived_layer(const DerivedTable& t, int layer) {
+    for (int i = 0; i < t.n; ++i)
+        if (t.s[i].layer == layer) return t.s[i];
+    return DerivedSection{-1, 0, 0, 0, 0, 0};
+}
+// the section that pair e < t.pairs belongs to
+constexpr DerivedSection derived_section(const DerivedTable& t, int e) {
+    DerivedSection s = t.s[0];
+    for (int i = 1; i < DERIVED_MAX; ++i)
+        if (i < t.n && e >= t.s[i].pair0) s = t.s[i];
+    return s;
+}
+// Every section begins and ends on a multiple of 256 pairs: the 256 threads of a workgroup of the derivation kernel work on ONE section (one family: no divergence)
+constexpr bool derived_by_workgroups(const DerivedTable& t, int i = 0) {
+    return i == t.n || (t.s[i].pair0 % 256 == 0 && t.s[i].cin * t.s[i].cout % 256 == 0 && derived_by_workgroups(t, i + 1));
+}
+static_assert(derived_by_workgroups(derived_trunk16()) && derived_by_workgroups(derived_hardnet_poly()) && derived_by_workgroups(derived_hardnet_f43()) &&
+              derived_by_workgroups(derived_hardnet_form2()), "a 256-thread workgroup of derive_u_kernel stays within one section");
+
+// What the trunk kernels address the sections of a table through
+template <DerivedTable (*T)()>
+struct DerivedView {
+    static constexpr int FLOATS = T().floats, PAIRS = T().pairs;
+    static constexpr int offset(int layer) { return derived_layer(T(), layer).dst; }
+    static constexpr int floats(int layer) { return derived_floats(derived_layer(T(), layer)); }
+};
+struct Wino16 : DerivedView<derived_trunk16> { static constexpr int NB1 = 2, NB3 = 1; };   // (tile block, channel block) passes per wave of conv1 / conv3: 16 x 1 / 8, 4 x 2 / 8
+typedef DerivedView<derived_hardnet_poly> Poly32;
+struct F43 : DerivedView<derived_hardnet_f43> { static constexpr int BASE = Poly32::FLOATS; };   // float offset of the family from form 2's derived-weights pointer; offset(layer) is inside the family
+static_assert(derived_hardnet_form2().s[2].dst == F43::BASE + F43::offset(1) && derived_hardnet_form2().s[3].dst == F43::BASE + F43::offset(3) &&
+              derived_hardnet_form2().floats == F43::BASE + F43::FLOATS, "form 2's table = Poly32 with F43 at F43::BASE");
+
+// The context's buffer of derived weights, in floats: a region per net, each the base of that net's table(s)
+struct DerivedU {
+    static constexpr int AFFNET = 0, ORINET = AFFNET + Wino16::FLOATS;               // derived_trunk16() each
+    static constexpr int HARDNET = ORINET + Wino16::FLOATS;                          // derived_hardnet_poly() / derived_hardnet_form2()
+    static constexpr int HARDNET_F43 = HARDNET + F43::BASE;                          // ... whose F(4x4, 3x3) part is derived_hardnet_f43()
+    static constexpr int FLOATS = HARDNET_F43 + F43::FLOATS;                         // 3.0 MB
+    static constexpr int region(int kind) { return kind == AFFNET_NET_AFFNET ? AFFNET : (kind == AFFNET_NET_ORINET ? ORINET : HARDNET); }
+};
+static_assert(DerivedU::AFFNET == 0 && DerivedU::ORINET - DerivedU::AFFNET == derived_trunk16().floats && DerivedU::HARDNET - DerivedU::ORINET == derived_trunk16().floats &&
+              DerivedU::FLOATS - DerivedU::HARDNET == derived_hardnet_form2().floats && DerivedU::FLOATS == 2 * Wino16::FLOATS + Poly32::FLOATS + F43::FLOATS,
+              "the regions are disjoint, in this order, and fill the buffer");
+static_assert(DerivedU::ORINET % 64 == 0 && DerivedU::HARDNET % 64 == 0 && DerivedU::HARDNET_F43 % 64 == 0, "every region starts on a 256-byte boundary, as an allocation of its own would");
+// The work of thread e of a derivation launch over table t: pair e - pair0 of its section is pair (c, n) with e - pair0 == w_tap_index(0, c, n, cin, cout), and a position
+// (tap or transform position) p of that pair lies p planes of cin * cout floats further: w_tap_index(p, c, n, cin, cout) == p * cin * cout + w_tap_index(0, c, n, cin, cout).
+// So: the pair's 9 taps of the blob (w_off = NetOffsets::w) through the family's transform into that family's positions at U + dst, plane by plane.  The section is looked
+// up for the first pair of e's group of 256 (derived_by_workgroups): on the device that is the workgroup's, a scalar.
+static_assert(w_tap_index(7, 21, 13, 32, 64) == 7 * 32 * 64 + w_tap_index(0, 21, 13, 32, 64) && w_tap_index(35, 63, 63, 64, 64) == 35 * 64 * 64 + w_tap_index(0, 63, 63, 64, 64),
+              "a position is a plane of cin * cout floats");
+AFF_HOST_DEVICE inline void derive_u_pair(const DerivedTable& t, int e, const float* packed, const int (&w_off)[6], float* U) {
+    if (e >= t.pairs) return;
+    const DerivedSection s = derived_section(t, e & ~255);
+    const int plane = s.cin * s.cout;
+    const float* src = packed + w_off[s.layer] + (e - s.pair0);
+    float* dst = U + s.dst + (e - s.pair0);
+    float g[9];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) g[tap] = src[(size_t)tap * plane];
+    float u[F43_XI];                                    // the largest family
+    if (s.family == DERIVED_WINO) wino_weight_transform(g, u);
+    else if (s.family == DERIVED_POLY) poly_weight_transform(g, u);
+    else f43_weight_transform(g, u);
+#pragma unroll
+    for (int xi = 0; xi < F43_XI; ++xi)
+        if (xi < derived_xi(s.family)) dst[(size_t)xi * plane] = u[xi];
+}

@@ -147,7 +147,7 @@ def poly_conv3x3_s2(x, w):
 
 
 def poly_packed_weight_transform(sd, layers=(2, 4)):
-    """{layer: U} of HardNet's stride-2 layers as poly_derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: poly_weight_transform, w_tap_index over 25
+    """{layer: U} of HardNet's stride-2 layers as derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: derived_hardnet_poly, poly_weight_transform, w_tap_index over 25
     positions): flat float32 [xi (25)][ci / 16][(c / 4) % 4][co][c % 4] of the BN-folded fp32 taps"""
     out = {}
     for i in layers:
@@ -179,7 +179,7 @@ def poly16_conv(li, x, w):
 
 
 def poly16_packed_weight_transform(sd, layers=(2, 4)):
-    """{layer: U} of the stride-2 layers of an AffNet / OriNet state dict as wino_derive_u_kernel leaves them behind the Winograd sections (Wino16::offset(2 / 4)):
+    """{layer: U} of the stride-2 layers of an AffNet / OriNet state dict as derive_u_kernel leaves them behind the Winograd sections (Wino16::offset(2 / 4)):
     the layout of poly_packed_weight_transform, 25 x 16 x 32 and 25 x 32 x 64 floats"""
     return poly_packed_weight_transform(sd, layers)
 
@@ -246,7 +246,7 @@ def f43_conv3x3(x, w):
 
 
 def f43_packed_weight_transform(sd, layers=(1, 3)):
-    """{layer: U} of HardNet's conv1 / conv3 as f43_derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: f43_weight_transform, w_tap_index over 36
+    """{layer: U} of HardNet's conv1 / conv3 as derive_u_kernel leaves them (affnet_amd/csrc/weights_layout.h: derived_hardnet_f43, f43_weight_transform, w_tap_index over 36
     positions): flat float32 [xi (36)][ci / 16][(c / 4) % 4][co][c % 4] of the BN-folded fp32 taps"""
     out = {}
     for i in layers:
