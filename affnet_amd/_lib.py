@@ -36,7 +36,8 @@ SHAPE_FORM_DIRECT, SHAPE_FORM_WINOGRAD, SHAPE_FORM_POLYPHASE = 0, 1, 2          
 DESC_FORM_DIRECT, DESC_FORM_POLYPHASE, DESC_FORM_F43 = 0, 1, 2                             # include/affnet_hip.h AFFNET_DESC_FORM_*
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_EMPTY = 0, -1, -2, -3, -4
 VERIFY_AFFINE, VERIFY_HOMOGRAPHY, VERIFY_TILE, VERIFY_CHUNK = 0, 1, 128, 128                     # include/affnet_hip.h AFFNET_VERIFY_*
-VERIFY_FLAG_PAIR_RANGE = 8                                                                       # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
+KNN_MAX_K = 8                                                                                    # AFFNET_KNN_MAX_K: neighbours per query row of affnet_knn
+VERIFY_FLAG_PAIR_RANGE = 8                                                                     # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
 
 
 class Config(C.Structure):
@@ -130,6 +131,10 @@ SYMBOLS = {
     "affnet_match_snn_many": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "affnet_verify_many_scratch_bytes": (_SZ, [_I, _I]),
     "affnet_verify_matches_many": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "affnet_knn_chunks": (_I, [_P, _I, _I]),
+    "affnet_knn_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_knn": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "affnet_knn_vote": (_I, [_P, _P, _P, _I, _I, C.c_float, _P, _I, _I, _P, _P]),
     "affnet_extract_features": (_I, [_P, C.POINTER(Nets), _P, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_detect_image": (_I, [_P, _P, _P]),
     "affnet_detect_image_responses": (_I, [_P, _P, _P]),

@@ -1,0 +1,332 @@
+// Descriptor index for gfx950: k nearest neighbours of query descriptors among the concatenated descriptors of many
+// images, and one vote per image from them - the shortlist that affnet_match_snn_many / affnet_verify_matches_many (match.hip, spatial.hip) re-rank.
+//
+// The distance is the matcher's (match.hip, rowmin_dist_body; Losses.py:5-13): sqrt(((|a|^2 + |b|^2) - 2 a.b) + 1e-6), a.b by the same chain
+// of v_mfma_f32_16x16x4_f32 over the same K order, the squared norms by the same reduction, so every distance reported here is the element
+// affnet_distance_matrix writes for that (row, column), bit for bit.  The tile loop is the matcher's STAGE form restated (A fragments of 16 rows
+// per wave in registers, the B tile staged once per workgroup through two skewed LDS buffers, the next tile's loads in flight under the MFMAs);
+// what differs is that a workgroup walks only the 16-column tiles of ITS chunk of the database (grid = row blocks x chunks, so that a large
+// database fills the part whatever the number of query rows) and keeps up to 8 neighbours per row instead of one.
+//
+// Order of candidates, everywhere in this file: a NaN distance (the fp32 expansion can go below -1e-6 for near-identical vectors) in front of every
+// number, then the smaller distance, then the smaller database row.  The order is total and every distance is computed once, so the result does
+// not depend on the number of chunks.
+#include <math.h>
+
+#include "common.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+#define KNN_EMPTY 0x7fffffff          // row index of an unfilled slot inside the kernels (behind every real row in the order); written out as -1
+#define KNN_BS(DIM) ((DIM) + 4)       // floats per staged column: the 16-byte skew spreads the 16 columns over the banks (match.hip ROWMIN_BS)
+#define KNN_WG_PER_CU 3               // affnet_knn_chunks: workgroups per CU the grid aims at (what the k = 8 kernel keeps resident; DESIGN.md, descriptor index)
+#define KNN_MIN_TILES 5               // affnet_knn_chunks: no chunk below this many 16-column tiles (descriptor index: the measured floor)
+#define KNN_MAX_CHUNKS 1024           // affnet_knn_chunks never chooses more; the size affnet_knn_scratch_bytes assumes for n_chunks = 0
+
+// (d, c) stands in front of (s, si)
+__device__ __forceinline__ bool knn_before(float d, int c, float s, int si) {
+    const bool dn = d != d, sn = s != s;
+    return dn ? (!sn || c < si) : (!sn && (d < s || (d == s && c < si)));
+}
+
+// A sorted list of CAP candidates in registers (compile-time indices only: a dynamically indexed array would live in scratch memory).
+template <int CAP>
+struct KnnList {
+    float d[CAP];
+    int i[CAP];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int s = 0; s < CAP; ++s) { d[s] = INFINITY; i[s] = KNN_EMPTY; }
+    }
+    // the candidate replaces the last slot when it stands in front of it, then rises to its place
+    __device__ __forceinline__ void insert(float nd, int ni) {
+        if (!knn_before(nd, ni, d[CAP - 1], i[CAP - 1])) return;
+        d[CAP - 1] = nd; i[CAP - 1] = ni;
+#pragma unroll
+        for (int s = CAP - 1; s > 0; --s) {
+            const bool up = knn_before(d[s], i[s], d[s - 1], i[s - 1]);
+            const float td = d[s - 1]; const int ti = i[s - 1];
+            d[s - 1] = up ? d[s] : td; i[s - 1] = up ? i[s] : ti;
+            d[s] = up ? td : d[s]; i[s] = up ? ti : i[s];
+        }
+    }
+    __device__ __forceinline__ void pop(bool yes) {
+#pragma unroll
+        for (int s = 0; s + 1 < CAP; ++s) { d[s] = yes ? d[s + 1] : d[s]; i[s] = yes ? i[s + 1] : i[s]; }
+        d[CAP - 1] = yes ? INFINITY : d[CAP - 1]; i[CAP - 1] = yes ? KNN_EMPTY : i[CAP - 1];
+    }
+};
+
+// One round of the merge of the sorted lists of W neighbouring lanes (W = 16 or 64, a power of two): a butterfly minimum over the lists' heads,
+// after which every lane holds the winner (bd, bi), and the lane whose head it was (real rows are unique over the lanes) drops it.
+template <int CAP, int W>
+__device__ __forceinline__ void knn_lanes_next(KnnList<CAP>& L, float& bd, int& bi) {
+    bd = L.d[0];
+    bi = L.i[0];
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+        const float od = __shfl_xor(bd, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const bool take = knn_before(od, oi, bd, bi);
+        bd = take ? od : bd; bi = take ? oi : bi;
+    }
+    L.pop(bi != KNN_EMPTY && L.i[0] == bi);
+}
+
+// The first k of the union of those lists: lane `writer` of the group stores round j at out[j].
+template <int CAP, int W>
+__device__ __forceinline__ void knn_lanes_merge(KnnList<CAP>& L, int k, bool writer, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+        if (j < k) {        // uniform
+            float bd;
+            int bi;
+            knn_lanes_next<CAP, W>(L, bd, bi);
+            if (writer) { out_d[j] = bd; out_i[j] = bi == KNN_EMPTY ? -1 : bi; }
+        }
+    }
+}
+
+// The distance of the k-th candidate of that union (+inf while it has fewer than k), on a copy of the lists: nothing behind it can reach a
+// row's result, so the tile loop takes it as the row's bound.
+template <int CAP, int W>
+__device__ __forceinline__ float knn_lanes_kth(KnnList<CAP> L, int k) {
+    float kth = INFINITY;
+    int bi;
+#pragma unroll
+    for (int j = 0; j < CAP; ++j)
+        if (j < k) knn_lanes_next<CAP, W>(L, kth, bi);        // uniform
+    return kth;
+}
+
+// one wavefront per row; torch.sum(a * a, dim=1) - the reduction of match.hip's sqnorm_body, operation by operation
+__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    float s = 0.f;
+    for (int k = lane; k < dim; k += 64) { const float v = x[(size_t)row * dim + k]; s = fmaf(v, v, s); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) out[row] = s;
+}
+
+// grid (cdiv(n1, 64), n_chunks).  Workgroup = 4 wavefronts = 64 rows of `a`; wave w owns rows 16w..16w+15 and walks the tiles
+// [chunk * tpc, (chunk + 1) * tpc) of `b`.  MFMA roles and result layout as in rowmin_dist_body: lane (n = l & 15, g = l >> 4) holds
+// D[row 4 g + r][col n], r = 0..3, so a lane keeps four lists (one per row) over the columns = n mod 16 of the chunk; the 16 column lanes of a
+// row are merged once, at the end of the chunk.  Columns skip_lo <= c < skip_hi are no candidates.
+// out_d / out_i: (n1, n_chunks, k) - the result itself when there is one chunk, else the partial lists knn_merge_kernel reduces.
+// A wave whose 16 rows lie behind n1 computes on clamped rows (every wave must reach the barriers) and writes nothing.
+template <int DIM, int CAP>
+__global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
+                                                       const float* __restrict__ a_sq, const float* __restrict__ b_sq, int k, int skip_lo,
+                                                       int skip_hi, int tpc, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+    constexpr int NG = DIM / 16;
+    constexpr int BS = KNN_BS(DIM), Q = DIM / 4, NPRE = 16 * Q / 256;      // float4 per column, float4 per thread and tile
+    static_assert((16 * Q) % 256 == 0, "the staged tile is loaded by 256 threads in whole rounds");
+    __shared__ __attribute__((aligned(16))) float s_b[2 * 16 * BS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int m = lane & 15, kq = lane >> 4;
+    const int row0 = blockIdx.x * 64 + wave * 16;
+    const int chunk = blockIdx.y, n_chunks = gridDim.y;
+    const int tiles = (n2 + 15) >> 4;
+    const long long t0l = (long long)chunk * tpc;
+    const int t0 = t0l < tiles ? (int)t0l : tiles, t1 = min(tiles, t0 + tpc);          // uniform over the workgroup
+    KnnList<CAP> L[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) L[r].clear();
+    if (t0 < t1) {
+        f32x4 fa[NG];
+        {
+            const int r = min(row0 + m, n1 - 1);
+#pragma unroll
+            for (int t = 0; t < NG; ++t) fa[t] = *reinterpret_cast<const f32x4*>(&a[(size_t)r * DIM + 16 * t + 4 * kq]);
+        }
+        float asq[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) asq[r] = a_sq[min(row0 + 4 * kq + r, n1 - 1)];
+        float bound[4] = {INFINITY, INFINITY, INFINITY, INFINITY};      // per row: no candidate behind it can reach the row's k
+        f32x4 pre[NPRE];
+        // tile at column c0 -> registers (columns clamped to the last row of b); registers -> LDS buffer `buf`
+        auto tile_fetch = [&](int c0) {
+#pragma unroll
+            for (int j = 0; j < NPRE; ++j) {
+                const int e = (int)threadIdx.x + 256 * j;
+                pre[j] = *reinterpret_cast<const f32x4*>(&b[(size_t)min(c0 + e / Q, n2 - 1) * DIM + 4 * (e % Q)]);
+            }
+        };
+        auto tile_store = [&](int buf) {
+#pragma unroll
+            for (int j = 0; j < NPRE; ++j) {
+                const int e = (int)threadIdx.x + 256 * j;
+                *reinterpret_cast<f32x4*>(&s_b[buf * 16 * BS + (e / Q) * BS + 4 * (e % Q)]) = pre[j];
+            }
+        };
+        tile_fetch(16 * t0);
+        tile_store(0);
+        __syncthreads();
+        for (int t = t0; t < t1; ++t) {
+            const int c0 = 16 * t;
+            const int col = c0 + m;
+            const int cc = min(col, n2 - 1);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 fb[NG];
+            const int buf = (t - t0) & 1;
+            const bool more = t + 1 < t1;
+            if (more) tile_fetch(c0 + 16);
+            // in front of the MFMAs, and no branch between the last MFMA and the accumulator reads (match.hip, NOTES.md)
+            const float bsq = b_sq[cc];
+            const bool cand = col < n2 && !(col >= skip_lo && col < skip_hi);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) fb[g] = *reinterpret_cast<const f32x4*>(&s_b[buf * 16 * BS + m * BS + 16 * g + 4 * kq]);
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[g][j], fb[g][j], acc, 0, 0, 0);
+            float d[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[r] = sqrtf(((asq[r] + bsq) - 2.0f * acc[r]) + 1e-6f);      // Losses.py:12-13
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // the common case is the first comparison, against the row's bound (a NaN on either side goes on to the full test)
+                if (cand && !(d[r] > bound[r]) && !(d[r] > L[r].d[CAP - 1])) L[r].insert(d[r], col);
+            }
+            // A lane's own last slot is a weak bound (its list covers a sixteenth of the row's columns): after 8, 16, 32, ... tiles, and then every
+            // 256, the row's k-th candidate over its 16 lanes becomes the bound.  Uniform over the workgroup.
+            const int seen = t - t0 + 1;
+            if (seen >= 8 && ((seen & (seen - 1)) == 0 || (seen & 255) == 0)) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) bound[r] = knn_lanes_kth<CAP, 16>(L[r], k);
+            }
+            if (more) tile_store(buf ^ 1);      // the other buffer was last read one tile ago, in front of that tile's barrier
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = min(row0 + 4 * kq + r, n1 - 1);
+        const size_t o = ((size_t)row * n_chunks + chunk) * k;
+        knn_lanes_merge<CAP, 16>(L[r], k, m == 0 && row0 + 4 * kq + r < n1, out_d + o, out_i + o);
+    }
+}
+
+// One wavefront per row: the n_chunks partial lists (n_chunks * k slots, unfilled ones hold -1) -> the row's k neighbours.
+template <int CAP>
+__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_chunks,
+                                                        int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n1) return;      // uniform over the wave
+    KnnList<CAP> L;
+    L.clear();
+    const size_t base = (size_t)row * n_chunks * k;
+    const long long total = (long long)n_chunks * k;
+    for (long long e = lane; e < total; e += 64) {
+        const int ci = part_i[base + e];
+        if (ci >= 0) L.insert(part_d[base + e], ci);
+    }
+    knn_lanes_merge<CAP, 64>(L, k, lane == 0, out_d + (size_t)row * k, out_i + (size_t)row * k);
+}
+
+template <int CAP>
+static void knn_launch(hipStream_t st, int nc, const float* q, int n1, const float* db, int n2, const float* a_sq, const float* b_sq, int k, int lo,
+                       int hi, int tpc, float* part_d, int32_t* part_i, float* d_dist, int32_t* d_idx) {
+    const dim3 grid(aff_cdiv(n1, 64), nc);
+    if (nc == 1) {
+        hipLaunchKernelGGL((knn_tile_kernel<128, CAP>), grid, dim3(256), 0, st, q, n1, db, n2, a_sq, b_sq, k, lo, hi, tpc, d_dist, d_idx);
+        return;
+    }
+    hipLaunchKernelGGL((knn_tile_kernel<128, CAP>), grid, dim3(256), 0, st, q, n1, db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i);
+    hipLaunchKernelGGL((knn_merge_kernel<CAP>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, (const float*)part_d, (const int32_t*)part_i, n1, nc, k,
+                       d_dist, d_idx);
+}
+
+extern "C" int affnet_knn_chunks(const affnet_ctx* ctx, int n1, int n2) {
+    int cus = 256;
+    if (ctx) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && v > 0) cus = v;
+        else (void)hipGetLastError();
+    }
+    const long long row_blocks = n1 > 0 ? aff_cdiv(n1, 64) : 1, tiles = n2 > 0 ? ((long long)n2 + 15) / 16 : 0;
+    const long long want = ((long long)KNN_WG_PER_CU * cus + row_blocks - 1) / row_blocks, most = tiles / KNN_MIN_TILES;
+    long long nc = want < most ? want : most;
+    if (nc > KNN_MAX_CHUNKS) nc = KNN_MAX_CHUNKS;
+    return nc < 1 ? 1 : (int)nc;
+}
+
+// scratch: a_sq float (n1) | b_sq float (n2) | partial distances float (n1, n_chunks, k) | partial rows int32 (n1, n_chunks, k)
+static size_t knn_norm_bytes(size_t n1, size_t n2) { return aff_align((n1 + n2) * sizeof(float), 16); }
+
+extern "C" size_t affnet_knn_scratch_bytes(int n1, int n2, int k, int n_chunks) {
+    const size_t a = n1 > 0 ? (size_t)n1 : 0, b = n2 > 0 ? (size_t)n2 : 0, kk = k > 0 ? (size_t)k : 0;
+    const size_t nc = n_chunks > 0 ? (size_t)n_chunks : (n_chunks == 0 ? (size_t)KNN_MAX_CHUNKS : 0);
+    return knn_norm_bytes(a, b) + a * nc * kk * (sizeof(float) + sizeof(int32_t)) + 64;
+}
+
+extern "C" int affnet_knn(affnet_ctx* ctx, const float* d_q, int n1, const float* d_db, int n2, int dim, int k, int skip_row, int skip_n,
+                          int n_chunks, float* d_dist, int32_t* d_idx, void* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_q || !d_db || !d_dist || !d_idx || !d_scratch || n1 < 0 || n2 < 0 || skip_n < 0 || n_chunks < 0)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "knn: bad argument");
+    if (dim != 128) return aff_fail(ctx, AFFNET_ERR_INVALID, "knn: descriptor length %d (only 128 is built)", dim);
+    if (k < 1 || k > AFFNET_KNN_MAX_K) return aff_fail(ctx, AFFNET_ERR_INVALID, "knn: k = %d (1..%d)", k, AFFNET_KNN_MAX_K);
+    if (n_chunks > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "knn: %d chunks (at most 65535 per call)", n_chunks);
+    if (n1 == 0) return AFFNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = n_chunks ? n_chunks : affnet_knn_chunks(ctx, n1, n2);
+    const int tiles = (int)(((long long)n2 + 15) / 16), tpc = aff_cdiv(tiles, nc);
+    const long long lo64 = skip_row < 0 ? 0 : skip_row, hi64 = (long long)skip_row + skip_n;
+    const int lo = (int)(lo64 < n2 ? lo64 : n2), hi = (int)(hi64 < 0 ? 0 : (hi64 < n2 ? hi64 : n2));      // [lo, hi) inside [0, n2); lo >= hi: no skip
+    float* a_sq = (float*)d_scratch;
+    float* b_sq = a_sq + n1;
+    float* part_d = (float*)((char*)d_scratch + knn_norm_bytes((size_t)n1, (size_t)n2));
+    int32_t* part_i = (int32_t*)(part_d + (size_t)n1 * nc * k);
+    hipLaunchKernelGGL(knn_sqnorm_kernel, dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, d_q, n1, dim, a_sq);
+    if (n2 > 0) hipLaunchKernelGGL(knn_sqnorm_kernel, dim3(aff_cdiv(n2, 4)), dim3(256), 0, st, d_db, n2, dim, b_sq);
+    const int cap = k == 1 ? 1 : (k == 2 ? 2 : (k <= 4 ? 4 : 8));
+    switch (cap) {
+        case 1: knn_launch<1>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
+        case 2: knn_launch<2>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
+        case 4: knn_launch<4>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
+        default: knn_launch<8>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
+    }
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// One thread per query row.  voted[]: the images this row has voted for, compile-time indices only.
+__global__ __launch_bounds__(256) void knn_vote_kernel(const float* __restrict__ dist, const int32_t* __restrict__ idx, int n1, int k, float ratio,
+                                                       const int32_t* __restrict__ row_image, int n2, int n_images, int32_t* __restrict__ votes) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n1) return;
+    const float bound = ratio * dist[(size_t)r * k + (k - 1)];
+    int voted[AFFNET_KNN_MAX_K - 1];
+#pragma unroll
+    for (int j = 0; j < AFFNET_KNN_MAX_K - 1; ++j) {
+        voted[j] = -1;
+        if (j < k - 1) {
+            const int c = idx[(size_t)r * k + j];
+            if (c >= 0 && c < n2) {
+                const int img = row_image[c];
+                bool ok = img >= 0 && img < n_images && !(dist[(size_t)r * k + j] > bound);
+#pragma unroll
+                for (int e = 0; e < j; ++e) ok = ok && voted[e] != img;
+                if (ok) { voted[j] = img; atomicAdd(&votes[img], 1); }
+            }
+        }
+    }
+}
+
+extern "C" int affnet_knn_vote(affnet_ctx* ctx, const float* d_dist, const int32_t* d_idx, int n1, int k, float ratio, const int32_t* d_row_image,
+                               int n2, int n_images, int32_t* d_votes, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_dist || !d_idx || !d_row_image || !d_votes || n1 < 0 || n2 < 0 || n_images < 0)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "knn_vote: bad argument");
+    if (k < 1 || k > AFFNET_KNN_MAX_K) return aff_fail(ctx, AFFNET_ERR_INVALID, "knn_vote: k = %d (1..%d)", k, AFFNET_KNN_MAX_K);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_images == 0) return AFFNET_OK;
+    { int zrc = aff_zero_async(ctx, d_votes, (size_t)n_images * sizeof(int32_t), st); if (zrc) return zrc; }
+    if (n1 == 0 || k == 1) return AFFNET_OK;
+    hipLaunchKernelGGL(knn_vote_kernel, dim3(aff_cdiv(n1, 256)), dim3(256), 0, st, d_dist, d_idx, n1, k, ratio, d_row_image, n2, n_images, d_votes);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}

@@ -543,6 +543,47 @@ int affnet_verify_matches_many(affnet_ctx* ctx, const float* d_lafs1, int rows1,
                                int n_pairs, const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters,
                                int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
 
+/* ---- descriptor index: k nearest neighbours over many images, shortlist by votes ---- */
+
+/* The front of the retrieval loop extract -> index -> shortlist -> verify: the rows of all database images lie back to back in one (n2,128)
+ * buffer (side 2 of the *_many calls above), a query image's rows are searched against all of them at once, and every image collects votes
+ * from the neighbours found among its rows.  No allocation, no synchronisation, all work on `stream`; all buffers are the caller's. */
+#define AFFNET_KNN_MAX_K 8
+
+/* Host only.  The library's own choice of column chunks for an n1 x n2 search, >= 1 for every size: enough chunks to give the device of `ctx`
+ * (NULL: a 256-CU part) a few workgroups per CU, but no chunk below a floor of 16-column tiles (descriptor index). */
+int affnet_knn_chunks(const affnet_ctx* ctx, int n1, int n2);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_knn called with this n_chunks; n_chunks = 0: enough for whatever affnet_knn_chunks
+ * may choose.  Negative arguments count as 0. */
+size_t affnet_knn_scratch_bytes(int n1, int n2, int k, int n_chunks);
+
+/* For every row of d_q (n1,128) the k rows of d_db (n2,128) at the smallest distance sqrt(|a|^2 + |b|^2 - 2 a.b + 1e-6): d_dist (n1,k) ascending,
+ * d_idx (n1,k) the database rows.  Every distance is, bit for bit, the element affnet_distance_matrix writes for that (row, column), and with
+ * no skip range column 0 is what affnet_match_snn writes to d_min_dist / d_idx.  Order: a NaN distance (the fp32 expansion can go below -1e-6
+ * for near-identical vectors) in front of every number, then the smaller distance, then the smaller database row - a total order, so the
+ * result does not depend on n_chunks.
+ * Rows skip_row <= c < skip_row + skip_n of the database are no candidates (a query against an index that contains the query's own image);
+ * the range is clipped to [0, n2), skip_n = 0 is no skip.  Slots for which no candidate is left hold idx = -1, dist = +inf; n2 = 0 is valid
+ * and gives only such slots; n1 = 0 writes nothing.
+ * The search runs on a grid of cdiv(n1, 64) x n_chunks workgroups: chunk c owns the 16-column tiles [c * tpc, (c + 1) * tpc),
+ * tpc = cdiv(cdiv(n2, 16), n_chunks) (a chunk that starts behind n2 is empty), and a second kernel merges the chunks' lists per row.
+ * n_chunks = 0: affnet_knn_chunks(ctx, n1, n2); at most 65535.
+ * AFFNET_ERR_INVALID in front of the first launch: k outside 1..AFFNET_KNN_MAX_K, dim != 128, a negative size, n_chunks < 0, a NULL pointer. */
+int affnet_knn(affnet_ctx* ctx, const float* d_q, int n1, const float* d_db, int n2, int dim, int k, int skip_row, int skip_n, int n_chunks,
+               float* d_dist, int32_t* d_idx, void* d_scratch, void* stream);
+
+/* One vote per (query row, image) from the neighbours affnet_knn found: d_votes (n_images) int32 is zeroed, then row r takes its LAST slot as the
+ * background distance d_last = dist[r][k-1], and neighbour j < k-1 with idx >= 0 votes for image d_row_image[idx] iff
+ * !(dist[r][j] > ratio * d_last) (one fp32 multiply, one compare: a NaN distance votes, and so does every neighbour of a row whose last slot is
+ * unfilled, +inf) and no earlier neighbour of the row voted for that image.  A row gives at most k-1 votes, at most one per image:
+ * k - 1 is the largest number of database images that can show the same feature and still all receive its vote.  k = 1 gives all zeros.
+ * (Plain counting of neighbours ranks images by their size; the ratio gate counts a neighbour only when it stands out from the background.)
+ * d_row_image (n2) int32 = the image of every database row.  An idx outside [0, n2) other than -1 and an image outside [0, n_images) are
+ * skipped, not trusted.  Integer atomics: the result does not depend on the order of execution. */
+int affnet_knn_vote(affnet_ctx* ctx, const float* d_dist, const int32_t* d_idx, int n1, int k, float ratio, const int32_t* d_row_image, int n2,
+                    int n_images, int32_t* d_votes, void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

@@ -126,6 +126,12 @@ DESIGN_KERNELS = [
     ("rowmin_many_kernel<128>", "SNN matching of many pairs per call: the same row-minimum body, pair index on the grid"),
     ("spv_many_score_kernel", "spatial verification of many pairs per call: the same scoring body, pair index on the grid"),
     ("spv_many_lo_kernel", "spatial verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
+    ("knn_tile_kernel<128, 1>", "descriptor index, k = 1: the matcher's distance tiles over one column chunk, one neighbour per row and lane"),
+    ("knn_tile_kernel<128, 2>", "descriptor index, k = 2: two neighbours per row and lane in registers"),
+    ("knn_tile_kernel<128, 4>", "descriptor index, k = 3, 4: four neighbours per row and lane"),
+    ("knn_tile_kernel<128, 8>", "descriptor index, k = 5 .. 8: eight neighbours per row and lane"),
+    ("knn_merge_kernel<8>", "descriptor index: merge of the chunks' lists, one wavefront per query row (k = 5 .. 8)"),
+    ("knn_vote_kernel", "descriptor index: one vote per (query row, image) behind the ratio gate"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
     ("blur2d_kernel<13, 4>", "Gaussian blur 13 x 13, 64 x 64 tiles"),
     ("blur2d_pair_kernel<15, 9, 4>", "paired blur 15 x 15 / 9 x 9"),
