@@ -135,6 +135,10 @@ SYMBOLS = {
     "affnet_knn_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_knn": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "affnet_knn_vote": (_I, [_P, _P, _P, _I, _I, C.c_float, _P, _I, _I, _P, _P]),
+    "affnet_quantize_desc": (_I, [_P, _P, _I, _I, C.c_float, _P, _P, _P]),
+    "affnet_knn_q8_chunks": (_I, [_P, _I, _I]),
+    "affnet_knn_q8_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_knn_q8": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P]),
     "affnet_extract_features": (_I, [_P, C.POINTER(Nets), _P, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_detect_image": (_I, [_P, _P, _P]),
     "affnet_detect_image_responses": (_I, [_P, _P, _P]),

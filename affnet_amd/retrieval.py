@@ -171,3 +171,125 @@ class DescriptorIndex(object):
             out.append({"image": images[p], "votes": votes[p], "num_inliers": row[3], "H": H[p], "tent_in_1": tent[p, :t, 0].long(),
                         "tent_in_2": tent[p, :t, 1].long(), "inliers": inl[p, :t].bool()})
         return sorted(out, key=lambda e: -e["num_inliers"])          # sorted() is stable: ties keep the shortlist's order
+
+
+# ---- int8 descriptors: exact integer k-NN on the i8 matrix instruction (csrc/knn_q8.hip) ----
+
+def _check_scale(scale, what):
+    try:
+        s = float(scale)
+    except (TypeError, ValueError):
+        s = float("nan")
+    with np.errstate(over="ignore"):
+        f = float(np.float32(s))          # what the library receives
+    if not (np.isfinite(f) and f > 0):
+        raise ValueError("%s: scale must be a finite number > 0 (got %r)" % (what, scale))
+    return f
+
+
+def _check_q8(q, sq, what):
+    if not (isinstance(q, torch.Tensor) and q.dim() == 2 and q.size(1) == DIM and q.dtype == torch.int8):
+        raise ValueError("affnet_amd.retrieval: %s must be an (n,%d) int8 tensor" % (what, DIM))
+    if not (isinstance(sq, torch.Tensor) and sq.dtype == torch.int32 and sq.numel() == q.size(0)):
+        raise ValueError("affnet_amd.retrieval: %s needs one int32 sum of squares per row" % what)
+
+
+def quantization_scale(descs):
+    """127 / max|x| over the given tensor or list of tensors: the largest scale at which the quantiser clips no entry.  One read-back; an
+    index-build-time call."""
+    ds = [descs] if isinstance(descs, torch.Tensor) else list(descs)
+    m = max([float(d.abs().max()) for d in ds if d.numel()] or [0.0])
+    if not (np.isfinite(m) and m > 0):
+        raise ValueError("quantization_scale: the descriptors have no finite non-zero entry")
+    return _check_scale(127.0 / m, "quantization_scale")
+
+
+def quantize(desc, scale):
+    """desc (n,128) -> (q (n,128) int8, sq (n,) int32): q = clamp(rint(x * scale), -127, 127) in fp32 (round half to even, NaN -> 0, +-inf ->
+    +-127), sq = the rows' sums of q^2 (affnet_quantize_desc).  Enqueued on the current stream, no synchronisation."""
+    scale = _check_scale(scale, "quantize")
+    d = _check_desc(desc, "desc")
+    n, dev = d.size(0), d.device
+    q = torch.empty(n, DIM, dtype=torch.int8, device=dev)
+    sq = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        ctx = engine.utility_ctx(dev)
+        check(lib.affnet_quantize_desc(ctx, ptr(d), n, DIM, scale, ptr(q), ptr(sq), engine.stream_of(dev)), ctx, "affnet_quantize_desc")
+    return q, sq
+
+
+def knn_q8(q, qsq, db, dbsq, k=2, scale=None, skip=None, n_chunks=0):
+    """For every row of q (n1,128) int8 the k rows of db (n2,128) int8 at the smallest d2 = (qsq + dbsq) - 2 q.db (exact, int32), ascending by
+    (d2, row): (dist2 (n1,k) int32, dist (n1,k) float32 = sqrt(float32(d2)) / scale, idx (n1,k) int32); slots without a candidate hold
+    (2^31 - 1, +inf, -1).  qsq / dbsq: the rows' sums of squares as quantize returns them; scale: the scale both sides were quantised with.
+    skip, n_chunks as in knn; the result does not depend on n_chunks.  Enqueued on the current stream, no synchronisation."""
+    k = _check_k(k, "knn_q8")
+    if scale is None:
+        raise ValueError("knn_q8: scale must be given (the scale the descriptors were quantised with)")
+    scale = _check_scale(scale, "knn_q8")
+    _check_q8(q, qsq, "q")
+    _check_q8(db, dbsq, "db")
+    for t, what in ((q, "q"), (qsq, "qsq"), (db, "db"), (dbsq, "dbsq")):
+        _device_tensor(t, what)
+    a, asq, b, bsq = q.contiguous(), qsq.contiguous(), db.contiguous(), dbsq.contiguous()
+    if len({a.device, asq.device, b.device, bsq.device}) != 1:
+        raise ValueError("knn_q8: the tensors live on different devices")
+    row, n = (0, 0) if skip is None else (int(skip[0]), int(skip[1]))
+    if n < 0 or int(n_chunks) < 0:
+        raise ValueError("knn_q8: negative skip length or n_chunks")
+    n1, n2, dev = a.size(0), b.size(0), a.device
+    dist2 = torch.empty(n1, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(n1, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(n1, k, dtype=torch.int32, device=dev)
+    if n1 == 0:
+        return dist2, dist, idx
+    ctx = engine.utility_ctx(dev)
+    nc = int(n_chunks)          # 0: the library's choice for this k, at most affnet_knn_q8_chunks
+    scratch = torch.empty(lib.affnet_knn_q8_scratch_bytes(n1, n2, k, nc or lib.affnet_knn_q8_chunks(ctx, n1, n2)), dtype=torch.uint8, device=dev)
+    one = torch.zeros(16, dtype=torch.int32, device=dev)          # stands in for an empty database: never read, but the boundary refuses NULL
+    rc = lib.affnet_knn_q8(ctx, ptr(a), ptr(asq), n1, ptr(b if n2 else one), ptr(bsq if n2 else one), n2, DIM, k, row, n, nc, scale, ptr(dist2), ptr(dist),
+                           ptr(idx), ptr(scratch), engine.stream_of(dev))
+    check(rc, ctx, "affnet_knn_q8")
+    return dist2, dist, idx
+
+
+class QuantizedDescriptorIndex(DescriptorIndex):
+    """DescriptorIndex whose search runs on int8 descriptors: Dq (N,128) int8, sq (N,) int32 and scale (None: quantization_scale(descs)) beside
+    the tables of the base class.  enqueue_votes quantises the query with the index's scale, searches with affnet_knn_q8 and votes with
+    affnet_knn_vote; shortlist and retrieve are inherited, so retrieve re-ranks with the exact fp32 matcher on D.  keep_float=False drops D after
+    quantising (132 bytes per row instead of 512); such an index searches identically and cannot retrieve."""
+
+    def __init__(self, descs, LAFs=None, scale=None, keep_float=True):
+        DescriptorIndex.__init__(self, descs, LAFs)
+        if scale is None:
+            if self.D.size(0) == 0:
+                raise ValueError("QuantizedDescriptorIndex: scale must be given for an index without rows")
+            scale = quantization_scale(self.D)
+        self.scale = _check_scale(scale, "QuantizedDescriptorIndex")
+        self.Dq, self.sq = quantize(self.D, self.scale)
+        self.n_rows = self.D.size(0)
+        if not keep_float:
+            self.D = None
+
+    def enqueue_votes(self, desc_q, k=4, ratio=0.8, exclude=None):
+        """DescriptorIndex.enqueue_votes on the quantised rows: (votes (M,) int32, dist (n1,k) = sqrt(d2) / scale, idx (n1,k)); no synchronisation."""
+        k = _check_k(k, "enqueue_votes")
+        skip = self.skip_range(exclude)
+        q = _check_desc(desc_q, "desc_q")
+        if q.device != self.device:
+            raise ValueError("enqueue_votes: desc_q and the index live on different devices")
+        qq, qsq = quantize(q, self.scale)
+        _, dist, idx = knn_q8(qq, qsq, self.Dq, self.sq, k, self.scale, skip)
+        votes = torch.empty(len(self.counts), dtype=torch.int32, device=self.device)
+        ctx = engine.utility_ctx(self.device)
+        one = torch.zeros(8, dtype=torch.int32, device=self.device)     # stands in for empty inputs: never read, but the boundary refuses NULL
+        n1, n2 = q.size(0), self.n_rows
+        rc = lib.affnet_knn_vote(ctx, ptr(dist if n1 else one), ptr(idx if n1 else one), n1, k, float(ratio), ptr(self.row_image if n2 else one), n2,
+                                 len(self.counts), ptr(votes), engine.stream_of(self.device))
+        check(rc, ctx, "affnet_knn_vote")
+        return votes, dist, idx
+
+    def retrieve(self, desc_q, LAFs_q, *args, **kwargs):
+        if self.D is None:
+            raise ValueError("retrieve: the index was built with keep_float=False - the exact re-ranking needs the float descriptors")
+        return DescriptorIndex.retrieve(self, desc_q, LAFs_q, *args, **kwargs)

@@ -1,14 +1,15 @@
 #!/usr/bin/env python
 """Retrieval of one query image from a set of images: descriptor index -> vote shortlist -> spatial verification, on the MI355X.
 
-    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] QUERY IMG [IMG ...]
+    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] QUERY IMG [IMG ...]
 
 Every image goes through the fused path (detect + AffNet + OriNet + descriptor, N = 1000 keypoints by default).  The IMGs become one
 DescriptorIndex; the query's descriptors are searched against all of them at once (affnet_knn, --k neighbours per descriptor, default 4), every image
 collects the votes of the neighbours that stand out from the background (affnet_knn_vote), and the --top (default 10) images with the most votes
 are matched and verified from their affine frames in one device call (affnet_match_snn_many / affnet_verify_matches_many).  Prints the vote
 shortlist and the verified order.  Without a HardNet checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative;
---desc sift needs no weights.  A demonstration of the calls, not a retrieval-quality claim.
+--desc sift needs no weights.  --q8 builds a QuantizedDescriptorIndex instead: the search runs on int8 descriptors
+(affnet_quantize_desc, affnet_knn_q8), the matching and verification of the shortlist on the float ones as before.  A demonstration of the calls, not a retrieval-quality claim.
 
     python examples/graf_matching/retrieve.py --desc sift tests/golden/graf_img1.png tests/golden/graf_img6.png tests/golden/graf_img1.png"""
 import os
@@ -43,6 +44,8 @@ def main(argv):
     k, argv = take(argv, "--k", "4")
     desc_kind, argv = take(argv, "--desc", "hardnet")
     hardnet_path, argv = take(argv, "--hardnet", None)
+    q8 = "--q8" in argv
+    argv = [a for a in argv if a != "--q8"]
     if desc_kind not in ("hardnet", "sift") or len(argv) < 2:
         sys.exit(__doc__)
     dev = torch.device("cuda:0")
@@ -62,7 +65,9 @@ def main(argv):
         descs.append(r["descriptors"])
         lafs.append(r["LAFs"])
     names = argv[1:]
-    index = affnet_amd.DescriptorIndex(descs[1:], lafs[1:])
+    index = (affnet_amd.QuantizedDescriptorIndex if q8 else affnet_amd.DescriptorIndex)(descs[1:], lafs[1:])
+    if q8:
+        print("int8 index: scale %.4f" % index.scale)
     print("query %s: %d keypoints against %d images, %d descriptors in the index" % (argv[0], descs[0].size(0), len(index), index.D.size(0)))
     images, votes = index.shortlist(descs[0], top=int(top), k=int(k))
     print("vote shortlist (k = %d):" % int(k))

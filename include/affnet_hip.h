@@ -584,6 +584,44 @@ int affnet_knn(affnet_ctx* ctx, const float* d_q, int n1, const float* d_db, int
 int affnet_knn_vote(affnet_ctx* ctx, const float* d_dist, const int32_t* d_idx, int n1, int k, float ratio, const int32_t* d_row_image, int n2,
                     int n_images, int32_t* d_votes, void* stream);
 
+/* ---- descriptor index on int8 descriptors: exact integer k-NN on the i8 matrix instruction ---- */
+
+/* The same search over descriptors stored as 8-bit integers (132 bytes per row with its squared norm instead of 512): the shortlist needs ranks and
+ * a ratio gate only, and the exact fp32 matcher and the spatial verification still decide what is reported about a pair.  d_dist / d_idx of
+ * affnet_knn_q8 have the shapes and the order affnet_knn_vote reads.  No allocation, no synchronisation, all work on `stream`. */
+
+/* d_desc (n,128) float -> d_q (n,128) int8, d_sq (n) int32.  The rule, in fp32: q = clamp(rintf(x * scale), -127, 127) - one multiply, round half
+ * to even, NaN -> 0, +-inf -> +-127; d_sq[r] = the sum of q^2 over the row, exact (at most 128 * 127^2).  d_desc and d_q are 16-byte aligned.
+ * n = 0 is a no-op.  AFFNET_ERR_INVALID in front of the first launch: dim != 128, a negative n, scale not finite or <= 0, a NULL pointer. */
+int affnet_quantize_desc(affnet_ctx* ctx, const float* d_desc, int n, int dim, float scale, int8_t* d_q, int32_t* d_sq, void* stream);
+
+/* Host only.  The most column chunks the library chooses for an n1 x n2 int8 search, >= 1 for every size: what k <= 2 takes - enough chunks to
+ * give the device of `ctx` (NULL: a 256-CU part) the workgroups it keeps resident, but no chunk below a floor of 32-column steps; k > 2 runs
+ * on twice the row blocks and takes about half (descriptor index, int8). */
+int affnet_knn_q8_chunks(const affnet_ctx* ctx, int n1, int n2);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_knn_q8 called with this n_chunks; n_chunks = 0: enough for whatever
+ * affnet_knn_q8_chunks may choose.  Negative arguments count as 0. */
+size_t affnet_knn_q8_scratch_bytes(int n1, int n2, int k, int n_chunks);
+
+/* For every row of d_q (n1,128) int8 the k rows of d_db (n2,128) int8 at the smallest d2 = (qsq[r] + dbsq[c]) - 2 dot(q[r], db[c]), all in int32:
+ * exact, 0 <= d2 <= 128 * 254^2 = 8 258 048 < 2^24.  d_qsq (n1) / d_dbsq (n2): the rows' sums of squares as affnet_quantize_desc writes them.
+ * Order: the smaller d2, then the smaller database row - a total order without NaN, so the result does not depend on n_chunks.
+ * Outputs, (n1,k) each, ascending in that order: d_dist2 = d2; d_dist = sqrtf((float)d2) / scale, exactly these two correctly rounded fp32
+ * operations ((float)d2 is exact), the distance in the units of the descriptors that were quantised with `scale`; d_idx = the database row.
+ * With descriptors whose entries were not clipped by the quantiser, d_dist is within sqrt(128) / scale of the true Euclidean distance (each
+ * row moves by at most 0.5 sqrt(128) / scale in the 2-norm).  Slots for which no candidate is left hold (INT32_MAX, +inf, -1).
+ * skip_row / skip_n, n_chunks (0 = the library's choice for this k, at most affnet_knn_q8_chunks(ctx, n1, n2); at most 65535), n2 = 0 and
+ * n1 = 0 as in affnet_knn.
+ * The search runs on a grid of cdiv(n1, R) x n_chunks workgroups, R = 256 query rows for k <= 2 and 128 above: chunk c owns the 32-column steps
+ * [c * spc, (c + 1) * spc), spc = cdiv(cdiv(n2, 32), n_chunks), and a second kernel merges the chunks' lists per row.  d_q and d_db are
+ * 16-byte aligned.
+ * AFFNET_ERR_INVALID in front of the first launch: k outside 1..AFFNET_KNN_MAX_K, dim != 128, a negative size, n_chunks < 0 or > 65535, scale
+ * not finite or <= 0, a NULL pointer. */
+int affnet_knn_q8(affnet_ctx* ctx, const int8_t* d_q, const int32_t* d_qsq, int n1, const int8_t* d_db, const int32_t* d_dbsq, int n2, int dim,
+                  int k, int skip_row, int skip_n, int n_chunks, float scale, int32_t* d_dist2, float* d_dist, int32_t* d_idx, void* d_scratch,
+                  void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

@@ -132,6 +132,12 @@ DESIGN_KERNELS = [
     ("knn_tile_kernel<128, 8>", "descriptor index, k = 5 .. 8: eight neighbours per row and lane"),
     ("knn_merge_kernel<8>", "descriptor index: merge of the chunks' lists, one wavefront per query row (k = 5 .. 8)"),
     ("knn_vote_kernel", "descriptor index: one vote per (query row, image) behind the ratio gate"),
+    ("q8_quantize_kernel", "descriptor index, int8: fp32 descriptors -> int8 rows and their sums of squares, 32 lanes per row"),
+    ("knn_q8_tile_kernel<1, 4>", "descriptor index, int8, k = 1: i8 MFMA distance steps of 32 columns over one chunk, 256 query rows per workgroup"),
+    ("knn_q8_tile_kernel<2, 4>", "descriptor index, int8, k = 2: two neighbours per row and lane, 256 query rows per workgroup"),
+    ("knn_q8_tile_kernel<4, 2>", "descriptor index, int8, k = 3, 4: four neighbours per row and lane, 128 query rows per workgroup"),
+    ("knn_q8_tile_kernel<8, 2>", "descriptor index, int8, k = 5 .. 8: eight neighbours per row and lane, 128 query rows per workgroup"),
+    ("knn_q8_merge_kernel<8>", "descriptor index, int8: merge of the chunks' lists, one wavefront per query row (k = 5 .. 8)"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
     ("blur2d_kernel<13, 4>", "Gaussian blur 13 x 13, 64 x 64 tiles"),
     ("blur2d_pair_kernel<15, 9, 4>", "paired blur 15 x 15 / 9 x 9"),
