@@ -14,6 +14,7 @@ from .ReprojectionStuff import pair_table, enqueue_match_and_verify_many, match_
 from . import retrieval  # noqa: F401
 from .retrieval import knn, DescriptorIndex  # noqa: F401
 from .retrieval import quantization_scale, quantize, knn_q8, QuantizedDescriptorIndex  # noqa: F401
+from .retrieval import train_cells, ivf_layout, ivf_knn, IVFParts, IVFDescriptorIndex  # noqa: F401
 from .synthetic import synthetic_image, synthetic_hardnet_state  # noqa: F401
 
 __version__ = "0.1.0"

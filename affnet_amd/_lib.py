@@ -37,6 +37,7 @@ DESC_FORM_DIRECT, DESC_FORM_POLYPHASE, DESC_FORM_F43 = 0, 1, 2                  
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_EMPTY = 0, -1, -2, -3, -4
 VERIFY_AFFINE, VERIFY_HOMOGRAPHY, VERIFY_TILE, VERIFY_CHUNK = 0, 1, 128, 128                     # include/affnet_hip.h AFFNET_VERIFY_*
 KNN_MAX_K = 8                                                                                    # AFFNET_KNN_MAX_K: neighbours per query row of affnet_knn
+IVF_MAX_PROBE = 8                                                                                # AFFNET_IVF_MAX_PROBE: cells per query row of affnet_ivf_search
 VERIFY_FLAG_PAIR_RANGE = 8                                                                     # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
 
 
@@ -139,6 +140,10 @@ SYMBOLS = {
     "affnet_knn_q8_chunks": (_I, [_P, _I, _I]),
     "affnet_knn_q8_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_knn_q8": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P]),
+    "affnet_ivf_sqnorm": (_I, [_P, _P, _I, _I, _P, _P]),
+    "affnet_ivf_cell_means": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "affnet_ivf_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_ivf_search": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "affnet_extract_features": (_I, [_P, C.POINTER(Nets), _P, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_detect_image": (_I, [_P, _P, _P]),
     "affnet_detect_image_responses": (_I, [_P, _P, _P]),

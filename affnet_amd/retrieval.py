@@ -1,6 +1,7 @@
 """Descriptor index over many images (csrc/knn.hip): k nearest neighbours of a query image's descriptors among the concatenated descriptors of
 a database, one vote per image from them, and the vote shortlist handed to the batched matching + spatial verification of ReprojectionStuff
-(enqueue_match_and_verify_many) - the loop extract -> index -> shortlist -> verify."""
+(enqueue_match_and_verify_many) - the loop extract -> index -> shortlist -> verify.  The same index on int8 descriptors (csrc/knn_q8.hip)
+and behind an inverted file over k-means cells (csrc/ivf.hip) further down."""
 import numpy as np
 import torch
 
@@ -293,3 +294,165 @@ class QuantizedDescriptorIndex(DescriptorIndex):
         if self.D is None:
             raise ValueError("retrieve: the index was built with keep_float=False - the exact re-ranking needs the float descriptors")
         return DescriptorIndex.retrieve(self, desc_q, LAFs_q, *args, **kwargs)
+
+
+# ---- inverted file: the search over the rows of a few k-means cells (csrc/ivf.hip) ----
+
+def _check_nprobe(nprobe, what):
+    if not (isinstance(nprobe, (int, np.integer)) and 1 <= int(nprobe) <= _lib.IVF_MAX_PROBE):
+        raise ValueError("%s: nprobe must be an integer in 1..%d" % (what, _lib.IVF_MAX_PROBE))
+    return int(nprobe)
+
+
+def _check_cells(n_cells, what):
+    if not (isinstance(n_cells, (int, np.integer)) and int(n_cells) >= 1):
+        raise ValueError("%s: n_cells must be an integer >= 1" % what)
+    return int(n_cells)
+
+
+def default_cells(n):
+    """The codebook size of an index over n rows: the power of two nearest sqrt(n), at least 1."""
+    s = float(np.sqrt(max(int(n), 1)))
+    lo = 1 << int(np.floor(np.log2(s)))
+    return lo if s - lo <= 2 * lo - s else 2 * lo
+
+
+def ivf_layout(assign, n_cells):
+    """assign (n,) = the cell of every row -> (perm (n,) int32, cell_start (n_cells + 1,) int32): perm lists the rows cell by cell and ascends
+    inside every cell (a stable sort), cell c owns the positions [cell_start[c], cell_start[c + 1]).  Works on CPU tensors too; one read-back
+    on the device (the range check), a build-time call."""
+    n_cells = _check_cells(n_cells, "ivf_layout")
+    if not isinstance(assign, torch.Tensor) or assign.dim() != 1 or assign.is_floating_point():
+        raise ValueError("ivf_layout: assign must be a 1-D integer tensor")
+    a = assign.long()
+    if a.numel() and not (0 <= int(a.min()) and int(a.max()) < n_cells):
+        raise ValueError("ivf_layout: a cell outside 0..%d" % (n_cells - 1))
+    return _ivf_layout(a, n_cells)
+
+
+def _ivf_layout(a, n_cells):
+    perm = torch.sort(a, stable=True)[1].to(torch.int32)
+    start = torch.zeros(n_cells + 1, dtype=torch.int64, device=a.device)
+    start[1:] = torch.cumsum(torch.bincount(a, minlength=n_cells), 0)
+    return perm.contiguous(), start.to(torch.int32).contiguous()
+
+
+def _cell_means(rows, perm, cell_start, centroids):
+    ctx = engine.utility_ctx(rows.device)
+    rc = lib.affnet_ivf_cell_means(ctx, ptr(rows), rows.size(0), DIM, ptr(perm), ptr(cell_start), centroids.size(0), ptr(centroids),
+                                   engine.stream_of(rows.device))
+    check(rc, ctx, "affnet_ivf_cell_means")
+
+
+def initial_cells(n, n_cells):
+    """The rows the centroids start as: centroid i = row floor(i * n / n_cells).  No random numbers."""
+    return [(i * int(n)) // int(n_cells) for i in range(int(n_cells))]
+
+
+def train_cells(rows, n_cells, iters=10, train_rows=None):
+    """k-means codebook of rows (n,128): centroids (n_cells,128).  Deterministic: centroid i starts as training row floor(i * n / n_cells); every
+    Lloyd iteration assigns with knn(rows, centroids, k=1) (ties go to the smaller cell) and updates with affnet_ivf_cell_means (double sums in
+    row order, an empty cell keeps its centroid).  train_rows: None = all rows, an integer = about that many rows at a fixed stride."""
+    n_cells = _check_cells(n_cells, "train_cells")
+    if not (isinstance(iters, (int, np.integer)) and int(iters) >= 0):
+        raise ValueError("train_cells: iters must be an integer >= 0")
+    x = _check_desc(rows, "rows")
+    if x.size(0) == 0:
+        raise ValueError("train_cells: no rows")
+    if train_rows is not None:
+        if not (isinstance(train_rows, (int, np.integer)) and int(train_rows) >= 1):
+            raise ValueError("train_cells: train_rows must be None or an integer >= 1")
+        x = x[::max(-(-x.size(0) // int(train_rows)), 1)].contiguous()
+    cent = x[torch.tensor(initial_cells(x.size(0), n_cells), dtype=torch.int64, device=x.device)].contiguous()
+    for _ in range(int(iters)):
+        assign = knn(x, cent, 1)[1][:, 0]
+        perm, start = _ivf_layout(assign.long(), n_cells)
+        _cell_means(x, perm, start, cent)
+    return cent
+
+
+class IVFParts(object):
+    """The tables of an inverted file over D (n2,128) (include/affnet_hip.h, affnet_ivf_search): centroids (n_cells,128), sorted (n2,128),
+    sorted_sq (n2,), perm (n2,) int32, cell_start (n_cells + 1,) int32."""
+
+    def __init__(self, D, centroids):
+        D, c = _check_desc(D, "D"), _check_desc(centroids, "centroids")
+        if c.size(0) < 1 or c.device != D.device:
+            raise ValueError("IVFParts: the centroids must be at least one row on the device of D")
+        self.centroids, self.n_cells = c, c.size(0)
+        assign = knn(D, c, 1)[1][:, 0] if D.size(0) else torch.zeros(0, dtype=torch.int32, device=D.device)
+        self.perm, self.cell_start = _ivf_layout(assign.long(), self.n_cells)
+        self.sorted = D[self.perm.long()].contiguous()
+        self.sorted_sq = torch.empty(D.size(0), dtype=torch.float32, device=D.device)
+        if D.size(0):
+            ctx = engine.utility_ctx(D.device)
+            check(lib.affnet_ivf_sqnorm(ctx, ptr(self.sorted), D.size(0), DIM, ptr(self.sorted_sq), engine.stream_of(D.device)), ctx, "affnet_ivf_sqnorm")
+
+
+def ivf_knn(desc_q, index_or_parts, k=2, nprobe=8, skip=None, return_probes=False):
+    """knn restricted to the database rows in the nprobe cells nearest to each query row: (dist (n1,k) float32, idx (n1,k) int32 = ORIGINAL
+    database rows), distances, order and unfilled slots as knn's.  index_or_parts: an IVFDescriptorIndex or IVFParts.  return_probes: also the
+    cells (n1,nprobe) int32 that were looked at, -1 where the codebook has fewer than nprobe cells.  Enqueued on the current stream, no
+    synchronisation."""
+    k, nprobe = _check_k(k, "ivf_knn"), _check_nprobe(nprobe, "ivf_knn")
+    p = getattr(index_or_parts, "ivf", index_or_parts)
+    if not isinstance(p, IVFParts):
+        raise ValueError("ivf_knn: index_or_parts must be an IVFDescriptorIndex or IVFParts")
+    a = _check_desc(desc_q, "desc_q")
+    if a.device != p.sorted.device:
+        raise ValueError("ivf_knn: desc_q and the index live on different devices")
+    row, n = (0, 0) if skip is None else (int(skip[0]), int(skip[1]))
+    if n < 0:
+        raise ValueError("ivf_knn: negative skip length")
+    n1, n2, dev = a.size(0), p.sorted.size(0), a.device
+    dist = torch.empty(n1, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(n1, k, dtype=torch.int32, device=dev)
+    probes = torch.empty(n1, nprobe, dtype=torch.int32, device=dev)
+    if n1:
+        ctx = engine.utility_ctx(dev)
+        scratch = torch.empty(lib.affnet_ivf_scratch_bytes(n1, p.n_cells, nprobe, k), dtype=torch.uint8, device=dev)
+        one = torch.zeros(8, dtype=torch.int32, device=dev)          # stands in for an empty database: never read, but the boundary refuses NULL
+        rc = lib.affnet_ivf_search(ctx, ptr(a), n1, ptr(p.sorted if n2 else one), ptr(p.sorted_sq if n2 else one), ptr(p.perm if n2 else one), n2,
+                                   ptr(p.cell_start), ptr(p.centroids), p.n_cells, DIM, k, nprobe, row, n, ptr(dist), ptr(idx), ptr(probes),
+                                   ptr(scratch), engine.stream_of(dev))
+        check(rc, ctx, "affnet_ivf_search")
+    return (dist, idx, probes) if return_probes else (dist, idx)
+
+
+class IVFDescriptorIndex(DescriptorIndex):
+    """DescriptorIndex whose search looks at the rows of the nprobe nearest k-means cells of every query row (affnet_ivf_search): ivf (IVFParts:
+    centroids, sorted, sorted_sq, perm, cell_start) beside the tables of the base class, D included - retrieve's matcher reads image segments.
+    n_cells: None = default_cells(N); centroids: a trained codebook (n_cells,128), None = train_cells(D, n_cells, iters, train_rows).
+    nprobe may be changed after the build.  enqueue_votes searches with ivf_knn and votes with affnet_knn_vote; shortlist and retrieve are
+    inherited, so retrieve re-ranks with the exact fp32 matcher on D."""
+
+    def __init__(self, descs, LAFs=None, n_cells=None, nprobe=8, iters=10, train_rows=None, centroids=None):
+        self.nprobe = _check_nprobe(nprobe, "IVFDescriptorIndex")
+        if n_cells is not None:
+            n_cells = _check_cells(n_cells, "IVFDescriptorIndex")
+        DescriptorIndex.__init__(self, descs, LAFs)
+        if centroids is None:
+            if self.D.size(0) == 0:
+                raise ValueError("IVFDescriptorIndex: centroids must be given for an index without rows")
+            centroids = train_cells(self.D, n_cells or default_cells(self.D.size(0)), iters, train_rows)
+        elif n_cells is not None and (not isinstance(centroids, torch.Tensor) or centroids.dim() != 2 or centroids.size(0) != n_cells):
+            raise ValueError("IVFDescriptorIndex: centroids must have n_cells = %d rows" % n_cells)
+        self.ivf = IVFParts(self.D, centroids)
+        self.n_cells = self.ivf.n_cells
+
+    def enqueue_votes(self, desc_q, k=4, ratio=0.8, exclude=None):
+        """DescriptorIndex.enqueue_votes with the search restricted to self.nprobe cells per query row; no synchronisation."""
+        k = _check_k(k, "enqueue_votes")
+        skip = self.skip_range(exclude)
+        q = _check_desc(desc_q, "desc_q")
+        if q.device != self.device:
+            raise ValueError("enqueue_votes: desc_q and the index live on different devices")
+        dist, idx = ivf_knn(q, self.ivf, k, _check_nprobe(self.nprobe, "enqueue_votes"), skip)
+        votes = torch.empty(len(self.counts), dtype=torch.int32, device=self.device)
+        ctx = engine.utility_ctx(self.device)
+        one = torch.zeros(8, dtype=torch.int32, device=self.device)     # stands in for empty inputs: never read, but the boundary refuses NULL
+        n1, n2 = q.size(0), self.D.size(0)
+        rc = lib.affnet_knn_vote(ctx, ptr(dist if n1 else one), ptr(idx if n1 else one), n1, k, float(ratio), ptr(self.row_image if n2 else one), n2,
+                                 len(self.counts), ptr(votes), engine.stream_of(self.device))
+        check(rc, ctx, "affnet_knn_vote")
+        return votes, dist, idx

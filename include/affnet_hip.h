@@ -622,6 +622,49 @@ int affnet_knn_q8(affnet_ctx* ctx, const int8_t* d_q, const int32_t* d_qsq, int 
                   int k, int skip_row, int skip_n, int n_chunks, float scale, int32_t* d_dist2, float* d_dist, int32_t* d_idx, void* d_scratch,
                   void* stream);
 
+/* ---- descriptor index, inverted file: the search over the rows of a few k-means cells ---- */
+
+/* A codebook of n_cells centroids cuts the database rows into cells; the rows are stored a second time in cell order, and a query row is
+ * compared with the rows of its nprobe nearest cells only.  The tables of an index over n2 rows:
+ *   d_sorted (n2,128)        the database rows, permuted so that each cell's rows are contiguous;
+ *   d_sorted_sq (n2)         their squared norms (affnet_ivf_sqnorm);
+ *   d_perm (n2) int32        sorted position -> original database row, ASCENDING INSIDE EVERY CELL (a stable sort of the assignment);
+ *   d_cell_start (n_cells+1) int32, cell c owns the positions [cell_start[c], cell_start[c+1]); cells may be empty and start anywhere;
+ *   d_centroids (n_cells,128).
+ * The distances are affnet_knn's, bit for bit, and so is the order; what is approximate is which rows are looked at.  d_dist / d_idx have the
+ * shapes and the order affnet_knn_vote reads, d_idx holds ORIGINAL database rows. */
+#define AFFNET_IVF_MAX_PROBE 8
+
+/* d_sq[r] = the squared norm of row r of d_x (n,128), by the reduction affnet_knn applies to its rows (the same bits).  n = 0 is a no-op.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, a negative n, a NULL pointer. */
+int affnet_ivf_sqnorm(affnet_ctx* ctx, const float* d_x, int n, int dim, float* d_sq, void* stream);
+
+/* The update of one Lloyd iteration: d_centroids[c] = (float)(sum / count) over the rows d_rows[d_perm[p]], p in [cell_start[c], cell_start[c+1]),
+ * summed in ascending p into double accumulators (no floating-point atomics: the bytes repeat run to run); an empty cell keeps its centroid.
+ * d_perm (n) / d_cell_start (n_cells+1) as above, for the assignment of the n rows of d_rows (n,128).  n = 0 is a no-op.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, a negative n, n_cells < 1, a NULL pointer. */
+int affnet_ivf_cell_means(affnet_ctx* ctx, const float* d_rows, int n, int dim, const int32_t* d_perm, const int32_t* d_cell_start, int n_cells,
+                          float* d_centroids, void* stream);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_ivf_search.  Negative arguments count as 0. */
+size_t affnet_ivf_scratch_bytes(int n1, int n_cells, int nprobe, int k);
+
+/* For every row of d_q (n1,128) the k nearest among the database rows of its nprobe nearest cells: d_dist (n1,k) ascending, d_idx (n1,k) the
+ * original rows, order and unfilled slots (+inf, -1) as in affnet_knn.  Original rows skip_row <= c < skip_row + skip_n are no candidates.
+ * Steps, one linear chain of launches on `stream`, no allocation, no synchronisation: the coarse step affnet_knn(d_q, d_centroids, k = nprobe)
+ * (ties go to the smaller cell; with n_cells < nprobe the last probe slots are -1 and are skipped) -> d_probes (n1,nprobe) int32 when not NULL;
+ * the (row, cell) pairs grouped by cell on the device (integer atomics, a scan, a scatter; the order inside a group may vary from run to run,
+ * the result cannot: every pair is processed once and every selection uses a total order); one workgroup per (cell, block of 16 rows of its
+ * group) - their number is known on the device only, the grid is cdiv(n1 * nprobe, 16) + min(n_cells, n1 * nprobe) and a workgroup past the
+ * last item returns at once; per row a merge of its nprobe partial lists.  A cell is not split over workgroups by columns: one very large
+ * cell is searched correctly and slowly.
+ * n1 = 0 is a no-op; n2 = 0 (d_cell_start all zeros) gives only unfilled slots.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, k outside 1..AFFNET_KNN_MAX_K, nprobe outside 1..AFFNET_IVF_MAX_PROBE,
+ * n_cells < 1, a negative size, n1 * nprobe * k above 2^31 - 1, a NULL pointer other than d_probes. */
+int affnet_ivf_search(affnet_ctx* ctx, const float* d_q, int n1, const float* d_sorted, const float* d_sorted_sq, const int32_t* d_perm, int n2,
+                      const int32_t* d_cell_start, const float* d_centroids, int n_cells, int dim, int k, int nprobe, int skip_row, int skip_n,
+                      float* d_dist, int32_t* d_idx, int32_t* d_probes, void* d_scratch, void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

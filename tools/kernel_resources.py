@@ -138,6 +138,13 @@ DESIGN_KERNELS = [
     ("knn_q8_tile_kernel<4, 2>", "descriptor index, int8, k = 3, 4: four neighbours per row and lane, 128 query rows per workgroup"),
     ("knn_q8_tile_kernel<8, 2>", "descriptor index, int8, k = 5 .. 8: eight neighbours per row and lane, 128 query rows per workgroup"),
     ("knn_q8_merge_kernel<8>", "descriptor index, int8: merge of the chunks' lists, one wavefront per query row (k = 5 .. 8)"),
+    ("ivf_tile_kernel<1>", "descriptor index, inverted file, k = 1: 16 gathered query rows against one cell, the four waves split its 16-column tiles"),
+    ("ivf_tile_kernel<2>", "descriptor index, inverted file, k = 2: two neighbours per row and lane"),
+    ("ivf_tile_kernel<4>", "descriptor index, inverted file, k = 3, 4: four neighbours per row and lane"),
+    ("ivf_tile_kernel<8>", "descriptor index, inverted file, k = 5 .. 8: eight neighbours per row and lane"),
+    ("ivf_merge_kernel<8>", "descriptor index, inverted file: merge of a row's nprobe partial lists, one wavefront per query row (k = 5 .. 8)"),
+    ("ivf_scan_kernel", "descriptor index, inverted file: scan over the cells' pair counts, group starts and the table of work items, one workgroup"),
+    ("ivf_cell_means_kernel", "descriptor index, inverted file: codebook update, one workgroup per cell, double sums in row order"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
     ("blur2d_kernel<13, 4>", "Gaussian blur 13 x 13, 64 x 64 tiles"),
     ("blur2d_pair_kernel<15, 9, 4>", "paired blur 15 x 15 / 9 x 9"),
