@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/affnet_hip.h"
@@ -372,6 +373,49 @@ int aff_finish_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int
 int aff_margin_affnet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B, int32_t* flags);
 int aff_finish_orinet(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int rows, int B);
 int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int B);
+
+// match.hip: out[r] = |x[r]|^2 of n rows (n <= 0: no launch) by the matcher's own kernel - the one reduction behind every distance of the matcher
+// and of the descriptor index (knn.hip, ivf.hip), which is what makes their distances equal bit for bit
+void aff_sqnorm_launch(hipStream_t st, const float* x, int n, int dim, float* out);
+// knn.hip: the n_lists partial lists (n1, n_lists, k) of every row -> its k neighbours (knn_merge_kernel; the chunks of affnet_knn, the probed cells of affnet_ivf_search)
+void aff_knn_merge_launch(hipStream_t st, const float* part_d, const int32_t* part_i, int n1, int n_lists, int k, float* out_d, int32_t* out_i);
+
+// ---- host helpers of the descriptor index's searches (knn.hip, knn_q8.hip, ivf.hip) ---------------
+// the rows [skip_row, skip_row + skip_n) that are no candidates, as [lo, hi) inside [0, n2); lo >= hi: no skip
+struct AffSkip { int lo, hi; };
+static inline AffSkip aff_skip_range(int skip_row, int skip_n, int n2) {
+    const long long lo64 = skip_row < 0 ? 0 : skip_row, hi64 = (long long)skip_row + skip_n;
+    return {(int)(lo64 < n2 ? lo64 : n2), (int)(hi64 < 0 ? 0 : (hi64 < n2 ? hi64 : n2))};
+}
+
+// capacity of the register lists (topk.h) that hold k candidates: the kernels are built for 1, 2, 4 and 8
+static inline int aff_topk_cap(int k) { return k == 1 ? 1 : (k == 2 ? 2 : (k <= 4 ? 4 : 8)); }
+// f(std::integral_constant<int, aff_topk_cap(k)>()): the capacity as a compile-time constant, for the kernels' template argument
+template <typename F>
+static inline void aff_topk_dispatch(int k, F f) {
+    switch (aff_topk_cap(k)) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+
+// Chunks of the database a search of `row_blocks` blocks of query rows is cut into (grid = row blocks x chunks): enough for workgroups_per_cu
+// workgroups on every CU (256 CUs without a context, or where the count cannot be read), no chunk below min_units of the `units` the tile loop
+// walks, at most max_chunks, at least 1.
+static inline int aff_chunk_choice(const affnet_ctx* ctx, long long row_blocks, long long units, int workgroups_per_cu, int min_units, int max_chunks) {
+    int cus = 256;
+    if (ctx) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && v > 0) cus = v;
+        else (void)hipGetLastError();
+    }
+    const long long want = ((long long)workgroups_per_cu * cus + row_blocks - 1) / row_blocks, most = units / min_units;
+    long long nc = want < most ? want : most;
+    if (nc > max_chunks) nc = max_chunks;
+    return nc < 1 ? 1 : (int)nc;
+}
 
 // ---- sampler math shared by laf_ops.hip, handcrafted.hip and cnn_trunk.h --------------------------
 // LDS-staged footprint of one patch (north_star: "coalesced HBM reads and LDS-staged image tiles"): the affine frame of a PS x PS

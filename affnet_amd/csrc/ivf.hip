@@ -3,85 +3,26 @@
 // Philbin et al. 2007 with exact distances inside the cells).
 //
 // The distance is knn.hip's: sqrt(((|a|^2 + |b|^2) - 2 a.b) + 1e-6), a.b by the same chain of 32 v_mfma_f32_16x16x4_f32 over the same K
-// order, the squared norms by the same reduction, so every distance reported here is the element affnet_distance_matrix writes for (query
-// row, ORIGINAL database row), bit for bit.  What is approximate is which rows are looked at, never what is reported about one.
+// order, the squared norms by the same kernel (aff_sqnorm_launch, match.hip), so every distance reported here is the element
+// affnet_distance_matrix writes for (query row, ORIGINAL database row), bit for bit.  What is approximate is which rows are looked at, never
+// what is reported about one.
 //
-// Order of candidates, as in knn.hip: a NaN distance in front of every number, then the smaller distance, then the smaller row.  Inside a
+// Order of candidates, topk.h's: a NaN distance in front of every number, then the smaller distance, then the smaller row.  Inside a
 // cell the row is the position in the cell-ordered copy (perm ascends inside every cell, so the order by position IS the order by original
 // row); across a row's cells the merge compares original rows.  The order is total and every (query row, cell) pair is processed exactly
 // once, so the result does not depend on the order in which the grouping's atomics hand out places.
 //
-// The list and merge helpers below restate knn.hip's (KnnList, knn_lanes_next, knn_merge_kernel) under names of their own: knn.hip and its
-// object stay as they are.
+// The lists and their merges are topk.h's, shared with knn.hip and knn_q8.hip, and a row's partial lists are reduced by knn.hip's merge kernel
+// (aff_knn_merge_launch).  The tile kernel and the grouping in front of it are this file's own.
 #include <math.h>
 
 #include "common.h"
+#include "topk.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#define IVF_EMPTY 0x7fffffff          // position of an unfilled slot inside the kernels (behind every real one in the order); written out as -1
 #define IVF_RB 16                     // query rows of one work item: one MFMA row block, shared by the four waves of the workgroup
 #define IVF_SCAN_THREADS 1024
-
-// (d, c) stands in front of (s, si)
-__device__ __forceinline__ bool ivf_before(float d, int c, float s, int si) {
-    const bool dn = d != d, sn = s != s;
-    return dn ? (!sn || c < si) : (!sn && (d < s || (d == s && c < si)));
-}
-
-// A sorted list of CAP candidates in registers (compile-time indices only: a dynamically indexed array would live in scratch memory).
-template <int CAP>
-struct IvfList {
-    float d[CAP];
-    int i[CAP];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int s = 0; s < CAP; ++s) { d[s] = INFINITY; i[s] = IVF_EMPTY; }
-    }
-    __device__ __forceinline__ void insert(float nd, int ni) {
-        if (!ivf_before(nd, ni, d[CAP - 1], i[CAP - 1])) return;
-        d[CAP - 1] = nd; i[CAP - 1] = ni;
-#pragma unroll
-        for (int s = CAP - 1; s > 0; --s) {
-            const bool up = ivf_before(d[s], i[s], d[s - 1], i[s - 1]);
-            const float td = d[s - 1]; const int ti = i[s - 1];
-            d[s - 1] = up ? d[s] : td; i[s - 1] = up ? i[s] : ti;
-            d[s] = up ? td : d[s]; i[s] = up ? ti : i[s];
-        }
-    }
-    __device__ __forceinline__ void pop(bool yes) {
-#pragma unroll
-        for (int s = 0; s + 1 < CAP; ++s) { d[s] = yes ? d[s + 1] : d[s]; i[s] = yes ? i[s + 1] : i[s]; }
-        d[CAP - 1] = yes ? INFINITY : d[CAP - 1]; i[CAP - 1] = yes ? IVF_EMPTY : i[CAP - 1];
-    }
-};
-
-// One round of the merge of the sorted lists of W neighbouring lanes: a butterfly minimum over the heads, after which every lane holds the
-// winner (bd, bi), and the lane whose head it was (real ids are unique over the lanes) drops it.
-template <int CAP, int W>
-__device__ __forceinline__ void ivf_lanes_next(IvfList<CAP>& L, float& bd, int& bi) {
-    bd = L.d[0];
-    bi = L.i[0];
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-        const float od = __shfl_xor(bd, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        const bool take = ivf_before(od, oi, bd, bi);
-        bd = take ? od : bd; bi = take ? oi : bi;
-    }
-    L.pop(bi != IVF_EMPTY && L.i[0] == bi);
-}
-
-// one wavefront per row; torch.sum(a * a, dim=1) - knn_sqnorm_kernel's reduction, operation by operation
-__global__ __launch_bounds__(256) void ivf_sqnorm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
-    float s = 0.f;
-    for (int k = lane; k < dim; k += 64) { const float v = x[(size_t)row * dim + k]; s = fmaf(v, v, s); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) out[row] = s;
-}
 
 // One workgroup per cell, one thread per column: the cell's rows, read through perm in ascending position order, summed into a double;
 // centroid = (float)(sum / count).  An empty cell keeps what it has.  No atomics: the bytes repeat run to run.
@@ -197,7 +138,7 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const float* __restrict__
     float asq[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) asq[r] = q_sq[min(max(pairs[g0 + min(4 * kq + r, cnt - 1)] / nprobe, 0), n1 - 1)];
-    IvfList<CAP> L[4];
+    TopkList<float, CAP> L[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) L[r].clear();
 
@@ -242,7 +183,7 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const float* __restrict__
             if (j < k) {          // uniform
                 float bd;
                 int bi;
-                ivf_lanes_next<CAP, 16>(L[r], bd, bi);
+                topk_lanes_next<16>(L[r], bd, bi);
                 if (m == 0) { s_d[wave][4 * kq + r][j] = bd; s_i[wave][4 * kq + r][j] = bi; }
             }
         }
@@ -252,11 +193,11 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const float* __restrict__
     for (int rr = 0; rr < 4; ++rr) {
         const int row = 4 * wave + rr;
         if (row >= cnt) break;          // uniform over the wave, no barrier behind
-        IvfList<CAP> M;
+        TopkList<float, CAP> M;
         M.clear();
         if (lane < 4 * k) {
             const int ci = s_i[lane / k][row][lane % k];
-            if (ci != IVF_EMPTY) M.insert(s_d[lane / k][row][lane % k], ci);
+            if (ci != TOPK_EMPTY) M.insert(s_d[lane / k][row][lane % k], ci);
         }
         const size_t o = (size_t)pairs[g0 + row] * k;
 #pragma unroll
@@ -264,35 +205,9 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const float* __restrict__
             if (j < k) {          // uniform
                 float bd;
                 int bi;
-                ivf_lanes_next<CAP, 64>(M, bd, bi);
-                if (lane == 0) { part_d[o + j] = bd; part_i[o + j] = bi == IVF_EMPTY ? -1 : perm[bi]; }
+                topk_lanes_next<64>(M, bd, bi);
+                if (lane == 0) { part_d[o + j] = bd; part_i[o + j] = bi == TOPK_EMPTY ? -1 : perm[bi]; }
             }
-        }
-    }
-}
-
-// One wavefront per query row: its nprobe partial lists (nprobe * k slots, unfilled ones hold -1) -> the row's k neighbours, by
-// (NaN, distance, original row) - knn_merge_kernel with n_chunks = nprobe.
-template <int CAP>
-__global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_lists,
-                                                        int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n1) return;      // uniform over the wave
-    IvfList<CAP> L;
-    L.clear();
-    const size_t base = (size_t)row * n_lists * k;
-    const int total = n_lists * k;
-    for (int e = lane; e < total; e += 64) {
-        const int ci = part_i[base + e];
-        if (ci >= 0) L.insert(part_d[base + e], ci);
-    }
-#pragma unroll
-    for (int j = 0; j < CAP; ++j) {
-        if (j < k) {          // uniform
-            float bd;
-            int bi;
-            ivf_lanes_next<CAP, 64>(L, bd, bi);
-            if (lane == 0) { out_d[(size_t)row * k + j] = bd; out_i[(size_t)row * k + j] = bi == IVF_EMPTY ? -1 : bi; }
         }
     }
 }
@@ -304,7 +219,7 @@ extern "C" int affnet_ivf_sqnorm(affnet_ctx* ctx, const float* d_x, int n, int d
     if (!ctx || !d_x || !d_sq || n < 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "ivf_sqnorm: bad argument");
     if (dim != 128) return aff_fail(ctx, AFFNET_ERR_INVALID, "ivf_sqnorm: descriptor length %d (only 128 is built)", dim);
     if (n == 0) return AFFNET_OK;
-    hipLaunchKernelGGL(ivf_sqnorm_kernel, dim3(aff_cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, d_x, n, dim, d_sq);
+    aff_sqnorm_launch((hipStream_t)stream, d_x, n, dim, d_sq);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }
@@ -363,17 +278,6 @@ extern "C" size_t affnet_ivf_scratch_bytes(int n1, int n_cells, int nprobe, int 
     return ivf_layout(n1 > 0 ? (size_t)n1 : 0, n_cells > 0 ? (size_t)n_cells : 0, nprobe > 0 ? (size_t)nprobe : 0, k > 0 ? (size_t)k : 0).total;
 }
 
-template <int CAP>
-static void ivf_launch(hipStream_t st, int grid, const float* q, const float* q_sq, int n1, const float* sorted, const float* sorted_sq,
-                       const int32_t* perm, int n2, const int32_t* cell_start, const int32_t* group_start, const int32_t* pairs, const int2* items,
-                       const int32_t* meta, int nprobe, int k, int lo, int hi, float* part_d, int32_t* part_i, float* d_dist, int32_t* d_idx) {
-    hipLaunchKernelGGL((ivf_tile_kernel<CAP>), dim3(grid), dim3(256), 0, st, q, q_sq, n1, sorted, sorted_sq, perm, n2, cell_start, group_start, pairs,
-                       items, meta, nprobe, k, lo, hi, part_d, part_i);
-    if (nprobe > 1)
-        hipLaunchKernelGGL((ivf_merge_kernel<CAP>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, (const float*)part_d, (const int32_t*)part_i, n1, nprobe,
-                           k, d_dist, d_idx);
-}
-
 extern "C" int affnet_ivf_search(affnet_ctx* ctx, const float* d_q, int n1, const float* d_sorted, const float* d_sorted_sq, const int32_t* d_perm,
                                  int n2, const int32_t* d_cell_start, const float* d_centroids, int n_cells, int dim, int k, int nprobe,
                                  int skip_row, int skip_n, float* d_dist, int32_t* d_idx, int32_t* d_probes, void* d_scratch, void* stream) {
@@ -406,12 +310,11 @@ extern "C" int affnet_ivf_search(affnet_ctx* ctx, const float* d_q, int n1, cons
     const int n_pairs = n1 * nprobe;
     const long long slots = (long long)n_pairs * k;
     const int max_items = (int)ivf_max_items(n_pairs, n_cells);
-    const long long lo64 = skip_row < 0 ? 0 : skip_row, hi64 = (long long)skip_row + skip_n;
-    const int lo = (int)(lo64 < n2 ? lo64 : n2), hi = (int)(hi64 < 0 ? 0 : (hi64 < n2 ? hi64 : n2));      // [lo, hi) inside [0, n2); lo >= hi: no skip
+    const AffSkip skip = aff_skip_range(skip_row, skip_n, n2);
 
     const long long init_n = slots > n_cells ? slots : n_cells;
     hipLaunchKernelGGL(ivf_init_kernel, dim3((unsigned)((init_n + 255) / 256)), dim3(256), 0, st, part_d, part_i, slots, count, n_cells);
-    hipLaunchKernelGGL(ivf_sqnorm_kernel, dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, d_q, n1, dim, q_sq);
+    aff_sqnorm_launch(st, d_q, n1, dim, q_sq);
     AFF_LAUNCH_CHECK(ctx);
     {
         const int rc = affnet_knn(ctx, d_q, n1, d_centroids, n_cells, dim, nprobe, 0, 0, ivf_coarse_chunks(n1, n_cells), cdist, probes, s + L.coarse, stream);
@@ -420,15 +323,12 @@ extern "C" int affnet_ivf_search(affnet_ctx* ctx, const float* d_q, int n1, cons
     hipLaunchKernelGGL(ivf_count_kernel, dim3(aff_cdiv(n_pairs, 256)), dim3(256), 0, st, (const int32_t*)probes, n_pairs, n_cells, count);
     hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), dim3(IVF_SCAN_THREADS), 0, st, (const int32_t*)count, n_cells, group_start, cursor, items, max_items, meta);
     hipLaunchKernelGGL(ivf_scatter_kernel, dim3(aff_cdiv(n_pairs, 256)), dim3(256), 0, st, (const int32_t*)probes, n_pairs, n_cells, cursor, pairs);
-    const int cap = k == 1 ? 1 : (k == 2 ? 2 : (k <= 4 ? 4 : 8));
-#define IVF_ARGS st, max_items, d_q, q_sq, n1, d_sorted, d_sorted_sq, d_perm, n2, d_cell_start, group_start, pairs, items, meta, nprobe, k, lo, hi, part_d, part_i, d_dist, d_idx
-    switch (cap) {
-        case 1: ivf_launch<1>(IVF_ARGS); break;
-        case 2: ivf_launch<2>(IVF_ARGS); break;
-        case 4: ivf_launch<4>(IVF_ARGS); break;
-        default: ivf_launch<8>(IVF_ARGS); break;
-    }
-#undef IVF_ARGS
+    aff_topk_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL((ivf_tile_kernel<decltype(cap)::value>), dim3(max_items), dim3(256), 0, st, d_q, (const float*)q_sq, n1, d_sorted, d_sorted_sq,
+                           d_perm, n2, d_cell_start, (const int32_t*)group_start, (const int32_t*)pairs, (const int2*)items, (const int32_t*)meta, nprobe,
+                           k, skip.lo, skip.hi, part_d, part_i);
+    });
+    if (nprobe > 1) aff_knn_merge_launch(st, part_d, part_i, n1, nprobe, k, d_dist, d_idx);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

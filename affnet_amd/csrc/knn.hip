@@ -8,106 +8,32 @@
 // what differs is that a workgroup walks only the 16-column tiles of ITS chunk of the database (grid = row blocks x chunks, so that a large
 // database fills the part whatever the number of query rows) and keeps up to 8 neighbours per row instead of one.
 //
-// Order of candidates, everywhere in this file: a NaN distance (the fp32 expansion can go below -1e-6 for near-identical vectors) in front of every
-// number, then the smaller distance, then the smaller database row.  The order is total and every distance is computed once, so the result does
-// not depend on the number of chunks.
+// The order of candidates, the lists and their merges: topk.h, shared with knn_q8.hip and ivf.hip.  The squared norms: match.hip's own kernel
+// (aff_sqnorm_launch), so the equality with affnet_distance_matrix rests on one definition.
 #include <math.h>
 
 #include "common.h"
+#include "topk.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#define KNN_EMPTY 0x7fffffff          // row index of an unfilled slot inside the kernels (behind every real row in the order); written out as -1
 #define KNN_BS(DIM) ((DIM) + 4)       // floats per staged column: the 16-byte skew spreads the 16 columns over the banks (match.hip ROWMIN_BS)
 #define KNN_WG_PER_CU 3               // affnet_knn_chunks: workgroups per CU the grid aims at (what the k = 8 kernel keeps resident; DESIGN.md, descriptor index)
 #define KNN_MIN_TILES 5               // affnet_knn_chunks: no chunk below this many 16-column tiles (descriptor index: the measured floor)
 #define KNN_MAX_CHUNKS 1024           // affnet_knn_chunks never chooses more; the size affnet_knn_scratch_bytes assumes for n_chunks = 0
 
-// (d, c) stands in front of (s, si)
-__device__ __forceinline__ bool knn_before(float d, int c, float s, int si) {
-    const bool dn = d != d, sn = s != s;
-    return dn ? (!sn || c < si) : (!sn && (d < s || (d == s && c < si)));
-}
-
-// A sorted list of CAP candidates in registers (compile-time indices only: a dynamically indexed array would live in scratch memory).
-template <int CAP>
-struct KnnList {
-    float d[CAP];
-    int i[CAP];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int s = 0; s < CAP; ++s) { d[s] = INFINITY; i[s] = KNN_EMPTY; }
-    }
-    // the candidate replaces the last slot when it stands in front of it, then rises to its place
-    __device__ __forceinline__ void insert(float nd, int ni) {
-        if (!knn_before(nd, ni, d[CAP - 1], i[CAP - 1])) return;
-        d[CAP - 1] = nd; i[CAP - 1] = ni;
-#pragma unroll
-        for (int s = CAP - 1; s > 0; --s) {
-            const bool up = knn_before(d[s], i[s], d[s - 1], i[s - 1]);
-            const float td = d[s - 1]; const int ti = i[s - 1];
-            d[s - 1] = up ? d[s] : td; i[s - 1] = up ? i[s] : ti;
-            d[s] = up ? td : d[s]; i[s] = up ? ti : i[s];
-        }
-    }
-    __device__ __forceinline__ void pop(bool yes) {
-#pragma unroll
-        for (int s = 0; s + 1 < CAP; ++s) { d[s] = yes ? d[s + 1] : d[s]; i[s] = yes ? i[s + 1] : i[s]; }
-        d[CAP - 1] = yes ? INFINITY : d[CAP - 1]; i[CAP - 1] = yes ? KNN_EMPTY : i[CAP - 1];
-    }
-};
-
-// One round of the merge of the sorted lists of W neighbouring lanes (W = 16 or 64, a power of two): a butterfly minimum over the lists' heads,
-// after which every lane holds the winner (bd, bi), and the lane whose head it was (real rows are unique over the lanes) drops it.
-template <int CAP, int W>
-__device__ __forceinline__ void knn_lanes_next(KnnList<CAP>& L, float& bd, int& bi) {
-    bd = L.d[0];
-    bi = L.i[0];
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-        const float od = __shfl_xor(bd, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        const bool take = knn_before(od, oi, bd, bi);
-        bd = take ? od : bd; bi = take ? oi : bi;
-    }
-    L.pop(bi != KNN_EMPTY && L.i[0] == bi);
-}
-
-// The first k of the union of those lists: lane `writer` of the group stores round j at out[j].
-template <int CAP, int W>
-__device__ __forceinline__ void knn_lanes_merge(KnnList<CAP>& L, int k, bool writer, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+// The first k of the union of the lists of W lanes: lane `writer` of the group stores round j at out[j], an unfilled slot as -1.
+template <int W, int CAP>
+__device__ __forceinline__ void knn_lanes_store(TopkList<float, CAP>& L, int k, bool writer, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
 #pragma unroll
     for (int j = 0; j < CAP; ++j) {
         if (j < k) {        // uniform
             float bd;
             int bi;
-            knn_lanes_next<CAP, W>(L, bd, bi);
-            if (writer) { out_d[j] = bd; out_i[j] = bi == KNN_EMPTY ? -1 : bi; }
+            topk_lanes_next<W>(L, bd, bi);
+            if (writer) { out_d[j] = bd; out_i[j] = bi == TOPK_EMPTY ? -1 : bi; }
         }
     }
-}
-
-// The distance of the k-th candidate of that union (+inf while it has fewer than k), on a copy of the lists: nothing behind it can reach a
-// row's result, so the tile loop takes it as the row's bound.
-template <int CAP, int W>
-__device__ __forceinline__ float knn_lanes_kth(KnnList<CAP> L, int k) {
-    float kth = INFINITY;
-    int bi;
-#pragma unroll
-    for (int j = 0; j < CAP; ++j)
-        if (j < k) knn_lanes_next<CAP, W>(L, kth, bi);        // uniform
-    return kth;
-}
-
-// one wavefront per row; torch.sum(a * a, dim=1) - the reduction of match.hip's sqnorm_body, operation by operation
-__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ x, int n, int dim, float* __restrict__ out) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
-    float s = 0.f;
-    for (int k = lane; k < dim; k += 64) { const float v = x[(size_t)row * dim + k]; s = fmaf(v, v, s); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) out[row] = s;
 }
 
 // grid (cdiv(n1, 64), n_chunks).  Workgroup = 4 wavefronts = 64 rows of `a`; wave w owns rows 16w..16w+15 and walks the tiles
@@ -131,7 +57,7 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__
     const int tiles = (n2 + 15) >> 4;
     const long long t0l = (long long)chunk * tpc;
     const int t0 = t0l < tiles ? (int)t0l : tiles, t1 = min(tiles, t0 + tpc);          // uniform over the workgroup
-    KnnList<CAP> L[4];
+    TopkList<float, CAP> L[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) L[r].clear();
     if (t0 < t1) {
@@ -195,7 +121,7 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__
             const int seen = t - t0 + 1;
             if (seen >= 8 && ((seen & (seen - 1)) == 0 || (seen & 255) == 0)) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) bound[r] = knn_lanes_kth<CAP, 16>(L[r], k);
+                for (int r = 0; r < 4; ++r) bound[r] = topk_lanes_kth<16>(L[r], k);
             }
             if (more) tile_store(buf ^ 1);      // the other buffer was last read one tile ago, in front of that tile's barrier
             __syncthreads();
@@ -205,52 +131,35 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__
     for (int r = 0; r < 4; ++r) {
         const int row = min(row0 + 4 * kq + r, n1 - 1);
         const size_t o = ((size_t)row * n_chunks + chunk) * k;
-        knn_lanes_merge<CAP, 16>(L[r], k, m == 0 && row0 + 4 * kq + r < n1, out_d + o, out_i + o);
+        knn_lanes_store<16>(L[r], k, m == 0 && row0 + 4 * kq + r < n1, out_d + o, out_i + o);
     }
 }
 
-// One wavefront per row: the n_chunks partial lists (n_chunks * k slots, unfilled ones hold -1) -> the row's k neighbours.
+// One wavefront per row: the n_lists partial lists of the row (the chunks of a search here, the probed cells of one in ivf.hip) -> its k neighbours.
 template <int CAP>
-__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_chunks,
+__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_lists,
                                                         int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n1) return;      // uniform over the wave
-    KnnList<CAP> L;
+    TopkList<float, CAP> L;
     L.clear();
-    const size_t base = (size_t)row * n_chunks * k;
-    const long long total = (long long)n_chunks * k;
-    for (long long e = lane; e < total; e += 64) {
+    const size_t base = (size_t)row * n_lists * k;
+    const long long total = (long long)n_lists * k;
+    for (long long e = lane; e < total; e += 64) {          // the row's partial slots, strided over the lanes; unfilled ones hold row -1
         const int ci = part_i[base + e];
         if (ci >= 0) L.insert(part_d[base + e], ci);
     }
-    knn_lanes_merge<CAP, 64>(L, k, lane == 0, out_d + (size_t)row * k, out_i + (size_t)row * k);
+    knn_lanes_store<64>(L, k, lane == 0, out_d + (size_t)row * k, out_i + (size_t)row * k);
 }
 
-template <int CAP>
-static void knn_launch(hipStream_t st, int nc, const float* q, int n1, const float* db, int n2, const float* a_sq, const float* b_sq, int k, int lo,
-                       int hi, int tpc, float* part_d, int32_t* part_i, float* d_dist, int32_t* d_idx) {
-    const dim3 grid(aff_cdiv(n1, 64), nc);
-    if (nc == 1) {
-        hipLaunchKernelGGL((knn_tile_kernel<128, CAP>), grid, dim3(256), 0, st, q, n1, db, n2, a_sq, b_sq, k, lo, hi, tpc, d_dist, d_idx);
-        return;
-    }
-    hipLaunchKernelGGL((knn_tile_kernel<128, CAP>), grid, dim3(256), 0, st, q, n1, db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i);
-    hipLaunchKernelGGL((knn_merge_kernel<CAP>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, (const float*)part_d, (const int32_t*)part_i, n1, nc, k,
-                       d_dist, d_idx);
+void aff_knn_merge_launch(hipStream_t st, const float* part_d, const int32_t* part_i, int n1, int n_lists, int k, float* out_d, int32_t* out_i) {
+    aff_topk_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL((knn_merge_kernel<decltype(cap)::value>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, part_d, part_i, n1, n_lists, k, out_d, out_i);
+    });
 }
 
 extern "C" int affnet_knn_chunks(const affnet_ctx* ctx, int n1, int n2) {
-    int cus = 256;
-    if (ctx) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && v > 0) cus = v;
-        else (void)hipGetLastError();
-    }
-    const long long row_blocks = n1 > 0 ? aff_cdiv(n1, 64) : 1, tiles = n2 > 0 ? ((long long)n2 + 15) / 16 : 0;
-    const long long want = ((long long)KNN_WG_PER_CU * cus + row_blocks - 1) / row_blocks, most = tiles / KNN_MIN_TILES;
-    long long nc = want < most ? want : most;
-    if (nc > KNN_MAX_CHUNKS) nc = KNN_MAX_CHUNKS;
-    return nc < 1 ? 1 : (int)nc;
+    return aff_chunk_choice(ctx, n1 > 0 ? aff_cdiv(n1, 64) : 1, n2 > 0 ? ((long long)n2 + 15) / 16 : 0, KNN_WG_PER_CU, KNN_MIN_TILES, KNN_MAX_CHUNKS);
 }
 
 // scratch: a_sq float (n1) | b_sq float (n2) | partial distances float (n1, n_chunks, k) | partial rows int32 (n1, n_chunks, k)
@@ -274,21 +183,21 @@ extern "C" int affnet_knn(affnet_ctx* ctx, const float* d_q, int n1, const float
     hipStream_t st = (hipStream_t)stream;
     const int nc = n_chunks ? n_chunks : affnet_knn_chunks(ctx, n1, n2);
     const int tiles = (int)(((long long)n2 + 15) / 16), tpc = aff_cdiv(tiles, nc);
-    const long long lo64 = skip_row < 0 ? 0 : skip_row, hi64 = (long long)skip_row + skip_n;
-    const int lo = (int)(lo64 < n2 ? lo64 : n2), hi = (int)(hi64 < 0 ? 0 : (hi64 < n2 ? hi64 : n2));      // [lo, hi) inside [0, n2); lo >= hi: no skip
+    const AffSkip skip = aff_skip_range(skip_row, skip_n, n2);
     float* a_sq = (float*)d_scratch;
     float* b_sq = a_sq + n1;
     float* part_d = (float*)((char*)d_scratch + knn_norm_bytes((size_t)n1, (size_t)n2));
     int32_t* part_i = (int32_t*)(part_d + (size_t)n1 * nc * k);
-    hipLaunchKernelGGL(knn_sqnorm_kernel, dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, d_q, n1, dim, a_sq);
-    if (n2 > 0) hipLaunchKernelGGL(knn_sqnorm_kernel, dim3(aff_cdiv(n2, 4)), dim3(256), 0, st, d_db, n2, dim, b_sq);
-    const int cap = k == 1 ? 1 : (k == 2 ? 2 : (k <= 4 ? 4 : 8));
-    switch (cap) {
-        case 1: knn_launch<1>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
-        case 2: knn_launch<2>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
-        case 4: knn_launch<4>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
-        default: knn_launch<8>(st, nc, d_q, n1, d_db, n2, a_sq, b_sq, k, lo, hi, tpc, part_d, part_i, d_dist, d_idx); break;
-    }
+    aff_sqnorm_launch(st, d_q, n1, dim, a_sq);
+    aff_sqnorm_launch(st, d_db, n2, dim, b_sq);
+    // one chunk: its lists are the result
+    float* tile_d = nc == 1 ? d_dist : part_d;
+    int32_t* tile_i = nc == 1 ? d_idx : part_i;
+    aff_topk_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL((knn_tile_kernel<128, decltype(cap)::value>), dim3(aff_cdiv(n1, 64), nc), dim3(256), 0, st, d_q, n1, d_db, n2,
+                           (const float*)a_sq, (const float*)b_sq, k, skip.lo, skip.hi, tpc, tile_d, tile_i);
+    });
+    if (nc > 1) aff_knn_merge_launch(st, part_d, part_i, n1, nc, k, d_dist, d_idx);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

@@ -5,22 +5,22 @@
 // Quantiser, in fp32: q = clamp(rintf(x * scale), -127, 127), one multiply, round half to even, NaN -> 0, +-inf -> +-127; sq = sum q^2 in int32.
 // Distance: d2 = (qsq[r] + dbsq[c]) - 2 dot(q[r], db[c]), all int32 and exact: 0 <= d2 <= 128 * 254^2 = 8 258 048 < 2^24, so (float)d2 is exact
 // too and the reported distance sqrtf((float)d2) / scale is two correctly rounded fp32 operations.
-// Order of candidates, everywhere in this file: the smaller d2, then the smaller database row.  There is no NaN, the order is total and every
-// d2 is computed once, so the result does not depend on the number of chunks.
+// Order of candidates: the smaller d2, then the smaller database row - topk.h's order for an int distance, where there is no NaN.  The lists and
+// their merges are topk.h's, shared with knn.hip and ivf.hip; an unfilled slot is written out as (INT32_MAX, +inf, -1).
 //
-// The tile loop is knn.hip's restated for the integer instruction (A fragments in registers, the database staged once per workgroup through two
-// skewed LDS buffers, the next step's load in flight under the MFMAs, per-lane sorted lists in registers, partial lists per chunk + merge).
+// The tile loop is this file's own, knn.hip's restated for the integer instruction (A fragments in registers, the database staged once per workgroup
+// through two skewed LDS buffers, the next step's load in flight under the MFMAs, per-lane sorted lists in registers, partial lists per chunk + merge).
 // What differs: one MFMA covers K = 64, so a 16 x 16 tile of dot products is 2 MFMAs instead of 32 and the matrix pipe is no longer the bound;
 // the staged bytes per workgroup are.  So a step stages 32 columns (4 KB, one 16-byte load per thread) and a wave owns RF fragments of 16
 // query rows (8 VGPRs each): 256 rows per workgroup where the lists are short (k <= 2), 128 where they are long (descriptor index, int8).
 #include <math.h>
 
 #include "common.h"
+#include "topk.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #define Q8_DIM 128                    // bytes per row
-#define Q8_EMPTY 0x7fffffff           // d2 and row index of an unfilled slot inside the kernels (behind every real candidate); written out as (INT32_MAX, +inf, -1)
 #define Q8_BS (Q8_DIM + 16)           // bytes per staged column: the 16-byte skew spreads the columns over the banks
 #define Q8_STEP 32                    // database columns staged per step = two 16-column MFMA tiles
 #define Q8_ROWS_MAX 256               // the larger of the two row blocks (k <= 2): the fewest row blocks, so the most chunks any k takes
@@ -63,80 +63,23 @@ extern "C" int affnet_quantize_desc(affnet_ctx* ctx, const float* d_desc, int n,
 
 // ---- search ----
 
-// (d, c) stands in front of (s, si)
-__device__ __forceinline__ bool q8_before(int d, int c, int s, int si) { return d < s || (d == s && c < si); }
-
-// A sorted list of CAP candidates in registers (compile-time indices only: a dynamically indexed array would live in scratch memory).
-template <int CAP>
-struct Q8List {
-    int d[CAP];
-    int i[CAP];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int s = 0; s < CAP; ++s) { d[s] = Q8_EMPTY; i[s] = Q8_EMPTY; }
-    }
-    // the candidate replaces the last slot when it stands in front of it, then rises to its place
-    __device__ __forceinline__ void insert(int nd, int ni) {
-        if (!q8_before(nd, ni, d[CAP - 1], i[CAP - 1])) return;
-        d[CAP - 1] = nd; i[CAP - 1] = ni;
-#pragma unroll
-        for (int s = CAP - 1; s > 0; --s) {
-            const bool up = q8_before(d[s], i[s], d[s - 1], i[s - 1]);
-            const int td = d[s - 1], ti = i[s - 1];
-            d[s - 1] = up ? d[s] : td; i[s - 1] = up ? i[s] : ti;
-            d[s] = up ? td : d[s]; i[s] = up ? ti : i[s];
-        }
-    }
-    __device__ __forceinline__ void pop(bool yes) {
-#pragma unroll
-        for (int s = 0; s + 1 < CAP; ++s) { d[s] = yes ? d[s + 1] : d[s]; i[s] = yes ? i[s + 1] : i[s]; }
-        d[CAP - 1] = yes ? Q8_EMPTY : d[CAP - 1]; i[CAP - 1] = yes ? Q8_EMPTY : i[CAP - 1];
-    }
-};
-
-// One round of the merge of the sorted lists of W neighbouring lanes (W = 16 or 64): a butterfly minimum over the lists' heads, after which every
-// lane holds the winner (bd, bi), and the lane whose head it was (real rows are unique over the lanes) drops it.
-template <int CAP, int W>
-__device__ __forceinline__ void q8_lanes_next(Q8List<CAP>& L, int& bd, int& bi) {
-    bd = L.d[0];
-    bi = L.i[0];
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-        const int od = __shfl_xor(bd, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        const bool take = q8_before(od, oi, bd, bi);
-        bd = take ? od : bd; bi = take ? oi : bi;
-    }
-    L.pop(bi != Q8_EMPTY && L.i[0] == bi);
-}
-
-// The first k of the union of those lists: lane `writer` of the group stores round j at slot j.  out_f: the float distance, or NULL (partial lists).
-template <int CAP, int W>
-__device__ __forceinline__ void q8_lanes_merge(Q8List<CAP>& L, int k, bool writer, float scale, int32_t* __restrict__ out_d2, float* __restrict__ out_f,
-                                               int32_t* __restrict__ out_i) {
+// The first k of the union of the lists of W lanes: lane `writer` of the group stores round j at slot j, an unfilled slot as (INT32_MAX, +inf, -1).
+// out_f: the float distance, or NULL (partial lists).
+template <int W, int CAP>
+__device__ __forceinline__ void q8_lanes_store(TopkList<int, CAP>& L, int k, bool writer, float scale, int32_t* __restrict__ out_d2,
+                                               float* __restrict__ out_f, int32_t* __restrict__ out_i) {
 #pragma unroll
     for (int j = 0; j < CAP; ++j) {
         if (j < k) {        // uniform
             int bd, bi;
-            q8_lanes_next<CAP, W>(L, bd, bi);
+            topk_lanes_next<W>(L, bd, bi);
             if (writer) {
                 out_d2[j] = bd;
-                out_i[j] = bi == Q8_EMPTY ? -1 : bi;
-                if (out_f) out_f[j] = bi == Q8_EMPTY ? INFINITY : sqrtf((float)bd) / scale;
+                out_i[j] = bi == TOPK_EMPTY ? -1 : bi;
+                if (out_f) out_f[j] = bi == TOPK_EMPTY ? INFINITY : sqrtf((float)bd) / scale;
             }
         }
     }
-}
-
-// The d2 of the k-th candidate of that union (Q8_EMPTY while it has fewer than k), on a copy of the lists: nothing behind it can reach a row's
-// result (a later candidate of the same d2 has a larger row), so the tile loop takes it as the row's bound.
-template <int CAP, int W>
-__device__ __forceinline__ int q8_lanes_kth(Q8List<CAP> L, int k) {
-    int kth = Q8_EMPTY, bi;
-#pragma unroll
-    for (int j = 0; j < CAP; ++j)
-        if (j < k) q8_lanes_next<CAP, W>(L, kth, bi);        // uniform
-    return kth;
 }
 
 // grid (cdiv(n1, 64 RF), n_chunks).  Workgroup = 4 wavefronts; wave w owns the RF fragments of 16 rows at 16 RF w of the workgroup's 64 RF rows
@@ -160,7 +103,7 @@ __global__ __launch_bounds__(256) void knn_q8_tile_kernel(const int8_t* __restri
     const int steps = (int)(((long long)n2 + Q8_STEP - 1) / Q8_STEP);
     const long long s0l = (long long)chunk * spc;
     const int s0 = s0l < steps ? (int)s0l : steps, s1 = min(steps, s0 + spc);          // uniform over the workgroup
-    Q8List<CAP> L[RF][4];
+    TopkList<int, CAP> L[RF][4];
 #pragma unroll
     for (int f = 0; f < RF; ++f)
 #pragma unroll
@@ -176,7 +119,7 @@ __global__ __launch_bounds__(256) void knn_q8_tile_kernel(const int8_t* __restri
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 asq[f][r4] = a_sq[min(row0 + 16 * f + 4 * kq + r4, n1 - 1)];
-                bound[f][r4] = Q8_EMPTY;
+                bound[f][r4] = topk_far<int>();
             }
         }
         // step at column c0 -> one register per thread (columns clamped to the last row of b) and the lane's two sums of squares of that step,
@@ -247,7 +190,7 @@ __global__ __launch_bounds__(256) void knn_q8_tile_kernel(const int8_t* __restri
 #pragma unroll
                 for (int f = 0; f < RF; ++f)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) bound[f][r] = q8_lanes_kth<CAP, 16>(L[f][r], k);
+                    for (int r = 0; r < 4; ++r) bound[f][r] = topk_lanes_kth<16>(L[f][r], k);
             }
             if (more) step_store(buf ^ 1);      // the other buffer was last read one step ago, in front of that step's barrier
             __syncthreads();
@@ -259,7 +202,7 @@ __global__ __launch_bounds__(256) void knn_q8_tile_kernel(const int8_t* __restri
         for (int r = 0; r < 4; ++r) {
             const int rr = row0 + 16 * f + 4 * kq + r;
             const size_t o = ((size_t)min(rr, n1 - 1) * n_chunks + chunk) * k;
-            q8_lanes_merge<CAP, 16>(L[f][r], k, m == 0 && rr < n1, scale, out_d2 + o, out_f ? out_f + o : nullptr, out_i + o);
+            q8_lanes_store<16>(L[f][r], k, m == 0 && rr < n1, scale, out_d2 + o, out_f ? out_f + o : nullptr, out_i + o);
         }
 }
 
@@ -270,16 +213,16 @@ __global__ __launch_bounds__(256) void knn_q8_merge_kernel(const int32_t* __rest
                                                            int32_t* __restrict__ out_i) {
     const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n1) return;      // uniform over the wave
-    Q8List<CAP> L;
+    TopkList<int, CAP> L;
     L.clear();
     const size_t base = (size_t)row * n_chunks * k;
     const long long total = (long long)n_chunks * k;
-    for (long long e = lane; e < total; e += 64) {
+    for (long long e = lane; e < total; e += 64) {          // the row's partial slots, strided over the lanes; unfilled ones hold row -1
         const int ci = part_i[base + e];
         if (ci >= 0) L.insert(part_d[base + e], ci);
     }
     const size_t o = (size_t)row * k;
-    q8_lanes_merge<CAP, 64>(L, k, lane == 0, scale, out_d2 + o, out_f + o, out_i + o);
+    q8_lanes_store<64>(L, k, lane == 0, scale, out_d2 + o, out_f + o, out_i + o);
 }
 
 struct Q8Args {
@@ -307,17 +250,8 @@ static void knn_q8_launch(hipStream_t st, const Q8Args& a) {
 
 // The chunks of an n1 x n2 search in row blocks of `rows` query rows: one resident round of workgroups, no chunk below the floor of steps.
 static int q8_chunks(const affnet_ctx* ctx, int n1, int n2, int rows) {
-    int cus = 256;
-    if (ctx) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && v > 0) cus = v;
-        else (void)hipGetLastError();
-    }
-    const long long row_blocks = n1 > 0 ? aff_cdiv(n1, rows) : 1, steps = n2 > 0 ? ((long long)n2 + Q8_STEP - 1) / Q8_STEP : 0;
-    const long long want = ((long long)Q8_WG_PER_CU * cus + row_blocks - 1) / row_blocks, most = steps / Q8_MIN_STEPS;
-    long long nc = want < most ? want : most;
-    if (nc > Q8_MAX_CHUNKS) nc = Q8_MAX_CHUNKS;
-    return nc < 1 ? 1 : (int)nc;
+    return aff_chunk_choice(ctx, n1 > 0 ? aff_cdiv(n1, rows) : 1, n2 > 0 ? ((long long)n2 + Q8_STEP - 1) / Q8_STEP : 0, Q8_WG_PER_CU, Q8_MIN_STEPS,
+                            Q8_MAX_CHUNKS);
 }
 
 extern "C" int affnet_knn_q8_chunks(const affnet_ctx* ctx, int n1, int n2) { return q8_chunks(ctx, n1, n2, Q8_ROWS_MAX); }
@@ -344,23 +278,19 @@ extern "C" int affnet_knn_q8(affnet_ctx* ctx, const int8_t* d_q, const int32_t* 
     Q8Args a;
     a.q = d_q; a.db = d_db; a.qsq = d_qsq; a.dbsq = d_dbsq;
     a.n1 = n1; a.n2 = n2; a.k = k; a.scale = scale;
-    const int cap = k == 1 ? 1 : (k == 2 ? 2 : (k <= 4 ? 4 : 8));
-    a.nc = n_chunks ? n_chunks : q8_chunks(ctx, n1, n2, cap <= 2 ? 256 : 128);          // <= affnet_knn_q8_chunks(ctx, n1, n2)
+    a.nc = n_chunks ? n_chunks : q8_chunks(ctx, n1, n2, aff_topk_cap(k) <= 2 ? 256 : 128);          // <= affnet_knn_q8_chunks(ctx, n1, n2)
     const int steps = (int)(((long long)n2 + Q8_STEP - 1) / Q8_STEP);
     a.spc = aff_cdiv(steps, a.nc);
-    const long long lo64 = skip_row < 0 ? 0 : skip_row, hi64 = (long long)skip_row + skip_n;
-    a.lo = (int)(lo64 < n2 ? lo64 : n2);          // [lo, hi) inside [0, n2); lo >= hi: no skip
-    a.hi = (int)(hi64 < 0 ? 0 : (hi64 < n2 ? hi64 : n2));
+    const AffSkip skip = aff_skip_range(skip_row, skip_n, n2);
+    a.lo = skip.lo; a.hi = skip.hi;
     a.part_d = (int32_t*)d_scratch;
     a.part_i = a.part_d + (size_t)n1 * a.nc * k;
     a.dist2 = d_dist2; a.dist = d_dist; a.idx = d_idx;
     hipStream_t st = (hipStream_t)stream;
-    switch (cap) {          // 256 query rows per workgroup where the lists are short, 128 where they are long
-        case 1: knn_q8_launch<1, 4>(st, a); break;
-        case 2: knn_q8_launch<2, 4>(st, a); break;
-        case 4: knn_q8_launch<4, 2>(st, a); break;
-        default: knn_q8_launch<8, 2>(st, a); break;
-    }
+    aff_topk_dispatch(k, [&](auto cap) {          // 256 query rows per workgroup where the lists are short, 128 where they are long
+        constexpr int CAP = decltype(cap)::value;
+        knn_q8_launch<CAP, CAP <= 2 ? 4 : 2>(st, a);
+    });
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

@@ -34,6 +34,10 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ x
     sqnorm_body(x, n, dim, out, blockIdx.x);
 }
 
+void aff_sqnorm_launch(hipStream_t st, const float* x, int n, int dim, float* out) {
+    if (n > 0) hipLaunchKernelGGL(sqnorm_kernel, dim3(aff_cdiv(n, 4)), dim3(256), 0, st, x, n, dim, out);
+}
+
 // Workgroup = 4 wavefronts = 64 rows of `a`; wave w owns rows 16w..16w+15 and walks all columns of `b` in tiles of 16.
 // MFMA roles: A operand = a rows (lane (m, kq) holds a[row m][16 t + 4 kq + j]), B operand = b rows (columns of the
 // distance matrix); the K order is permuted identically on both sides, which a dot product does not see.
@@ -214,8 +218,8 @@ extern "C" int affnet_match_snn(affnet_ctx* ctx, const float* d_desc1, int n1, c
     uint8_t* used = (uint8_t*)(b_sq + n2);
     int32_t* idx2 = (int32_t*)(used + aff_align((size_t)n2, 16));
     { int zrc = aff_zero_async(ctx, used, (size_t)n2, st); if (zrc) return zrc; }
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, d_desc1, n1, dim, a_sq);
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(aff_cdiv(n2, 4)), dim3(256), 0, st, d_desc2, n2, dim, b_sq);
+    aff_sqnorm_launch(st, d_desc1, n1, dim, a_sq);
+    aff_sqnorm_launch(st, d_desc2, n2, dim, b_sq);
     hipLaunchKernelGGL(rowmin_dist_kernel<128>, dim3(aff_cdiv(n1, 64)), dim3(256), 0, st, d_desc1, n1, d_desc2, n2, a_sq, b_sq,
                        (const uint8_t*)nullptr, d_min_dist, d_idx, (float*)nullptr);
     hipLaunchKernelGGL(mark_used_kernel, dim3(aff_cdiv(n1, 256)), dim3(256), 0, st, d_idx, n1, used);
@@ -236,8 +240,8 @@ extern "C" int affnet_distance_matrix(affnet_ctx* ctx, const float* d_desc1, int
     hipStream_t st = (hipStream_t)stream;
     float* a_sq = (float*)d_scratch;
     float* b_sq = a_sq + n1;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, d_desc1, n1, dim, a_sq);
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(aff_cdiv(n2, 4)), dim3(256), 0, st, d_desc2, n2, dim, b_sq);
+    aff_sqnorm_launch(st, d_desc1, n1, dim, a_sq);
+    aff_sqnorm_launch(st, d_desc2, n2, dim, b_sq);
     hipLaunchKernelGGL(rowmin_dist_kernel<128>, dim3(aff_cdiv(n1, 64)), dim3(256), 0, st, d_desc1, n1, d_desc2, n2, a_sq, b_sq,
                        (const uint8_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, d_out);
     AFF_LAUNCH_CHECK(ctx);

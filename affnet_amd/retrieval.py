@@ -83,7 +83,7 @@ def knn(desc_q, desc_db, k=2, skip=None, n_chunks=0):
 
 class DescriptorIndex(object):
     """The descriptors (and, for retrieve, the frames) of M images, concatenated once.  descs: list of (n_i,128) device tensors, LAFs: list of
-    (n_i,2,3) device tensors or None; empty images are allowed.  D (N,128), L (N,2,3) or None, counts, offsets (M + 1) and the device table
+    (n_i,2,3) device tensors or None; empty images are allowed.  D (N,128), n_rows = N, L (N,2,3) or None, counts, offsets (M + 1) and the device table
     row_image (N,) int32 = the image of every row."""
 
     def __init__(self, descs, LAFs=None):
@@ -110,6 +110,7 @@ class DescriptorIndex(object):
                 _device_tensor(l, "LAFs[%d]" % i)
             self.L = torch.cat([l.contiguous().float().reshape(-1, 2, 3) for l in LAFs], 0)
         self.D = torch.cat(ds, 0)
+        self.n_rows = self.D.size(0)          # kept beside D: a subclass may drop D
         self.device = dev
         self.row_image = torch.repeat_interleave(torch.arange(len(ds), dtype=torch.int32, device=dev),
                                                  torch.tensor(self.counts, dtype=torch.int64, device=dev)).contiguous()
@@ -120,21 +121,26 @@ class DescriptorIndex(object):
     def skip_range(self, exclude):
         return skip_range(self.counts, exclude)
 
+    def _search(self, q, k, skip):
+        """(dist (n1,k), idx (n1,k)) of the checked query rows q against the index's rows: here knn against the whole of D.  What a subclass
+        replaces; everything else of enqueue_votes is shared."""
+        return knn(q, self.D, k, skip)
+
     def enqueue_votes(self, desc_q, k=4, ratio=0.8, exclude=None):
-        """knn of desc_q against the whole index, then affnet_knn_vote: row r's neighbour j < k-1 votes for its image iff
-        !(dist[r][j] > ratio * dist[r][k-1]) and no earlier neighbour of the row voted for that image (so k - 1 is the largest number of
-        images that can show the same feature and all receive its vote).  exclude: an image whose rows are no candidates.
+        """The index's search (_search: knn of desc_q against the whole index), then affnet_knn_vote: row r's neighbour j < k-1 votes for its
+        image iff !(dist[r][j] > ratio * dist[r][k-1]) and no earlier neighbour of the row voted for that image (so k - 1 is the largest number
+        of images that can show the same feature and all receive its vote).  exclude: an image whose rows are no candidates.
         Returns device tensors (votes (M,) int32, dist (n1,k), idx (n1,k)); no synchronisation."""
         k = _check_k(k, "enqueue_votes")
         skip = self.skip_range(exclude)
         q = _check_desc(desc_q, "desc_q")
         if q.device != self.device:
             raise ValueError("enqueue_votes: desc_q and the index live on different devices")
-        dist, idx = knn(q, self.D, k, skip)
+        dist, idx = self._search(q, k, skip)
         votes = torch.empty(len(self.counts), dtype=torch.int32, device=self.device)
         ctx = engine.utility_ctx(self.device)
         one = torch.zeros(8, dtype=torch.int32, device=self.device)     # stands in for empty inputs: never read, but the boundary refuses NULL
-        n1, n2 = q.size(0), self.D.size(0)
+        n1, n2 = q.size(0), self.n_rows
         rc = lib.affnet_knn_vote(ctx, ptr(dist if n1 else one), ptr(idx if n1 else one), n1, k, float(ratio), ptr(self.row_image if n2 else one), n2,
                                  len(self.counts), ptr(votes), engine.stream_of(self.device))
         check(rc, ctx, "affnet_knn_vote")
@@ -268,27 +274,14 @@ class QuantizedDescriptorIndex(DescriptorIndex):
             scale = quantization_scale(self.D)
         self.scale = _check_scale(scale, "QuantizedDescriptorIndex")
         self.Dq, self.sq = quantize(self.D, self.scale)
-        self.n_rows = self.D.size(0)
         if not keep_float:
             self.D = None
 
-    def enqueue_votes(self, desc_q, k=4, ratio=0.8, exclude=None):
-        """DescriptorIndex.enqueue_votes on the quantised rows: (votes (M,) int32, dist (n1,k) = sqrt(d2) / scale, idx (n1,k)); no synchronisation."""
-        k = _check_k(k, "enqueue_votes")
-        skip = self.skip_range(exclude)
-        q = _check_desc(desc_q, "desc_q")
-        if q.device != self.device:
-            raise ValueError("enqueue_votes: desc_q and the index live on different devices")
+    def _search(self, q, k, skip):
+        """On the quantised rows: q quantised with the index's scale, then knn_q8; dist (n1,k) = sqrt(d2) / scale."""
         qq, qsq = quantize(q, self.scale)
         _, dist, idx = knn_q8(qq, qsq, self.Dq, self.sq, k, self.scale, skip)
-        votes = torch.empty(len(self.counts), dtype=torch.int32, device=self.device)
-        ctx = engine.utility_ctx(self.device)
-        one = torch.zeros(8, dtype=torch.int32, device=self.device)     # stands in for empty inputs: never read, but the boundary refuses NULL
-        n1, n2 = q.size(0), self.n_rows
-        rc = lib.affnet_knn_vote(ctx, ptr(dist if n1 else one), ptr(idx if n1 else one), n1, k, float(ratio), ptr(self.row_image if n2 else one), n2,
-                                 len(self.counts), ptr(votes), engine.stream_of(self.device))
-        check(rc, ctx, "affnet_knn_vote")
-        return votes, dist, idx
+        return dist, idx
 
     def retrieve(self, desc_q, LAFs_q, *args, **kwargs):
         if self.D is None:
@@ -440,19 +433,6 @@ class IVFDescriptorIndex(DescriptorIndex):
         self.ivf = IVFParts(self.D, centroids)
         self.n_cells = self.ivf.n_cells
 
-    def enqueue_votes(self, desc_q, k=4, ratio=0.8, exclude=None):
-        """DescriptorIndex.enqueue_votes with the search restricted to self.nprobe cells per query row; no synchronisation."""
-        k = _check_k(k, "enqueue_votes")
-        skip = self.skip_range(exclude)
-        q = _check_desc(desc_q, "desc_q")
-        if q.device != self.device:
-            raise ValueError("enqueue_votes: desc_q and the index live on different devices")
-        dist, idx = ivf_knn(q, self.ivf, k, _check_nprobe(self.nprobe, "enqueue_votes"), skip)
-        votes = torch.empty(len(self.counts), dtype=torch.int32, device=self.device)
-        ctx = engine.utility_ctx(self.device)
-        one = torch.zeros(8, dtype=torch.int32, device=self.device)     # stands in for empty inputs: never read, but the boundary refuses NULL
-        n1, n2 = q.size(0), self.D.size(0)
-        rc = lib.affnet_knn_vote(ctx, ptr(dist if n1 else one), ptr(idx if n1 else one), n1, k, float(ratio), ptr(self.row_image if n2 else one), n2,
-                                 len(self.counts), ptr(votes), engine.stream_of(self.device))
-        check(rc, ctx, "affnet_knn_vote")
-        return votes, dist, idx
+    def _search(self, q, k, skip):
+        """Restricted to self.nprobe (checked here: it may have been changed since the build) cells per query row: ivf_knn."""
+        return ivf_knn(q, self.ivf, k, _check_nprobe(self.nprobe, "enqueue_votes"), skip)

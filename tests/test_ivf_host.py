@@ -43,7 +43,7 @@ def test_python_names_are_exported():
         assert getattr(affnet_amd, name) is getattr(retrieval, name)
     assert issubclass(retrieval.IVFDescriptorIndex, retrieval.DescriptorIndex)
     own = set(vars(retrieval.IVFDescriptorIndex)) - {"__init__", "__doc__", "__module__"}
-    assert own == {"enqueue_votes"}, "shortlist and retrieve are inherited"
+    assert own == {"_search"}, "enqueue_votes, shortlist and retrieve are inherited: the class replaces the search alone"
 
 
 def test_scratch_bytes():

@@ -85,6 +85,26 @@ def test_chunks_choice():
         lib.affnet_ctx_destroy(h)
 
 
+CHUNK_N2 = (0, 1, 16, 79, 80, 415, 2000, 65536, 1 << 20, 2 ** 31 - 1)
+# affnet_knn_chunks(NULL, n1, n2) over CHUNK_N2, recorded from the build before the chunk choice became one function shared with the int8 search
+# (256 CUs, 3 workgroups per CU over cdiv(n1, 64) row blocks, no chunk below 5 tiles of 16 columns).  A slip there changes speed and no result byte.
+KNN_CHUNKS = {
+    1: (1, 1, 1, 1, 1, 5, 25, 768, 768, 768),
+    64: (1, 1, 1, 1, 1, 5, 25, 768, 768, 768),
+    65: (1, 1, 1, 1, 1, 5, 25, 384, 384, 384),
+    256: (1, 1, 1, 1, 1, 5, 25, 192, 192, 192),
+    257: (1, 1, 1, 1, 1, 5, 25, 154, 154, 154),
+    2000: (1, 1, 1, 1, 1, 5, 24, 24, 24, 24),
+    4000: (1, 1, 1, 1, 1, 5, 13, 13, 13, 13),
+}
+
+
+def test_chunks_table():
+    from affnet_amd import _lib
+    for n1, want in KNN_CHUNKS.items():
+        assert tuple(_lib.lib.affnet_knn_chunks(None, n1, n2) for n2 in CHUNK_N2) == want, n1
+
+
 def test_bad_arguments_are_refused_before_any_device_work():
     """The argument checks run on the host, in front of the first launch: they need no GPU, and no pointer below is ever dereferenced."""
     from affnet_amd import _lib

@@ -88,6 +88,39 @@ def test_chunks_choice():
         lib.affnet_ctx_destroy(h)
 
 
+CHUNK_N2 = (0, 1, 16, 79, 80, 415, 2000, 65536, 1 << 20, 2 ** 31 - 1)
+# affnet_knn_q8_chunks(NULL, n1, n2) over CHUNK_N2, recorded from the build before the chunk choice became one function shared with the fp32
+# search (256 CUs, 2 workgroups per CU over cdiv(n1, 256) row blocks, no chunk below 2 steps of 32 columns).  The second table is
+# affnet_knn_q8_chunks(NULL, 2 n1, n2): the choice for the 128-row blocks of k > 2 (tools/knn_q8_rate.py).  A slip changes speed and no result byte.
+Q8_CHUNKS = {
+    1: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    64: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    65: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    256: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    257: (1, 1, 1, 1, 1, 6, 31, 256, 256, 256),
+    2000: (1, 1, 1, 1, 1, 6, 31, 64, 64, 64),
+    4000: (1, 1, 1, 1, 1, 6, 31, 32, 32, 32),
+}
+Q8_CHUNKS_128 = {
+    1: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    64: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    65: (1, 1, 1, 1, 1, 6, 31, 512, 512, 512),
+    256: (1, 1, 1, 1, 1, 6, 31, 256, 256, 256),
+    257: (1, 1, 1, 1, 1, 6, 31, 171, 171, 171),
+    2000: (1, 1, 1, 1, 1, 6, 31, 32, 32, 32),
+    4000: (1, 1, 1, 1, 1, 6, 16, 16, 16, 16),
+}
+
+
+def test_chunks_table():
+    from affnet_amd import _lib
+    f = _lib.lib.affnet_knn_q8_chunks
+    for n1, want in Q8_CHUNKS.items():
+        assert tuple(f(None, n1, n2) for n2 in CHUNK_N2) == want, n1
+    for n1, want in Q8_CHUNKS_128.items():
+        assert tuple(f(None, 2 * n1, n2) for n2 in CHUNK_N2) == want, n1
+
+
 BAD_SCALES = (0.0, -1.0, float("nan"), float("inf"))
 
 

@@ -130,7 +130,7 @@ DESIGN_KERNELS = [
     ("knn_tile_kernel<128, 2>", "descriptor index, k = 2: two neighbours per row and lane in registers"),
     ("knn_tile_kernel<128, 4>", "descriptor index, k = 3, 4: four neighbours per row and lane"),
     ("knn_tile_kernel<128, 8>", "descriptor index, k = 5 .. 8: eight neighbours per row and lane"),
-    ("knn_merge_kernel<8>", "descriptor index: merge of the chunks' lists, one wavefront per query row (k = 5 .. 8)"),
+    ("knn_merge_kernel<8>", "descriptor index: merge of a row's partial lists (the chunks', or the inverted file's probed cells'), one wavefront per query row (k = 5 .. 8)"),
     ("knn_vote_kernel", "descriptor index: one vote per (query row, image) behind the ratio gate"),
     ("q8_quantize_kernel", "descriptor index, int8: fp32 descriptors -> int8 rows and their sums of squares, 32 lanes per row"),
     ("knn_q8_tile_kernel<1, 4>", "descriptor index, int8, k = 1: i8 MFMA distance steps of 32 columns over one chunk, 256 query rows per workgroup"),
@@ -142,7 +142,6 @@ DESIGN_KERNELS = [
     ("ivf_tile_kernel<2>", "descriptor index, inverted file, k = 2: two neighbours per row and lane"),
     ("ivf_tile_kernel<4>", "descriptor index, inverted file, k = 3, 4: four neighbours per row and lane"),
     ("ivf_tile_kernel<8>", "descriptor index, inverted file, k = 5 .. 8: eight neighbours per row and lane"),
-    ("ivf_merge_kernel<8>", "descriptor index, inverted file: merge of a row's nprobe partial lists, one wavefront per query row (k = 5 .. 8)"),
     ("ivf_scan_kernel", "descriptor index, inverted file: scan over the cells' pair counts, group starts and the table of work items, one workgroup"),
     ("ivf_cell_means_kernel", "descriptor index, inverted file: codebook update, one workgroup per cell, double sums in row order"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
