@@ -15,6 +15,7 @@ from . import retrieval  # noqa: F401
 from .retrieval import knn, DescriptorIndex  # noqa: F401
 from .retrieval import quantization_scale, quantize, knn_q8, QuantizedDescriptorIndex  # noqa: F401
 from .retrieval import train_cells, ivf_layout, ivf_knn, IVFParts, IVFDescriptorIndex  # noqa: F401
+from .retrieval import ivf_knn_q8, IVFQ8Parts, IVFQuantizedDescriptorIndex  # noqa: F401
 from .synthetic import synthetic_image, synthetic_hardnet_state  # noqa: F401
 
 __version__ = "0.1.0"

@@ -144,6 +144,8 @@ SYMBOLS = {
     "affnet_ivf_cell_means": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "affnet_ivf_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_ivf_search": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "affnet_ivf_q8_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_ivf_search_q8": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P]),
     "affnet_extract_features": (_I, [_P, C.POINTER(Nets), _P, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_detect_image": (_I, [_P, _P, _P]),
     "affnet_detect_image_responses": (_I, [_P, _P, _P]),

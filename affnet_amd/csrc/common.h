@@ -379,6 +379,10 @@ int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int 
 void aff_sqnorm_launch(hipStream_t st, const float* x, int n, int dim, float* out);
 // knn.hip: the n_lists partial lists (n1, n_lists, k) of every row -> its k neighbours (knn_merge_kernel; the chunks of affnet_knn, the probed cells of affnet_ivf_search)
 void aff_knn_merge_launch(hipStream_t st, const float* part_d, const int32_t* part_i, int n1, int n_lists, int k, float* out_d, int32_t* out_i);
+// knn_q8.hip: the same for int lists (knn_q8_merge_kernel; the chunks of affnet_knn_q8, the probed cells of affnet_ivf_search_q8): partial d2 and rows
+// (n1, n_lists, k), unfilled slots hold row -1 -> d2, sqrtf((float)d2) / scale and rows (n1, k), unfilled slots (INT32_MAX, +inf, -1)
+void aff_knn_q8_merge_launch(hipStream_t st, const int32_t* part_d, const int32_t* part_i, int n1, int n_lists, int k, float scale, int32_t* out_d2,
+                             float* out_f, int32_t* out_i);
 
 // ---- host helpers of the descriptor index's searches (knn.hip, knn_q8.hip, ivf.hip) ---------------
 // the rows [skip_row, skip_row + skip_n) that are no candidates, as [lo, hi) inside [0, n2); lo >= hi: no skip

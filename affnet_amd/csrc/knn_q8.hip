@@ -225,6 +225,14 @@ __global__ __launch_bounds__(256) void knn_q8_merge_kernel(const int32_t* __rest
     q8_lanes_store<64>(L, k, lane == 0, scale, out_d2 + o, out_f + o, out_i + o);
 }
 
+void aff_knn_q8_merge_launch(hipStream_t st, const int32_t* part_d, const int32_t* part_i, int n1, int n_lists, int k, float scale, int32_t* out_d2,
+                             float* out_f, int32_t* out_i) {
+    aff_topk_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL((knn_q8_merge_kernel<decltype(cap)::value>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, part_d, part_i, n1, n_lists, k, scale, out_d2,
+                           out_f, out_i);
+    });
+}
+
 struct Q8Args {
     const int8_t *q, *db;
     const int32_t *qsq, *dbsq;
@@ -244,8 +252,7 @@ static void knn_q8_launch(hipStream_t st, const Q8Args& a) {
     }
     hipLaunchKernelGGL((knn_q8_tile_kernel<CAP, RF>), grid, dim3(256), 0, st, a.q, a.n1, a.db, a.n2, a.qsq, a.dbsq, a.k, a.lo, a.hi, a.spc, a.scale,
                        a.part_d, (float*)nullptr, a.part_i);
-    hipLaunchKernelGGL((knn_q8_merge_kernel<CAP>), dim3(aff_cdiv(a.n1, 4)), dim3(256), 0, st, (const int32_t*)a.part_d, (const int32_t*)a.part_i, a.n1,
-                       a.nc, a.k, a.scale, a.dist2, a.dist, a.idx);
+    aff_knn_q8_merge_launch(st, a.part_d, a.part_i, a.n1, a.nc, a.k, a.scale, a.dist2, a.dist, a.idx);
 }
 
 // The chunks of an n1 x n2 search in row blocks of `rows` query rows: one resident round of workgroups, no chunk below the floor of steps.

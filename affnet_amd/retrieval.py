@@ -1,7 +1,7 @@
 """Descriptor index over many images (csrc/knn.hip): k nearest neighbours of a query image's descriptors among the concatenated descriptors of
 a database, one vote per image from them, and the vote shortlist handed to the batched matching + spatial verification of ReprojectionStuff
 (enqueue_match_and_verify_many) - the loop extract -> index -> shortlist -> verify.  The same index on int8 descriptors (csrc/knn_q8.hip)
-and behind an inverted file over k-means cells (csrc/ivf.hip) further down."""
+and behind an inverted file over k-means cells (csrc/ivf.hip) further down, and last the two combined: int8 rows in the cells."""
 import numpy as np
 import torch
 
@@ -436,3 +436,88 @@ class IVFDescriptorIndex(DescriptorIndex):
     def _search(self, q, k, skip):
         """Restricted to self.nprobe (checked here: it may have been changed since the build) cells per query row: ivf_knn."""
         return ivf_knn(q, self.ivf, k, _check_nprobe(self.nprobe, "enqueue_votes"), skip)
+
+
+# ---- inverted file over int8 rows: the cells of ivf.hip hold knn_q8.hip's rows (csrc/ivf.hip, affnet_ivf_search_q8) ----
+
+class IVFQ8Parts(object):
+    """The tables of an inverted file over the int8 rows of D (n2,128) (include/affnet_hip.h, affnet_ivf_search_q8): centroids (n_cells,128)
+    float, sorted_q (n2,128) int8, sorted_sq (n2,) int32, perm (n2,) int32, cell_start (n_cells + 1,) int32 and scale.  The rows are assigned by
+    knn(D, centroids, 1) on the float rows, exactly as in IVFParts, so perm and cell_start are IVFParts(D, centroids)'s; sorted_q / sorted_sq are
+    the gather of quantize(D, scale) through perm (Dq, sq: that pair when the caller has it already).  136 bytes per row."""
+
+    def __init__(self, D, centroids, scale, Dq=None, sq=None):
+        self.scale = _check_scale(scale, "IVFQ8Parts")
+        D, c = _check_desc(D, "D"), _check_desc(centroids, "centroids")
+        if c.size(0) < 1 or c.device != D.device:
+            raise ValueError("IVFQ8Parts: the centroids must be at least one row on the device of D")
+        self.centroids, self.n_cells = c, c.size(0)
+        assign = knn(D, c, 1)[1][:, 0] if D.size(0) else torch.zeros(0, dtype=torch.int32, device=D.device)
+        self.perm, self.cell_start = _ivf_layout(assign.long(), self.n_cells)
+        if Dq is None or sq is None:
+            Dq, sq = quantize(D, self.scale)
+        self.sorted_q = Dq[self.perm.long()].contiguous()
+        self.sorted_sq = sq[self.perm.long()].contiguous()
+
+
+def ivf_knn_q8(desc_q, index_or_parts, k=2, nprobe=8, skip=None, return_probes=False):
+    """knn_q8 restricted to the database rows in the nprobe cells nearest to each query row: (dist2 (n1,k) int32, dist (n1,k) float32 =
+    sqrt(float32(d2)) / scale, idx (n1,k) int32 = ORIGINAL database rows), order (d2, original row) and unfilled slots (2^31 - 1, +inf, -1) as
+    knn_q8's.  desc_q: the float query rows; the coarse step reads them as they are (the cells are ivf_knn's), the search inside the cells their
+    quantisation with the parts' scale.  index_or_parts: an IVFQuantizedDescriptorIndex or IVFQ8Parts.  return_probes: also the cells
+    (n1,nprobe) int32 that were looked at, -1 where the codebook has fewer than nprobe cells.  Enqueued on the current stream, no
+    synchronisation."""
+    k, nprobe = _check_k(k, "ivf_knn_q8"), _check_nprobe(nprobe, "ivf_knn_q8")
+    p = getattr(index_or_parts, "ivf", index_or_parts)
+    if not isinstance(p, IVFQ8Parts):
+        raise ValueError("ivf_knn_q8: index_or_parts must be an IVFQuantizedDescriptorIndex or IVFQ8Parts")
+    a = _check_desc(desc_q, "desc_q")
+    if a.device != p.sorted_q.device:
+        raise ValueError("ivf_knn_q8: desc_q and the index live on different devices")
+    row, n = (0, 0) if skip is None else (int(skip[0]), int(skip[1]))
+    if n < 0:
+        raise ValueError("ivf_knn_q8: negative skip length")
+    n1, n2, dev = a.size(0), p.sorted_q.size(0), a.device
+    dist2 = torch.empty(n1, k, dtype=torch.int32, device=dev)
+    dist = torch.empty(n1, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(n1, k, dtype=torch.int32, device=dev)
+    probes = torch.empty(n1, nprobe, dtype=torch.int32, device=dev)
+    if n1:
+        qq, qsq = quantize(a, p.scale)
+        ctx = engine.utility_ctx(dev)
+        scratch = torch.empty(lib.affnet_ivf_q8_scratch_bytes(n1, p.n_cells, nprobe, k), dtype=torch.uint8, device=dev)
+        one = torch.zeros(16, dtype=torch.int32, device=dev)          # stands in for an empty database: never read, but the boundary refuses NULL
+        rc = lib.affnet_ivf_search_q8(ctx, ptr(a), ptr(qq), ptr(qsq), n1, ptr(p.sorted_q if n2 else one), ptr(p.sorted_sq if n2 else one),
+                                      ptr(p.perm if n2 else one), n2, ptr(p.cell_start), ptr(p.centroids), p.n_cells, DIM, k, nprobe, row, n, p.scale,
+                                      ptr(dist2), ptr(dist), ptr(idx), ptr(probes), ptr(scratch), engine.stream_of(dev))
+        check(rc, ctx, "affnet_ivf_search_q8")
+    return (dist2, dist, idx, probes) if return_probes else (dist2, dist, idx)
+
+
+class IVFQuantizedDescriptorIndex(QuantizedDescriptorIndex):
+    """QuantizedDescriptorIndex whose search looks at the int8 rows of the nprobe nearest k-means cells of every query row
+    (affnet_ivf_search_q8): ivf (IVFQ8Parts: centroids, sorted_q, sorted_sq, perm, cell_start, scale) beside the tables of the base classes.
+    The codebook is trained on the float rows exactly as IVFDescriptorIndex trains it (n_cells, iters, train_rows, centroids as there); nprobe
+    may be changed after the build.  enqueue_votes, shortlist and retrieve are inherited: retrieve re-ranks with the exact fp32 matcher on D.
+    keep_float=False drops D and the unpermuted Dq / sq after the build: what remains is ivf and the image tables, 136 bytes per row; such an
+    index searches identically and cannot retrieve."""
+
+    def __init__(self, descs, LAFs=None, scale=None, keep_float=True, n_cells=None, nprobe=8, iters=10, train_rows=None, centroids=None):
+        self.nprobe = _check_nprobe(nprobe, "IVFQuantizedDescriptorIndex")
+        if n_cells is not None:
+            n_cells = _check_cells(n_cells, "IVFQuantizedDescriptorIndex")
+        QuantizedDescriptorIndex.__init__(self, descs, LAFs, scale, True)
+        if centroids is None:
+            if self.D.size(0) == 0:
+                raise ValueError("IVFQuantizedDescriptorIndex: centroids must be given for an index without rows")
+            centroids = train_cells(self.D, n_cells or default_cells(self.D.size(0)), iters, train_rows)
+        elif n_cells is not None and (not isinstance(centroids, torch.Tensor) or centroids.dim() != 2 or centroids.size(0) != n_cells):
+            raise ValueError("IVFQuantizedDescriptorIndex: centroids must have n_cells = %d rows" % n_cells)
+        self.ivf = IVFQ8Parts(self.D, centroids, self.scale, self.Dq, self.sq)
+        self.n_cells = self.ivf.n_cells
+        if not keep_float:
+            self.D = self.Dq = self.sq = None
+
+    def _search(self, q, k, skip):
+        """Restricted to self.nprobe (checked here: it may have been changed since the build) cells per query row: ivf_knn_q8."""
+        return ivf_knn_q8(q, self.ivf, k, _check_nprobe(self.nprobe, "enqueue_votes"), skip)[1:]

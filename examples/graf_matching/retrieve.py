@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Retrieval of one query image from a set of images: descriptor index -> vote shortlist -> spatial verification, on the MI355X.
 
-    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8 | --ivf [--cells N --nprobe P]] QUERY IMG [IMG ...]
+    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] [--ivf [--cells N --nprobe P]] QUERY IMG [IMG ...]
 
 Every image goes through the fused path (detect + AffNet + OriNet + descriptor, N = 1000 keypoints by default).  The IMGs become one
 DescriptorIndex; the query's descriptors are searched against all of them at once (affnet_knn, --k neighbours per descriptor, default 4), every image
@@ -11,7 +11,8 @@ shortlist and the verified order.  Without a HardNet checkpoint the seeded synth
 --desc sift needs no weights.  --q8 builds a QuantizedDescriptorIndex instead: the search runs on int8 descriptors
 (affnet_quantize_desc, affnet_knn_q8), the matching and verification of the shortlist on the float ones as before.  --ivf builds an IVFDescriptorIndex: a k-means codebook of --cells
 cells (default: the power of two nearest the square root of the number of descriptors) is trained on the index's descriptors, and every query descriptor
-is compared with the descriptors of its --nprobe (default 8, at most 8) nearest cells only (affnet_ivf_search).  A demonstration of the calls, not a retrieval-quality claim.
+is compared with the descriptors of its --nprobe (default 8, at most 8) nearest cells only (affnet_ivf_search).  --q8 --ivf together build
+an IVFQuantizedDescriptorIndex: the same codebook, the cells hold the int8 rows (affnet_ivf_search_q8).  A demonstration of the calls, not a retrieval-quality claim.
 
     python examples/graf_matching/retrieve.py --desc sift tests/golden/graf_img1.png tests/golden/graf_img6.png tests/golden/graf_img1.png"""
 import os
@@ -50,7 +51,7 @@ def main(argv):
     nprobe, argv = take(argv, "--nprobe", "8")
     q8, ivf = "--q8" in argv, "--ivf" in argv
     argv = [a for a in argv if a not in ("--q8", "--ivf")]
-    if desc_kind not in ("hardnet", "sift") or len(argv) < 2 or (q8 and ivf):
+    if desc_kind not in ("hardnet", "sift") or len(argv) < 2:
         sys.exit(__doc__)
     dev = torch.device("cuda:0")
     ld = lambda p: torch.load(p, map_location="cpu", weights_only=False)["state_dict"]
@@ -70,7 +71,8 @@ def main(argv):
         lafs.append(r["LAFs"])
     names = argv[1:]
     if ivf:
-        index = affnet_amd.IVFDescriptorIndex(descs[1:], lafs[1:], n_cells=int(cells) if cells else None, nprobe=int(nprobe))
+        index = (affnet_amd.IVFQuantizedDescriptorIndex if q8 else affnet_amd.IVFDescriptorIndex)(descs[1:], lafs[1:], n_cells=int(cells) if cells else None,
+                                                                                                  nprobe=int(nprobe))
         print("inverted file: %d cells, %d probed per descriptor" % (index.n_cells, index.nprobe))
     else:
         index = (affnet_amd.QuantizedDescriptorIndex if q8 else affnet_amd.DescriptorIndex)(descs[1:], lafs[1:])

@@ -665,6 +665,38 @@ int affnet_ivf_search(affnet_ctx* ctx, const float* d_q, int n1, const float* d_
                       const int32_t* d_cell_start, const float* d_centroids, int n_cells, int dim, int k, int nprobe, int skip_row, int skip_n,
                       float* d_dist, int32_t* d_idx, int32_t* d_probes, void* d_scratch, void* stream);
 
+/* ---- descriptor index, inverted file over int8 rows: the cells hold the quantised rows, the distances inside them are affnet_knn_q8's ---- */
+
+/* The two ideas combined: the codebook, the coarse step and the cell layout of affnet_ivf_search, the rows of the cells stored as int8
+ * (affnet_quantize_desc) with their int32 sums of squares.  The tables of an index over n2 rows:
+ *   d_sorted_q (n2,128) int8   the quantised database rows in cell order (row p = the quantised original row d_perm[p]);
+ *   d_sorted_sq (n2) int32     their sums of squares, in cell order;
+ *   d_perm, d_cell_start, d_centroids (float) as above.
+ * 136 bytes per database row.  Every reported d2 is exact, the order (d2, ORIGINAL row) is total, so the result is a function of the inputs. */
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_ivf_search_q8.  Negative arguments count as 0. */
+size_t affnet_ivf_q8_scratch_bytes(int n1, int n_cells, int nprobe, int k);
+
+/* For every query row the k nearest, by the exact integer d2 of affnet_knn_q8, among the database rows of its nprobe nearest cells.
+ * d_q (n1,128) float: the query rows, read by the coarse step only - affnet_knn(d_q, d_centroids, k = nprobe) as it stands, so the cells looked
+ * at (d_probes (n1,nprobe) when not NULL, -1 where the codebook has fewer cells) are bit for bit affnet_ivf_search's for the same rows and
+ * centroids.  d_qq (n1,128) int8 / d_qsq (n1): the same rows quantised with `scale` (affnet_quantize_desc).
+ * Inside the cells d2 = (qsq[r] + sorted_sq[c]) - 2 dot(qq[r], sorted_q[c]) in int32; order: the smaller d2, then the smaller ORIGINAL row.
+ * Outputs, (n1,k) each, exactly as affnet_knn_q8 writes them: d_dist2 = d2, d_dist = sqrtf((float)d2) / scale, d_idx = the original row;
+ * unfilled slots hold (INT32_MAX, +inf, -1).  Original rows skip_row <= c < skip_row + skip_n are no candidates.  With every cell probed
+ * the three outputs are affnet_knn_q8's bytes on the unpermuted int8 rows.
+ * Steps, one linear chain of launches on `stream`, no allocation, no synchronisation: the coarse step and the grouping of affnet_ivf_search
+ * (the result does not depend on the order in which its atomics hand out places); one workgroup per (cell, block of 16 rows of its group),
+ * each wave walking 64-column steps of the cell on v_mfma_i32_16x16x64_i8; per row the merge of its nprobe partial lists.  A cell is not split
+ * over workgroups by columns.  d_qq and d_sorted_q are 16-byte aligned.
+ * n1 = 0 is a no-op; n2 = 0 (d_cell_start all zeros) gives only unfilled slots.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, k outside 1..AFFNET_KNN_MAX_K, nprobe outside 1..AFFNET_IVF_MAX_PROBE,
+ * n_cells < 1, a negative size, n1 * nprobe * k above 2^31 - 1, scale not finite or <= 0, a NULL pointer other than d_probes. */
+int affnet_ivf_search_q8(affnet_ctx* ctx, const float* d_q, const int8_t* d_qq, const int32_t* d_qsq, int n1, const int8_t* d_sorted_q,
+                         const int32_t* d_sorted_sq, const int32_t* d_perm, int n2, const int32_t* d_cell_start, const float* d_centroids,
+                         int n_cells, int dim, int k, int nprobe, int skip_row, int skip_n, float scale, int32_t* d_dist2, float* d_dist,
+                         int32_t* d_idx, int32_t* d_probes, void* d_scratch, void* stream);
+
 /* ---- fused pipeline ------------------------------------------------------------------------ */
 
 typedef struct affnet_nets {

@@ -142,6 +142,10 @@ DESIGN_KERNELS = [
     ("ivf_tile_kernel<2>", "descriptor index, inverted file, k = 2: two neighbours per row and lane"),
     ("ivf_tile_kernel<4>", "descriptor index, inverted file, k = 3, 4: four neighbours per row and lane"),
     ("ivf_tile_kernel<8>", "descriptor index, inverted file, k = 5 .. 8: eight neighbours per row and lane"),
+    ("ivf_q8_tile_kernel<1>", "descriptor index, inverted file, int8, k = 1: 16 gathered query rows against one cell of int8 rows, the four waves split its 64-column steps"),
+    ("ivf_q8_tile_kernel<2>", "descriptor index, inverted file, int8, k = 2: two neighbours per row and lane"),
+    ("ivf_q8_tile_kernel<4>", "descriptor index, inverted file, int8, k = 3, 4: four neighbours per row and lane"),
+    ("ivf_q8_tile_kernel<8>", "descriptor index, inverted file, int8, k = 5 .. 8: eight neighbours per row and lane"),
     ("ivf_scan_kernel", "descriptor index, inverted file: scan over the cells' pair counts, group starts and the table of work items, one workgroup"),
     ("ivf_cell_means_kernel", "descriptor index, inverted file: codebook update, one workgroup per cell, double sums in row order"),
     ("hessian_nms_kernel<5>", "Hessian + 3-D NMS + centroid, 5 levels per octave"),
