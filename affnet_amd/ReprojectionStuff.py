@@ -1,7 +1,8 @@
 """Homography reprojection of LAFs and ground-truth correspondences with the reference's names
 (ReprojectionStuff.py:23-40,126-137), plus the SNN matcher of train_AffNet_test_on_graffity.py:292-300 as one call, and the geometric
 verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify), and both for many image pairs per device call (pair_table,
-enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank)."""
+enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank).  The epipolar model of a scene with depth is csrc/epipolar.hip
+(verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance)."""
 import ctypes as C
 
 import numpy as np
@@ -83,7 +84,7 @@ def _verify_model(model):
         return VERIFY_MODELS[model]
     if model in (_lib.VERIFY_AFFINE, _lib.VERIFY_HOMOGRAPHY):
         return int(model)
-    raise ValueError("model must be 'affine' or 'homography'")
+    raise ValueError("model must be 'affine' or 'homography' ('fundamental': verify_matches, match_and_verify, verify_epipolar)")
 
 
 def enqueue_verify(LAFs1, LAFs2, tent, count=None, inl_th=3.0, model="homography", lo_iters=3):
@@ -119,22 +120,88 @@ def _verify_info(counts, summary_host):
             "flags": int(summary_host[3])}
 
 
-def verify_matches(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=3.0, model="homography", lo_iters=3):
+def _tent_tensor(LAFs1, tent_in_1, tent_in_2):
+    tent = torch.stack([torch.as_tensor(tent_in_1, device=LAFs1.device).reshape(-1), torch.as_tensor(tent_in_2, device=LAFs1.device).reshape(-1)], 1)
+    return tent.to(torch.int32).contiguous()
+
+
+def verify_matches(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
     """Geometric verification of tentative matches without ground truth.  Every tentative (tent_in_1[t], tent_in_2[t]) - the index tensors
     match_snn returns - is one affine hypothesis LAFs2[j] LAFs1[i]^-1; all are scored against all matches (centre error <= inl_th px), the
     best one is refined by lo_iters least-squares refits of `model` ('homography' or 'affine') on its inliers.  Deterministic.
     Returns (H (3,3) float64 device tensor mapping image 1 to image 2, inliers (T,) bool, info) with info = {counts (T,) int32 inliers per
-    hypothesis, best, best_count, num_inliers, flags: 1 no valid hypothesis, 2 too few inliers to refit, 4 degenerate system}."""
+    hypothesis, best, best_count, num_inliers, flags: 1 no valid hypothesis, 2 too few inliers to refit, 4 degenerate system}.
+    model='fundamental' is verify_epipolar (a scene with depth; `rounds` and `seed` are read by that model only)."""
     engine.require_cuda(LAFs1, "LAFs1")
-    tent = torch.stack([torch.as_tensor(tent_in_1, device=LAFs1.device).reshape(-1), torch.as_tensor(tent_in_2, device=LAFs1.device).reshape(-1)], 1)
-    tent = tent.to(torch.int32).contiguous()
-    H, inl, counts, summary = enqueue_verify(LAFs1, LAFs2, tent, None, inl_th, model, lo_iters)
+    if model == "fundamental":
+        return verify_epipolar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th, rounds, seed, lo_iters)
+    H, inl, counts, summary = enqueue_verify(LAFs1, LAFs2, _tent_tensor(LAFs1, tent_in_1, tent_in_2), None, inl_th, model, lo_iters)
     return H, inl.bool(), _verify_info(counts, summary.cpu().tolist())
 
 
-def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
+def enqueue_verify_epipolar(LAFs1, LAFs2, tent, count=None, inl_th=2.0, rounds=8, seed=0, lo_iters=3):
+    """Epipolar verification (affnet_epipolar_verify) of the tentative matches `tent` (cap,2) int32, of which the first count[0] rows are valid
+    (count: (1,) int32 device tensor as affnet_match_snn writes it, or None = all rows), enqueued on the current stream with no synchronisation.
+    Returns capacity-sized device tensors: (F (3,3) float64 with x2^T F x1 = 0, inliers (cap,) uint8, counts (cap*rounds,) int32 inliers per
+    hypothesis h = s * rounds + r, summary (4,) int32 = [best, counts[best], final inlier count, flags]); rows at or beyond the count are zero."""
+    engine.require_cuda(LAFs1, "LAFs1")
+    engine.require_cuda(LAFs2, "LAFs2")
+    engine.require_cuda(tent, "tent")
+    if tent.dtype != torch.int32 or tent.dim() != 2 or tent.size(1) != 2 or not tent.is_contiguous():
+        raise ValueError("enqueue_verify_epipolar: tent must be a contiguous (cap,2) int32 tensor")
+    if count is not None and (count.dtype != torch.int32 or count.numel() != 1 or not count.is_cuda):
+        raise ValueError("enqueue_verify_epipolar: count must be a (1,) int32 device tensor or None")
+    rounds, seed = int(rounds), int(seed)
+    if not 1 <= rounds <= _lib.EPI_MAX_ROUNDS:
+        raise ValueError("enqueue_verify_epipolar: rounds must be in 1..%d" % _lib.EPI_MAX_ROUNDS)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("enqueue_verify_epipolar: seed must fit 32 unsigned bits")
+    l1, l2 = LAFs1.contiguous().float(), LAFs2.contiguous().float()
+    dev, cap = l1.device, tent.size(0)
+    F = torch.zeros(3, 3, dtype=torch.float64, device=dev)
+    inl = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+    counts = torch.zeros(max(cap * rounds, 1), dtype=torch.int32, device=dev)
+    summary = torch.zeros(4, dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib.affnet_epipolar_scratch_bytes(cap, rounds), dtype=torch.uint8, device=dev)
+    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty frame / match list: never read, but the boundary refuses NULL
+    ctx = engine.utility_ctx(dev)
+    rc = lib.affnet_epipolar_verify(ctx, ptr(l1 if l1.numel() else one), l1.size(0), ptr(l2 if l2.numel() else one), l2.size(0),
+                                    ptr(tent if cap else one), ptr(count), cap, float(inl_th), rounds, seed, int(lo_iters),
+                                    ptr(counts), ptr(F), ptr(inl), ptr(summary), ptr(scratch), engine.stream_of(dev))
+    check(rc, ctx, "affnet_epipolar_verify")
+    return F, inl[:cap], counts[:cap * rounds], summary
+
+
+def verify_epipolar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=2.0, rounds=8, seed=0, lo_iters=3):
+    """Epipolar verification of tentative matches: for two views of a scene with depth, where one homography explains only the dominant plane.
+    A frame is three point correspondences, so tentative s and two partners chosen by an integer hash of (s, r, seed) give one 8-point
+    hypothesis; all T * rounds of them are scored against all matches (Sampson error of the centres <= inl_th px), the best one is refined by
+    lo_iters rank-2 least-squares refits on its inliers.  Deterministic: the same bytes on every run.
+    Returns (F (3,3) float64 device tensor, unit Frobenius norm, x2^T F x1 = 0; inliers (T,) bool; info) with the keys of verify_matches
+    (counts has T * rounds entries, best = s * rounds + r; flag 1 comes with an all-zero F) plus rounds and seed.
+    When most matches lie on one plane F is one of a family; it is then good as an inlier test only."""
+    engine.require_cuda(LAFs1, "LAFs1")
+    F, inl, counts, summary = enqueue_verify_epipolar(LAFs1, LAFs2, _tent_tensor(LAFs1, tent_in_1, tent_in_2), None, inl_th, rounds, seed, lo_iters)
+    return F, inl.bool(), dict(_verify_info(counts, summary.cpu().tolist()), rounds=int(rounds), seed=int(seed))
+
+
+def sampson_distance(F, LAFs1, LAFs2, tent_in_1, tent_in_2):
+    """Square root of the Sampson error (pixels) of every tentative match's two centres under F (x2^T F x1 = 0): (T,) float64 on LAFs1's device."""
+    F = torch.as_tensor(F, dtype=torch.float64, device=LAFs1.device).reshape(3, 3)
+    i = torch.as_tensor(tent_in_1, device=LAFs1.device).reshape(-1).long()
+    j = torch.as_tensor(tent_in_2, device=LAFs1.device).reshape(-1).long()
+    one = torch.ones(i.numel(), 1, dtype=torch.float64, device=LAFs1.device)
+    x1 = torch.cat([LAFs1[i][:, :, 2].double(), one], 1)
+    x2 = torch.cat([LAFs2.to(LAFs1.device)[j][:, :, 2].double(), one], 1)
+    l, m = x1 @ F.t(), x2 @ F                         # F x1, F^T x2
+    r = (x2 * l).sum(1)
+    return torch.sqrt(r * r / (l[:, 0] ** 2 + l[:, 1] ** 2 + m[:, 0] ** 2 + m[:, 1] ** 2))
+
+
+def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
     """match_snn followed by verify_matches as one chain on the stream: the tentative list and its device-side count go from
-    affnet_match_snn straight into affnet_verify_matches, and the host reads back once, at the end.
+    affnet_match_snn straight into affnet_verify_matches (model='fundamental': affnet_epipolar_verify, which alone reads `rounds` and
+    `seed`), and the host reads back once, at the end.
     Returns (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info) - the pieces of match_snn and verify_matches."""
     engine.require_cuda(descriptors1, "descriptors1")
     engine.require_cuda(descriptors2, "descriptors2")
@@ -155,9 +222,14 @@ def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8
         rc = lib.affnet_match_snn(ctx, ptr(a), n1, ptr(b), n2, a.size(1), float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt),
                                   ptr(scratch), engine.stream_of(dev))
         check(rc, ctx, "affnet_match_snn")
-    H, inl, counts, summary = enqueue_verify(LAFs1, LAFs2, tent, cnt, inl_th, model, lo_iters)
+    if model == "fundamental":
+        H, inl, counts, summary = enqueue_verify_epipolar(LAFs1, LAFs2, tent, cnt, inl_th, rounds, seed, lo_iters)
+    else:
+        H, inl, counts, summary = enqueue_verify(LAFs1, LAFs2, tent, cnt, inl_th, model, lo_iters)
     host = torch.cat([cnt, summary]).cpu().tolist()          # the one read-back
     k = host[0]
+    if model == "fundamental":
+        return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), dict(_verify_info(counts[:k * int(rounds)], host[1:]), rounds=int(rounds), seed=int(seed))
     return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), _verify_info(counts[:k], host[1:])
 
 

@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "spatial_dev.h"
 
 #define SPV_HT 128          // hypotheses per workgroup of the scoring kernel = its workgroup size (AFFNET_VERIFY_TILE)
 #define SPV_MC 128          // matches per LDS chunk (AFFNET_VERIFY_CHUNK)
@@ -31,21 +32,6 @@
 #define SPV_NSUM 44         // sums of the homography normal equations: 36 of the upper triangle + 8 of the right-hand side
 
 static_assert(SPV_HT == AFFNET_VERIFY_TILE && SPV_MC == AFFNET_VERIFY_CHUNK, "include/affnet_hip.h states the tile sizes");
-
-struct SpvIn {
-    const float* lafs1; int n1;
-    const float* lafs2; int n2;
-    const int32_t* tent;
-    const int32_t* count;      // device row count or NULL (= t_max rows)
-    int t_max;
-};
-
-__device__ __forceinline__ int spv_rows(const int32_t* count, int t_max) {
-    if (!count) return t_max;
-    return min(max(*count, 0), t_max);
-}
-
-__device__ __forceinline__ bool spv_finite(float x) { return fabsf(x) <= 3.402823466e38f; }     // false for NaN and +-inf
 
 // The scoring rule, fp32, centre-relative: e = | M (c1_t - c1_h) - (c2_t - c2_h) |^2 <= th^2.  No fused multiply-add (the file is built with
 // -ffp-contract=off), so the local optimisation's start mask below is the scoring kernel's inlier set bit for bit.
@@ -63,19 +49,15 @@ __device__ __forceinline__ void spv_prep_body(const SpvIn& in, float4* __restric
     if (t >= spv_rows(in.count, in.t_max)) return;
     const float qn = __builtin_nanf("");
     float4 p = make_float4(qn, qn, qn, qn), m = p;
-    const int i = in.tent[2 * t], j = in.tent[2 * t + 1];
-    if (i >= 0 && i < in.n1 && j >= 0 && j < in.n2) {        // the bounds guard: an index outside its frame list never becomes a load
-        const float* A = in.lafs1 + 6 * (size_t)i;
-        const float* B = in.lafs2 + 6 * (size_t)j;
+    float A[6], B[6];
+    if (spv_gather(in, t, A, B)) {
         const float a = A[0], b = A[1], x1 = A[2], c = A[3], d = A[4], y1 = A[5];
         const float a2 = B[0], b2 = B[1], x2 = B[2], c2 = B[3], d2 = B[4], y2 = B[5];
-        const bool centres = spv_finite(x1) && spv_finite(y1) && spv_finite(x2) && spv_finite(y2);
+        const bool centres = spv_centres_finite(A, B);
         if (centres) p = make_float4(x1, y1, x2, y2);
         const float det = a * d - b * c;
-        const bool shapes = spv_finite(a) && spv_finite(b) && spv_finite(c) && spv_finite(d) && spv_finite(a2) && spv_finite(b2) && spv_finite(c2) &&
-                            spv_finite(d2);
         // M = L2 L1^-1, L1^-1 = [d -b; -c a] / det
-        if (centres && shapes && fabsf(det) > 1e-12f)
+        if (centres && spv_shapes_finite(A, B) && fabsf(det) > 1e-12f)
             m = make_float4((a2 * d - b2 * c) / det, (b2 * a - a2 * b) / det, (c2 * d - d2 * c) / det, (d2 * a - c2 * b) / det);
     }
     pts[t] = p; hyp[t] = m; counts[t] = 0;
@@ -109,26 +91,7 @@ __global__ __launch_bounds__(SPV_HT) void spv_score_kernel(const float4* __restr
 
 // best[0] = smallest h with the largest count, best[1] = that count; {-1, 0} when no hypothesis has an inlier (no valid hypothesis, or no rows)
 __device__ __forceinline__ void spv_select_body(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max, int32_t* __restrict__ best) {
-    __shared__ int s_c[4], s_i[4];
-    const int rows = spv_rows(count, t_max);
-    int bc = 0, bi = 0x7fffffff;
-    for (int h = threadIdx.x; h < rows; h += 256) {           // ascending h: the strict > keeps the smallest index
-        const int c = counts[h];
-        if (c > bc) { bc = c; bi = h; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
-        if (oc > bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = bc; s_i[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (s_c[w] > bc || (s_c[w] == bc && s_i[w] < bi)) { bc = s_c[w]; bi = s_i[w]; }
-        best[0] = bc > 0 ? bi : -1;
-        best[1] = bc > 0 ? bc : 0;
-    }
+    spv_select_rows(counts, spv_rows(count, t_max), best);
 }
 
 __global__ __launch_bounds__(256) void spv_select_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max,
@@ -145,27 +108,6 @@ struct SpvLo {
     uint8_t* cur;              // scratch: the current mask
     double* model_out; uint8_t* inlier; int32_t* summary;
 };
-
-// v[k] <- sum over the workgroup, the same on every thread.  Fixed order: wave butterfly, then waves 0..3 left to right.
-template <int K>
-__device__ __forceinline__ void spv_block_sum(double (&v)[K], double* s_part, double* s_sum) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) s_part[wave * K + k] = v[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < K) s_sum[threadIdx.x] = ((s_part[threadIdx.x] + s_part[K + threadIdx.x]) + s_part[2 * K + threadIdx.x]) + s_part[3 * K + threadIdx.x];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = s_sum[k];
-    __syncthreads();
-}
 
 // Gaussian elimination with partial pivoting of the n x m augmented matrix A (m - n right-hand sides) in LDS, by one thread; the solutions
 // replace the right-hand sides.  false: a pivot below `tiny` (or a NaN).

@@ -3,7 +3,7 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
 missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
@@ -15,7 +15,12 @@ fixtures.  With the trained weights at N = 500 the reference gives 34 tentatives
 --verify: matching and geometric verification WITHOUT the ground truth in one device chain (match_and_verify: every tentative's pair of affine
 frames is an affine hypothesis, all scored against all, the best refined as a homography); a second line per run gives the inlier count, how
 many of the inliers the ground-truth homography confirms (the same 6 px centre rule) and how far the recovered H moves the image corners from
-where the file's H puts them."""
+where the file's H puts them.
+--model fundamental (with --verify): the epipolar model instead (model="fundamental": three tentatives' frames give one 8-point hypothesis, the
+best refined as a rank-2 fundamental matrix, Sampson error <= 2 px); the line gives the epipolar inliers next to the ground-truth check and the
+median Sampson distance of the ground-truth matches under the recovered F.  graf is a PLANAR scene: every F compatible with its homography
+explains the wall, so the F printed here is one of a family - good as an inlier test, not as the pair's epipolar geometry.  The model is
+meant for two views of a scene with depth, where a homography keeps only the dominant plane."""
 import os
 import sys
 
@@ -26,7 +31,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import affnet_amd  # noqa: E402
-from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, get_GT_correspondence_indexes  # noqa: E402
+from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, get_GT_correspondence_indexes, sampson_distance  # noqa: E402
 
 
 def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
@@ -56,6 +61,13 @@ def main(argv):
         if i + 1 >= len(argv):
             sys.exit("--tfeat-weights takes a path")
         tfeat_path = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    model = "homography"
+    if "--model" in argv:
+        i = argv.index("--model")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("homography", "fundamental"):
+            sys.exit("--model takes homography or fundamental")
+        model = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
     if "--desc" in argv:
         i = argv.index("--desc")
@@ -89,7 +101,15 @@ def main(argv):
         t1, t2, _, _ = match_snn(r1["descriptors"], r2["descriptors"], 0.8)
         _, plain, _ = get_GT_correspondence_indexes(r1["LAFs"][t1], r2["LAFs"][t2], H1to2, dist_threshold=6)
         print("Test on %s, %d tentatives %d true matches %s  inl.ratio" % (tag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))
-        if verify:
+        if verify and model == "fundamental":
+            v1, v2, F, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0, model="fundamental")
+            assert torch.equal(v1, t1) and torch.equal(v2, t2)
+            _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)
+            d = sampson_distance(F, r1["LAFs"], r2["LAFs"], t1[plain], t2[plain])
+            print("Verified on %s (fundamental; planar scene: F is one of a family), %d epipolar inliers of %d tentatives (best hypothesis %d, flags %d), %d of them "
+                  "true matches, median Sampson distance of the %d true matches %.2f px"
+                  % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), plain.numel(), d.median().item() if d.numel() else float("nan")))
+        elif verify:
             v1, v2, H, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0)
             assert torch.equal(v1, t1) and torch.equal(v2, t2)
             _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)

@@ -543,6 +543,77 @@ int affnet_verify_matches_many(affnet_ctx* ctx, const float* d_lafs1, int rows1,
                                int n_pairs, const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int model, int lo_iters,
                                int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
 
+/* ---- epipolar verification of tentative matches: a fundamental matrix from affine frames ---------- */
+
+/* The planar models above report only the inliers of the dominant plane of a scene with depth.  An affine frame is three point
+ * correspondences (its centre and its two axis tips), so three tentative matches give nine - enough for the linear 8-point solve of a
+ * fundamental matrix F, x2^T F x1 = 0, F row-major.  Same design as above: deterministic, bounded work, all hypotheses scored against
+ * all matches, a best-first refit in fp64, no host synchronisation, all buffers the caller's.  Inputs as for affnet_verify_matches;
+ * d_scratch affnet_epipolar_scratch_bytes(t_max, rounds) bytes, 16-byte aligned.  T below is the device-side row count.
+ *
+ * Known limit (not detected here): when most matches lie on one plane, F is one of a family - every F compatible with the plane's
+ * homography explains them - and the matches off the plane decide which; the returned F is then reliable only as an inlier test.
+ *
+ * Prep, per tentative t: indices are tested before any load.  Match t is usable (can be an inlier) when its indices are in range and
+ * its two centres are finite, otherwise its points are NaN; it is usable as a MEMBER of a hypothesis when all twelve numbers of its
+ * two frames are finite.  A frame [a b x; c d y] gives the points c = (x, y), c + (a, c), c + (b, d), formed in fp64 from the fp32 numbers.
+ *
+ * Hypotheses: h = s * rounds + r, s in [0,T), r in [0,rounds), 1 <= rounds <= AFFNET_EPI_MAX_ROUNDS.  Members m0 = s and, for k = 1, 2,
+ * m_k = j with x = lowbias32((s * 0x9E3779B1) ^ (r * 0x85EBCA77) ^ (k * 0xC2B2AE3D) ^ seed) in uint32 wrap-around arithmetic,
+ * lowbias32(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16;  j = ((uint64)x * T) >> 32, and while j
+ * equals an earlier member j = (j + 1) % T.  A hypothesis is invalid - NaN model, count 0, never chosen - when T < 3, when a member is
+ * not usable as one, when a normalisation scale is zero or not finite, when a pivot is below 1e-12 or when the final norm is zero or
+ * not finite.
+ *
+ * Solve (fp64, no fused multiply-add, one thread per hypothesis): the nine correspondences in the order m0: centre, tip 0, tip 1; m1;
+ * m2.  Per image Hartley normalisation of the nine points: centroid (sums left to right, / 9), mean distance (sum of
+ * sqrt(dx*dx + dy*dy) left to right, / 9), s = sqrt(2) / mean, point -> (p - centroid) * s.  Equation row
+ * [u*x, u*y, u, v*x, v*y, v, x, y, 1], (x, y) in image 1 and (u, v) in image 2; only the first eight rows are used.  Null vector by Gaussian
+ * elimination with complete pivoting (largest remaining |entry|, ties to the smallest row, then the smallest column; row r below pivot
+ * row k: f = A[r][k] / A[k][k], A[r][c] = A[r][c] - f * A[k][c]), the free unknown is 1, back-substitution
+ * y[i] = -(A[i][8] + A[i][i+1] y[i+1] + ... + A[i][7] y[7]) / A[i][i] summed left to right, column permutation undone.
+ * Denormalisation F = T2^T Fn T1 with T = [s 0 -s cx; 0 s -s cy; 0 0 1]: G[r] = (Fn[r][0] s1, Fn[r][1] s1, (Fn[r][0] (-s1 cx1) +
+ * Fn[r][1] (-s1 cy1)) + Fn[r][2]), F[0] = s2 G[0], F[1] = s2 G[1], F[2] = ((-s2 cx2) G[0] + (-s2 cy2) G[1]) + G[2].  Then F / sqrt(sum of
+ * squares, row-major, left to right), and the sign that makes the largest-magnitude entry (the first in row-major order on ties)
+ * positive.  Stored as nine fp32 numbers.
+ *
+ * Score (fp32, no fused multiply-add), match centres (x, y), (u, v): l_k = (F[k][0]*x + F[k][1]*y) + F[k][2], k = 0..2;
+ * m_k = (F[0][k]*u + F[1][k]*v) + F[2][k], k = 0, 1; r = (u*l_0 + v*l_1) + l_2; e = (r*r) / (((l_0*l_0 + l_1*l_1) + m_0*m_0) + m_1*m_1)
+ * (the Sampson error).  Inlier iff e <= inl_th*inl_th; NaN and a zero denominator give false.  Select: the smallest h with the largest
+ * count, -1 when that count is 0.
+ *
+ * Local optimisation (fp64): model 0 is the best hypothesis widened to double (not forced to rank 2), its mask the fp32 inlier set.
+ * lo_iters (0..8) times { fewer than 8 matches in the mask: stop with flag 2; Hartley-normalise the masked centres; N = A^T A (9 x 9) of
+ * the rows above; eigenvectors of N by cyclic Jacobi: exactly 12 sweeps over p < q in row-major order, a rotation skipped when
+ * a_pq == 0, else theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta*theta + 1)) (sign(0) = +1),
+ * c = 1 / sqrt(t*t + 1), s = t*c, columns p, q of A, then rows p, q of A, then columns p, q of V through
+ * (x_p, x_q) <- (c x_p - s x_q, s x_p + c x_q); the eigenvector of the smallest diagonal entry (the first on ties); stop with flag 4
+ * when the second-smallest diagonal entry is <= 1e-12 x the largest or anything is not finite; rank 2: Fn <- Fn - (Fn v) v^T with v the
+ * smallest eigenvector of Fn^T Fn (same Jacobi, n = 3); denormalise, unit norm, sign as above; new mask = Sampson error in fp64, same
+ * expression tree, <= inl_th^2 }, keeping the model with the largest mask (ties: the earliest). */
+#define AFFNET_EPI_MAX_ROUNDS 64
+#define AFFNET_EPI_TILE 128       /* hypotheses per workgroup of the scoring kernel */
+#define AFFNET_EPI_CHUNK 128      /* matches per chunk of the scoring kernel        */
+#define AFFNET_EPI_SOLVE_TILE 64  /* hypotheses per workgroup of the solve kernel   */
+
+/* Host only.  Negative arguments count as 0. */
+size_t affnet_epipolar_scratch_bytes(int t_max, int rounds);
+
+/* Prep + solve + score + select.  d_hyp (t_max*rounds, 9) fp32 or NULL; d_counts (t_max*rounds) int32; d_best int32[2] = {smallest h with
+ * the largest count, that count}, {-1, 0} when no hypothesis is valid.  Rows at or beyond the count and hypotheses at or beyond
+ * count*rounds are neither read nor written.  AFFNET_ERR_INVALID: a NULL pointer (but d_count, d_hyp), inl_th not finite or <= 0, rounds
+ * outside [1, AFFNET_EPI_MAX_ROUNDS], t_max < 0 or t_max * rounds above INT32_MAX. */
+int affnet_epipolar_score(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                          const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed, float* d_hyp, int32_t* d_counts,
+                          int32_t* d_best, void* d_scratch, void* stream);
+
+/* The above + local optimisation.  d_model double[9] row-major, unit Frobenius norm; d_inlier (t_max) uint8; d_summary int32[4] =
+ * {best h, counts[best], final inlier count, flags}, flags 1 = no valid hypothesis (best = -1, model all zero), 2 = too few inliers to
+ * refit, 4 = degenerate.  t_max == 0 is valid and gives {-1, 0, 0, 1}.  lo_iters outside 0..8 is AFFNET_ERR_INVALID. */
+int affnet_epipolar_verify(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                           const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed, int lo_iters, int32_t* d_counts,
+                           double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
+
 /* ---- descriptor index: k nearest neighbours over many images, shortlist by votes ---- */
 
 /* The front of the retrieval loop extract -> index -> shortlist -> verify: the rows of all database images lie back to back in one (n2,128)

@@ -123,6 +123,9 @@ DESIGN_KERNELS = [
     ("rowmin_dist_kernel<128>", "SNN matching: MFMA distance tiles with a running row minimum"),
     ("spv_score_kernel", "spatial verification: T x T scoring of the affine-frame hypotheses"),
     ("spv_lo_kernel", "spatial verification: fp64 local optimisation, one workgroup"),
+    ("epi_solve_kernel", "epipolar verification: one 8-point solve per thread in fp64, the 8 x 9 system in LDS as [element][thread]"),
+    ("epi_score_kernel", "epipolar verification: (T x rounds) x T scoring of the hypotheses by the Sampson error"),
+    ("epi_lo_kernel", "epipolar verification: fp64 local optimisation (9 x 9 and 3 x 3 Jacobi in LDS), one workgroup"),
     ("rowmin_many_kernel<128>", "SNN matching of many pairs per call: the same row-minimum body, pair index on the grid"),
     ("spv_many_score_kernel", "spatial verification of many pairs per call: the same scoring body, pair index on the grid"),
     ("spv_many_lo_kernel", "spatial verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
