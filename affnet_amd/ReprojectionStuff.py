@@ -2,7 +2,8 @@
 (ReprojectionStuff.py:23-40,126-137), plus the SNN matcher of train_AffNet_test_on_graffity.py:292-300 as one call, and the geometric
 verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify), and both for many image pairs per device call (pair_table,
 enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank).  The epipolar model of a scene with depth is csrc/epipolar.hip
-(verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance)."""
+(verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance).  Guided matching under a
+verified model of either family is csrc/guided.hip (match_guided, enqueue_match_guided, guided_mask, match_verify_guided)."""
 import ctypes as C
 
 import numpy as np
@@ -331,3 +332,136 @@ def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0,
     n = [r[4]["num_inliers"] for r in res]
     rank = sorted(range(len(shortlist)), key=lambda i: -n[i])          # sorted() is stable: ties keep the shortlist's order
     return [shortlist[i] for i in rank], [n[i] for i in rank]
+
+
+# ---- guided matching (csrc/guided.hip: affnet_match_guided, affnet_guided_mask) ----------------------------------------------------------------
+
+GUIDED_KINDS = {"homography": _lib.GUIDED_PLANAR, "affine": _lib.GUIDED_PLANAR, "fundamental": _lib.GUIDED_EPIPOLAR}
+GUIDED_RADIUS = {_lib.GUIDED_PLANAR: 10.0, _lib.GUIDED_EPIPOLAR: 4.0}          # px: the default search radius of a model family
+
+
+def _guided_kind(kind, radius):
+    if kind not in GUIDED_KINDS:
+        raise ValueError("kind must be 'homography', 'affine' or 'fundamental'")
+    code = GUIDED_KINDS[kind]
+    return code, float(GUIDED_RADIUS[code] if radius is None else radius)
+
+
+def _guided_model(model, dev):
+    """(3,3) float64 on `dev`: a device tensor is read where it lies, a host value is uploaded."""
+    m = model if torch.is_tensor(model) else torch.as_tensor(np.asarray(model, np.float64))
+    if m.numel() != 9:
+        raise ValueError("model must have 9 entries")
+    return m.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _guided_frames(what, desc1, desc2, LAFs1, LAFs2):
+    for t, name in ((desc1, "desc1"), (desc2, "desc2"), (LAFs1, "LAFs1"), (LAFs2, "LAFs2")):
+        engine.require_cuda(t, name)
+    a, b = desc1.contiguous().float(), desc2.contiguous().float()
+    if b.size(0) == 0:
+        raise ValueError("%s: descriptors2 is empty" % what)
+    if LAFs1.size(0) != a.size(0) or LAFs2.size(0) != b.size(0):
+        raise ValueError("%s: one LAF per descriptor row (%d / %d frames for %d / %d descriptors)" % (what, LAFs1.size(0), LAFs2.size(0), a.size(0), b.size(0)))
+    return a, b, LAFs1.contiguous().float(), LAFs2.contiguous().float()
+
+
+def enqueue_match_guided(desc1, desc2, LAFs1, LAFs2, model, kind="homography", radius=None, SNN_threshold=0.9, max_dist=float("inf"), mutual=True,
+                         gate=None, n_chunks=0):
+    """Guided matching (affnet_match_guided) enqueued on the current stream with no synchronisation: every row of desc1 is matched among the rows
+    of desc2 whose frame centre the model allows - within `radius` px of where a 'homography' / 'affine' model (3,3 map of image 1 to image 2)
+    sends the row's centre, or within `radius` px (Sampson) of its epipolar line under a 'fundamental' model.  model: (3,3) float64, a device
+    tensor as a verification call returns it (read in place) or a host value (uploaded).  radius: default 10 px planar, 4 px 'fundamental'.
+    A pair is kept when its distance is <= max_dist, its ratio to the second admissible neighbour is <= SNN_threshold and, with `mutual`, the
+    row is also the nearest admissible row of its column.  gate: the (4,) int32 summary of a verification call, or None; when its flags say
+    "no valid hypothesis" nothing is matched.
+    Returns capacity-sized device tensors (tent (n1,2) int32, count (1,) int32, dist (n1,2), idx (n1,2) int32: the two nearest admissible columns
+    per row, (+inf, -1) where there is none); rows of tent at or beyond the count are zero."""
+    a, b, l1, l2 = _guided_frames("enqueue_match_guided", desc1, desc2, LAFs1, LAFs2)
+    code, radius = _guided_kind(kind, radius)
+    n1, n2, dev = a.size(0), b.size(0), a.device
+    if gate is not None and (gate.dtype != torch.int32 or gate.numel() != 4 or not gate.is_cuda):
+        raise ValueError("enqueue_match_guided: gate must be a (4,) int32 device tensor or None")
+    m = _guided_model(model, dev)
+    tent = torch.zeros(max(n1, 1), 2, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    dist = torch.full((max(n1, 1), 2), float("inf"), dtype=torch.float32, device=dev)
+    idx = torch.full((max(n1, 1), 2), -1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib.affnet_match_guided_scratch_bytes(n1, n2, int(n_chunks)), dtype=torch.uint8, device=dev)
+    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty side: never read, but the boundary refuses NULL
+    ctx = engine.utility_ctx(dev)
+    rc = lib.affnet_match_guided(ctx, ptr(a if n1 else one), n1, ptr(b), n2, a.size(1), ptr(l1 if n1 else one), ptr(l2), ptr(m), code, radius,
+                                 float(SNN_threshold), float(max_dist), _lib.GUIDED_MUTUAL if mutual else 0, int(n_chunks), ptr(gate), ptr(dist), ptr(idx),
+                                 ptr(tent), ptr(cnt), ptr(scratch), engine.stream_of(dev))
+    check(rc, ctx, "affnet_match_guided")
+    return tent[:n1], cnt, dist[:n1], idx[:n1]
+
+
+def match_guided(desc1, desc2, LAFs1, LAFs2, model, kind="homography", radius=None, SNN_threshold=0.9, max_dist=float("inf"), mutual=True, gate=None,
+                 n_chunks=0):
+    """enqueue_match_guided and one read-back.  Returns (tent_matches_in_1, tent_matches_in_2, dist (n1,2), idx (n1,2)) - the first two int64, as
+    match_snn returns them."""
+    tent, cnt, dist, idx = enqueue_match_guided(desc1, desc2, LAFs1, LAFs2, model, kind, radius, SNN_threshold, max_dist, mutual, gate, n_chunks)
+    k = int(cnt.item())
+    return tent[:k, 0].long(), tent[:k, 1].long(), dist, idx
+
+
+def guided_mask(LAFs1, LAFs2, model, kind="homography", radius=None):
+    """(n1,n2) bool: the pairs of frames that guided matching under this model, kind and radius admits (affnet_guided_mask)."""
+    engine.require_cuda(LAFs1, "LAFs1")
+    engine.require_cuda(LAFs2, "LAFs2")
+    code, radius = _guided_kind(kind, radius)
+    l1, l2 = LAFs1.contiguous().float(), LAFs2.contiguous().float()
+    n1, n2, dev = l1.size(0), l2.size(0), l1.device
+    mask = torch.zeros(max(n1 * n2, 1), dtype=torch.uint8, device=dev)
+    if n1 and n2:
+        m = _guided_model(model, dev)
+        scratch = torch.empty(lib.affnet_match_guided_scratch_bytes(n1, n2, 1), dtype=torch.uint8, device=dev)
+        ctx = engine.utility_ctx(dev)
+        check(lib.affnet_guided_mask(ctx, ptr(l1), n1, ptr(l2), n2, ptr(m), code, radius, ptr(mask), ptr(scratch), engine.stream_of(dev)), ctx,
+              "affnet_guided_mask")
+    return mask[:n1 * n2].view(n1, n2).bool()
+
+
+def match_verify_guided(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", guided_threshold=0.9, radius=None,
+                        mutual=True, lo_iters=3, rounds=8, seed=0):
+    """match_snn, verification, guided matching under the verified model, verification of the guided matches - one chain on the stream: the
+    tentative lists, their device-side counts, the first model and its summary (the guided call's gate) pass from call to call on the device,
+    and the host reads back once, at the end.  model: 'homography', 'affine' or 'fundamental', as in match_and_verify.
+    Returns match_and_verify's tuple for the final stage: (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), with
+    info["seed_stage"] = {tentatives, num_inliers, flags} of the first stage.  When the first stage found no model (its flags & 1) the final
+    lists are empty and the final flags say so too."""
+    a, b, l1, l2 = _guided_frames("match_verify_guided", descriptors1, descriptors2, LAFs1, LAFs2)
+    if model not in GUIDED_KINDS:
+        raise ValueError("model must be 'homography', 'affine' or 'fundamental'")
+    n1, n2, dev = a.size(0), b.size(0), a.device
+    epi = model == "fundamental"
+
+    def verify(tent, cnt):
+        if epi:
+            return enqueue_verify_epipolar(l1, l2, tent, cnt, inl_th, rounds, seed, lo_iters)
+        return enqueue_verify(l1, l2, tent, cnt, inl_th, model, lo_iters)
+
+    tent0 = torch.empty(n1, 2, dtype=torch.int32, device=dev)
+    cnt0 = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n1:
+        md = torch.empty(n1, dtype=torch.float32, device=dev)
+        md2 = torch.empty(n1, dtype=torch.float32, device=dev)
+        idx = torch.empty(n1, dtype=torch.int32, device=dev)
+        scratch = torch.empty(lib.affnet_match_scratch_bytes(n1, n2), dtype=torch.uint8, device=dev)
+        ctx = engine.utility_ctx(dev)
+        rc = lib.affnet_match_snn(ctx, ptr(a), n1, ptr(b), n2, a.size(1), float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent0), ptr(cnt0),
+                                  ptr(scratch), engine.stream_of(dev))
+        check(rc, ctx, "affnet_match_snn")
+    H0, _, _, summary0 = verify(tent0, cnt0)
+    tent, cnt, _, _ = enqueue_match_guided(a, b, l1, l2, H0, model, radius, guided_threshold, float("inf"), mutual, summary0)
+    tent = tent.contiguous()
+    H, inl, counts, summary = verify(tent, cnt)
+    host = torch.cat([cnt0, summary0, cnt, summary]).cpu().tolist()          # the one read-back
+    k = host[5]
+    per = int(rounds) if epi else 1
+    info = _verify_info(counts[:k * per], host[6:])
+    if epi:
+        info.update(rounds=int(rounds), seed=int(seed))
+    info["seed_stage"] = {"tentatives": host[0], "num_inliers": host[3], "flags": host[4]}
+    return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), info

@@ -39,7 +39,8 @@ VERIFY_AFFINE, VERIFY_HOMOGRAPHY, VERIFY_TILE, VERIFY_CHUNK = 0, 1, 128, 128    
 KNN_MAX_K = 8                                                                                    # AFFNET_KNN_MAX_K: neighbours per query row of affnet_knn
 IVF_MAX_PROBE = 8                                                                                # AFFNET_IVF_MAX_PROBE: cells per query row of affnet_ivf_search
 EPI_MAX_ROUNDS, EPI_TILE, EPI_CHUNK, EPI_SOLVE_TILE = 64, 128, 128, 64                            # include/affnet_hip.h AFFNET_EPI_*
-VERIFY_FLAG_PAIR_RANGE = 8                                                                     # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
+GUIDED_PLANAR, GUIDED_EPIPOLAR, GUIDED_MUTUAL = 0, 1, 1                                           # include/affnet_hip.h AFFNET_GUIDED_*
+VERIFY_FLAG_PAIR_RANGE = 8                                                                    # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
 
 
 class Config(C.Structure):
@@ -136,6 +137,9 @@ SYMBOLS = {
     "affnet_epipolar_scratch_bytes": (_SZ, [_I, _I]),
     "affnet_epipolar_score": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, C.c_float, _I, C.c_uint32, _P, _P, _P, _P, _P]),
     "affnet_epipolar_verify": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, C.c_float, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P]),
+    "affnet_match_guided_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "affnet_match_guided": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "affnet_guided_mask": (_I, [_P, _P, _I, _P, _I, _P, _I, C.c_float, _P, _P, _P]),
     "affnet_knn_chunks": (_I, [_P, _I, _I]),
     "affnet_knn_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_knn": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -3,7 +3,7 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental] [--guided]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
 missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
@@ -20,7 +20,10 @@ where the file's H puts them.
 best refined as a rank-2 fundamental matrix, Sampson error <= 2 px); the line gives the epipolar inliers next to the ground-truth check and the
 median Sampson distance of the ground-truth matches under the recovered F.  graf is a PLANAR scene: every F compatible with its homography
 explains the wall, so the F printed here is one of a family - good as an inlier test, not as the pair's epipolar geometry.  The model is
-meant for two views of a scene with depth, where a homography keeps only the dominant plane."""
+meant for two views of a scene with depth, where a homography keeps only the dominant plane.
+--guided (with --verify): guided matching behind the verification (match_verify_guided: the descriptors are searched again, every keypoint among
+the keypoints the verified model allows, and the result is verified once more); a further line gives the guided tentatives, their verified
+inliers and how many of each the ground-truth homography confirms, by the same 6 px rule."""
 import os
 import sys
 
@@ -31,7 +34,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import affnet_amd  # noqa: E402
-from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, get_GT_correspondence_indexes, sampson_distance  # noqa: E402
+from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, match_verify_guided, get_GT_correspondence_indexes, sampson_distance  # noqa: E402
 
 
 def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
@@ -55,7 +58,10 @@ def main(argv):
     desc_kind = "hardnet"
     tfeat_path = None
     verify = "--verify" in argv
-    argv = [a for a in argv if a != "--verify"]
+    guided = "--guided" in argv
+    if guided and not verify:
+        sys.exit("--guided goes with --verify")
+    argv = [a for a in argv if a not in ("--verify", "--guided")]
     if "--tfeat-weights" in argv:
         i = argv.index("--tfeat-weights")
         if i + 1 >= len(argv):
@@ -119,6 +125,12 @@ def main(argv):
             err = ((a[:, :2] / a[:, 2:] - b[:, :2] / b[:, 2:]) ** 2).sum(1).sqrt().max().item()
             print("Verified on %s, %d inliers of %d tentatives (best hypothesis %d, flags %d), %d of them true matches, corner error vs H1to2 %.1f px"
                   % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), err))
+        if verify and guided:
+            g1, g2, _, ginl, ginfo = match_verify_guided(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0 if model == "fundamental" else 3.0,
+                                                         model=model)
+            gt = lambda a, b: get_GT_correspondence_indexes(r1["LAFs"][a], r2["LAFs"][b], H1to2, dist_threshold=6)[1].numel() if a.numel() else 0
+            print("Guided on %s (%s), %d guided tentatives %d true matches, %d inliers (flags %d, seed stage flags %d), %d of them true matches"
+                  % (tag, model, g1.numel(), gt(g1, g2), ginfo["num_inliers"], ginfo["flags"], ginfo["seed_stage"]["flags"], gt(g1[ginl], g2[ginl])))
 
 
 if __name__ == "__main__":

@@ -614,6 +614,64 @@ int affnet_epipolar_verify(affnet_ctx* ctx, const float* d_lafs1, int n1, const 
                            const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed, int lo_iters, int32_t* d_counts,
                            double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
 
+/* ---- guided matching: the descriptors searched again under a verified model ----
+ *
+ * affnet_match_snn refuses every match whose global second-nearest ratio is poor, also where the model that affnet_verify_matches /
+ * affnet_epipolar_verify found afterwards would have made it unambiguous (repeated structure, a strong viewpoint change).  Here every
+ * keypoint of image 1 is matched among the keypoints of image 2 that the model allows; the caller refits on the result.
+ *
+ * Inputs: d_desc1 (n1,128), d_desc2 (n2,128); d_lafs1 (n1,2,3), d_lafs2 (n2,2,3), of which the centres are read; d_model double[9]
+ * row-major ON THE DEVICE (what a verification call wrote: no read-back in between); kind; radius r in px; snn_threshold thr; max_dist; flags.
+ *
+ * Model: m[k] = (float)d_model[k].  Everything below is fp32, one rounding per written operation (no fused multiply-add).
+ *
+ * Admissible pair (i, j), centres (x, y) of d_lafs1[i] and (u, v) of d_lafs2[j]:
+ *   AFFNET_GUIDED_PLANAR (any 3x3 map of image 1 to image 2: the homography or the affine model of affnet_verify_matches)
+ *     X = (m0*x + m1*y) + m2, Y = (m3*x + m4*y) + m5, W = (m6*x + m7*y) + m8; px = X / W, py = Y / W; dx = px - u, dy = py - v;
+ *     admissible iff W > 0 && (dx*dx + dy*dy) <= r*r.
+ *   AFFNET_GUIDED_EPIPOLAR (x2^T F x1 = 0: the model of affnet_epipolar_verify), the scoring tree of that call with th = r:
+ *     l0 = (m0*x + m1*y) + m2, l1 = (m3*x + m4*y) + m5, l2 = (m6*x + m7*y) + m8; m0' = (m0*u + m3*v) + m6, m1' = (m1*u + m4*v) + m7;
+ *     rr = (u*l0 + v*l1) + l2; e = (rr*rr) / (((l0*l0 + l1*l1) + m0'*m0') + m1'*m1'); admissible iff e <= r*r.
+ *   A non-finite centre, model entry or intermediate makes the comparison false.  The per-point terms (px, py, W > 0 / l0, l1, l2 per point
+ *   of image 1; m0', m1' per point of image 2) are computed once and read by every stage, so no two stages disagree about a pair.
+ *
+ * Distance of a pair: the element affnet_distance_matrix writes for it, bit for bit.  Order of candidates: a NaN distance in front of
+ * every number, then the smaller distance, then the smaller index (affnet_knn's order).
+ *   d_dist (n1,2), d_idx (n1,2): per row i the first two admissible columns in that order; an unfilled slot is (+inf, -1).
+ *   With AFFNET_GUIDED_MUTUAL, back[j] = the first admissible row of column j in that order, or -1 (kept in the scratch).
+ *
+ * Selection, in row order: (i, idx[i][0]) is kept iff idx[i][0] >= 0 && dist[i][0] <= max_dist &&
+ * dist[i][0] / (dist[i][1] + 1e-8f) <= thr (with one admissible column the ratio is 0) && (no AFFNET_GUIDED_MUTUAL || back[idx[i][0]] == i).
+ * A NaN nearest distance is refused, as affnet_match_snn refuses it.  d_tent (n1,2) int32 receives the kept pairs, d_count their number;
+ * rows of d_tent at or beyond the count are not written.
+ *
+ * Gate: d_gate, optional, is the d_summary int32[4] of a verification call.  When it is not NULL and d_gate[3] & 1 (no valid hypothesis -
+ * affnet_verify_matches then leaves the identity as its model) nothing is matched: the count is 0, the lists are unfilled.
+ *
+ * The search runs like affnet_knn's: row blocks x n_chunks column chunks, a merge over the chunks; n_chunks = 0: the library chooses; the
+ * result does not depend on it.  The backward pass is the same kernel with the sides exchanged.  One linear chain of launches on `stream`,
+ * no allocation, no synchronisation.  n1 == 0 or n2 == 0 is valid and gives count 0.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, an unknown kind or flag bit, a radius that is not finite and > 0, a NaN
+ * max_dist, a negative size, n_chunks outside 0..65535, a NULL pointer other than d_gate. */
+#define AFFNET_GUIDED_PLANAR 0
+#define AFFNET_GUIDED_EPIPOLAR 1
+#define AFFNET_GUIDED_MUTUAL 1    /* flags bit 0: keep (i, j) only if i is also the first admissible row of column j */
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_match_guided called with this n_chunks (0: enough for whatever the library
+ * may choose) and of affnet_guided_mask at these sizes.  Negative arguments count as 0. */
+size_t affnet_match_guided_scratch_bytes(int n1, int n2, int n_chunks);
+
+int affnet_match_guided(affnet_ctx* ctx, const float* d_desc1, int n1, const float* d_desc2, int n2, int dim, const float* d_lafs1,
+                        const float* d_lafs2, const double* d_model, int kind, float radius, float snn_threshold, float max_dist, int flags,
+                        int n_chunks, const int32_t* d_gate, float* d_dist, int32_t* d_idx, int32_t* d_tent, int32_t* d_count,
+                        void* d_scratch, void* stream);
+
+/* d_mask (n1,n2) uint8: 1 where the pair is admissible by the rule above - the very function affnet_match_guided applies.  For tests and
+ * inspection.  d_scratch: affnet_match_guided_scratch_bytes(n1, n2, 1).  AFFNET_ERR_INVALID: an unknown kind, a radius that is not finite
+ * and > 0, a negative size, a NULL pointer. */
+int affnet_guided_mask(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const double* d_model, int kind,
+                       float radius, uint8_t* d_mask, void* d_scratch, void* stream);
+
 /* ---- descriptor index: k nearest neighbours over many images, shortlist by votes ---- */
 
 /* The front of the retrieval loop extract -> index -> shortlist -> verify: the rows of all database images lie back to back in one (n2,128)

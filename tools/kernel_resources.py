@@ -126,6 +126,11 @@ DESIGN_KERNELS = [
     ("epi_solve_kernel", "epipolar verification: one 8-point solve per thread in fp64, the 8 x 9 system in LDS as [element][thread]"),
     ("epi_score_kernel", "epipolar verification: (T x rounds) x T scoring of the hypotheses by the Sampson error"),
     ("epi_lo_kernel", "epipolar verification: fp64 local optimisation (9 x 9 and 3 x 3 Jacobi in LDS), one workgroup"),
+    ("guided_tile_kernel<0, 2, false>", "guided matching, planar model, forward pass: the matcher's distance tiles over one column chunk, two admissible neighbours per row and lane"),
+    ("guided_tile_kernel<0, 1, true>", "guided matching, planar model, backward pass: the sides exchanged, one admissible neighbour"),
+    ("guided_tile_kernel<1, 2, false>", "guided matching, epipolar model, forward pass"),
+    ("guided_tile_kernel<1, 1, true>", "guided matching, epipolar model, backward pass"),
+    ("guided_select_kernel", "guided matching: distance bound, ratio and mutual test, compaction in row order, one workgroup"),
     ("rowmin_many_kernel<128>", "SNN matching of many pairs per call: the same row-minimum body, pair index on the grid"),
     ("spv_many_score_kernel", "spatial verification of many pairs per call: the same scoring body, pair index on the grid"),
     ("spv_many_lo_kernel", "spatial verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
