@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import affnet_oracle as orc
+from _head_fp32 import _layout_head_offset, unpack_head
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -232,8 +233,8 @@ def test_packed_weights_reproduce_the_network(kind, name, weights):
     for i, (W, b) in enumerate(layers):
         x = F.relu(F.conv2d(x, W, b, stride=2 if i in (2, 4) else 1, padding=1))
     if kind == 2:
-        Bw = blob[off:off + 8192 * 128].view(512, 4, 128, 4).permute(0, 1, 3, 2).reshape(8192, 128)   # [k/16][(k/4)%4][n][k%4] -> [k][n]
-        bias = blob[off + 8192 * 128: off + 8192 * 128 + 128]
+        assert off == _layout_head_offset("hardnet")[0]
+        Bw, bias = (torch.from_numpy(v) for v in unpack_head(blob, "hardnet"))                       # [k/16][(k/4)%4][n][k%4] -> [k][n]; the bias behind it
         y = x.permute(0, 2, 3, 1).reshape(6, -1) @ Bw + bias      # head K order = [pixel][channel] (the trunk kernel's store order)
         got = y / torch.sqrt((y * y).sum(1, keepdim=True) + 1e-8)
         want = orc.hardnet_forward(sd, p)
@@ -380,7 +381,8 @@ def test_split_weight_copies_are_exact(kind, name, weights):
         K = 8192
         head_off = off - sum((5 if layers[i][0].shape[1] == 16 else 9 * (layers[i][0].shape[1] // 32)) * 3 * 4 * layers[i][0].shape[0] * 4 for i in range(1, 6)) \
             - (K * 128 + 128)
-        Wf = blob.numpy()[head_off: head_off + K * 128].reshape(K // 16, 4, 128, 4).transpose(0, 1, 3, 2).reshape(K, 128).astype(np.float64)
+        assert head_off == _layout_head_offset("hardnet")[0]
+        Wf = unpack_head(blob, "hardnet")[0].astype(np.float64)
         n_fl = K * 128 * 3 // 2
         raw = bits[2 * off: 2 * (off + n_fl)].astype(np.uint32) << 16
         t = raw.view(np.float32).astype(np.float64).reshape(K // 32, 3, 4, 128, 8).transpose(1, 0, 2, 4, 3).reshape(3, K, 128)
