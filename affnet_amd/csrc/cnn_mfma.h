@@ -1495,6 +1495,60 @@ __device__ __forceinline__ void f43_store_lds(float* act, f32x4 bias, const f32x
     }
 }
 
+// ---- conv5 of HardNet's descriptor form 3: F(4x4, 3x3) over FOUR patches per workgroup (hardnet_conv5_f43.hip: hardnet_conv5_f43_kernel) ----------------------
+// conv5 (128 -> 128 at 8 x 8) has four 4x4 tiles per patch; four consecutive patches fill the MFMA's 16 columns, m = 4 patch + 2 ty + tx.  Wave w owns channel block w,
+// all 36 positions and all of K: 36 accumulators live over the whole layer, no exchange between waves (no f43_combine).  K runs in four quarters of 32 channels (two K
+// groups): a quarter's input, global [c / 4][pixel][4] per patch (wino_store_global_c4), goes into a zero-haloed 10 x 10 LDS tile per (patch, channel group); thread
+// (channel group, m, e) transforms ONE channel of one window (f43_bt_lo / f43_bt_hi along y, then x: f43_window_half's operations) into V [G (2)][xi][kq][m][4]; then every wave
+// runs 2 x 36 positions x 4 k-steps with no VALU in the loop.  The next quarter's input is requested in front of the transform and lands under the loop.
+struct F43C5L {                                           // float offsets in the kernel's LDS
+    static constexpr int WPI = 10;                        // row of the padded input tile
+    static constexpr int CGS = WPI * WPI * 4;             // a channel group (4 interleaved channels) of a patch
+    static constexpr int PS = 8 * CGS + 4;                // a patch: the quarter's 8 channel groups, + 4 floats: the transform's ds_read_b32 of 4 patches x 2 tx x 4 channels cover the 32 banks
+    static constexpr int IN = 0, IN_FLOATS = 4 * PS;
+    static constexpr int V = IN_FLOATS, V_FLOATS = 2 * F43_XI * 256;
+    static constexpr int TOTAL = V + V_FLOATS;            // 124 992 bytes
+};
+static_assert(F43C5L::V % 4 == 0 && F43C5L::PS % 4 == 0 && F43C5L::TOTAL * 4 <= 160 * 1024, "16-byte aligned sections within the CU's LDS");
+
+// One channel of one 6x6 window at `in` (floats, row pitch WPI * 4, column pitch 4) -> its 36 positions, position xi at v[xi * 256]: B^T d B along y, then along x
+__device__ __forceinline__ void f43c5_transform(const float* in, float* v) {
+    float t[6][6];                                        // t[i][c]
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        float d[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) d[r] = in[(r * F43C5L::WPI + c) * 4];
+        f43_bt_lo(d[0], d[1], d[2], d[3], d[4], t[0][c], t[1][c], t[2][c]);
+        f43_bt_hi(d[1], d[2], d[3], d[4], d[5], t[3][c], t[4][c], t[5][c]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        float o[6];
+        f43_bt_lo(t[i][0], t[i][1], t[i][2], t[i][3], t[i][4], o[0], o[1], o[2]);
+        f43_bt_hi(t[i][1], t[i][2], t[i][3], t[i][4], t[i][5], o[3], o[4], o[5]);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[(6 * i + j) * 256] = o[j];
+    }
+}
+
+// Y = A^T M A of the lane's 4 output channels (x first, then y: f43_at_axis both ways, the sums f43_combine forms over a wave pair): y[4 dy + c]
+__device__ __forceinline__ void f43c5_output(const f32x4 (&acc)[F43_XI], f32x4 (&y)[16]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t[6][4];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) f43_at_axis(acc[6 * i][e], acc[6 * i + 1][e], acc[6 * i + 2][e], acc[6 * i + 3][e], acc[6 * i + 4][e], acc[6 * i + 5][e], t[i][0], t[i][1], t[i][2], t[i][3]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float yr[4];
+            f43_at_axis(t[0][c], t[1][c], t[2][c], t[3][c], t[4][c], t[5][c], yr[0], yr[1], yr[2], yr[3]);
+#pragma unroll
+            for (int dy = 0; dy < 4; ++dy) y[4 * dy + c][e] = yr[dy];
+        }
+    }
+}
+
 // The same layer for the 16-channel trunks (AffNet / OriNet conv1, conv3), which live on 128 registers per lane (two workgroups per CU): acc[16] + U[16] +
 // V[16] of a whole-window loop do not fit.  The output transform is linear in the positions, so a wave walks ONE ROW of four positions xi = 4 i .. 4 i + 3 at a
 // time: row i of V needs two rows of the window (B^T along y: rows (0, 2), (1, 2), (2, 1), (1, 3)), 8 ds_read_b128 and 32 VALU operations; the row's four
@@ -1724,6 +1778,23 @@ __device__ __forceinline__ void wino_store_global(float* __restrict__ dst, const
             const int p = (2 * ty + (k >> 1)) * H + 2 * tx + (k & 1);
             const f32x4 v = bias_relu(y[q][k], bias[q]);
             *reinterpret_cast<f32x4*>(dst + p * COUT + cb * 16 + 4 * g) = v;
+        }
+    }
+}
+
+// Same for conv4 of HardNet's descriptor form 3: global [c / 4][pixel p][4], wino_store_lds's layout without the halo (hardnet_conv5_f43_kernel reads it back)
+template <int COUT, int H, int NB>
+__device__ __forceinline__ void wino_store_global_c4(float* __restrict__ dst, const f32x4 (&bias)[NB], const f32x4 (&y)[NB][4], int wave, int lane) {
+    const int g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        int ty, tx, cb;
+        wino_tile<H, COUT, NB>(wave, q, lane & 15, ty, tx, cb);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p = (2 * ty + (k >> 1)) * H + 2 * tx + (k & 1);
+            const f32x4 v = bias_relu(y[q][k], bias[q]);
+            *reinterpret_cast<f32x4*>(dst + ((cb * 4 + g) * (H * H) + p) * 4) = v;
         }
     }
 }

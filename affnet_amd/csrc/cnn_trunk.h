@@ -1,6 +1,6 @@
 // Trunk kernel of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet) for gfx950 on the fp32 matrix cores: cnn32_trunk_kernel and its
-// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip / cnn_trunk_hardnet_f43.hip: HardNet forms 1 / 2), which instantiate one net's six kernels each
-// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1 / 2),
+// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip / cnn_trunk_hardnet_f43.hip / cnn_trunk_hardnet_c5.hip: HardNet forms 1 / 2 / 3), which instantiate one net's six kernels each
+// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1 / 2 / 3),
 // exact AffNet / OriNet, split HardNet, split AffNet / OriNet.
 //
 // Replaces architectures.py:204-252 (AffNetFast), :33-82 (OriNetFast), HardNet.py:61-101
@@ -235,13 +235,15 @@ struct TrunkShape {
 template <int KIND, int S3>
 struct TrunkTraits {
     static_assert(S3 == TRUNK_EXACT || S3 == TRUNK_SPLIT2 || S3 == TRUNK_SPLIT3 || (S3 == TRUNK_WINO && KIND != AFFNET_NET_ORINET) ||
-                  (S3 == TRUNK_WINO_F43 && KIND == AFFNET_NET_HARDNET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET), "no such trunk form of this net (common.h: TRUNK_*)");
+                  ((S3 == TRUNK_WINO_F43 || S3 == TRUNK_WINO_F43_C5) && KIND == AFFNET_NET_HARDNET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET), "no such trunk form of this net (common.h: TRUNK_*)");
     static constexpr bool EXACT = S3 != TRUNK_SPLIT2 && S3 != TRUNK_SPLIT3;     // fp32 operands on v_mfma_f32_16x16x4_f32
     // 16-channel trunks: conv1 / conv3 / conv5 as Winograd F(2x2, 3x3) on 128 registers (conv5: a wave pair per channel block); conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
     static constexpr bool WINO13 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || ((S3 == TRUNK_WINO || S3 == TRUNK_WINO_POLY) && KIND == AFFNET_NET_AFFNET);
     static constexpr bool POLY16 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET);
     // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2); form 2: conv3 as Winograd F(4x4, 3x3), V shared through LDS (conv1 in F(4x4, 3x3) has no loop yet: NOTES.md)
-    static constexpr bool POLY = (S3 == TRUNK_WINO || S3 == TRUNK_WINO_F43) && KIND == AFFNET_NET_HARDNET, F43_3 = S3 == TRUNK_WINO_F43 && KIND == AFFNET_NET_HARDNET;
+    // form 3 (CUT5): form 2 up to conv4's loop; conv4's tensor goes to HBM and hardnet_conv5_f43_kernel (hardnet_conv5_f43.hip) runs conv5 for four patches per workgroup
+    static constexpr bool CUT5 = S3 == TRUNK_WINO_F43_C5 && KIND == AFFNET_NET_HARDNET;
+    static constexpr bool POLY = (S3 == TRUNK_WINO || S3 == TRUNK_WINO_F43 || CUT5) && KIND == AFFNET_NET_HARDNET, F43_3 = (S3 == TRUNK_WINO_F43 || CUT5) && KIND == AFFNET_NET_HARDNET;
 };
 
 template <int C, typename L, int NTHR>
@@ -272,7 +274,7 @@ struct SplitLays {
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = the trunk form (TRUNK_*, common.h;
 // TrunkTraits above says what each does - for the split-operand forms the value is the number of terms).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
-// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 and conv3 in F(4x4, 3x3) in form 2), exact AffNet / OriNet, split HardNet,
+// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2 / 3: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 / 3, conv3 in F(4x4, 3x3) in forms 2 / 3, and the body cut behind conv4 in form 3), exact AffNet / OriNet, split HardNet,
 // split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
@@ -283,7 +285,7 @@ struct SplitLays {
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
     using F = TrunkTraits<KIND, S3>;
-    constexpr bool EXACT = F::EXACT, WINO13 = F::WINO13, POLY16 = F::POLY16, POLY = F::POLY, F43_3 = F::F43_3;
+    constexpr bool EXACT = F::EXACT, WINO13 = F::WINO13, POLY16 = F::POLY16, POLY = F::POLY, F43_3 = F::F43_3, CUT5 = F::CUT5;
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -509,8 +511,16 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             conv3x3_poly_mfma_rows<NW, 2 * CB, 4 * CB, LayC3, NBP4, 1>(act, a.wino_u + Poly32::offset(4), P4a, P4b, y, wave, lane);
             __builtin_amdgcn_s_setprio(3);
             CNN_STAMP(9);
-            wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
+            if constexpr (!CUT5) wino_prefetch_u<NW, 4 * CB, 4 * CB, 8, NB5>(a.packed + a.off.w_wino[2], Uw, wave, lane);
             wino_bias<NW, 8, 4 * CB, NBP4>(a.packed + a.off.b[4], bw, wave, lane);
+            if constexpr (CUT5) {
+                // form 3 ends here: bias, ReLU and conv4's tensor into the patch's slot of a.out as [c / 4][pixel][4], the LDS layout without its halo
+                if (!STAMPS || a.dbg_layer < 0) {
+                    wino_store_global_c4<4 * CB, 8, NBP4>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
+                    CNN_STAMP(13);
+                    return;
+                }
+            }
             __syncthreads();
             zero_halo<LayC4, NTHR>(act, 4 * CB);
             wino_store_lds<4 * CB, LayC4, NBP4>(act, bw, y, wave, lane);
@@ -532,23 +542,25 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         if (STAMPS && a.dbg_layer == 4) { dump_planes<4 * CB, LayC4, NTHR>(act, a.dbg_out); return; }
 
         // ---- conv5: 4CB -> 4CB @8x8, Winograd; conv5 tensor -> HBM as [pixel][channel], the head GEMM runs over all patches ----
-        f32x4 y[NB5][4], bw[NB5];
-        __builtin_amdgcn_s_setprio(0);
-        static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
-        conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
-        __builtin_amdgcn_s_setprio(3);
-        CNN_STAMP(11);
-        wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
-        if (!STAMPS || a.dbg_layer < 0) {
-            wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
-            CNN_STAMP(13);
-            return;
+        if constexpr (!CUT5) {
+            f32x4 y[NB5][4], bw[NB5];
+            __builtin_amdgcn_s_setprio(0);
+            static_assert(NB5 == 1 && (4 * CB / 16) * 4096 <= TrunkLds<CB>::ACT, "conv5: one pass per wave, V of the layer fits the activation buffer");
+            conv3x3_wino_mfma_shared_v<NW, 4 * CB, 4 * CB, LayC4>(act, a.packed + a.off.w_wino[2], Uw, y, wave, lane);
+            __builtin_amdgcn_s_setprio(3);
+            CNN_STAMP(11);
+            wino_bias<NW, 8, 4 * CB, NB5>(a.packed + a.off.b[5], bw, wave, lane);
+            if (!STAMPS || a.dbg_layer < 0) {
+                wino_store_global<4 * CB, 8, NB5>(a.out + pidx * (64 * 4 * CB), bw, y, wave, lane);
+                CNN_STAMP(13);
+                return;
+            }
+            __syncthreads();
+            wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
+            __syncthreads();
+            CNN_STAMP(12);
+            if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
         }
-        __syncthreads();
-        wino_store_lds<4 * CB, LayC5, NB5>(act, bw, y, wave, lane);   // debug dump only
-        __syncthreads();
-        CNN_STAMP(12);
-        if (STAMPS && a.dbg_layer == 5) { dump_planes<4 * CB, LayC5, NTHR>(act, a.dbg_out); return; }
     } else if constexpr (EXACT) {
         // Exact AffNet / OriNet.  OriNet: conv1, conv3 and conv5 (stride 1) as Winograd F(2x2, 3x3), one row of four transform positions at a time
         // (conv3x3_wino_mfma_rows: the 128-register budget of two workgroups per CU) - 4/9 of their MFMAs; U = G g G^T comes from a.wino_u, which

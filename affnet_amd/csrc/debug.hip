@@ -168,3 +168,37 @@ extern "C" int affnet_probe_hardnet_f43_u(affnet_ctx* ctx, const float* d_packed
     if (!ctx || !d_packed || !d_out || (layer != 1 && layer != 3)) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_f43_u: layer 1 or 3");
     return probe_derived_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO_F43, d_packed, F43::BASE + F43::offset(layer), F43::floats(layer), d_out, stream);
 }
+
+// Descriptor form 3 (AFFNET_DESC_FORM_F43_CONV5): the trunk's layers 0 .. 4, the whole forward, conv5's kernel alone on caller-made slots, and its derived weights
+extern "C" int affnet_probe_hardnet_c5_trunk_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patch || !d_out || layer < 0 || layer > 4) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_trunk_layer: layer 0 .. 4");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patch, 1, d_out, nullptr, layer, (hipStream_t)stream, AFFNET_DESC_FORM_F43_CONV5);
+}
+
+extern "C" int affnet_probe_hardnet_c5_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patches || !d_out || !d_scratch || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_forward: bad argument");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patches, n, d_out, d_scratch, -1, (hipStream_t)stream, AFFNET_DESC_FORM_F43_CONV5);
+}
+
+extern "C" int affnet_probe_hardnet_c5_layer(affnet_ctx* ctx, const float* d_packed, float* d_slots, int n, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_slots || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_layer: bad argument");
+    if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_layer: AFFNET_ARITH_FP32_MFMA only");
+    const NetLayout L = net_layout(AFFNET_NET_HARDNET);
+    const float* u;
+    const int rc = aff_derive_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO_F43_C5, d_packed, L, (hipStream_t)stream, &u);
+    if (rc) return rc;
+    Conv5Args v;
+    v.io = d_slots; v.U = u + F43C5::BASE; v.bias = d_packed + L.b_off[5];
+    v.count = nullptr; v.n_max = n; v.row_begin = 0; v.row_end = n;
+    v.skip_cnt = nullptr; v.skip_n = 0; v.dbg_time = nullptr;
+    return aff_hardnet_conv5_f43(ctx, v, aff_cdiv(n, 4), 1, false, (hipStream_t)stream);
+}
+
+extern "C" int affnet_probe_hardnet_c5_u(affnet_ctx* ctx, const float* d_packed, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_out) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_u: null argument");
+    return probe_derived_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO_F43_C5, d_packed, F43C5::BASE, F43C5::FLOATS, d_out, stream);
+}

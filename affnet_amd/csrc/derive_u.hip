@@ -16,12 +16,12 @@ int aff_derived_u_ensure(affnet_ctx* ctx) {
 
 // the sections the exact trunk (kind, form) reads; n == 0: none
 static DerivedTable table_of(int kind, int form) {
-    if (kind == AFFNET_NET_HARDNET) return form == TRUNK_WINO ? derived_hardnet_poly() : (form == TRUNK_WINO_F43 ? derived_hardnet_form2() : DerivedTable{});
+    if (kind == AFFNET_NET_HARDNET) return form == TRUNK_WINO ? derived_hardnet_poly() : (form == TRUNK_WINO_F43 ? derived_hardnet_form2() : (form == TRUNK_WINO_F43_C5 ? derived_hardnet_form3() : DerivedTable{}));
     const bool wino = kind == AFFNET_NET_ORINET ? form == TRUNK_EXACT : (form == TRUNK_WINO || form == TRUNK_WINO_POLY);
     return wino ? derived_trunk16() : DerivedTable{};
 }
 
-// On the launch stream, ONE launch of a thread per pair (7936 threads, 286 KB read, 600 KB written for a 16-channel net; 15360, 0.55 MB, 1.8 MB for HardNet form 2).
+// On the launch stream, ONE launch of a thread per pair (7936 threads, 286 KB read, 600 KB written for a 16-channel net; 15360, 0.55 MB, 1.8 MB for HardNet form 2; 31744, 1.1 MB, 4.1 MB for form 3).
 // In front of EVERY launch of a trunk that reads them, so that a blob rewritten in place (load_state_dict into the same device buffer) can never meet stale weights, eagerly or in a replayed graph.
 int aff_derive_u(affnet_ctx* ctx, int kind, int form, const float* packed, const NetLayout& L, hipStream_t st, const float** region) {
     *region = nullptr;

@@ -99,6 +99,7 @@ static int check_kind(int kind) {
 static_assert(Wino16::offset(1) == 0 && Wino16::offset(3) == 4096 && Wino16::offset(5) == 20480 && Wino16::offset(2) == 86016 && Wino16::offset(4) == 98816 && Wino16::FLOATS == 150016 && Wino16::PAIRS == 7936, "Wino16");
 static_assert(Poly32::offset(2) == 0 && Poly32::offset(4) == 51200 && Poly32::FLOATS == 256000 && Poly32::PAIRS == 10240, "Poly32");
 static_assert(F43::BASE == 256000 && F43::offset(1) == 0 && F43::offset(3) == 36864 && F43::FLOATS == 184320 && F43::PAIRS == 5120, "F43");
+static_assert(F43C5::BASE == 440320 && F43C5::FLOATS == 589824 && derived_hardnet_form3().pairs == 15360 + 16384, "F43C5");
 
 // Table t of a `kind` blob: derive_u_pair for every pair index into a destination of exactly want_floats floats; every float is written by the pair that owns it and by
 // no other, and holds the family's transform of the 9 taps that plain (layer, tap, cin, cout) indexing finds in the blob.
@@ -138,12 +139,14 @@ static int check_derived(const char* name, int kind, const DerivedTable& t, int 
     return 0;
 }
 
-// the regions of the context's buffer: disjoint, back to back in this order, and together the buffer; form 2's one launch fills the last two
+// the regions of the context's buffer: disjoint, back to back in this order, and together the buffer; form 2's one launch fills the two behind the 16-channel nets', form 3's the last three
 static int check_regions() {
     const size_t t16 = derived_trunk16().floats, poly = derived_hardnet_poly().floats, f43 = derived_hardnet_f43().floats;
-    CHECK(DerivedU::AFFNET == 0 && DerivedU::ORINET == t16 && DerivedU::HARDNET == 2 * t16 && DerivedU::HARDNET_F43 == 2 * t16 + poly && DerivedU::FLOATS == 2 * t16 + poly + f43);
+    const size_t c5 = F43C5::FLOATS;
+    CHECK(DerivedU::AFFNET == 0 && DerivedU::ORINET == t16 && DerivedU::HARDNET == 2 * t16 && DerivedU::HARDNET_F43 == 2 * t16 + poly && DerivedU::HARDNET_C5 == 2 * t16 + poly + f43 &&
+          DerivedU::FLOATS == 2 * t16 + poly + f43 + c5);
     CHECK(DerivedU::region(AFFNET_NET_AFFNET) == DerivedU::AFFNET && DerivedU::region(AFFNET_NET_ORINET) == DerivedU::ORINET && DerivedU::region(AFFNET_NET_HARDNET) == DerivedU::HARDNET);
-    CHECK(derived_hardnet_form2().floats == poly + f43);
+    CHECK(derived_hardnet_form2().floats == poly + f43 && derived_hardnet_form3().floats == poly + f43 + c5);
     return 0;
 }
 
@@ -152,7 +155,8 @@ int main() {
         if (check_kind(kind)) return 1;
     if (check_derived("AffNet", AFFNET_NET_AFFNET, derived_trunk16(), 5, 150016) || check_derived("OriNet", AFFNET_NET_ORINET, derived_trunk16(), 5, 150016) ||
         check_derived("HardNet polyphase", AFFNET_NET_HARDNET, derived_hardnet_poly(), 2, 256000) || check_derived("HardNet F(4x4, 3x3)", AFFNET_NET_HARDNET, derived_hardnet_f43(), 2, 184320) ||
-        check_derived("HardNet form 2", AFFNET_NET_HARDNET, derived_hardnet_form2(), 4, 256000 + 184320) || check_regions())
+        check_derived("HardNet form 2", AFFNET_NET_HARDNET, derived_hardnet_form2(), 4, 256000 + 184320) ||
+        check_derived("HardNet form 3", AFFNET_NET_HARDNET, derived_hardnet_form3(), 5, 256000 + 184320 + 589824) || check_regions())
         return 1;
     return 0;
 }

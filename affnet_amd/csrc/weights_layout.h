@@ -239,6 +239,8 @@ constexpr DerivedTable derived_hardnet_poly() { return derived_add(derived_add(D
 constexpr DerivedTable derived_hardnet_f43() { return derived_add(derived_add(DerivedTable{}, 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }
 // ... and what descriptor form 2 reads: those directly BEHIND form 1's polyphase sections - its trunk takes one derived-weights pointer (CnnArgs::wino_u) and finds both there
 constexpr DerivedTable derived_hardnet_form2() { return derived_add(derived_add(derived_hardnet_poly(), 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }
+// ... and descriptor form 3: form 2's table with conv5 (128 -> 128) in F(4x4, 3x3) behind it (2.36 MB), which hardnet_conv5_f43_kernel reads; its trunk reads form 2's sections where form 2's does
+constexpr DerivedTable derived_hardnet_form3() { return derived_add(derived_hardnet_form2(), 32, 5, DERIVED_F43); }
 // the section of conv `layer` (layer -1: not in the table)
 constexpr DerivedSection derived_layer(const DerivedTable& t, int layer) {
     for (int i = 0; i < t.n; ++i)
@@ -257,7 +259,7 @@ constexpr bool derived_by_workgroups(const DerivedTable& t, int i = 0) {
     return i == t.n || (t.s[i].pair0 % 256 == 0 && t.s[i].cin * t.s[i].cout % 256 == 0 && derived_by_workgroups(t, i + 1));
 }
 static_assert(derived_by_workgroups(derived_trunk16()) && derived_by_workgroups(derived_hardnet_poly()) && derived_by_workgroups(derived_hardnet_f43()) &&
-              derived_by_workgroups(derived_hardnet_form2()), "a 256-thread workgroup of derive_u_kernel stays within one section");
+              derived_by_workgroups(derived_hardnet_form2()) && derived_by_workgroups(derived_hardnet_form3()), "a 256-thread workgroup of derive_u_kernel stays within one section");
 
 // What the trunk kernels address the sections of a table through
 template <DerivedTable (*T)()>
@@ -271,19 +273,24 @@ typedef DerivedView<derived_hardnet_poly> Poly32;
 struct F43 : DerivedView<derived_hardnet_f43> { static constexpr int BASE = Poly32::FLOATS; };   // float offset of the family from form 2's derived-weights pointer; offset(layer) is inside the family
 static_assert(derived_hardnet_form2().s[2].dst == F43::BASE + F43::offset(1) && derived_hardnet_form2().s[3].dst == F43::BASE + F43::offset(3) &&
               derived_hardnet_form2().floats == F43::BASE + F43::FLOATS, "form 2's table = Poly32 with F43 at F43::BASE");
+struct F43C5 {                                                                                   // conv5 of descriptor form 3: float offset from form 3's derived-weights pointer, and its size
+    static constexpr int BASE = derived_hardnet_form2().floats, FLOATS = F43_XI * 128 * 128;
+};
+static_assert(derived_hardnet_form3().n == 5 && derived_hardnet_form3().s[4].dst == F43C5::BASE && derived_hardnet_form3().floats == F43C5::BASE + F43C5::FLOATS, "form 3's table = form 2's with conv5 at F43C5::BASE");
 
 // The context's buffer of derived weights, in floats: a region per net, each the base of that net's table(s)
 struct DerivedU {
     static constexpr int AFFNET = 0, ORINET = AFFNET + Wino16::FLOATS;               // derived_trunk16() each
     static constexpr int HARDNET = ORINET + Wino16::FLOATS;                          // derived_hardnet_poly() / derived_hardnet_form2()
     static constexpr int HARDNET_F43 = HARDNET + F43::BASE;                          // ... whose F(4x4, 3x3) part is derived_hardnet_f43()
-    static constexpr int FLOATS = HARDNET_F43 + F43::FLOATS;                         // 3.0 MB
+    static constexpr int HARDNET_C5 = HARDNET + F43C5::BASE;                         // ... and behind it conv5 of descriptor form 3 (derived_hardnet_form3())
+    static constexpr int FLOATS = HARDNET_C5 + F43C5::FLOATS;                        // 5.4 MB
     static constexpr int region(int kind) { return kind == AFFNET_NET_AFFNET ? AFFNET : (kind == AFFNET_NET_ORINET ? ORINET : HARDNET); }
 };
 static_assert(DerivedU::AFFNET == 0 && DerivedU::ORINET - DerivedU::AFFNET == derived_trunk16().floats && DerivedU::HARDNET - DerivedU::ORINET == derived_trunk16().floats &&
-              DerivedU::FLOATS - DerivedU::HARDNET == derived_hardnet_form2().floats && DerivedU::FLOATS == 2 * Wino16::FLOATS + Poly32::FLOATS + F43::FLOATS,
+              DerivedU::FLOATS - DerivedU::HARDNET == derived_hardnet_form3().floats && DerivedU::FLOATS == 2 * Wino16::FLOATS + Poly32::FLOATS + F43::FLOATS + F43C5::FLOATS,
               "the regions are disjoint, in this order, and fill the buffer");
-static_assert(DerivedU::ORINET % 64 == 0 && DerivedU::HARDNET % 64 == 0 && DerivedU::HARDNET_F43 % 64 == 0, "every region starts on a 256-byte boundary, as an allocation of its own would");
+static_assert(DerivedU::ORINET % 64 == 0 && DerivedU::HARDNET % 64 == 0 && DerivedU::HARDNET_F43 % 64 == 0 && DerivedU::HARDNET_C5 % 64 == 0, "every region starts on a 256-byte boundary, as an allocation of its own would");
 // The work of thread e of a derivation launch over table t: pair e - pair0 of its section is pair (c, n) with e - pair0 == w_tap_index(0, c, n, cin, cout), and a position
 // (tap or transform position) p of that pair lies p planes of cin * cout floats further: w_tap_index(p, c, n, cin, cout) == p * cin * cout + w_tap_index(0, c, n, cin, cout).
 // So: the pair's 9 taps of the blob (w_off = NetOffsets::w) through the family's transform into that family's positions at U + dst, plane by plane.  The section is looked

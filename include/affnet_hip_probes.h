@@ -83,6 +83,17 @@ int affnet_probe_hardnet_f43_layer(affnet_ctx* ctx, const float* d_packed, const
 int affnet_probe_hardnet_f43_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
 int affnet_probe_hardnet_f43_u(affnet_ctx* ctx, const float* d_packed, int layer, float* d_out, void* stream);
 
+/* Descriptor form AFFNET_DESC_FORM_F43_CONV5 (form 2 with conv5 as Winograd F(4x4, 3x3) in a kernel of its own, four patches per workgroup):
+ *   _trunk_layer: affnet_cnn32_debug_layer's arguments and output for layers 0 .. 4 of its trunk kernel;
+ *   _forward:     as affnet_probe_hardnet_f43_forward; with a stamp buffer the conv5 kernel writes stamps 24 .. 31 into the record of the first patch of every group of four;
+ *   _layer:       the conv5 kernel alone, in place on n slots of 8192 floats: conv4's post-ReLU tensor as [c / 4][pixel][c % 4] in, conv5's post-ReLU tensor as
+ *                 [pixel][channel] out (the order the head GEMM reads); groups of four consecutive slots, the last may hold 1 .. 3;
+ *   _u:           the derived F(4x4, 3x3) weights of layer 5 (36 x 128 x 128 floats), in the order the kernel reads them. */
+int affnet_probe_hardnet_c5_trunk_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+int affnet_probe_hardnet_c5_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
+int affnet_probe_hardnet_c5_layer(affnet_ctx* ctx, const float* d_packed, float* d_slots, int n, void* stream);
+int affnet_probe_hardnet_c5_u(affnet_ctx* ctx, const float* d_packed, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,8 @@ if hasattr(lib, "affnet_probe_hardnet_poly_forward"):
     nets.append((HardNetForm1(), "HardNet form 1", 8))
     if hasattr(lib, "affnet_probe_hardnet_f43_forward"):
         nets.append((HardNetForm1("affnet_probe_hardnet_f43_forward"), "HardNet form 2", 8))
+    if hasattr(lib, "affnet_probe_hardnet_c5_forward"):
+        nets.append((HardNetForm1("affnet_probe_hardnet_c5_forward"), "HardNet form 3", 8))
 else:
     print("(no table of HardNet's polyphase trunk: this library has no affnet_probe_hardnet_poly_forward - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 if hasattr(lib, "affnet_probe_affnet_wino_partials"):
@@ -69,6 +71,7 @@ if hasattr(lib, "affnet_probe_affnet_wino_partials"):
         nets.insert(2, (AffNetForm1("affnet_probe_affnet_poly_partials"), "AffNet form 2", 8))
 else:
     print("(no table of AffNet's Winograd trunk: this library has no affnet_probe_affnet_wino_partials - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
+wg_ticks = {}                                          # per table: mean ticks of a workgroup from its first stamp 0 to its last stamp 13 (start to end of the trunk kernel)
 for net, nm, nw in nets:
     if only and nm not in only.split(","):
         continue
@@ -78,7 +81,7 @@ for net, nm, nw in nets:
     net(p); torch.cuda.synchronize()
     lib.affnet_cnn32_debug_timing(engine.utility_ctx(dev), None)
     t = st.cpu().numpy().reshape(n, nw, 32).astype(np.float64)
-    nst = 12
+    nst = 10 if nm == "HardNet form 3" else 12      # form 3's trunk ends behind conv4's loop (stamps 0 .. 9, then 13); conv5 is a kernel of its own, tabled below
     d = np.diff(t[:, :, :nst], axis=2)              # cycles per phase per wave
     wg = t[:, :, :nst].max(axis=1) - t[:, :, 0:1].min(axis=1)   # per patch: boundary times relative to WG start
     print("== %s (%d waves): mean phase cycles per wave (s_memtime ticks, 100 MHz const clock?)" % (nm, nw))
@@ -89,7 +92,7 @@ for net, nm, nw in nets:
         print("  %-12s mean %9.0f  max-over-waves %9.0f" % (names[i], d[:, :, i].mean(), d[:, :, i].max(axis=1).mean()))
     print("  total per patch (WG) %.0f ticks" % tot)
     simd = (st.cpu().numpy().reshape(n, nw, 32)[:, :, 14] >> 4) & 3
-    for i in (2, 6, 10):
+    for i in (j for j in (2, 6, 10) if j < nst - 1):
         print("  %-12s per wave:" % names[i], " ".join("%6.0f" % v for v in d[:, :, i].mean(axis=0)))
     # the two waves of a workgroup that share a SIMD: how far apart do they finish a loop?
     first, second = [], []
@@ -104,6 +107,8 @@ for net, nm, nw in nets:
               (np.mean(first), np.mean(second), nw - 1, simd[0].tolist()))
     ti = st.cpu().numpy().reshape(n, nw, 32)
     start, end = ti[:, :, 0].min(axis=1).astype(np.float64), ti[:, :, 13].max(axis=1).astype(np.float64)
+    wg_ticks[nm] = float((end - start).mean())
+    print("  workgroup, first stamp 0 -> last stamp 13: %.0f ticks" % wg_ticks[nm])
     print("  last phase stamp -> kernel end (head / global store): %.0f ticks" % (ti[:, :, 13] - ti[:, :, nst - 1]).mean())
     hw, xcc = ti[:, 0, 14], ti[:, 0, 15] & 0xF
     cu = ((hw >> 8) & 0xF) | (((hw >> 12) & 1) << 4) | (((hw >> 13) & 7) << 5) | (xcc << 8)
@@ -127,9 +132,25 @@ for net, nm, nw in nets:
     sub = t[:, :, [3, 21, 22, 4]]
     ds = np.diff(sub, axis=2).mean(axis=(0, 1))
     print("  conv1 epilogue: barrier1 %.0f | halo+stores %.0f | barrier2 %.0f" % tuple(ds))
-    if nm == "HardNet form 2":        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
+    if nm in ("HardNet form 2", "HardNet form 3"):        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
         ds = np.diff(t[:, :, [6, 23, 7]], axis=2).mean(axis=(0, 1))
         print("  conv3 F(4x4, 3x3): transform + V through LDS + loop + fold along x %.0f | barrier + exchange of the halves %.0f" % tuple(ds))
+    if nm == "HardNet form 3":
+        # hardnet_conv5_f43_kernel, one workgroup per four patches: stamps 24 .. 31 of every wave in the record of the group's first patch
+        # 24 start | 25 quarter 0 in LDS | 26 its transform done | 27 its loop done | 28 quarter 3's transform done | 29 its loop done | 30 output transform done | 31 stored
+        g = t[0::4, :, 24:32]
+        dg = np.diff(g, axis=2)
+        c5 = (g[:, :, 7].max(axis=1) - g[:, :, 0].min(axis=1)).mean()
+        print("  conv5 kernel (%d groups of four patches): mean ticks per wave [max over waves]" % g.shape[0])
+        for i, what in enumerate(("input of quarter 0: load + LDS + barrier", "transform of quarter 0 (+ barrier)", "loop of quarter 0 (288 MFMAs)", "quarters 1, 2 and 3 up to its transform",
+                                  "loop of quarter 3 (288 MFMAs)", "barrier + output transform", "bias, ReLU, store")):
+            print("    %-42s %9.0f [%9.0f]" % (what, dg[:, :, i].mean(), dg[:, :, i].max(axis=1).mean()))
+        print("    loop of quarter 0: %.1f cycles per MFMA" % (dg[:, :, 2].max(axis=1).mean() / 288.0))
+        print("    workgroup, first stamp 24 -> last stamp 31: %.0f ticks = %.0f per patch" % (c5, c5 / 4.0))
+        if "HardNet form 2" in wg_ticks:
+            f3 = wg_ticks[nm] + c5 / 4.0
+            print("  GATE: form 3 trunk %.0f + conv5 kernel per patch %.0f = %.0f ticks against form 2's workgroup %.0f: %.1f %% shorter (needed: 5 %% or more)" %
+                  (wg_ticks[nm], c5 / 4.0, f3, wg_ticks["HardNet form 2"], 100.0 * (1.0 - f3 / wg_ticks["HardNet form 2"])))
     if nm in ("AffNet form 2", "OriNet") and t[:, :, 24].min() > 0:        # polyphase conv4: "conv4 mfma" = stamp 8 -> 9 spans the loop and the pair's exchange
         ds = np.diff(t[:, :, [8, 24, 9]], axis=2).mean(axis=(0, 1))
         print("  conv4 polyphase: loop %.0f | exchange of the K groups' partial y (one barrier) %.0f" % tuple(ds))
@@ -142,5 +163,5 @@ for net, nm, nw in nets:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "AffNet form 2": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "AffNet form 2": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0, "HardNet form 3": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

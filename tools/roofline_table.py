@@ -5,7 +5,7 @@
                                                              that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's;
                                                              so is AffNet's Winograd trunk of shape form 1, <0, 8, false, 1> (WINO_AFFNET), and HardNet's trunk of descriptor form 1,
                                                              <2, 8, false, 1>, whose conv2 / conv4 run as polyphase Winograd F(2x2, 2x2) besides (POLY_HARDNET), and of descriptor form 2, <2, 8, false, 4>,
-                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET); AffNet's trunk of shape form 2, <0, 8, false, 5>, whose
+                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET), and of descriptor form 3, <2, 8, false, 6> + hardnet_conv5_f43_kernel (F43C5_*); AffNet's trunk of shape form 2, <0, 8, false, 5>, whose
                                                              conv2 / conv4 run as polyphase Winograd besides (POLY_AFFNET), and - in evidence of a build that has that kernel - the
                                                              exact OriNet trunk, which runs the same five forms (POLY_ORINET)
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
@@ -32,6 +32,11 @@ POLY_HARDNET = WINO_HARDNET - NKP * 2 * 9437184.0 * (1.0 - 25.0 / 36.0)
 # Descriptor form 2, <2, 8, false, 4>: conv3 as Winograd F(4x4, 3x3) executes 36 products per 16 outputs = 9 / 36 of the direct form's instead of F(2x2, 3x3)'s 16 / 36:
 # 35.2 instead of 38.9 M executed MFMA FLOPs per patch
 F43_HARDNET = POLY_HARDNET - NKP * 18874368.0 * (16.0 / 36.0 - 9.0 / 36.0)
+# Descriptor form 3: the trunk <2, 8, false, 6> is form 2's without conv5 (F43C5_TRUNK_HARDNET) and hardnet_conv5_f43_kernel runs conv5 as Winograd F(4x4, 3x3), 9 / 36 of
+# the direct form's 18874368 FLOPs per patch (F43C5_CONV5): 26.8 + 4.7 instead of 35.2 M executed MFMA FLOPs per patch
+F43C5_TRUNK_HARDNET = F43_HARDNET - NKP * 18874368.0 * (16.0 / 36.0)
+F43C5_CONV5 = NKP * 18874368.0 * (9.0 / 36.0)
+FLOP["hardnet_conv5_f43_kernel"] = F43C5_CONV5
 # AffNet's Winograd trunk (shape form 1): conv1 / conv3 / conv5 are 4718592 direct FLOPs per patch each and execute 16 / 36 of them.  conv1 .. conv5 together:
 # 11.0 M executed MFMA FLOPs per patch (13.6 M while conv5 was direct: 288 instead of 128 MFMAs per wave), against OriNet's 11.0 M; conv0 and the head as in the direct form
 WINO_AFFNET = 19193856.0 - 3 * 4718592.0 * (1.0 - 16.0 / 36.0)
@@ -105,7 +110,7 @@ def main(prefix, winograd=False):
                                                           100 * prod * tf / 2516.8))
             elif key in name:
                 if winograd and key == "cnn32_trunk_kernel<2":
-                    fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else WINO_HARDNET)
+                    fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else (F43C5_TRUNK_HARDNET if name.rstrip().endswith(", 6>") else WINO_HARDNET))
                 poly16_build = any("cnn32_trunk_kernel<0, 8, false, 5>" in k for k in stats)
                 wino_aff = winograd and ((key == "cnn32_trunk_kernel<0" and (name.rstrip().endswith(", 1>") or name.rstrip().endswith(", 5>"))) or
                                          (key == "cnn32_trunk_kernel<1" and poly16_build))

@@ -10,9 +10,9 @@ The contraction over input channels is one matmul per transform position (the ke
 summation order changes the last bits, not the size of the error).  BatchNorm is folded into the conv weights and a bias, as the packed
 weights of the kernel are.
 
-HardNet's descriptor forms 1 and 2 have their mirrors further down: polyphase F(2x2, 2x2) for conv2 / conv4 (poly_*), F(4x4, 3x3) for conv3 (f43_*).
+HardNet's descriptor forms 1 and 2 have their mirrors further down: polyphase F(2x2, 2x2) for conv2 / conv4 (poly_*), F(4x4, 3x3) for conv3 and - form 3 - conv5 (f43_*).
 
-    python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32, Winograd fp32, form 1 and form 2
+    python tools/winograd_numerics.py [--n 2000]   -> max / mean |descriptor - float64 forward| of direct fp32, Winograd fp32, form 1, form 2 and form 3
     python tools/winograd_numerics.py --net affnet|orinet [--layers 1,3,5]
         -> per trunk layer and at the pooled head output: max |x - float64 forward| of direct fp32 and Winograd fp32 (shipped checkpoints,
            tests/golden/cnn_random_patches.npz and --n smooth seeded patches); OriNet also the error of the angle
@@ -257,6 +257,20 @@ def f43_packed_weight_transform(sd, layers=(1, 3)):
 
 
 F43_LAYERS = (3,)                # the layers HardNet's descriptor form 2 runs as F(4x4, 3x3)
+F43_LAYERS_FORM3 = (3, 5)        # ... and descriptor form 3: conv5 as well, in a kernel of its own (affnet_amd/csrc/hardnet_conv5_f43.hip)
+
+
+def f43_conv5_grouped(x, w):
+    """conv5 of descriptor form 3 (hardnet_conv5_f43_kernel): 128 -> 128 at 8 x 8, the four 4x4 tiles of a patch, four patches per workgroup.  A patch's result does not
+    depend on its group: every accumulator (tile, cout, position) sums its own 128 products, lane-local transforms on both sides (cnn_mfma.h: f43c5_transform = f43_bt_lo /
+    f43_bt_hi along y, then x; f43c5_output = f43_at_axis along x, then y), so the mirror is f43_conv3x3 at this shape - with its one contraction per position, as everywhere here"""
+    assert tuple(x.shape[1:]) == (128, 8, 8) and tuple(w.shape) == (128, 128, 3, 3)
+    return f43_conv3x3(x, w)
+
+
+def f43_conv5_packed_weight_transform(sd):
+    """U of conv5 as derive_u_kernel leaves it for descriptor form 3 (weights_layout.h: derived_hardnet_form3, F43C5): flat float32 [xi (36)][8][(c / 4) % 4][128][c % 4]"""
+    return f43_packed_weight_transform(sd, layers=(5,))[5]
 
 
 def folded(sd, dtype):
@@ -296,13 +310,13 @@ def packed_weight_transform(sd):
 
 def hardnet_forward(sd, patches, wino=True, dtype=torch.float32, poly=False, f43=()):
     """HardNet descriptors in `dtype`; conv1 / conv3 / conv5 as Winograd when `wino`, conv2 / conv4 as polyphase F(2x2, 2x2) when `poly`, the layers in `f43`
-    (of 1, 3; descriptor form 2: F43_LAYERS) as F(4x4, 3x3) instead of F(2x2, 3x3)"""
+    (of 1, 3, 5; descriptor form 2: F43_LAYERS, form 3: F43_LAYERS_FORM3) as F(4x4, 3x3) instead of F(2x2, 3x3)"""
     x = orc.input_norm(patches.to(dtype))
     for li, (w, b, st) in enumerate(folded(sd, dtype)):
         if poly and li in POLY_LAYERS:
             y = poly_conv3x3_s2(x, w)
         elif li in f43:
-            y = f43_conv3x3(x, w)
+            y = f43_conv5_grouped(x, w) if li == 5 else f43_conv3x3(x, w)
         else:
             y = wino_conv3x3(x, w) if (wino and li in WINO_LAYERS) else F.conv2d(x, w, None, stride=st, padding=1)
         x = F.relu(y + b.view(1, -1, 1, 1))
@@ -363,11 +377,11 @@ def load_net16(net):
 
 
 def errors(sd, patches):
-    """(max, mean) |descriptor - float64 forward| of direct fp32, of Winograd fp32, of Winograd + polyphase fp32 (form 1) and of form 2 (conv3 as F(4x4, 3x3))"""
+    """(max, mean) |descriptor - float64 forward| of direct fp32, of Winograd fp32, of Winograd + polyphase fp32 (form 1), of form 2 (conv3 as F(4x4, 3x3)) and of form 3 (conv5 as well)"""
     with torch.no_grad():
         ref = orc.hardnet_forward({k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}, patches.double())
         out = {}
-        for name, wino, poly, f43 in (("direct", False, False, ()), ("winograd", True, False, ()), ("polyphase", True, True, ()), ("f43", True, True, F43_LAYERS)):
+        for name, wino, poly, f43 in (("direct", False, False, ()), ("winograd", True, False, ()), ("polyphase", True, True, ()), ("f43", True, True, F43_LAYERS), ("f43_conv5", True, True, F43_LAYERS_FORM3)):
             d = (hardnet_forward(sd, patches, wino=wino, poly=poly, f43=f43).double() - ref).abs()
             out[name] = (float(d.max()), float(d.mean()))
     return out
