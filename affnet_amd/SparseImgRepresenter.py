@@ -67,7 +67,8 @@ class ScaleSpaceAffinePatchExtractor(nn.Module):
                                    # equals the staged path and getAffineShape / getOrientation bit for bit, which forms 1 / 2 do not (A of an unflagged
                                    # candidate carries the Winograd rounding, <= 4e-6)
 
-        self.desc_form = 3         # fused path, arith "fp32": 3 = form 2 with conv5 as Winograd F(4x4, 3x3) in a kernel of its own behind the trunk, four patches per
+        self.desc_form = 4         # fused path, arith "fp32": 4 = form 3 with conv0 + conv1 streamed over conv1's input channels and conv1 as Winograd F(4x4, 3x3);
+                                   # 3 = form 2 with conv5 as Winograd F(4x4, 3x3) in a kernel of its own behind the trunk, four patches per
                                    # workgroup; 2 = HardNet trunk with conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2) and conv3 as Winograd
                                    # F(4x4, 3x3), 1 = conv3 as F(2x2, 3x3) as conv1 / conv5 are, 0 = conv2 / conv4 in the direct form besides
                                    # (affnet_set_desc_form; read at every call, a captured graph keeps its form).  Descriptors differ by rounding only

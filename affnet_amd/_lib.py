@@ -33,7 +33,7 @@ def arith_code(arith):
         raise ValueError("arith must be AFFNET_ARITH_FP32_MFMA (0), AFFNET_ARITH_FP32_SPLIT3 (1) or AFFNET_ARITH_FP32_SPLIT2H (2)")
     return int(arith)
 SHAPE_FORM_DIRECT, SHAPE_FORM_WINOGRAD, SHAPE_FORM_POLYPHASE = 0, 1, 2                         # include/affnet_hip.h AFFNET_SHAPE_FORM_*
-DESC_FORM_DIRECT, DESC_FORM_POLYPHASE, DESC_FORM_F43, DESC_FORM_F43_CONV5 = 0, 1, 2, 3      # include/affnet_hip.h AFFNET_DESC_FORM_*
+DESC_FORM_DIRECT, DESC_FORM_POLYPHASE, DESC_FORM_F43, DESC_FORM_F43_CONV5, DESC_FORM_F43_CONV1 = 0, 1, 2, 3, 4      # include/affnet_hip.h AFFNET_DESC_FORM_*
 OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_EMPTY = 0, -1, -2, -3, -4
 VERIFY_AFFINE, VERIFY_HOMOGRAPHY, VERIFY_TILE, VERIFY_CHUNK = 0, 1, 128, 128                     # include/affnet_hip.h AFFNET_VERIFY_*
 KNN_MAX_K = 8                                                                                    # AFFNET_KNN_MAX_K: neighbours per query row of affnet_knn
@@ -207,6 +207,8 @@ PROBE_SYMBOLS = {
     "affnet_probe_hardnet_c5_forward": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "affnet_probe_hardnet_c5_layer": (_I, [_P, _P, _P, _I, _P]),
     "affnet_probe_hardnet_c5_u": (_I, [_P, _P, _P, _P]),
+    "affnet_probe_hardnet_c1_trunk_layer": (_I, [_P, _P, _P, _I, _P, _P]),
+    "affnet_probe_hardnet_c1_forward": (_I, [_P, _P, _P, _I, _P, _P, _P]),
 }
 
 

@@ -34,10 +34,10 @@ static int cnn_check(affnet_ctx* ctx, const CnnCall& c, int* rows) {
 TrunkKernel aff_trunk_kernel(int kind, int form, bool stamps) {
     typedef TrunkKernel (*Unit)(int, bool);
     static_assert(AFFNET_NET_AFFNET == 0 && AFFNET_NET_ORINET == 1 && AFFNET_NET_HARDNET == 2 && TRUNK_EXACT == 0 && TRUNK_WINO == 1 && TRUNK_SPLIT2 == 2 && TRUNK_SPLIT3 == 3 &&
-                  TRUNK_WINO_F43 == 4 && TRUNK_WINO_POLY == 5 && TRUNK_WINO_F43_C5 == 6 && TRUNK_FORMS == 7, "order of the table");
-    static const Unit unit[3][TRUNK_FORMS] = {{aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, nullptr, aff_trunk_affnet_poly, nullptr},
-                                              {aff_trunk_orinet, nullptr, aff_trunk_orinet, aff_trunk_orinet, nullptr, nullptr, nullptr},
-                                              {aff_trunk_hardnet, aff_trunk_hardnet_poly, aff_trunk_hardnet, aff_trunk_hardnet, aff_trunk_hardnet_f43, nullptr, aff_trunk_hardnet_c5}};
+                  TRUNK_WINO_F43 == 4 && TRUNK_WINO_POLY == 5 && TRUNK_WINO_F43_C5 == 6 && TRUNK_WINO_F43_C1 == 7 && TRUNK_FORMS == 8, "order of the table");
+    static const Unit unit[3][TRUNK_FORMS] = {{aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, aff_trunk_affnet, nullptr, aff_trunk_affnet_poly, nullptr, nullptr},
+                                              {aff_trunk_orinet, nullptr, aff_trunk_orinet, aff_trunk_orinet, nullptr, nullptr, nullptr, nullptr},
+                                              {aff_trunk_hardnet, aff_trunk_hardnet_poly, aff_trunk_hardnet, aff_trunk_hardnet, aff_trunk_hardnet_f43, nullptr, aff_trunk_hardnet_c5, aff_trunk_hardnet_c1}};
     if (kind < 0 || kind > 2 || form < 0 || form >= TRUNK_FORMS || !unit[kind][form]) return nullptr;
     return unit[kind][form](form, stamps);
 }
@@ -48,7 +48,7 @@ int aff_trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3
     if (ctx->arith != AFFNET_ARITH_FP32_MFMA) form = ctx->arith == AFFNET_ARITH_FP32_SPLIT2H ? TRUNK_SPLIT2 : TRUNK_SPLIT3;
     else if (c.kind == AFFNET_NET_AFFNET && wino) form = wino == 2 ? TRUNK_WINO_POLY : TRUNK_WINO;
     else if (c.kind == AFFNET_NET_HARDNET && c.desc_form != AFFNET_DESC_FORM_DIRECT)
-        form = c.desc_form == AFFNET_DESC_FORM_F43_CONV5 ? TRUNK_WINO_F43_C5 : (c.desc_form == AFFNET_DESC_FORM_F43 ? TRUNK_WINO_F43 : TRUNK_WINO);
+        form = c.desc_form == AFFNET_DESC_FORM_F43_CONV1 ? TRUNK_WINO_F43_C1 : (c.desc_form == AFFNET_DESC_FORM_F43_CONV5 ? TRUNK_WINO_F43_C5 : (c.desc_form == AFFNET_DESC_FORM_F43 ? TRUNK_WINO_F43 : TRUNK_WINO));
     const bool stamps = ctx->dbg_time || c.dbg_layer >= 0;             // the stamped instantiation: dbg_time or a layer dump (exact mode only, see cnn_check)
     const TrunkKernel kernel = aff_trunk_kernel(c.kind, form, stamps);
     if (!kernel) return aff_fail(ctx, AFFNET_ERR_INVALID, "cnn32: no trunk kernel of net %d in form %d is built", c.kind, form);
@@ -67,8 +67,8 @@ int aff_trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3
     aff_fill_pyr_src(ctx, &ps);
     hipLaunchKernelGGL(kernel, grid, dim3(512), 0, c.st, a, ps);
     AFF_LAUNCH_CHECK(ctx);
-    if (form == TRUNK_WINO_F43_C5 && c.dbg_layer < 0) {
-        // descriptor form 3 is a pair: the trunk left conv4's tensor in the slots of a.out, hardnet_conv5_f43_kernel rewrites them in place - the same rows under the same predicate
+    if ((form == TRUNK_WINO_F43_C5 || form == TRUNK_WINO_F43_C1) && c.dbg_layer < 0) {
+        // descriptor forms 3 / 4 are a pair: the trunk left conv4's tensor in the slots of a.out, hardnet_conv5_f43_kernel rewrites them in place - the same rows under the same predicate
         Conv5Args v;
         v.io = a.out; v.U = a.wino_u + F43C5::BASE; v.bias = c.packed + L.b_off[5];
         v.count = c.count; v.n_max = c.n_max; v.row_begin = c.row_begin; v.row_end = c.row_begin + (int)grid.x;
@@ -163,7 +163,8 @@ int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const f
 
 int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st, int form) {
     if (ctx->arith != AFFNET_ARITH_FP32_MFMA) return aff_fail(ctx, AFFNET_ERR_INVALID, "hardnet_poly: AFFNET_ARITH_FP32_MFMA only");
-    if (form == AFFNET_DESC_FORM_F43_CONV5 && dbg_layer > 4) return aff_fail(ctx, AFFNET_ERR_INVALID, "hardnet_poly: the trunk of form 3 ends behind layer 4 (conv5: affnet_probe_hardnet_c5_layer)");
+    if ((form == AFFNET_DESC_FORM_F43_CONV5 || form == AFFNET_DESC_FORM_F43_CONV1) && dbg_layer > 4) return aff_fail(ctx, AFFNET_ERR_INVALID, "hardnet_poly: the trunk of forms 3 / 4 ends behind layer 4 (conv5: affnet_probe_hardnet_c5_layer)");
+    if (form == AFFNET_DESC_FORM_F43_CONV1 && dbg_layer == 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "hardnet_poly: form 4 streams conv0 into conv1, 16 channels at a time: the tensor of layer 0 never exists");
     CnnCall c;
     c.kind = AFFNET_NET_HARDNET; c.packed = packed; c.patches = patches; c.n_max = n; c.out = out; c.scratch = scratch; c.st = st;
     c.dbg_layer = dbg_layer; c.dbg_out = dbg_layer >= 0 ? out : nullptr;

@@ -1511,14 +1511,15 @@ struct F43C5L {                                           // float offsets in th
 };
 static_assert(F43C5L::V % 4 == 0 && F43C5L::PS % 4 == 0 && F43C5L::TOTAL * 4 <= 160 * 1024, "16-byte aligned sections within the CU's LDS");
 
-// One channel of one 6x6 window at `in` (floats, row pitch WPI * 4, column pitch 4) -> its 36 positions, position xi at v[xi * 256]: B^T d B along y, then along x
-__device__ __forceinline__ void f43c5_transform(const float* in, float* v) {
+// One channel of one 6x6 window at `in` (floats, row pitch WPI * 4, column pitch 4) -> its 36 positions, position xi at v[xi * XS]: B^T d B along y, then along x
+template <int WPI, int XS>
+__device__ __forceinline__ void f43_transform_channel(const float* in, float* v) {
     float t[6][6];                                        // t[i][c]
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         float d[6];
 #pragma unroll
-        for (int r = 0; r < 6; ++r) d[r] = in[(r * F43C5L::WPI + c) * 4];
+        for (int r = 0; r < 6; ++r) d[r] = in[(r * WPI + c) * 4];
         f43_bt_lo(d[0], d[1], d[2], d[3], d[4], t[0][c], t[1][c], t[2][c]);
         f43_bt_hi(d[1], d[2], d[3], d[4], d[5], t[3][c], t[4][c], t[5][c]);
     }
@@ -1528,9 +1529,10 @@ __device__ __forceinline__ void f43c5_transform(const float* in, float* v) {
         f43_bt_lo(t[i][0], t[i][1], t[i][2], t[i][3], t[i][4], o[0], o[1], o[2]);
         f43_bt_hi(t[i][1], t[i][2], t[i][3], t[i][4], t[i][5], o[3], o[4], o[5]);
 #pragma unroll
-        for (int j = 0; j < 6; ++j) v[(6 * i + j) * 256] = o[j];
+        for (int j = 0; j < 6; ++j) v[(6 * i + j) * XS] = o[j];
     }
 }
+__device__ __forceinline__ void f43c5_transform(const float* in, float* v) { f43_transform_channel<F43C5L::WPI, 256>(in, v); }
 
 // Y = A^T M A of the lane's 4 output channels (x first, then y: f43_at_axis both ways, the sums f43_combine forms over a wave pair): y[4 dy + c]
 __device__ __forceinline__ void f43c5_output(const f32x4 (&acc)[F43_XI], f32x4 (&y)[16]) {
@@ -1547,6 +1549,90 @@ __device__ __forceinline__ void f43c5_output(const f32x4 (&acc)[F43_XI], f32x4 (
             for (int dy = 0; dy < 4; ++dy) y[4 * dy + c][e] = yr[dy];
         }
     }
+}
+
+// ---- conv0 + conv1 of HardNet's descriptor form 4: conv1 as F(4x4, 3x3), the layer pair streamed over conv1's K (cnn_trunk.h: the STREAM1 block) ----------------
+// conv1 (32 -> 32 at 32 x 32) has 64 4x4 tiles = four blocks of 16 (tile t = 8 ty + tx, block t >> 4 = two tile rows, m = t & 15) and two channel blocks; wave w owns
+// (tile block w >> 1, channel block w & 1), all 36 positions and all of K: 36 accumulators live over the whole layer, no exchange between waves.  V of the layer would be
+// 295 KB, and conv0's output fills the activation buffer - but conv0 reads only the resident patch, so it runs ONE channel block (= one K group of conv1) at a time into a
+// half-size layout, and a K group runs in two quarters of 8 channels: k-steps 2 jh and 2 jh + 1 = channels 16 G + 4 kq + 2 jh + {0, 1}, the .xy / .zw of U's float4.
+// Per quarter thread (tile, kq, j) transforms ONE channel of one window (f43_transform_channel) into V [xi][tile block][slot(kq, m)][2]; then every wave runs 36 positions x
+// 2 k-steps with no VALU in the loop: U as 8-byte buffer loads, V as one ds_read_b64 per position (512 bytes contiguous per wave).
+// Banks (32 for ds_read_b32 and every ds_write, per 32-lane half; tests/test_winograd_f43_conv1_numerics.py runs the model): a half of the transform = (j, kq, tx & 3).  Its
+// window reads hit j + 4 kq + 16 (tx & 1): 16 banks, 2-way - a quarter reads half of every 16-byte cell, so no group stride does better; GS = 4 (mod 32) reaches the 16.  Its
+// V stores would meet 4-way in [kq][m][2] (kq is 64 floats apart), so the 16 m of a kq are rotated by 4 kq: slot = 16 kq + ((m + 4 kq) & 15), conflict-free for the
+// stores and, a rotation within 128 bytes, for the loop's ds_read_b64 as well.
+struct F43C1L {                                           // float offsets from the start of the activation buffer
+    static constexpr int GS = 4676;                       // group stride of conv0's half output [kq][padded pixel 34 x 34][4]
+    static constexpr int C0_FLOATS = 4 * GS;
+    static constexpr int XS = 4 * 64 * 2;                 // a position of V: four tile blocks x 64 slots x 2 channels
+    static constexpr int V = C0_FLOATS, V_FLOATS = F43_XI * XS;
+    static constexpr int TOTAL = V + V_FLOATS;            // 148 544 bytes
+    __device__ static __forceinline__ int slot(int kq, int m) { return 16 * kq + ((m + 4 * kq) & 15); }
+};
+typedef Lay<32, 34, F43C1L::GS> LayS1;                    // conv0's half output -> the quarter transforms
+static_assert(F43C1L::TOTAL <= 8 * LayC0::PSG && 8 * LayC1::PSG <= 8 * LayC0::PSG && F43C1L::V % 4 == 0 && F43C1L::GS % 32 == 4, "the pair fits the activation buffer, 16-byte aligned");
+
+// conv0 of ONE channel tile (16 channels) into LayS1: conv0_mfma's chain for every value (accumulator = bias, then the taps in three MFMAs) and store_tiles_lds's ReLU and
+// address, but each of the wave's eight pixel tiles is stored as soon as it is complete - the 144 accumulators of conv1 are live beside it, 4 registers here instead of 32.
+// b = the lane's taps of the channel tile (conv0_load_w's b[.][tile]), bv = its bias
+__device__ __forceinline__ void f43c1_conv0_tile(const float* patch, const float (&b)[3], f32x4 bv, float* act, int wave, int lane) {
+    const int m = lane & 15, kq = lane >> 4;
+    int toff[3];
+#pragma unroll
+    for (int s3 = 0; s3 < 3; ++s3) {
+        const int t = 4 * s3 + kq;
+        toff[s3] = t < 9 ? (t / 3) * WP32 + (t % 3) : 0;              // taps 9..11: any valid address (weight is zero)
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int p = (wave * 8 + i) * 16 + m, oy = p >> 5, ox = p & 31;
+        f32x4 acc = bv;
+#pragma unroll
+        for (int s3 = 0; s3 < 3; ++s3) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(b[s3], patch[oy * WP32 + ox + toff[s3]], acc, 0, 0, 0);
+        *reinterpret_cast<f32x4*>(&act[kq * LayS1::PSG + ((oy + 1) * LayS1::WP + ox + 1) * 4]) = relu4(acc);
+    }
+}
+
+typedef __attribute__((address_space(3))) const f32x2 LdsF2;
+__device__ __forceinline__ f32x2 lds_read2(unsigned byte_addr) { return *(LdsF2*)(size_t)byte_addr; }
+// U of position k, the two k-steps of a quarter: `q_off` = the quarter's byte offset inside a position's block, G * 16 * COUT * 4 + 8 jh
+template <int CIN, int COUT>
+__device__ __forceinline__ f32x2 f43c1_load_u(__amdgpu_buffer_rsrc_t r, int u_lane, int k, int q_off) {
+    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, u_lane, k * (CIN / 16) * 16 * COUT * 4 + q_off, 0));
+}
+// One quarter's loop: 36 positions x 2 k-steps.  U enters holding positions 0 .. DU - 1 of this quarter and leaves holding those of the next (q_next; the last quarter
+// re-requests itself: unused); V (v0: positions 0 .. 17, v1: 18 .. 35 - a position is 2 KB, the DS offset field ends at 64 KB) rolls DV positions ahead within the quarter.
+template <int CIN, int COUT, int DU, int DV>
+__device__ __forceinline__ void f43c1_quarter_loop(__amdgpu_buffer_rsrc_t wrsrc, int u_lane, int q_off, int q_next, unsigned v0, unsigned v1, f32x2 (&Ur)[DU], f32x4 (&acc)[F43_XI]) {
+    static_assert(F43_XI % DU == 0 && F43_XI % DV == 0 && DU % 2 == 0 && DV % 2 == 0 && DV <= 18, "the sets roll with compile-time indices");
+    f32x2 Vr[DV];
+#pragma unroll
+    for (int k = 0; k < DV; ++k) Vr[k] = lds_read2(v0 + k * (F43C1L::XS * 4));
+    __builtin_amdgcn_sched_barrier(0);                    // pinned: two positions' chains interleave, their U and V reloads follow
+#pragma unroll
+    for (int k = 0; k < F43_XI; k += 2) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ur[k % DU][s], Vr[k % DV][s], acc[k], 0, 0, 0);
+            acc[k + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ur[(k + 1) % DU][s], Vr[(k + 1) % DV][s], acc[k + 1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int kk = k; kk < k + 2; ++kk) {
+            const int ku = kk + DU, kv = kk + DV;
+            Ur[kk % DU] = ku < F43_XI ? f43c1_load_u<CIN, COUT>(wrsrc, u_lane, ku, q_off) : f43c1_load_u<CIN, COUT>(wrsrc, u_lane, ku - F43_XI, q_next);
+            if (kv < F43_XI) Vr[kk % DV] = kv < 18 ? lds_read2(v0 + kv * (F43C1L::XS * 4)) : lds_read2(v1 + (kv - 18) * (F43C1L::XS * 4));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// + bias, ReLU, store the lane's 4 x 4 pixels x 4 channels (f43c5_output's y) into the LDS layout LO (H = 32)
+template <typename LO>
+__device__ __forceinline__ void f43c1_store_lds(float* act, f32x4 bias, const f32x4 (&y)[16], int wave, int lane) {
+    const int t = (wave >> 1) * 16 + (lane & 15), oy = 4 * (t >> 3), ox = 4 * (t & 7);
+    float* dst = act + ((wave & 1) * 4 + (lane >> 4)) * LO::PSG + ((oy + 1) * LO::WP + ox + 1) * 4;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) *reinterpret_cast<f32x4*>(dst + ((k >> 2) * LO::WP + (k & 3)) * 4) = bias_relu(y[k], bias);
 }
 
 // The same layer for the 16-channel trunks (AffNet / OriNet conv1, conv3), which live on 128 registers per lane (two workgroups per CU): acc[16] + U[16] +

@@ -1,6 +1,6 @@
 // Trunk kernel of the 32x32-patch CNNs (AffNetFast / OriNetFast / HardNet) for gfx950 on the fp32 matrix cores: cnn32_trunk_kernel and its
-// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip / cnn_trunk_hardnet_f43.hip / cnn_trunk_hardnet_c5.hip: HardNet forms 1 / 2 / 3), which instantiate one net's six kernels each
-// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1 / 2 / 3),
+// device helpers.  Included by cnn_trunk_affnet.hip / cnn_trunk_orinet.hip / cnn_trunk_hardnet.hip (and cnn_trunk_hardnet_poly.hip / cnn_trunk_hardnet_f43.hip / cnn_trunk_hardnet_c5.hip / cnn_trunk_hardnet_c1.hip: HardNet forms 1 / 2 / 3 / 4), which instantiate one net's six kernels each
+// (three arithmetic modes x product / stamped), and by cnn_probe.hip for the LDS footprint.  The kernel holds four bodies: exact HardNet (descriptor forms 0 / 1 / 2 / 3 / 4),
 // exact AffNet / OriNet, split HardNet, split AffNet / OriNet.
 //
 // Replaces architectures.py:204-252 (AffNetFast), :33-82 (OriNetFast), HardNet.py:61-101
@@ -235,14 +235,16 @@ struct TrunkShape {
 template <int KIND, int S3>
 struct TrunkTraits {
     static_assert(S3 == TRUNK_EXACT || S3 == TRUNK_SPLIT2 || S3 == TRUNK_SPLIT3 || (S3 == TRUNK_WINO && KIND != AFFNET_NET_ORINET) ||
-                  ((S3 == TRUNK_WINO_F43 || S3 == TRUNK_WINO_F43_C5) && KIND == AFFNET_NET_HARDNET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET), "no such trunk form of this net (common.h: TRUNK_*)");
+                  ((S3 == TRUNK_WINO_F43 || S3 == TRUNK_WINO_F43_C5 || S3 == TRUNK_WINO_F43_C1) && KIND == AFFNET_NET_HARDNET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET), "no such trunk form of this net (common.h: TRUNK_*)");
     static constexpr bool EXACT = S3 != TRUNK_SPLIT2 && S3 != TRUNK_SPLIT3;     // fp32 operands on v_mfma_f32_16x16x4_f32
     // 16-channel trunks: conv1 / conv3 / conv5 as Winograd F(2x2, 3x3) on 128 registers (conv5: a wave pair per channel block); conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2)
     static constexpr bool WINO13 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || ((S3 == TRUNK_WINO || S3 == TRUNK_WINO_POLY) && KIND == AFFNET_NET_AFFNET);
     static constexpr bool POLY16 = (S3 == TRUNK_EXACT && KIND == AFFNET_NET_ORINET) || (S3 == TRUNK_WINO_POLY && KIND == AFFNET_NET_AFFNET);
-    // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2); form 2: conv3 as Winograd F(4x4, 3x3), V shared through LDS (conv1 in F(4x4, 3x3) has no loop yet: NOTES.md)
+    // HardNet descriptor forms 1 / 2: conv2 / conv4 (stride 2) as polyphase Winograd F(2x2, 2x2); form 2: conv3 as Winograd F(4x4, 3x3), V shared through LDS (conv1 in F(4x4, 3x3): form 4 below)
     // form 3 (CUT5): form 2 up to conv4's loop; conv4's tensor goes to HBM and hardnet_conv5_f43_kernel (hardnet_conv5_f43.hip) runs conv5 for four patches per workgroup
-    static constexpr bool CUT5 = S3 == TRUNK_WINO_F43_C5 && KIND == AFFNET_NET_HARDNET;
+    // form 4 (STREAM1): form 3 with conv0 + conv1 streamed over conv1's K, conv1 as Winograd F(4x4, 3x3) (cnn_mfma.h: F43C1L); implies CUT5, F43_3 and POLY
+    static constexpr bool STREAM1 = S3 == TRUNK_WINO_F43_C1 && KIND == AFFNET_NET_HARDNET;
+    static constexpr bool CUT5 = (S3 == TRUNK_WINO_F43_C5 || STREAM1) && KIND == AFFNET_NET_HARDNET;
     static constexpr bool POLY = (S3 == TRUNK_WINO || S3 == TRUNK_WINO_F43 || CUT5) && KIND == AFFNET_NET_HARDNET, F43_3 = (S3 == TRUNK_WINO_F43 || CUT5) && KIND == AFFNET_NET_HARDNET;
 };
 
@@ -274,7 +276,7 @@ struct SplitLays {
 
 // One workgroup = one patch through one trunk.  KIND: 0 AffNet, 1 OriNet, 2 HardNet (CB = 16 / 16 / 32); NW = 8 wavefronts; S3 = the trunk form (TRUNK_*, common.h;
 // TrunkTraits above says what each does - for the split-operand forms the value is the number of terms).  After the prologue that all flows share (counters, lazy skip, priority, conv0 weights, input phase) the
-// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2 / 3: Winograd, with polyphase conv2 / conv4 in forms 1 / 2 / 3, conv3 in F(4x4, 3x3) in forms 2 / 3, and the body cut behind conv4 in form 3), exact AffNet / OriNet, split HardNet,
+// kernel is one straight-line body per flow, four in all: exact HardNet (forms 0 / 1 / 2 / 3 / 4: Winograd, with polyphase conv2 / conv4 in forms 1 .. 4, conv3 in F(4x4, 3x3) in forms 2 .. 4, the body cut behind conv4 in forms 3 / 4, and conv0 + conv1 streamed with conv1 in F(4x4, 3x3) in form 4), exact AffNet / OriNet, split HardNet,
 // split AffNet / OriNet; what a form or net of a flow does differently is an `if constexpr` inside that body (functions per flow or phase move registers: profiles/trunk_bodies_report.md).  Every
 // layer: MFMA loop -> request the next layer's first weight chunk and bias -> barrier (all waves done reading the input) -> zero the halo of
 // the OUTPUT layout, bias + ReLU + store in place -> barrier.  No HBM traffic between layers.
@@ -285,7 +287,7 @@ struct SplitLays {
 template <int KIND, int NW, bool STAMPS, int S3 = 0>
 __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4) void cnn32_trunk_kernel(CnnArgs a, PyrSrc ps) {
     using F = TrunkTraits<KIND, S3>;
-    constexpr bool EXACT = F::EXACT, WINO13 = F::WINO13, POLY16 = F::POLY16, POLY = F::POLY, F43_3 = F::F43_3, CUT5 = F::CUT5;
+    constexpr bool EXACT = F::EXACT, WINO13 = F::WINO13, POLY16 = F::POLY16, POLY = F::POLY, F43_3 = F::F43_3, CUT5 = F::CUT5, STREAM1 = F::STREAM1;
     using S = TrunkShape<KIND, NW>;
     constexpr int CB = S::CB, NTHR = S::NTHR;
     static_assert((CB / 4) * LayC1::PSG <= TrunkLds<CB>::ACT && (CB / 2) * LayC3::PSG <= TrunkLds<CB>::ACT, "LDS layout");
@@ -354,7 +356,8 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         const int y = e < 34 ? 0 : (e < 68 ? 33 : 1 + ((e - 68) >> 1)), x = e < 34 ? e : (e < 68 ? e - 34 : ((e - 68) & 1) * 33);
         patch[y * WP32 + x] = 0.0f;
     }
-    if constexpr (EXACT) zero_halo<LayC0, NTHR>(act, CB);                          // the halo of the flow's conv0 output layout
+    if constexpr (STREAM1) zero_halo<LayS1, NTHR>(act, 16);                        // the halo of the flow's conv0 output layout (form 4: of one channel block, written once for both)
+    else if constexpr (EXACT) zero_halo<LayC0, NTHR>(act, CB);
     else if constexpr (S3 == TRUNK_SPLIT2) zero_halo_q<typename SplitLays<CB>::LR0, NTHR>(act);
     else zero_halo_q<typename SplitLays<CB>::LQH, NTHR>(act);
     float sum = 0.f;
@@ -385,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         // channel block.  Their transformed weights come from a.wino_u (Poly32), which derive_u_kernel fills from the blob's taps in front of the launch; the first
         // fragments are requested in front of the barrier before the layer.  conv0, conv1, conv3, conv5 and every epilogue are the same statements for both forms.
         // Form 2 (F43_3) = form 1 with conv3 as Winograd F(4x4, 3x3) (cnn_mfma.h: conv3x3_f43_mfma_shared_v, f43_combine) - 288 instead of 512 MFMAs per wave; its
-        // weights lie behind the polyphase ones at a.wino_u + F43::BASE.  conv1 has no F(4x4, 3x3) loop yet (NOTES.md); its U is derived all the same.
+        // weights lie behind the polyphase ones at a.wino_u + F43::BASE.  conv1 runs as F(4x4, 3x3) in form 4 only (the STREAM1 block below); its U is derived in every form from 2 on.
         constexpr int T1M = S::T1M, T1N = S::T1N, T2M = S::T2M, T2N = S::T2N, T4M = S::T4M, T4N = S::T4N;
         constexpr int NB1 = (16 * 16 / 16) * (CB / 16) / NW, NB3 = (8 * 8 / 16) * (2 * CB / 16) / NW, NB5 = (4 * 4 / 16) * (4 * CB / 16) / NW;
         constexpr int NBP2 = (8 * 8 / 16) * (2 * CB / 16) / NW, NBP4 = (4 * 4 / 16) * (4 * CB / 16) / NW;      // polyphase passes per wave: conv2 a pair, conv4 one
@@ -394,7 +397,71 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
         f32x4 Up[2][4];                                               // the rolling U register set of conv1 / conv3: one position row, both channel blocks of a pair
         f32x4 Uw[16];                                                 // the rolling U register set of conv5
         f32x4 Uf[18];                                                 // form 2: the rolling U register set of conv3
-        {
+        f32x4 b2[S::G2][T2N];                                         // form 0: conv2's first weight chunk and bias
+        f32x4 bias2[T2N];
+        f32x4 P2a[2][3], P2b[2][3];                                   // form 1: the two rolling U register sets of conv2
+        if constexpr (STREAM1) {
+            // ---- form 4: conv0 + conv1 streamed over conv1's K (cnn_mfma.h: F43C1L) ---------------------------------------------
+            // Per K group G of conv1: conv0 of channel block G (f43c1_conv0_tile: conv0_mfma's chain, so every conv0 value keeps the bits it has in the other forms) into the half-size
+            // layout LayS1; per quarter jh of the group: every thread transforms one channel of one window into V beside it, barrier, the wave's 36 positions x 2 k-steps.
+            // Wave w = (tile block w >> 1, channel block w & 1); every accumulator receives its MFMAs in the order G ascending, k-step ascending.  Stamps (the slots of the
+            // phases this form does not have): 19 conv0 of G = 0 and its barrier, 20 the first quarter's transform and barrier, 2 its loop, 3 the last quarter's loop,
+            // 21 output transform and barrier, 22 halo and stores, 4 barrier.
+            static_assert(NW == 8 && CB == 32 && T1M == 8 && F43C1L::TOTAL <= TrunkLds<CB>::ACT, "four tile blocks x two channel blocks; conv0's half and a quarter's V fit the activation buffer");
+            constexpr int DU = 6, DV = 12;                            // rolling register sets: U (L2) 6 positions = 12 MFMAs ahead - it stays live across conv0 and the transforms, and 12 spills -, V (LDS) 12 positions
+            const __amdgpu_buffer_rsrc_t wrsrc = weight_rsrc(a.wino_u + F43::BASE + F43::offset(1), F43_XI * CB * CB);
+            const int u_lane = ((lane >> 4) * CB + (wave & 1) * 16 + (lane & 15)) * 16;
+            f32x2 Ur[DU];
+#pragma unroll
+            for (int k = 0; k < DU; ++k) Ur[k] = f43c1_load_u<CB, CB>(wrsrc, u_lane, k, 0);
+            // the transform's thread: channel 4 kq + 2 jh + j of the K group, window (ty, tx) = (wave, lane >> 3); a 32-lane half = (j, kq, tx & 3)
+            const int tj = lane & 1, tkq = (lane >> 1) & 3, ttx = lane >> 3;
+            const float* t_in = act + tkq * F43C1L::GS + (4 * wave * LayS1::WP + 4 * ttx) * 4 + tj;
+            float* t_v = act + F43C1L::V + (wave >> 1) * 128 + F43C1L::slot(tkq, (wave & 1) * 8 + ttx) * 2 + tj;
+            unsigned v0 = lds_byte_addr(act + F43C1L::V + (wave >> 1) * 128 + F43C1L::slot(lane >> 4, lane & 15) * 2), v1 = v0 + 18 * F43C1L::XS * 4;
+            asm("" : "+v"(v0));
+            asm("" : "+v"(v1));
+            f32x4 acc[F43_XI];
+#pragma unroll
+            for (int k = 0; k < F43_XI; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+            for (int G = 0; G < 2; ++G) {
+                // every wave is past the previous K group's last transform (which read LayS1) since the barrier in front of that quarter's loop
+                {
+                    float wg[3];
+#pragma unroll
+                    for (int s3 = 0; s3 < 3; ++s3) wg[s3] = G ? w0[s3][1] : w0[s3][0];
+                    f43c1_conv0_tile(patch, wg, G ? bias0[1] : bias0[0], act, wave, lane);
+                }
+                __syncthreads();                                      // conv0's channel block is in place; every wave has finished the previous quarter's loop (V is free)
+                if (G == 0) CNN_STAMP(19);
+#pragma unroll 1
+                for (int jh = 0; jh < 2; ++jh) {
+                    if (jh) __syncthreads();                          // every wave has finished the previous quarter's loop: V is free
+                    f43_transform_channel<LayS1::WP, F43C1L::XS>(t_in + 2 * jh, t_v);
+                    __syncthreads();                                  // V of the quarter is in place
+                    if (G == 0 && jh == 0) CNN_STAMP(20);
+                    const int q_off = G * (16 * CB * 4) + jh * 8, q_next = jh == 0 ? q_off + 8 : (G == 0 ? 16 * CB * 4 : q_off);
+                    __builtin_amdgcn_s_setprio(0);
+                    f43c1_quarter_loop<CB, CB, DU, DV>(wrsrc, u_lane, q_off, q_next, v0, v1, Ur, acc);
+                    __builtin_amdgcn_s_setprio(3);
+                    if (G == 0 && jh == 0) CNN_STAMP(2);
+                }
+            }
+            CNN_STAMP(3);
+            f32x4 y[16];
+            f43c5_output(acc, y);
+            poly_prefetch_u<NW, CB, 2 * CB, 16, NBP2, 2>(a.wino_u + Poly32::offset(2), P2a, P2b, wave, lane);
+            const f32x4 bf = *reinterpret_cast<const f32x4*>(&a.packed[a.off.b[1] + (wave & 1) * 16 + 4 * (lane >> 4)]);
+            __syncthreads();                                          // every wave has finished reading V
+            CNN_STAMP(21);
+            zero_halo<LayC1, NTHR>(act, CB);
+            f43c1_store_lds<LayC1>(act, bf, y, wave, lane);
+            CNN_STAMP(22);
+            __syncthreads();
+            CNN_STAMP(4);
+        }
+        if constexpr (!STREAM1) {
             f32x4 acc[T1M][T1N];
             conv0_mfma<NW, CB, T1M, T1N>(patch, w0, bias0, acc, wave, lane);
             CNN_STAMP(19);
@@ -403,14 +470,11 @@ __global__ __launch_bounds__(NW * 64, (KIND == AFFNET_NET_HARDNET) ? NW / 4 : 4)
             wino_prefetch_u_pair<NW, CB, CB, 32, NB1>(a.packed + a.off.w_wino[0], Up, wave, lane);
             __syncthreads();
         }
-        if (STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
-        CNN_STAMP(2);
+        if (!STREAM1 && STAMPS && a.dbg_layer == 0) { dump_planes<CB, LayC0, NTHR>(act, a.dbg_out); return; }
+        if constexpr (!STREAM1) CNN_STAMP(2);
 
         // ---- conv1: CB -> CB @32x32, Winograd -------------------------------------------------------------
-        f32x4 b2[S::G2][T2N];                                         // form 0: conv2's first weight chunk and bias
-        f32x4 bias2[T2N];
-        f32x4 P2a[2][3], P2b[2][3];                                   // form 1: the two rolling U register sets of conv2
-        {
+        if constexpr (!STREAM1) {
             f32x4 y[NB1][4], bw[NB1];
             __builtin_amdgcn_s_setprio(0);
             conv3x3_wino_mfma_pair_rows<NW, CB, CB, LayC0, NB1>(act, a.packed + a.off.w_wino[0], Up, y, wave, lane);

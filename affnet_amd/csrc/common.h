@@ -122,7 +122,7 @@ struct affnet_ctx {
     // The transformed weights that are no blob sections (weights_layout.h: DerivedU, a region per net), derived from the caller's blob in front of every trunk launch that
     // reads them (derive_u.hip: aff_derive_u); the only device memory a context owns, allocated on first use (aff_derived_u_ensure)
     float* derived_u = nullptr;
-    int desc_form = AFFNET_DESC_FORM_F43_CONV5;     // fused exact-fp32 HardNet trunk (affnet_set_desc_form): stride-2 layers in the direct form, or as polyphase Winograd F(2x2, 2x2), or that with conv3 as F(4x4, 3x3), or that with conv5 as F(4x4, 3x3) in a kernel of its own
+    int desc_form = AFFNET_DESC_FORM_F43_CONV1;     // fused exact-fp32 HardNet trunk (affnet_set_desc_form): stride-2 layers in the direct form, or as polyphase Winograd F(2x2, 2x2), or that with conv3 as F(4x4, 3x3), or that with conv5 as F(4x4, 3x3) in a kernel of its own, or that with conv1 as F(4x4, 3x3) streamed with conv0
     ~affnet_ctx() {
         if (derived_u) (void)hipFree(derived_u);
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
@@ -268,7 +268,8 @@ constexpr int TRUNK_SPLIT3 = 3;      // three bf16 terms per operand (AFFNET_ARI
 constexpr int TRUNK_WINO_F43 = 4;    // exact fp32, HardNet: TRUNK_WINO with conv3 as Winograd F(4x4, 3x3) (descriptor form 2)
 constexpr int TRUNK_WINO_POLY = 5;   // exact fp32, AffNet: TRUNK_WINO with conv2 / conv4 polyphase (shape form 2)
 constexpr int TRUNK_WINO_F43_C5 = 6; // exact fp32, HardNet: TRUNK_WINO_F43 cut behind conv4, whose tensor goes to HBM; conv5 follows as hardnet_conv5_f43_kernel, four patches per workgroup (descriptor form 3)
-constexpr int TRUNK_FORMS = 7;
+constexpr int TRUNK_WINO_F43_C1 = 7; // exact fp32, HardNet: TRUNK_WINO_F43_C5 with conv0 + conv1 streamed over conv1's K, conv1 as Winograd F(4x4, 3x3) (descriptor form 4)
+constexpr int TRUNK_FORMS = 8;
 
 // the lazy-evaluation predicate above, for the trunk and finish kernels
 __device__ __forceinline__ bool lazy_skip(const int32_t* skip_cnt, int skip_n, int image, int which = CNT_SURVIVED1) {
@@ -295,7 +296,7 @@ struct CnnCall {
     int row_begin = 0, row_count = -1;                               // row window of every image; -1 = up to n_max
     const int32_t* skip_cnt = nullptr; int skip_n = 0;               // lazy-evaluation predicate (see CnnArgs)
     const ShapeFuse* fuse = nullptr; int shape_op = 0;               // AffNet: shape filter in the finish kernel, counter bookkeeping in the trunk
-    int desc_form = AFFNET_DESC_FORM_DIRECT;                         // HardNet, exact fp32: AFFNET_DESC_FORM_* - 1: conv2 / conv4 as polyphase Winograd F(2x2, 2x2), 2: conv3 as F(4x4, 3x3) besides, 3: conv5 as F(4x4, 3x3) in a kernel of its own besides
+    int desc_form = AFFNET_DESC_FORM_DIRECT;                         // HardNet, exact fp32: AFFNET_DESC_FORM_* - 1: conv2 / conv4 as polyphase Winograd F(2x2, 2x2), 2: conv3 as F(4x4, 3x3) besides, 3: conv5 as F(4x4, 3x3) in a kernel of its own besides, 4: conv0 + conv1 streamed, conv1 as F(4x4, 3x3) besides
     int wino_reeval = 0;                                             // AffNet, exact fp32, fused filter: 1 / 2 = Winograd trunk of that shape form, margin rule, direct trunk on the flagged rows; 0 = direct only
     float* rot_lafs = nullptr; const DenormSel* denorm = nullptr;    // OriNet: LAF <- LAF * R in the finish kernel (+ denormalisation and level choice)
 };
@@ -362,7 +363,7 @@ int aff_orinet_rotate(affnet_ctx* ctx, const float* packed, float* lafs, const i
 int aff_hardnet_forward_pyr_marked(affnet_ctx* ctx, const float* packed, const float* lafs, const int32_t* ids, const int32_t* count,
                                    int n_max, float* out, float* scratch, hipStream_t st);
 
-// cnn32.hip: HardNet on a patch tensor in descriptor form `form` (1, 2 or 3), for the probe library (the public patch-tensor calls run form 0); dbg_layer >= 0: layer dump of patch 0
+// cnn32.hip: HardNet on a patch tensor in descriptor form `form` (1, 2, 3 or 4), for the probe library (the public patch-tensor calls run form 0); dbg_layer >= 0: layer dump of patch 0
 int aff_hardnet_poly_patches(affnet_ctx* ctx, const float* packed, const float* patches, int n, float* out, float* scratch, int dbg_layer, hipStream_t st,
                              int form = AFFNET_DESC_FORM_POLYPHASE);
 // cnn32.hip: the instantiation of net `kind` in trunk form `form` (TRUNK_*) [phase stamps]; NULL for a pair that is not built
@@ -373,7 +374,7 @@ int aff_trunk_launch(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, dim3
 // cnn_trunk_*.hip: the unit's instantiations, by trunk form [phase stamps]; NULL for a form the unit does not build.  Called by aff_trunk_kernel only.
 TrunkKernel aff_trunk_affnet(int form, bool stamps), aff_trunk_affnet_poly(int form, bool stamps), aff_trunk_orinet(int form, bool stamps);
 TrunkKernel aff_trunk_hardnet(int form, bool stamps), aff_trunk_hardnet_poly(int form, bool stamps), aff_trunk_hardnet_f43(int form, bool stamps);
-TrunkKernel aff_trunk_hardnet_c5(int form, bool stamps);
+TrunkKernel aff_trunk_hardnet_c5(int form, bool stamps), aff_trunk_hardnet_c1(int form, bool stamps);
 // hardnet_conv5_f43.hip: conv5 of descriptor form 3 behind its trunk launch, on `groups` groups of four rows of B images
 int aff_hardnet_conv5_f43(affnet_ctx* ctx, const Conv5Args& a, int groups, int B, bool stamps, hipStream_t st);
 // derive_u.hip: allocate the context's buffer of derived weights (before a stream capture begins: no allocation inside one)

@@ -236,7 +236,7 @@ extern "C" int affnet_get_shape_form(const affnet_ctx* ctx) { return ctx ? ctx->
 
 extern "C" int affnet_set_desc_form(affnet_ctx* ctx, int form) {
     if (!ctx) return AFFNET_ERR_INVALID;
-    if (form != AFFNET_DESC_FORM_DIRECT && form != AFFNET_DESC_FORM_POLYPHASE && form != AFFNET_DESC_FORM_F43 && form != AFFNET_DESC_FORM_F43_CONV5) return aff_fail(ctx, AFFNET_ERR_INVALID, "descriptor form=%d (AFFNET_DESC_FORM_*)", form);
+    if (form != AFFNET_DESC_FORM_DIRECT && form != AFFNET_DESC_FORM_POLYPHASE && form != AFFNET_DESC_FORM_F43 && form != AFFNET_DESC_FORM_F43_CONV5 && form != AFFNET_DESC_FORM_F43_CONV1) return aff_fail(ctx, AFFNET_ERR_INVALID, "descriptor form=%d (AFFNET_DESC_FORM_*)", form);
     ctx->desc_form = form;
     return AFFNET_OK;
 }

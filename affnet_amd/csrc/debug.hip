@@ -202,3 +202,16 @@ extern "C" int affnet_probe_hardnet_c5_u(affnet_ctx* ctx, const float* d_packed,
     if (!ctx || !d_packed || !d_out) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c5_u: null argument");
     return probe_derived_u(ctx, AFFNET_NET_HARDNET, TRUNK_WINO_F43_C5, d_packed, F43C5::BASE, F43C5::FLOATS, d_out, stream);
 }
+
+// Descriptor form 4 (AFFNET_DESC_FORM_F43_CONV1): the trunk's layers 1 .. 4 and the whole forward
+extern "C" int affnet_probe_hardnet_c1_trunk_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patch || !d_out || layer < 1 || layer > 4) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c1_trunk_layer: layer 1 .. 4");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patch, 1, d_out, nullptr, layer, (hipStream_t)stream, AFFNET_DESC_FORM_F43_CONV1);
+}
+
+extern "C" int affnet_probe_hardnet_c1_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_packed || !d_patches || !d_out || !d_scratch || n < 1 || n > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "probe_hardnet_c1_forward: bad argument");
+    return aff_hardnet_poly_patches(ctx, d_packed, d_patches, n, d_out, d_scratch, -1, (hipStream_t)stream, AFFNET_DESC_FORM_F43_CONV1);
+}

@@ -16,7 +16,7 @@ int aff_derived_u_ensure(affnet_ctx* ctx) {
 
 // the sections the exact trunk (kind, form) reads; n == 0: none
 static DerivedTable table_of(int kind, int form) {
-    if (kind == AFFNET_NET_HARDNET) return form == TRUNK_WINO ? derived_hardnet_poly() : (form == TRUNK_WINO_F43 ? derived_hardnet_form2() : (form == TRUNK_WINO_F43_C5 ? derived_hardnet_form3() : DerivedTable{}));
+    if (kind == AFFNET_NET_HARDNET) return form == TRUNK_WINO ? derived_hardnet_poly() : (form == TRUNK_WINO_F43 ? derived_hardnet_form2() : (form == TRUNK_WINO_F43_C5 || form == TRUNK_WINO_F43_C1 ? derived_hardnet_form3() : DerivedTable{}));
     const bool wino = kind == AFFNET_NET_ORINET ? form == TRUNK_EXACT : (form == TRUNK_WINO || form == TRUNK_WINO_POLY);
     return wino ? derived_trunk16() : DerivedTable{};
 }

@@ -235,7 +235,7 @@ constexpr DerivedTable derived_trunk16() {
 }
 // HardNet descriptor form 1: conv2 / conv4 as polyphase Winograd (205 KB + 819 KB)
 constexpr DerivedTable derived_hardnet_poly() { return derived_add(derived_add(DerivedTable{}, 32, 2, DERIVED_POLY), 32, 4, DERIVED_POLY); }
-// HardNet's conv1 / conv3 in Winograd F(4x4, 3x3) (144 KB + 576 KB; conv1's has no loop yet, NOTES.md) ...
+// HardNet's conv1 / conv3 in Winograd F(4x4, 3x3) (144 KB + 576 KB; conv1's is read by descriptor form 4 only) ...
 constexpr DerivedTable derived_hardnet_f43() { return derived_add(derived_add(DerivedTable{}, 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }
 // ... and what descriptor form 2 reads: those directly BEHIND form 1's polyphase sections - its trunk takes one derived-weights pointer (CnnArgs::wino_u) and finds both there
 constexpr DerivedTable derived_hardnet_form2() { return derived_add(derived_add(derived_hardnet_poly(), 32, 1, DERIVED_F43), 32, 3, DERIVED_F43); }

@@ -48,7 +48,7 @@ class Context(object):
                                          onepass=onepass, lazy_shape_rows=lazy_shape_rows, arith=arith)
         self.arith = _lib.arith_code(arith)
         self.shape_form = _lib.SHAPE_FORM_WINOGRAD             # the library's default (affnet_set_shape_form)
-        self.desc_form = _lib.DESC_FORM_F43_CONV5              # the library's default (affnet_set_desc_form)
+        self.desc_form = _lib.DESC_FORM_F43_CONV1              # the library's default (affnet_set_desc_form)
         self.device = device
         self.handle = C.c_void_p()
         idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -74,8 +74,8 @@ class Context(object):
 
     def set_desc_form(self, form):
         """Form of the exact-fp32 HardNet trunk of the fused calls (affnet_set_desc_form): 0 = conv2 / conv4 in the direct form, 1 = as polyphase Winograd
-        F(2x2, 2x2), 2 = that with conv3 as Winograd F(4x4, 3x3), 3 = form 2 with conv5 as Winograd F(4x4, 3x3) in a kernel of its own, four patches per workgroup
-        (default; descriptors differ by rounding only).  Read when a call is enqueued; a captured graph keeps its form."""
+        F(2x2, 2x2), 2 = that with conv3 as Winograd F(4x4, 3x3), 3 = form 2 with conv5 as Winograd F(4x4, 3x3) in a kernel of its own, four patches per workgroup,
+        4 = form 3 with conv0 + conv1 streamed over conv1's input channels and conv1 as Winograd F(4x4, 3x3) (default; descriptors differ by rounding only).  Read when a call is enqueued; a captured graph keeps its form."""
         check(lib.affnet_set_desc_form(self.handle, int(form)), self.handle, "affnet_set_desc_form")
         self.desc_form = int(form)
 

@@ -197,14 +197,18 @@ int affnet_get_shape_form(const affnet_ctx* ctx);
  *                                tile.  Descriptors differ from form 0 by rounding only (both within 1e-6 of a float64 forward); nothing else of a call changes.
  *   AFFNET_DESC_FORM_F43       : form 1 with conv3 (64 -> 64 at 16 x 16) as Winograd F(4x4, 3x3) instead of F(2x2, 3x3): 36 products per 16 outputs instead of 16
  *                                per 4.  Descriptors within 1e-6 of a float64 forward as well (about 3x the direct form's rounding); nothing else of a call changes.
- *   AFFNET_DESC_FORM_F43_CONV5 : (default) form 2 with conv5 (128 -> 128 at 8 x 8) moved out of the trunk kernel: the trunk stores conv4's tensor into the 32 KB slot of the patch
+ *   AFFNET_DESC_FORM_F43_CONV5 : form 2 with conv5 (128 -> 128 at 8 x 8) moved out of the trunk kernel: the trunk stores conv4's tensor into the 32 KB slot of the patch
  *                                and a second kernel runs conv5 as Winograd F(4x4, 3x3) for four patches per workgroup (36 instead of 64 products per 16 outputs), in place
  *                                in those slots.  One launch and one 32 KB round trip per patch more; descriptors differ by rounding only.
+ *   AFFNET_DESC_FORM_F43_CONV1 : (default) form 3 with conv1 (32 -> 32 at 32 x 32) as Winograd F(4x4, 3x3) as well: conv0 and conv1 run as a pair streamed over conv1's input channels,
+ *                                conv0 one block of 16 channels at a time, conv1's transformed input 8 channels at a time, so that both fit the trunk's LDS.  288 instead of
+ *                                512 matrix instructions per wave in conv1; descriptors differ by rounding only (within 2e-6 of a float64 forward).
  * Read when a call is enqueued; a graph captured earlier keeps the form it was captured with. */
 #define AFFNET_DESC_FORM_DIRECT 0
 #define AFFNET_DESC_FORM_POLYPHASE 1
 #define AFFNET_DESC_FORM_F43 2
 #define AFFNET_DESC_FORM_F43_CONV5 3
+#define AFFNET_DESC_FORM_F43_CONV1 4
 int affnet_set_desc_form(affnet_ctx* ctx, int form);
 int affnet_get_desc_form(const affnet_ctx* ctx);
 

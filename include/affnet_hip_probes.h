@@ -94,6 +94,13 @@ int affnet_probe_hardnet_c5_forward(affnet_ctx* ctx, const float* d_packed, cons
 int affnet_probe_hardnet_c5_layer(affnet_ctx* ctx, const float* d_packed, float* d_slots, int n, void* stream);
 int affnet_probe_hardnet_c5_u(affnet_ctx* ctx, const float* d_packed, float* d_out, void* stream);
 
+/* Descriptor form AFFNET_DESC_FORM_F43_CONV1 (form 3 with conv0 + conv1 streamed, conv1 as Winograd F(4x4, 3x3)):
+ *   _trunk_layer: affnet_cnn32_debug_layer's arguments and output for layers 1 .. 4 of its trunk kernel (layer 0 never exists as a tensor: refused);
+ *   _forward:     as affnet_probe_hardnet_c5_forward.
+ * conv1's derived weights are affnet_probe_hardnet_f43_u's layer 1. */
+int affnet_probe_hardnet_c1_trunk_layer(affnet_ctx* ctx, const float* d_packed, const float* d_patch, int layer, float* d_out, void* stream);
+int affnet_probe_hardnet_c1_forward(affnet_ctx* ctx, const float* d_packed, const float* d_patches, int n, float* d_out, float* d_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,8 @@ if hasattr(lib, "affnet_probe_hardnet_poly_forward"):
         nets.append((HardNetForm1("affnet_probe_hardnet_f43_forward"), "HardNet form 2", 8))
     if hasattr(lib, "affnet_probe_hardnet_c5_forward"):
         nets.append((HardNetForm1("affnet_probe_hardnet_c5_forward"), "HardNet form 3", 8))
+    if hasattr(lib, "affnet_probe_hardnet_c1_forward"):
+        nets.append((HardNetForm1("affnet_probe_hardnet_c1_forward"), "HardNet form 4", 8))
 else:
     print("(no table of HardNet's polyphase trunk: this library has no affnet_probe_hardnet_poly_forward - AFFNET_HIP_LIB=affnet_amd/libaffnet_hip_probes.so)")
 if hasattr(lib, "affnet_probe_affnet_wino_partials"):
@@ -81,7 +83,11 @@ for net, nm, nw in nets:
     net(p); torch.cuda.synchronize()
     lib.affnet_cnn32_debug_timing(engine.utility_ctx(dev), None)
     t = st.cpu().numpy().reshape(n, nw, 32).astype(np.float64)
-    nst = 10 if nm == "HardNet form 3" else 12      # form 3's trunk ends behind conv4's loop (stamps 0 .. 9, then 13); conv5 is a kernel of its own, tabled below
+    cut5 = nm in ("HardNet form 3", "HardNet form 4")
+    nms = names
+    nst = 10 if cut5 else 12                        # the trunk of forms 3 / 4 ends behind conv4's loop (stamps 0 .. 9, then 13); conv5 is a kernel of its own, tabled below
+    if nm == "HardNet form 4":                      # conv0 + conv1 streamed: stamp 2 stands behind the first quarter's loop, stamp 3 behind the last quarter's
+        nms = ["input+norm", "c0 half+q0", "c0 half+q1-3", "conv1 out+st"] + names[4:]
     d = np.diff(t[:, :, :nst], axis=2)              # cycles per phase per wave
     wg = t[:, :, :nst].max(axis=1) - t[:, :, 0:1].min(axis=1)   # per patch: boundary times relative to WG start
     print("== %s (%d waves): mean phase cycles per wave (s_memtime ticks, 100 MHz const clock?)" % (nm, nw))
@@ -89,11 +95,11 @@ for net, nm, nw in nets:
     span = (t[:, :, nst - 1].max() - t[:, :, 0].min())
     print("  kernel span %.0f ticks for %d patches -> %.0f ticks / patch / CU-slot (256 CUs)" % (span, n, span / (n / 256.0)))
     for i in range(nst - 1):
-        print("  %-12s mean %9.0f  max-over-waves %9.0f" % (names[i], d[:, :, i].mean(), d[:, :, i].max(axis=1).mean()))
+        print("  %-12s mean %9.0f  max-over-waves %9.0f" % (nms[i], d[:, :, i].mean(), d[:, :, i].max(axis=1).mean()))
     print("  total per patch (WG) %.0f ticks" % tot)
     simd = (st.cpu().numpy().reshape(n, nw, 32)[:, :, 14] >> 4) & 3
     for i in (j for j in (2, 6, 10) if j < nst - 1):
-        print("  %-12s per wave:" % names[i], " ".join("%6.0f" % v for v in d[:, :, i].mean(axis=0)))
+        print("  %-12s per wave:" % nms[i], " ".join("%6.0f" % v for v in d[:, :, i].mean(axis=0)))
     # the two waves of a workgroup that share a SIMD: how far apart do they finish a loop?
     first, second = [], []
     for k in range(0, n, max(1, n // 128)):
@@ -128,14 +134,33 @@ for net, nm, nw in nets:
                 gaps.append(s_[k] - prev.max())
     sub = t[:, :, [0, 16, 17, 18, 1, 19, 20, 2]]
     ds = np.diff(sub, axis=2).mean(axis=(0, 1))
-    print("  input: load %.0f | halo+sum1 %.0f | sum2 %.0f | patch write+barrier %.0f || conv0: mfma %.0f | stores %.0f | barrier %.0f" % tuple(ds))
-    sub = t[:, :, [3, 21, 22, 4]]
-    ds = np.diff(sub, axis=2).mean(axis=(0, 1))
-    print("  conv1 epilogue: barrier1 %.0f | halo+stores %.0f | barrier2 %.0f" % tuple(ds))
-    if nm in ("HardNet form 2", "HardNet form 3"):        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
+    if nm == "HardNet form 4":
+        # the slots of the phases this form does not have: 19 conv0 of K group 0 + barrier | 20 first quarter's transform + barrier | 2 its loop | 3 last quarter's loop |
+        # 21 output transform + barrier | 22 halo + stores | 4 barrier.  Mean over waves [max over waves]; the model's line (NOTES.md) beside each
+        dm = np.diff(sub, axis=2).max(axis=1).mean(axis=0)
+        print("  input: load %.0f | halo+sum1 %.0f | sum2 %.0f | patch write+barrier %.0f" % tuple(ds[:4]))
+        print("  conv0 + conv1 streamed:            mean [max over waves]   model")
+        print("    conv0 half + barrier             %6.0f [%6.0f]          3.4 k" % (ds[4], dm[4]))
+        print("    quarter transform + barrier      %6.0f [%6.0f]          2.7 k" % (ds[5], dm[5]))
+        print("    quarter loop (72 MFMAs)          %6.0f [%6.0f]          4.9 k" % (ds[6], dm[6]))
+        rest = np.diff(t[:, :, [2, 3]], axis=2)
+        print("    second half + quarters 1 - 3     %6.0f [%6.0f]          3.4 k + 3 x 7.6 k = 26.2 k" % (rest.mean(), rest.max(axis=1).mean()))
+        ep = np.diff(t[:, :, [3, 21, 22, 4]], axis=2)
+        print("    output transform + barrier %.0f | halo + stores %.0f | barrier %.0f [sum of max over waves %.0f]   about 7 k" %
+              (tuple(ep.mean(axis=(0, 1))) + (ep.max(axis=1).mean(axis=0).sum(),)))
+        c1 = (t[:, :, 4].max(axis=1) - t[:, :, 1].min(axis=1)).mean()
+        print("    conv0 + conv1, first stamp 1 -> last stamp 4: %.0f ticks (model about 44 k; form 3: conv0 6.3 k + conv1 loop 42.8 k + store 7.9 k, critical path about 52.5 k)" % c1)
+    else:
+        print("  input: load %.0f | halo+sum1 %.0f | sum2 %.0f | patch write+barrier %.0f || conv0: mfma %.0f | stores %.0f | barrier %.0f" % tuple(ds))
+        sub = t[:, :, [3, 21, 22, 4]]
+        ds = np.diff(sub, axis=2).mean(axis=(0, 1))
+        print("  conv1 epilogue: barrier1 %.0f | halo+stores %.0f | barrier2 %.0f" % tuple(ds))
+        c1 = (t[:, :, 4].max(axis=1) - t[:, :, 1].min(axis=1)).mean()
+        print("  conv0 + conv1, first stamp 1 -> last stamp 4: %.0f ticks" % c1)
+    if nm in ("HardNet form 2", "HardNet form 3", "HardNet form 4"):        # "conv3 mfma" = stamp 6 -> 7 spans the whole F(4x4, 3x3) layer but its store
         ds = np.diff(t[:, :, [6, 23, 7]], axis=2).mean(axis=(0, 1))
         print("  conv3 F(4x4, 3x3): transform + V through LDS + loop + fold along x %.0f | barrier + exchange of the halves %.0f" % tuple(ds))
-    if nm == "HardNet form 3":
+    if cut5:
         # hardnet_conv5_f43_kernel, one workgroup per four patches: stamps 24 .. 31 of every wave in the record of the group's first patch
         # 24 start | 25 quarter 0 in LDS | 26 its transform done | 27 its loop done | 28 quarter 3's transform done | 29 its loop done | 30 output transform done | 31 stored
         g = t[0::4, :, 24:32]
@@ -147,7 +172,11 @@ for net, nm, nw in nets:
             print("    %-42s %9.0f [%9.0f]" % (what, dg[:, :, i].mean(), dg[:, :, i].max(axis=1).mean()))
         print("    loop of quarter 0: %.1f cycles per MFMA" % (dg[:, :, 2].max(axis=1).mean() / 288.0))
         print("    workgroup, first stamp 24 -> last stamp 31: %.0f ticks = %.0f per patch" % (c5, c5 / 4.0))
-        if "HardNet form 2" in wg_ticks:
+        wg_ticks[nm + " + conv5"] = wg_ticks[nm] + c5 / 4.0
+        if nm == "HardNet form 4" and "HardNet form 3 + conv5" in wg_ticks:
+            f3, f4 = wg_ticks["HardNet form 3 + conv5"], wg_ticks[nm + " + conv5"]
+            print("  GATE: form 4 trunk %.0f + conv5 kernel per patch %.0f = %.0f ticks against form 3's %.0f: %.0f ticks shorter (needed: 4000 or more)" % (wg_ticks[nm], c5 / 4.0, f4, f3, f3 - f4))
+        if nm == "HardNet form 3" and "HardNet form 2" in wg_ticks:
             f3 = wg_ticks[nm] + c5 / 4.0
             print("  GATE: form 3 trunk %.0f + conv5 kernel per patch %.0f = %.0f ticks against form 2's workgroup %.0f: %.1f %% shorter (needed: 5 %% or more)" %
                   (wg_ticks[nm], c5 / 4.0, f3, wg_ticks["HardNet form 2"], 100.0 * (1.0 - f3 / wg_ticks["HardNet form 2"])))
@@ -163,5 +192,5 @@ for net, nm, nw in nets:
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); net(big); e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
-    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "AffNet form 2": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0, "HardNet form 3": 78184448.0}[nm]      # direct-form FLOP per patch
+    fl = {"AffNet": 19193856.0, "AffNet form 1": 19193856.0, "AffNet form 2": 19193856.0, "OriNet": 19316736.0, "HardNet": 78184448.0, "HardNet form 1": 78184448.0, "HardNet form 2": 78184448.0, "HardNet form 3": 78184448.0, "HardNet form 4": 78184448.0}[nm]      # direct-form FLOP per patch
     print("  48000 contiguous patches: %.3f ms -> %.1f TFLOP/s (incl. head / allocation)" % (ms, 48000 * fl / ms / 1e9))

@@ -107,8 +107,9 @@ DESIGN_KERNELS = [
     ("cnn32_trunk_kernel<2, 8, false, 0>", "HardNet trunk, exact fp32 MFMA"),
     ("cnn32_trunk_kernel<2, 8, false, 1>", "HardNet trunk, exact fp32 MFMA, polyphase Winograd conv2 / conv4 (descriptor form 1)"),
     ("cnn32_trunk_kernel<2, 8, false, 4>", "HardNet trunk, exact fp32 MFMA, form 1 with conv3 as Winograd F(4x4, 3x3) (descriptor form 2)"),
-    ("cnn32_trunk_kernel<2, 8, false, 6>", "HardNet trunk, exact fp32 MFMA, form 2 cut behind conv4 (descriptor form 3, default)"),
-    ("hardnet_conv5_f43_kernel<false>", "HardNet conv5 as Winograd F(4x4, 3x3), four patches per workgroup (descriptor form 3)"),
+    ("cnn32_trunk_kernel<2, 8, false, 6>", "HardNet trunk, exact fp32 MFMA, form 2 cut behind conv4 (descriptor form 3)"),
+    ("cnn32_trunk_kernel<2, 8, false, 7>", "HardNet trunk, exact fp32 MFMA, form 3 with conv0 + conv1 streamed, conv1 as Winograd F(4x4, 3x3) (descriptor form 4, default)"),
+    ("hardnet_conv5_f43_kernel<false>", "HardNet conv5 as Winograd F(4x4, 3x3), four patches per workgroup (descriptor forms 3 / 4)"),
     ("cnn32_trunk_kernel<2, 8, false, 3>", "HardNet trunk, arith fp32_split3"),
     ("cnn32_trunk_kernel<2, 8, false, 2>", "HardNet trunk, arith fp32_split2h"),
     ("cnn32_trunk_kernel<0, 8, false, 0>", "AffNet trunk, exact fp32 MFMA"),

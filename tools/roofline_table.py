@@ -5,7 +5,7 @@
                                                              that trunk is priced on the MFMA FLOPs it executes (WINO_HARDNET), not the direct form's;
                                                              so is AffNet's Winograd trunk of shape form 1, <0, 8, false, 1> (WINO_AFFNET), and HardNet's trunk of descriptor form 1,
                                                              <2, 8, false, 1>, whose conv2 / conv4 run as polyphase Winograd F(2x2, 2x2) besides (POLY_HARDNET), and of descriptor form 2, <2, 8, false, 4>,
-                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET), and of descriptor form 3, <2, 8, false, 6> + hardnet_conv5_f43_kernel (F43C5_*); AffNet's trunk of shape form 2, <0, 8, false, 5>, whose
+                                                             whose conv3 runs as Winograd F(4x4, 3x3) (F43_HARDNET), and of descriptor forms 3 / 4, <2, 8, false, 6> / <2, 8, false, 7> + hardnet_conv5_f43_kernel (F43C5_*, F43C1_*); AffNet's trunk of shape form 2, <0, 8, false, 5>, whose
                                                              conv2 / conv4 run as polyphase Winograd besides (POLY_AFFNET), and - in evidence of a build that has that kernel - the
                                                              exact OriNet trunk, which runs the same five forms (POLY_ORINET)
 Per kernel: launches per 32-image call, mean duration (rocprofv3 --kernel-trace --stats), HBM bytes per launch from the
@@ -36,6 +36,9 @@ F43_HARDNET = POLY_HARDNET - NKP * 18874368.0 * (16.0 / 36.0 - 9.0 / 36.0)
 # the direct form's 18874368 FLOPs per patch (F43C5_CONV5): 26.8 + 4.7 instead of 35.2 M executed MFMA FLOPs per patch
 F43C5_TRUNK_HARDNET = F43_HARDNET - NKP * 18874368.0 * (16.0 / 36.0)
 F43C5_CONV5 = NKP * 18874368.0 * (9.0 / 36.0)
+# Descriptor form 4: the trunk <2, 8, false, 7> is form 3's with conv1 as Winograd F(4x4, 3x3) as well, 9 / 36 instead of 16 / 36 of its 18874368 direct FLOPs per patch:
+# 23.1 + 4.7 M executed MFMA FLOPs per patch
+F43C1_TRUNK_HARDNET = F43C5_TRUNK_HARDNET - NKP * 18874368.0 * (16.0 / 36.0 - 9.0 / 36.0)
 FLOP["hardnet_conv5_f43_kernel"] = F43C5_CONV5
 # AffNet's Winograd trunk (shape form 1): conv1 / conv3 / conv5 are 4718592 direct FLOPs per patch each and execute 16 / 36 of them.  conv1 .. conv5 together:
 # 11.0 M executed MFMA FLOPs per patch (13.6 M while conv5 was direct: 288 instead of 128 MFMAs per wave), against OriNet's 11.0 M; conv0 and the head as in the direct form
@@ -110,7 +113,7 @@ def main(prefix, winograd=False):
                                                           100 * prod * tf / 2516.8))
             elif key in name:
                 if winograd and key == "cnn32_trunk_kernel<2":
-                    fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else (F43C5_TRUNK_HARDNET if name.rstrip().endswith(", 6>") else WINO_HARDNET))
+                    fl = F43_HARDNET if name.rstrip().endswith(", 4>") else (POLY_HARDNET if name.rstrip().endswith(", 1>") else (F43C5_TRUNK_HARDNET if name.rstrip().endswith(", 6>") else (F43C1_TRUNK_HARDNET if name.rstrip().endswith(", 7>") else WINO_HARDNET)))
                 poly16_build = any("cnn32_trunk_kernel<0, 8, false, 5>" in k for k in stats)
                 wino_aff = winograd and ((key == "cnn32_trunk_kernel<0" and (name.rstrip().endswith(", 1>") or name.rstrip().endswith(", 5>"))) or
                                          (key == "cnn32_trunk_kernel<1" and poly16_build))

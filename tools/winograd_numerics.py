@@ -258,6 +258,8 @@ def f43_packed_weight_transform(sd, layers=(1, 3)):
 
 F43_LAYERS = (3,)                # the layers HardNet's descriptor form 2 runs as F(4x4, 3x3)
 F43_LAYERS_FORM3 = (3, 5)        # ... and descriptor form 3: conv5 as well, in a kernel of its own (affnet_amd/csrc/hardnet_conv5_f43.hip)
+F43_LAYERS_FORM4 = (1, 3, 5)     # ... and descriptor form 4: conv1 as well, streamed with conv0 over its K (affnet_amd/csrc/cnn_trunk.h: STREAM1) - every accumulator sums
+                                 # its K in the order f43_conv3x3's contraction stands for (K group ascending, k-step ascending), lane-local transforms on both sides
 
 
 def f43_conv5_grouped(x, w):
@@ -381,7 +383,7 @@ def errors(sd, patches):
     with torch.no_grad():
         ref = orc.hardnet_forward({k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}, patches.double())
         out = {}
-        for name, wino, poly, f43 in (("direct", False, False, ()), ("winograd", True, False, ()), ("polyphase", True, True, ()), ("f43", True, True, F43_LAYERS), ("f43_conv5", True, True, F43_LAYERS_FORM3)):
+        for name, wino, poly, f43 in (("direct", False, False, ()), ("winograd", True, False, ()), ("polyphase", True, True, ()), ("f43", True, True, F43_LAYERS), ("f43_conv5", True, True, F43_LAYERS_FORM3), ("f43_conv1", True, True, F43_LAYERS_FORM4)):
             d = (hardnet_forward(sd, patches, wino=wino, poly=poly, f43=f43).double() - ref).abs()
             out[name] = (float(d.max()), float(d.mean()))
     return out
