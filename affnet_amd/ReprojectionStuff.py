@@ -3,7 +3,9 @@
 verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify), and both for many image pairs per device call (pair_table,
 enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank).  The epipolar model of a scene with depth is csrc/epipolar.hip
 (verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance).  Guided matching under a
-verified model of either family is csrc/guided.hip (match_guided, enqueue_match_guided, guided_mask, match_verify_guided)."""
+verified model of either family is csrc/guided.hip (match_guided, enqueue_match_guided, guided_mask, match_verify_guided).  Both have their
+many-pairs form too (affnet_epipolar_verify_many, affnet_match_guided_many): model="fundamental" of the *_many functions,
+enqueue_match_verify_guided_many, match_verify_guided_many, guided=True of spatial_rerank."""
 import ctypes as C
 
 import numpy as np
@@ -262,73 +264,215 @@ def _many_buf(dev, dtype, *shape):
     return torch.zeros(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
 
 
-def enqueue_match_and_verify_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
-    """match_and_verify for P image pairs in one chain of launches on the current stream, no synchronisation.  desc1 (rows1,128) / LAFs1 (rows1,2,3)
-    hold the images of side 1 back to back, counts1[i] rows for image i; side 2 likewise (it may be the same tensors); pairs = [(a, b), ...] image
-    indices into the two sides.  Returns capacity-sized device tensors, cap = the largest n1 of a pair: (tent (P,cap,2) int32 with indices local to
-    the pair's images, count (P,) int32, H (P,3,3) float64, inliers (P,cap) uint8, counts (P,cap) int32, summary (P,4) int32); per pair, rows below
-    count[p] are what match_and_verify gives for that pair, bit for bit, rows at or beyond it are zero."""
+def _many_model(model, rounds, seed, what):
+    """-> (epi, model code or None, rounds, seed, hypotheses per tentative); ValueError on an unknown model or rounds / seed out of range."""
+    if model != "fundamental":
+        return False, _verify_model(model), int(rounds), int(seed), 1
+    rounds, seed = int(rounds), int(seed)
+    if not 1 <= rounds <= _lib.EPI_MAX_ROUNDS:
+        raise ValueError("%s: rounds must be in 1..%d" % (what, _lib.EPI_MAX_ROUNDS))
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("%s: seed must fit 32 unsigned bits" % what)
+    return True, None, rounds, seed, rounds
+
+
+def _many_sides(what, desc1, LAFs1, counts1, desc2, LAFs2, counts2):
     for t, name in ((desc1, "desc1"), (LAFs1, "LAFs1"), (desc2, "desc2"), (LAFs2, "LAFs2")):
         engine.require_cuda(t, name)
     a, b = desc1.contiguous().float(), desc2.contiguous().float()
     l1, l2 = LAFs1.contiguous().float(), LAFs2.contiguous().float()
-    rows1, rows2, dev = a.size(0), b.size(0), a.device
+    rows1, rows2 = a.size(0), b.size(0)
     if l1.size(0) != rows1 or l2.size(0) != rows2:
-        raise ValueError("enqueue_match_and_verify_many: one LAF per descriptor row (%d / %d frames for %d / %d descriptors)" % (l1.size(0), l2.size(0), rows1, rows2))
+        raise ValueError("%s: one LAF per descriptor row (%d / %d frames for %d / %d descriptors)" % (what, l1.size(0), l2.size(0), rows1, rows2))
     if sum(int(c) for c in counts1) != rows1 or sum(int(c) for c in counts2) != rows2:
-        raise ValueError("enqueue_match_and_verify_many: the counts do not add up to the rows of the buffers")
+        raise ValueError("%s: the counts do not add up to the rows of the buffers" % what)
+    return a, b, l1, l2
+
+
+class _ManyCall:
+    """The buffers that the calls of one *_many chain share, and the calls themselves: every method enqueues on the current stream and returns
+    device tensors, nothing synchronises."""
+
+    def __init__(self, a, b, l1, l2, table, cap, n2_max, epi, code, rounds, seed, inl_th, lo_iters):
+        self.a, self.b, self.l1, self.l2 = a, b, l1, l2
+        self.rows1, self.rows2, self.dev = a.size(0), b.size(0), a.device
+        self.P, self.cap, self.n2_max = table.shape[0], cap, n2_max
+        self.epi, self.code, self.rounds, self.seed, self.per = epi, code, rounds, seed, rounds if epi else 1
+        self.inl_th, self.lo_iters = float(inl_th), int(lo_iters)
+        P = self.P
+        self.d_pairs = torch.from_numpy(table).to(self.dev)
+        verify_bytes = lib.affnet_epipolar_many_scratch_bytes(P, cap, rounds) if epi else lib.affnet_verify_many_scratch_bytes(P, cap)
+        self.scratch = torch.empty(max(lib.affnet_match_many_scratch_bytes(P, cap, n2_max), lib.affnet_match_guided_many_scratch_bytes(P, cap, n2_max, 0),
+                                       verify_bytes), dtype=torch.uint8, device=self.dev)
+        self.one = torch.zeros(8, dtype=torch.float32, device=self.dev)           # stands in for an empty side: never read, but the boundary refuses NULL
+        self.ctx, self.st = engine.utility_ctx(self.dev), engine.stream_of(self.dev)
+
+    def _side(self, t, rows):
+        return ptr(t if rows else self.one)
+
+    def match(self, SNN_threshold):
+        P, cap, dev = self.P, self.cap, self.dev
+        tent, cnt = _many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P)
+        md, md2, idx = _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.int32, P, cap)
+        rc = lib.affnet_match_snn_many(self.ctx, self._side(self.a, self.rows1), self.rows1, self._side(self.b, self.rows2), self.rows2, self.a.size(1),
+                                       ptr(self.d_pairs), P, cap, self.n2_max, float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt),
+                                       ptr(self.scratch), self.st)
+        check(rc, self.ctx, "affnet_match_snn_many")
+        return tent, cnt
+
+    def verify(self, tent, cnt):
+        P, cap, dev = self.P, self.cap, self.dev
+        H, inl = _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap)
+        counts, summary = _many_buf(dev, torch.int32, P, cap * self.per), _many_buf(dev, torch.int32, P, 4)
+        l1, l2 = self._side(self.l1, self.rows1), self._side(self.l2, self.rows2)
+        if self.epi:
+            rc = lib.affnet_epipolar_verify_many(self.ctx, l1, self.rows1, l2, self.rows2, ptr(self.d_pairs), P, ptr(tent), ptr(cnt), cap, self.inl_th,
+                                                 self.rounds, self.seed, self.lo_iters, ptr(counts), ptr(H), ptr(inl), ptr(summary), ptr(self.scratch), self.st)
+            check(rc, self.ctx, "affnet_epipolar_verify_many")
+        else:
+            rc = lib.affnet_verify_matches_many(self.ctx, l1, self.rows1, l2, self.rows2, ptr(self.d_pairs), P, ptr(tent), ptr(cnt), cap, self.inl_th,
+                                                self.code, self.lo_iters, ptr(counts), ptr(H), ptr(inl), ptr(summary), ptr(self.scratch), self.st)
+            check(rc, self.ctx, "affnet_verify_matches_many")
+        return H, inl, counts, summary
+
+    def guided(self, H, gate, kind, radius, threshold, mutual):
+        P, cap, dev = self.P, self.cap, self.dev
+        tent, cnt = _many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P)
+        dist, idx = _many_buf(dev, torch.float32, P, cap, 2), _many_buf(dev, torch.int32, P, cap, 2)
+        rc = lib.affnet_match_guided_many(self.ctx, self._side(self.a, self.rows1), self.rows1, self._side(self.b, self.rows2), self.rows2, self.a.size(1),
+                                          self._side(self.l1, self.rows1), self._side(self.l2, self.rows2), ptr(self.d_pairs), P, cap, self.n2_max, ptr(H), kind,
+                                          radius, float(threshold), float("inf"), _lib.GUIDED_MUTUAL if mutual else 0, 0, ptr(gate), ptr(dist), ptr(idx),
+                                          ptr(tent), ptr(cnt), ptr(self.scratch), self.st)
+        check(rc, self.ctx, "affnet_match_guided_many")
+        return tent, cnt
+
+
+def enqueue_match_and_verify_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3,
+                                  rounds=8, seed=0):
+    """match_and_verify for P image pairs in one chain of launches on the current stream, no synchronisation.  desc1 (rows1,128) / LAFs1 (rows1,2,3)
+    hold the images of side 1 back to back, counts1[i] rows for image i; side 2 likewise (it may be the same tensors); pairs = [(a, b), ...] image
+    indices into the two sides.  Returns capacity-sized device tensors, cap = the largest n1 of a pair: (tent (P,cap,2) int32 with indices local to
+    the pair's images, count (P,) int32, H (P,3,3) float64, inliers (P,cap) uint8, counts (P,cap) int32, summary (P,4) int32); per pair, rows below
+    count[p] are what match_and_verify gives for that pair, bit for bit, rows at or beyond it are zero.
+    model='fundamental' verifies with affnet_epipolar_verify_many, which alone reads `rounds` and `seed`: H is then F, and counts is (P, cap*rounds),
+    hypothesis h = s * rounds + r of pair p in counts[p, h]."""
+    what = "enqueue_match_and_verify_many"
+    epi, code, rounds, seed, per = _many_model(model, rounds, seed, what)
+    a, b, l1, l2 = _many_sides(what, desc1, LAFs1, counts1, desc2, LAFs2, counts2)
     table, cap, n2_max = pair_table(counts1, counts2, pairs)
-    P = table.shape[0]
-    tent, cnt = _many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P)
-    H, inl = _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap)
-    counts, summary = _many_buf(dev, torch.int32, P, cap), _many_buf(dev, torch.int32, P, 4)
+    P, dev = table.shape[0], a.device
     if P == 0:
-        return tent, cnt, H, inl, counts, summary
-    d_pairs = torch.from_numpy(table).to(dev)
-    md, md2, idx = _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.float32, P, cap), _many_buf(dev, torch.int32, P, cap)
-    scratch = torch.empty(max(lib.affnet_match_many_scratch_bytes(P, cap, n2_max), lib.affnet_verify_many_scratch_bytes(P, cap)), dtype=torch.uint8, device=dev)
-    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty side: never read, but the boundary refuses NULL
-    ctx, st = engine.utility_ctx(dev), engine.stream_of(dev)
-    rc = lib.affnet_match_snn_many(ctx, ptr(a if rows1 else one), rows1, ptr(b if rows2 else one), rows2, a.size(1), ptr(d_pairs), P, cap, n2_max,
-                                   float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt), ptr(scratch), st)
-    check(rc, ctx, "affnet_match_snn_many")
-    rc = lib.affnet_verify_matches_many(ctx, ptr(l1 if rows1 else one), rows1, ptr(l2 if rows2 else one), rows2, ptr(d_pairs), P, ptr(tent), ptr(cnt), cap,
-                                        float(inl_th), _verify_model(model), int(lo_iters), ptr(counts), ptr(H), ptr(inl), ptr(summary), ptr(scratch), st)
-    check(rc, ctx, "affnet_verify_matches_many")
+        return (_many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P), _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap),
+                _many_buf(dev, torch.int32, P, cap * per), _many_buf(dev, torch.int32, P, 4))
+    call = _ManyCall(a, b, l1, l2, table, cap, n2_max, epi, code, rounds, seed, inl_th, lo_iters)
+    tent, cnt = call.match(SNN_threshold)
+    H, inl, counts, summary = call.verify(tent, cnt)
     return tent, cnt, H, inl, counts, summary
 
 
-def match_and_verify_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
-    """match_and_verify for every pair (a, b) of `pairs`, image indices into the lists descs / LAFs (one (n_i,128) / (n_i,2,3) device tensor per
-    image; both sides of a pair come from the same lists), as one device call chain and ONE read-back.
-    Returns a list of P tuples (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), each what match_and_verify returns for that pair."""
+def _many_lists(what, descs, LAFs, pairs):
+    """The image lists of the list-taking *_many functions as one (D, L, counts) side, or None for an empty list (with no pairs)."""
     if len(descs) != len(LAFs):
-        raise ValueError("match_and_verify_many: one LAF tensor per descriptor tensor")
+        raise ValueError("%s: one LAF tensor per descriptor tensor" % what)
     for t in list(descs) + list(LAFs):
         engine.require_cuda(t, "descs / LAFs")
     if not len(descs):
         if len(pairs):
-            raise ValueError("match_and_verify_many: pairs of an empty image list")
-        return []
+            raise ValueError("%s: pairs of an empty image list" % what)
+        return None
     counts = [int(d.size(0)) for d in descs]
     if any(int(l.size(0)) != c for l, c in zip(LAFs, counts)):
-        raise ValueError("match_and_verify_many: one LAF per descriptor row")
+        raise ValueError("%s: one LAF per descriptor row" % what)
     D = torch.cat([d.contiguous().float() for d in descs], 0)
     L = torch.cat([l.contiguous().float().reshape(-1, 2, 3) for l in LAFs], 0)
-    tent, cnt, H, inl, hyp_counts, summary = enqueue_match_and_verify_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model, lo_iters)
+    return D, L, counts
+
+
+def match_and_verify_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
+    """match_and_verify for every pair (a, b) of `pairs`, image indices into the lists descs / LAFs (one (n_i,128) / (n_i,2,3) device tensor per
+    image; both sides of a pair come from the same lists), as one device call chain and ONE read-back.  model: 'homography', 'affine' or
+    'fundamental' (which alone reads `rounds` and `seed`).
+    Returns a list of P tuples (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), each what match_and_verify returns for that pair."""
+    epi, _, rounds, seed, per = _many_model(model, rounds, seed, "match_and_verify_many")
+    side = _many_lists("match_and_verify_many", descs, LAFs, pairs)
+    if side is None:
+        return []
+    D, L, counts = side
+    tent, cnt, H, inl, hyp_counts, summary = enqueue_match_and_verify_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed)
     host = torch.cat([cnt.view(-1, 1), summary], 1).cpu().tolist()          # the one read-back
     out = []
     for p, row in enumerate(host):
         k = row[0]
-        out.append((tent[p, :k, 0].long(), tent[p, :k, 1].long(), H[p], inl[p, :k].bool(), _verify_info(hyp_counts[p, :k], row[1:])))
+        info = _verify_info(hyp_counts[p, :k * per], row[1:])
+        if epi:
+            info.update(rounds=rounds, seed=seed)
+        out.append((tent[p, :k, 0].long(), tent[p, :k, 1].long(), H[p], inl[p, :k].bool(), info))
     return out
 
 
-def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
-    """Re-ranks `shortlist` (image indices into descs / LAFs) by the number of spatially verified inliers against image `query`, all pairs in one
-    device call.  Returns (order, num_inliers): the shortlist sorted by descending inlier count, ties in shortlist order, and the counts in that order."""
+def enqueue_match_verify_guided_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography",
+                                     guided_threshold=0.9, radius=None, mutual=True, lo_iters=3, rounds=8, seed=0):
+    """match_verify_guided for P image pairs in one chain of launches on the current stream, no synchronisation: affnet_match_snn_many,
+    verification, affnet_match_guided_many - which reads row p of the first stage's models as pair p's model and row p of its summaries as pair
+    p's gate, on the device - and verification of the guided matches.  Sides, counts and pairs as for enqueue_match_and_verify_many; model:
+    'homography', 'affine' or 'fundamental'.
+    Returns (tent, count, H, inliers, counts, summary) of the final stage, shaped as enqueue_match_and_verify_many returns them, then count0 (P,)
+    int32 and summary0 (P,4) int32 of the first stage."""
+    what = "enqueue_match_verify_guided_many"
+    if model not in GUIDED_KINDS:
+        raise ValueError("model must be 'homography', 'affine' or 'fundamental'")
+    kind, radius = _guided_kind(model, radius)
+    epi, code, rounds, seed, per = _many_model(model, rounds, seed, what)
+    a, b, l1, l2 = _many_sides(what, desc1, LAFs1, counts1, desc2, LAFs2, counts2)
+    table, cap, n2_max = pair_table(counts1, counts2, pairs)
+    P, dev = table.shape[0], a.device
+    if P == 0:
+        return (_many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P), _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap),
+                _many_buf(dev, torch.int32, P, cap * per), _many_buf(dev, torch.int32, P, 4), _many_buf(dev, torch.int32, P), _many_buf(dev, torch.int32, P, 4))
+    call = _ManyCall(a, b, l1, l2, table, cap, n2_max, epi, code, rounds, seed, inl_th, lo_iters)
+    tent0, cnt0 = call.match(SNN_threshold)
+    H0, _, _, summary0 = call.verify(tent0, cnt0)
+    tent, cnt = call.guided(H0, summary0, kind, radius, guided_threshold, mutual)
+    H, inl, counts, summary = call.verify(tent, cnt)
+    return tent, cnt, H, inl, counts, summary, cnt0, summary0
+
+
+def match_verify_guided_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", guided_threshold=0.9, radius=None, mutual=True,
+                             lo_iters=3, rounds=8, seed=0):
+    """match_verify_guided for every pair (a, b) of `pairs`, image indices into the lists descs / LAFs as for match_and_verify_many, as one device
+    call chain and ONE read-back.  Returns a list of P tuples, each what match_verify_guided returns for that pair, info["seed_stage"] included."""
+    if model not in GUIDED_KINDS:
+        raise ValueError("model must be 'homography', 'affine' or 'fundamental'")
+    epi, _, rounds, seed, per = _many_model(model, rounds, seed, "match_verify_guided_many")
+    side = _many_lists("match_verify_guided_many", descs, LAFs, pairs)
+    if side is None:
+        return []
+    D, L, counts = side
+    tent, cnt, H, inl, hyp_counts, summary, cnt0, summary0 = enqueue_match_verify_guided_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model,
+                                                                                              guided_threshold, radius, mutual, lo_iters, rounds, seed)
+    host = torch.cat([cnt0.view(-1, 1), summary0, cnt.view(-1, 1), summary], 1).cpu().tolist()          # the one read-back
+    out = []
+    for p, row in enumerate(host):
+        k = row[5]
+        info = _verify_info(hyp_counts[p, :k * per], row[6:])
+        if epi:
+            info.update(rounds=rounds, seed=seed)
+        info["seed_stage"] = {"tentatives": row[0], "num_inliers": row[3], "flags": row[4]}
+        out.append((tent[p, :k, 0].long(), tent[p, :k, 1].long(), H[p], inl[p, :k].bool(), info))
+    return out
+
+
+def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0, guided=False):
+    """Re-ranks `shortlist` (image indices into descs / LAFs) by the number of verified inliers against image `query`, all pairs in one device call
+    chain.  model: 'homography', 'affine' or 'fundamental' (a scene with depth; it alone reads `rounds` and `seed`); guided: the inliers of
+    match_verify_guided_many (defaults of its guided_threshold and radius) instead of match_and_verify_many's.
+    Returns (order, num_inliers): the shortlist sorted by descending inlier count, ties in shortlist order, and the counts in that order."""
     shortlist = [int(s) for s in shortlist]
-    res = match_and_verify_many(descs, LAFs, [(int(query), s) for s in shortlist], SNN_threshold, inl_th, model, lo_iters)
+    pairs = [(int(query), s) for s in shortlist]
+    if guided:
+        res = match_verify_guided_many(descs, LAFs, pairs, SNN_threshold, inl_th, model, lo_iters=lo_iters, rounds=rounds, seed=seed)
+    else:
+        res = match_and_verify_many(descs, LAFs, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed)
     n = [r[4]["num_inliers"] for r in res]
     rank = sorted(range(len(shortlist)), key=lambda i: -n[i])          # sorted() is stable: ties keep the shortlist's order
     return [shortlist[i] for i in rank], [n[i] for i in rank]

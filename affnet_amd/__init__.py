@@ -13,6 +13,7 @@ from .ReprojectionStuff import verify_matches, enqueue_verify, match_and_verify 
 from .ReprojectionStuff import verify_epipolar, enqueue_verify_epipolar, sampson_distance  # noqa: F401
 from .ReprojectionStuff import enqueue_match_guided, match_guided, guided_mask, match_verify_guided  # noqa: F401
 from .ReprojectionStuff import pair_table, enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank  # noqa: F401
+from .ReprojectionStuff import enqueue_match_verify_guided_many, match_verify_guided_many  # noqa: F401
 from . import retrieval  # noqa: F401
 from .retrieval import knn, DescriptorIndex  # noqa: F401
 from .retrieval import quantization_scale, quantize, knn_q8, QuantizedDescriptorIndex  # noqa: F401

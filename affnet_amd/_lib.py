@@ -140,6 +140,11 @@ SYMBOLS = {
     "affnet_match_guided_scratch_bytes": (_SZ, [_I, _I, _I]),
     "affnet_match_guided": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "affnet_guided_mask": (_I, [_P, _P, _I, _P, _I, _P, _I, C.c_float, _P, _P, _P]),
+    "affnet_epipolar_many_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "affnet_epipolar_verify_many": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, C.c_float, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P]),
+    "affnet_match_guided_many_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_match_guided_many": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P,
+                                      _P, _P]),
     "affnet_knn_chunks": (_I, [_P, _I, _I]),
     "affnet_knn_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_knn": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

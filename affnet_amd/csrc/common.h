@@ -393,8 +393,17 @@ int aff_hardnet_head(affnet_ctx* ctx, const CnnCall& c, const NetLayout& L, int 
 // match.hip: out[r] = |x[r]|^2 of n rows (n <= 0: no launch) by the matcher's own kernel - the one reduction behind every distance of the matcher
 // and of the descriptor index (knn.hip, ivf.hip), which is what makes their distances equal bit for bit
 void aff_sqnorm_launch(hipStream_t st, const float* x, int n, int dim, float* out);
+// match.hip: the same per pair of a *_many call (sqnorm_many_kernel): a_sq (P, n1_max) and b_sq (P, n2_max) of the pairs' segments; a pair out
+// of range or with an empty side gets neither (no distance of such a pair is ever formed)
+void aff_sqnorm_many_launch(hipStream_t st, const float* desc1, int rows1, const float* desc2, int rows2, int dim, const int32_t* pairs, int n_pairs,
+                            int n1_max, int n2_max, float* a_sq, float* b_sq);
 // knn.hip: the n_lists partial lists (n1, n_lists, k) of every row -> its k neighbours (knn_merge_kernel; the chunks of affnet_knn, the probed cells of affnet_ivf_search)
 void aff_knn_merge_launch(hipStream_t st, const float* part_d, const int32_t* part_i, int n1, int n_lists, int k, float* out_d, int32_t* out_i);
+// knn.hip: the same per pair of a *_many call (knn_merge_pairs_kernel): side 0 merges each pair's n1 rows (pitch n1_max), side 1 its n2 rows (pitch
+// n2_max), of pair-major partial lists (P, pitch, n_lists, k) into (P, pitch, k); pairs out of range or with n1 == 0 and rows at or beyond a pair's
+// count are neither read nor written
+void aff_knn_merge_pairs_launch(hipStream_t st, const float* part_d, const int32_t* part_i, const int32_t* pairs, int n_pairs, int rows1, int rows2,
+                                int n1_max, int n2_max, int side, int n_lists, int k, float* out_d, int32_t* out_i);
 // knn_q8.hip: the same for int lists (knn_q8_merge_kernel; the chunks of affnet_knn_q8, the probed cells of affnet_ivf_search_q8): partial d2 and rows
 // (n1, n_lists, k), unfilled slots hold row -1 -> d2, sqrtf((float)d2) / scale and rows (n1, k), unfilled slots (INT32_MAX, +inf, -1)
 void aff_knn_q8_merge_launch(hipStream_t st, const int32_t* part_d, const int32_t* part_i, int n1, int n_lists, int k, float scale, int32_t* out_d2,

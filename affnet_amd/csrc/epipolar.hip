@@ -15,6 +15,9 @@
 //   epi_select_kernel  spv_select_rows over the T x rounds counts.
 //   epi_lo_kernel      one workgroup, fp64: refits on the inliers of the best hypothesis - 9 x 9 normal matrix by the fixed-order sums of
 //                      spv_block_sum, cyclic Jacobi by one thread on matrices held in LDS, rank 2 through a second 3 x 3 Jacobi.
+//
+// affnet_epipolar_verify_many (end of the file) runs the same five stages for P image pairs per launch: epi_many_*_kernel take the pair index
+// from the grid, find the pair's segments in a device table (spv_many_in) and call the bodies of the kernels above.
 #include <math.h>
 
 #include "common.h"
@@ -104,8 +107,10 @@ __device__ __forceinline__ bool epi_denormalise(double (&F)[9], double s1, doubl
 
 // ---- prep -----------------------------------------------------------------------------------------------------------------------------
 // frm: three float4 per row = (a b x c) (d y a2 b2) (x2 c2 d2 y2), i.e. the twelve numbers in frame order
-__global__ __launch_bounds__(256) void epi_prep_kernel(SpvIn in, float4* __restrict__ pts, float4* __restrict__ frm) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+// The *_body functions are the kernels of one image pair; the __global__ kernels, single-pair here and batched at the end of the file (pair index on
+// a grid dimension), only choose the pointers and the workgroup indices they run on.
+__device__ __forceinline__ void epi_prep_body(const SpvIn& in, float4* __restrict__ pts, float4* __restrict__ frm, int blk) {
+    const int t = blk * 256 + threadIdx.x;
     if (t >= spv_rows(in.count, in.t_max)) return;
     const float qn = __builtin_nanf("");
     float4 p = make_float4(qn, qn, qn, qn), f0 = p, f1 = p, f2 = p;
@@ -120,17 +125,21 @@ __global__ __launch_bounds__(256) void epi_prep_kernel(SpvIn in, float4* __restr
     pts[t] = p; frm[3 * (size_t)t] = f0; frm[3 * (size_t)t + 1] = f1; frm[3 * (size_t)t + 2] = f2;
 }
 
+__global__ __launch_bounds__(256) void epi_prep_kernel(SpvIn in, float4* __restrict__ pts, float4* __restrict__ frm) {
+    epi_prep_body(in, pts, frm, blockIdx.x);
+}
+
 // ---- solve ----------------------------------------------------------------------------------------------------------------------------
 #define EPI_A(r, c) s_A[((r) * 9 + (c)) * EPI_ST + tid]
 
-__global__ __launch_bounds__(EPI_ST) void epi_solve_kernel(const float4* __restrict__ frm, const int32_t* __restrict__ count, int t_max, int rounds, uint32_t seed,
-                                                           float* __restrict__ hyp, int32_t* __restrict__ counts) {
+__device__ __forceinline__ void epi_solve_body(const float4* __restrict__ frm, const int32_t* __restrict__ count, int t_max, int rounds, uint32_t seed,
+                                               float* __restrict__ hyp, int32_t* __restrict__ counts, int blk) {
     __shared__ double s_A[72 * EPI_ST];
     __shared__ double s_f[9 * EPI_ST];
     __shared__ int s_perm[9 * EPI_ST];
     const int tid = threadIdx.x;
     const int rows = spv_rows(count, t_max);
-    const long long h64 = (long long)blockIdx.x * EPI_ST + tid;
+    const long long h64 = (long long)blk * EPI_ST + tid;
     if (h64 >= (long long)rows * rounds) return;
     const int h = (int)h64;
     double F[9];
@@ -214,14 +223,19 @@ __global__ __launch_bounds__(EPI_ST) void epi_solve_kernel(const float4* __restr
     counts[h] = 0;
 }
 
+__global__ __launch_bounds__(EPI_ST) void epi_solve_kernel(const float4* __restrict__ frm, const int32_t* __restrict__ count, int t_max, int rounds, uint32_t seed,
+                                                           float* __restrict__ hyp, int32_t* __restrict__ counts) {
+    epi_solve_body(frm, count, t_max, rounds, seed, hyp, counts, blockIdx.x);
+}
+
 // ---- score + select -------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(EPI_HT) void epi_score_kernel(const float4* __restrict__ pts, const float* __restrict__ hyp, const int32_t* __restrict__ count,
-                                                           int t_max, int rounds, float th2, int32_t* __restrict__ counts) {
+__device__ __forceinline__ void epi_score_body(const float4* __restrict__ pts, const float* __restrict__ hyp, const int32_t* __restrict__ count, int t_max,
+                                               int rounds, float th2, int32_t* __restrict__ counts, int blk_h, int blk_t) {
     __shared__ float4 s_pt[EPI_MC];
     const int rows = spv_rows(count, t_max);
     const long long nh = (long long)rows * rounds;
-    const long long h0 = (long long)blockIdx.x * EPI_HT;
-    const int t0 = blockIdx.y * EPI_MC;
+    const long long h0 = (long long)blk_h * EPI_HT;
+    const int t0 = blk_t * EPI_MC;
     if (h0 >= nh || t0 >= rows) return;                       // uniform over the workgroup
     const int nt = min(EPI_MC, rows - t0);
     for (int k = threadIdx.x; k < nt; k += EPI_HT) s_pt[k] = pts[t0 + k];
@@ -236,9 +250,19 @@ __global__ __launch_bounds__(EPI_HT) void epi_score_kernel(const float4* __restr
     if (c) atomicAdd(&counts[h], c);
 }
 
+__global__ __launch_bounds__(EPI_HT) void epi_score_kernel(const float4* __restrict__ pts, const float* __restrict__ hyp, const int32_t* __restrict__ count,
+                                                           int t_max, int rounds, float th2, int32_t* __restrict__ counts) {
+    epi_score_body(pts, hyp, count, t_max, rounds, th2, counts, blockIdx.x, blockIdx.y);
+}
+
+__device__ __forceinline__ void epi_select_body(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max, int rounds,
+                                                int32_t* __restrict__ best) {
+    spv_select_rows(counts, spv_rows(count, t_max) * rounds, best);
+}
+
 __global__ __launch_bounds__(256) void epi_select_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ count, int t_max, int rounds,
                                                          int32_t* __restrict__ best) {
-    spv_select_rows(counts, spv_rows(count, t_max) * rounds, best);
+    epi_select_body(counts, count, t_max, rounds, best);
 }
 
 // ---- local optimisation ---------------------------------------------------------------------------------------------------------------
@@ -301,7 +325,7 @@ struct EpiLo {
     double* model_out; uint8_t* inlier; int32_t* summary;
 };
 
-__global__ __launch_bounds__(EPI_LO_THREADS) void epi_lo_kernel(EpiLo a) {
+__device__ __forceinline__ void epi_lo_body(const EpiLo& a) {
     __shared__ double s_part[4 * EPI_NSUM], s_sum[EPI_NSUM];
     __shared__ double s_N[81], s_V[81], s_M[9], s_W[9];
     __shared__ double s_m[2][9];           // 0: candidate model, 1: kept model
@@ -420,6 +444,8 @@ __global__ __launch_bounds__(EPI_LO_THREADS) void epi_lo_kernel(EpiLo a) {
     if (tid == 0) { a.summary[0] = best; a.summary[1] = a.best[1]; a.summary[2] = n_best; a.summary[3] = flags; }
 }
 
+__global__ __launch_bounds__(EPI_LO_THREADS) void epi_lo_kernel(EpiLo a) { epi_lo_body(a); }
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 // scratch: pts float4 [t_max] | frm float4 [3 t_max] | hyp float [9 t_max rounds] (+ pad to 16) | best int32 [2] (+ pad to 16) | current mask uint8 [t_max]
 static size_t epi_hyp_bytes(size_t t, size_t rounds) { return aff_align(9 * t * rounds * sizeof(float), 16); }
@@ -493,6 +519,114 @@ extern "C" int affnet_epipolar_verify(affnet_ctx* ctx, const float* d_lafs1, int
     lo.count = d_count; lo.t_max = t_max; lo.pts = b.pts; lo.hyp = b.hyp; lo.best = b.best; lo.th = inl_th; lo.lo_iters = lo_iters; lo.cur = b.cur;
     lo.model_out = d_model; lo.inlier = d_inlier; lo.summary = d_summary;
     hipLaunchKernelGGL(epi_lo_kernel, dim3(1), dim3(EPI_LO_THREADS), 0, st, lo);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// ---- many pairs in one call: the pair index on a grid dimension of every stage --------------------------------------------------------------
+// One pair is latency: five dependent launches, the last of them one workgroup whose Jacobi sweeps run on one thread.  P pairs are P x the
+// workgroups in the same five launches and P concurrent local optimisations.  Every kernel reads its row of the pair table, tests it
+// (spv_many_in -> aff_pair_row, before any load through it), builds the pair's SpvIn from the segments and runs the single-pair body above: per
+// pair the outputs are affnet_epipolar_verify's bit for bit.  SpvMany::hyp holds the frames here, (P, 3 t_max) float4.
+struct EpiMany {
+    SpvMany m;
+    int rounds;
+    float* hyp;                // scratch: (P, 9 t_max rounds)
+    int32_t* counts;           // (P, t_max rounds)
+};
+
+__device__ __forceinline__ size_t epi_many_nh(const EpiMany& e) { return (size_t)e.m.t_max * e.rounds; }
+
+// grid (t_max / 256, P)
+__global__ __launch_bounds__(256) void epi_many_prep_kernel(EpiMany e) {
+    const int p = blockIdx.y;
+    SpvIn in;
+    if (!spv_many_in(e.m, p, in)) return;
+    const size_t o = (size_t)p * e.m.t_max;
+    epi_prep_body(in, e.m.pts + o, e.m.hyp + 3 * o, blockIdx.x);
+}
+
+// grid (t_max rounds / EPI_ST, P)
+__global__ __launch_bounds__(EPI_ST) void epi_many_solve_kernel(EpiMany e, uint32_t seed) {
+    const int p = blockIdx.y;
+    SpvIn in;
+    if (!spv_many_in(e.m, p, in)) return;
+    const size_t oh = (size_t)p * epi_many_nh(e);
+    epi_solve_body(e.m.hyp + 3 * (size_t)p * e.m.t_max, in.count, e.m.t_max, e.rounds, seed, e.hyp + 9 * oh, e.counts + oh, blockIdx.x);
+}
+
+// grid (t_max rounds / EPI_HT, t_max / EPI_MC, P)
+__global__ __launch_bounds__(EPI_HT) void epi_many_score_kernel(EpiMany e, float th2) {
+    const int p = blockIdx.z;
+    SpvIn in;
+    if (!spv_many_in(e.m, p, in)) return;
+    const size_t oh = (size_t)p * epi_many_nh(e);
+    epi_score_body(e.m.pts + (size_t)p * e.m.t_max, e.hyp + 9 * oh, in.count, e.m.t_max, e.rounds, th2, e.counts + oh, blockIdx.x, blockIdx.y);
+}
+
+// grid (P); an out-of-range pair has no rows
+__global__ __launch_bounds__(256) void epi_many_select_kernel(EpiMany e) {
+    const int p = blockIdx.x;
+    SpvIn in;
+    if (!spv_many_in(e.m, p, in)) return;
+    epi_select_body(e.counts + (size_t)p * epi_many_nh(e), in.count, e.m.t_max, e.rounds, e.m.best + 4 * (size_t)p);
+}
+
+// grid (P)
+__global__ __launch_bounds__(EPI_LO_THREADS) void epi_many_lo_kernel(EpiMany e, float th, int lo_iters, uint8_t* __restrict__ cur, int cur_pitch,
+                                                                     double* __restrict__ model_out, uint8_t* __restrict__ inlier, int32_t* __restrict__ summary) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    SpvIn in;
+    if (!spv_many_in(e.m, p, in)) {        // the zero model of flag 1, nothing of the mask, flags 1 | 8
+        if (tid < 9) model_out[9 * (size_t)p + tid] = 0.0;
+        if (tid == 0) { int32_t* s = summary + 4 * (size_t)p; s[0] = -1; s[1] = 0; s[2] = 0; s[3] = 1 | AFFNET_VERIFY_FLAG_PAIR_RANGE; }
+        return;
+    }
+    const size_t o = (size_t)p * e.m.t_max;
+    EpiLo a;
+    a.count = in.count; a.t_max = e.m.t_max; a.pts = e.m.pts + o; a.hyp = e.hyp + 9 * (size_t)p * epi_many_nh(e); a.best = e.m.best + 4 * (size_t)p;
+    a.th = th; a.lo_iters = lo_iters;
+    a.cur = cur + (size_t)p * cur_pitch;
+    a.model_out = model_out + 9 * (size_t)p; a.inlier = inlier + o; a.summary = summary + 4 * (size_t)p;
+    epi_lo_body(a);
+}
+
+// scratch: pts float4 (P, t_max) | frm float4 (P, 3 t_max) | hyp float (P, 9 t_max rounds) in P x epi_hyp_bytes | best int32 (P, 4) |
+// current mask uint8 (P, align16(t_max))
+extern "C" size_t affnet_epipolar_many_scratch_bytes(int n_pairs, int t_max, int rounds) {
+    const size_t P = n_pairs > 0 ? (size_t)n_pairs : 0, t = t_max > 0 ? (size_t)t_max : 0, r = rounds > 0 ? (size_t)rounds : 0;
+    return P * (4 * t * sizeof(float4) + epi_hyp_bytes(t, r) + 16 + aff_align(t, 16)) + 64;
+}
+
+extern "C" int affnet_epipolar_verify_many(affnet_ctx* ctx, const float* d_lafs1, int rows1, const float* d_lafs2, int rows2, const int32_t* d_pairs, int n_pairs,
+                                           const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed, int lo_iters,
+                                           int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    { int rc = epi_check(ctx, "epipolar_verify_many", d_lafs1, rows1, d_lafs2, rows2, d_tent, t_max, inl_th, rounds, d_counts, d_scratch); if (rc) return rc; }
+    if (!d_pairs || !d_model || !d_inlier || !d_summary || n_pairs < 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "epipolar_verify_many: bad argument");
+    if (n_pairs > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "epipolar_verify_many: %d pairs (at most 65535 per call)", n_pairs);
+    if (lo_iters < 0 || lo_iters > 8) return aff_fail(ctx, AFFNET_ERR_INVALID, "epipolar_verify_many: lo_iters %d outside 0..8", lo_iters);
+    if (n_pairs == 0) return AFFNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t P = (size_t)n_pairs;
+    const unsigned gp = (unsigned)n_pairs;
+    EpiMany e;
+    e.m.lafs1 = d_lafs1; e.m.rows1 = rows1; e.m.lafs2 = d_lafs2; e.m.rows2 = rows2; e.m.pairs = d_pairs; e.m.tent = d_tent; e.m.count = d_count; e.m.t_max = t_max;
+    e.m.pts = (float4*)d_scratch;
+    e.m.hyp = e.m.pts + P * t_max;
+    e.hyp = (float*)(e.m.hyp + 3 * P * t_max);
+    e.m.best = (int32_t*)((char*)e.hyp + P * epi_hyp_bytes((size_t)t_max, (size_t)rounds));
+    uint8_t* cur = (uint8_t*)(e.m.best + 4 * P);
+    e.rounds = rounds; e.counts = d_counts;
+    if (t_max > 0) {
+        const int nh = t_max * rounds;
+        hipLaunchKernelGGL(epi_many_prep_kernel, dim3(aff_cdiv(t_max, 256), gp), dim3(256), 0, st, e);
+        hipLaunchKernelGGL(epi_many_solve_kernel, dim3(aff_cdiv(nh, EPI_ST), gp), dim3(EPI_ST), 0, st, e, seed);
+        hipLaunchKernelGGL(epi_many_score_kernel, dim3(aff_cdiv(nh, EPI_HT), aff_cdiv(t_max, EPI_MC), gp), dim3(EPI_HT), 0, st, e, inl_th * inl_th);
+    }
+    hipLaunchKernelGGL(epi_many_select_kernel, dim3(gp), dim3(256), 0, st, e);
+    hipLaunchKernelGGL(epi_many_lo_kernel, dim3(gp), dim3(EPI_LO_THREADS), 0, st, e, inl_th, lo_iters, cur, (int)aff_align((size_t)t_max, 16), d_model, d_inlier,
+                       d_summary);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;
 }

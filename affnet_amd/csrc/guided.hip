@@ -9,6 +9,9 @@
 //
 // The per-point terms of the geometric test are computed once (guided_prep_kernel) and read by the forward pass, the backward pass and the
 // mask kernel through ONE function (guided_ok), so the three cannot disagree about a pair.  -ffp-contract=off: one rounding per operation.
+//
+// affnet_match_guided_many (end of the file) runs the same stages for P image pairs per launch: guided_many_*_kernel take the pair index from
+// the grid, find the pair's segments in a device table and call the bodies of the kernels below, each pair under its own model and gate.
 #include <math.h>
 
 #include "common.h"
@@ -25,14 +28,16 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 //   planar    image 1: (px, py, W > 0 ? 1 : 0, -)   image 2: (u, v, -, -)
 //   epipolar  image 1: (l0, l1, l2, -)              image 2: (u, v, m0, m1)
 // grid (cdiv(max(n1, n2), 256), 2): blockIdx.y = 0 image 1, 1 image 2
+// The *_body functions are the kernels of one image pair; the __global__ kernels, single-pair here and batched at the end of the file (pair index on
+// a grid dimension), only choose the pointers and the workgroup indices they run on.
 template <int KIND>
-__global__ __launch_bounds__(256) void guided_prep_kernel(const float* __restrict__ lafs1, int n1, const float* __restrict__ lafs2, int n2,
-                                                          const double* __restrict__ model, float4* __restrict__ p1, float4* __restrict__ p2) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void guided_prep_body(const float* __restrict__ lafs1, int n1, const float* __restrict__ lafs2, int n2,
+                                                 const double* __restrict__ model, float4* __restrict__ p1, float4* __restrict__ p2, int blk, int side) {
+    const int i = blk * 256 + threadIdx.x;
     float m[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) m[k] = (float)model[k];
-    if (blockIdx.y == 0) {
+    if (side == 0) {
         if (i >= n1) return;
         const float x = lafs1[6 * (size_t)i + 2], y = lafs1[6 * (size_t)i + 5];
         if (KIND == AFFNET_GUIDED_PLANAR) {
@@ -52,6 +57,12 @@ __global__ __launch_bounds__(256) void guided_prep_kernel(const float* __restric
             p2[i] = make_float4(u, v, m0, m1);
         }
     }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void guided_prep_kernel(const float* __restrict__ lafs1, int n1, const float* __restrict__ lafs2, int n2,
+                                                          const double* __restrict__ model, float4* __restrict__ p1, float4* __restrict__ p2) {
+    guided_prep_body<KIND>(lafs1, n1, lafs2, n2, model, p1, p2, blockIdx.x, blockIdx.y);
 }
 
 // The admissible test of the pair (image-1 point with terms a, image-2 point with terms b).  Epipolar: epi_inlier's tree (epipolar.hip).
@@ -96,11 +107,11 @@ __device__ __forceinline__ void guided_lanes_store(TopkList<float, CAP>& L, bool
 // its one column per tile, in front of the MFMAs.  gate != NULL and gate[3] & 1: no tile is walked, every list stays unfilled.
 // out_d / out_i: (n1, n_chunks, CAP).
 template <int KIND, int CAP, bool SWAP>
-__global__ __launch_bounds__(256) void guided_tile_kernel(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
-                                                          const float* __restrict__ a_sq, const float* __restrict__ b_sq,
-                                                          const float4* __restrict__ ta, const float4* __restrict__ tb, float r2,
-                                                          const int32_t* __restrict__ gate, int tpc, float* __restrict__ out_d,
-                                                          int32_t* __restrict__ out_i) {
+__device__ __forceinline__ void guided_tile_body(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
+                                                 const float* __restrict__ a_sq, const float* __restrict__ b_sq,
+                                                 const float4* __restrict__ ta, const float4* __restrict__ tb, float r2,
+                                                 const int32_t* __restrict__ gate, int tpc, float* __restrict__ out_d,
+                                                 int32_t* __restrict__ out_i, int blk, int chunk, int n_chunks) {
     constexpr int DIM = 128;
     constexpr int NG = DIM / 16;
     constexpr int BS = GUIDED_BS(DIM), Q = DIM / 4, NPRE = 16 * Q / 256;
@@ -108,8 +119,7 @@ __global__ __launch_bounds__(256) void guided_tile_kernel(const float* __restric
     __shared__ __attribute__((aligned(16))) float s_b[2 * 16 * BS];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int m = lane & 15, kq = lane >> 4;
-    const int row0 = blockIdx.x * 64 + wave * 16;
-    const int chunk = blockIdx.y, n_chunks = gridDim.y;
+    const int row0 = blk * 64 + wave * 16;
     const int tiles = (n2 + 15) >> 4;
     const long long t0l = (long long)chunk * tpc;
     const bool closed = gate && (gate[3] & 1);                                            // uniform over the grid
@@ -197,10 +207,19 @@ __global__ __launch_bounds__(256) void guided_tile_kernel(const float* __restric
     }
 }
 
+template <int KIND, int CAP, bool SWAP>
+__global__ __launch_bounds__(256) void guided_tile_kernel(const float* __restrict__ a, int n1, const float* __restrict__ b, int n2,
+                                                          const float* __restrict__ a_sq, const float* __restrict__ b_sq,
+                                                          const float4* __restrict__ ta, const float4* __restrict__ tb, float r2,
+                                                          const int32_t* __restrict__ gate, int tpc, float* __restrict__ out_d,
+                                                          int32_t* __restrict__ out_i) {
+    guided_tile_body<KIND, CAP, SWAP>(a, n1, b, n2, a_sq, b_sq, ta, tb, r2, gate, tpc, out_d, out_i, blockIdx.x, blockIdx.y, gridDim.y);
+}
+
 // One workgroup: the selection rule + order-preserving compaction (match.hip, snn_select_body).  dist / idx: (n1, 2); back: (n2) or NULL.
-__global__ __launch_bounds__(1024) void guided_select_kernel(const float* __restrict__ dist, const int32_t* __restrict__ idx,
-                                                             const int32_t* __restrict__ back, int n1, float thr, float max_dist,
-                                                             int32_t* __restrict__ tent, int32_t* __restrict__ count) {
+__device__ __forceinline__ void guided_select_body(const float* __restrict__ dist, const int32_t* __restrict__ idx,
+                                                   const int32_t* __restrict__ back, int n1, float thr, float max_dist,
+                                                   int32_t* __restrict__ tent, int32_t* __restrict__ count) {
     __shared__ int s_wave[16];
     __shared__ int s_base;
     if (threadIdx.x == 0) s_base = 0;
@@ -232,6 +251,12 @@ __global__ __launch_bounds__(1024) void guided_select_kernel(const float* __rest
     if (threadIdx.x == 0) *count = s_base;
 }
 
+__global__ __launch_bounds__(1024) void guided_select_kernel(const float* __restrict__ dist, const int32_t* __restrict__ idx,
+                                                             const int32_t* __restrict__ back, int n1, float thr, float max_dist,
+                                                             int32_t* __restrict__ tent, int32_t* __restrict__ count) {
+    guided_select_body(dist, idx, back, n1, thr, max_dist, tent, count);
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 // the most chunks the library chooses for `cols` columns (aff_chunk_choice never goes above units / min_units)
 static size_t guided_most_chunks(size_t cols) {
@@ -239,10 +264,11 @@ static size_t guided_most_chunks(size_t cols) {
     return most < 1 ? 1 : (most > GUIDED_MAX_CHUNKS ? GUIDED_MAX_CHUNKS : most);
 }
 
-static int guided_chunks(const affnet_ctx* ctx, int rows, int cols, int n_chunks) {
+// `pairs` searches of `rows` x `cols` each share the part: the grid's row blocks are theirs together
+static int guided_chunks(const affnet_ctx* ctx, int rows, int cols, int n_chunks, int pairs = 1) {
     if (n_chunks) return n_chunks;
-    return aff_chunk_choice(ctx, rows > 0 ? aff_cdiv(rows, 64) : 1, cols > 0 ? ((long long)cols + 15) / 16 : 0, GUIDED_WG_PER_CU, GUIDED_MIN_TILES,
-                            GUIDED_MAX_CHUNKS);
+    return aff_chunk_choice(ctx, (long long)pairs * (rows > 0 ? aff_cdiv(rows, 64) : 1), cols > 0 ? ((long long)cols + 15) / 16 : 0, GUIDED_WG_PER_CU,
+                            GUIDED_MIN_TILES, GUIDED_MAX_CHUNKS);
 }
 
 // scratch: terms of image 1 float4 (n1) | terms of image 2 float4 (n2) | a_sq float (n1) | b_sq float (n2) | back distance float (n2) |
@@ -361,6 +387,147 @@ extern "C" int affnet_match_guided(affnet_ctx* ctx, const float* d_desc1, int n1
         guided_passes_launch<AFFNET_GUIDED_EPIPOLAR>(st, c);
     }
     hipLaunchKernelGGL(guided_select_kernel, dim3(1), dim3(1024), 0, st, (const float*)d_dist, (const int32_t*)d_idx, (const int32_t*)c.back_i, n1,
+                       snn_threshold, max_dist, d_tent, d_count);
+    AFF_LAUNCH_CHECK(ctx);
+    return AFFNET_OK;
+}
+
+// ---- many pairs in one call: the pair index on a grid dimension of every stage --------------------------------------------------------------
+// One pair of 2000 x 2000 is 32 row blocks on 256 CUs and a chain of short launches; P pairs are P x the workgroups in the same launches.  Every
+// kernel reads its row of the pair table, tests it (aff_pair_row, before any load through it) and runs the single-pair body above on the pair's
+// segments under the pair's own model row and gate row: per pair the outputs are affnet_match_guided's bit for bit.  The chunk count is one per
+// launch (from the caps), which the result does not depend on; a chunk past a pair's own columns leaves unfilled lists for the merge.
+struct GuidedMany {
+    const float* desc1; int rows1;
+    const float* desc2; int rows2;
+    const float* lafs1; const float* lafs2;
+    const int32_t* pairs;
+    int n1_max, n2_max;
+    const double* model;               // (P, 9)
+    const int32_t* gate;               // (P, 4) or NULL
+    float4* p1; float4* p2;            // scratch: (P, n1_max), (P, n2_max)
+    float* a_sq; float* b_sq;          // scratch: (P, n1_max), (P, n2_max)
+    float* back_d; int32_t* back_i;    // scratch: (P, n2_max)
+};
+
+// false: the row is out of range, or image 1 of the pair is empty - nothing to do either way (d_count was cleared)
+__device__ __forceinline__ bool guided_many_row(const GuidedMany& g, int p, AffPairRow& r) {
+    return aff_pair_row(g.pairs, p, g.rows1, g.rows2, g.n1_max, g.n2_max, r) && r.n1 > 0;
+}
+
+// grid (cdiv(max(n1_max, n2_max), 256), 2, P)
+template <int KIND>
+__global__ __launch_bounds__(256) void guided_many_prep_kernel(GuidedMany g) {
+    const int p = blockIdx.z;
+    AffPairRow r;
+    if (!guided_many_row(g, p, r)) return;
+    guided_prep_body<KIND>(g.lafs1 + 6 * (size_t)r.row1, r.n1, g.lafs2 + 6 * (size_t)r.row2, r.n2, g.model + 9 * (size_t)p, g.p1 + (size_t)p * g.n1_max,
+                           g.p2 + (size_t)p * g.n2_max, blockIdx.x, blockIdx.y);
+}
+
+// grid (cdiv(rows_max, 64), n_chunks, P), rows = image 1 (forward) or, SWAP, image 2 (backward: a pair without rows in image 2 has no backward
+// pass).  out_d / out_i: (P, rows_max, n_chunks, CAP).
+template <int KIND, int CAP, bool SWAP>
+__global__ __launch_bounds__(256) void guided_many_tile_kernel(GuidedMany g, float r2, int tpc, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+    const int p = blockIdx.z;
+    AffPairRow r;
+    if (!guided_many_row(g, p, r)) return;
+    if (SWAP && r.n2 == 0) return;
+    const float* d1 = g.desc1 + 128 * (size_t)r.row1;
+    const float* d2 = g.desc2 + 128 * (size_t)r.row2;
+    const size_t o1 = (size_t)p * g.n1_max, o2 = (size_t)p * g.n2_max;
+    const int32_t* gate = g.gate ? g.gate + 4 * (size_t)p : nullptr;
+    const size_t o = (SWAP ? o2 : o1) * gridDim.y * CAP;
+    if (SWAP)
+        guided_tile_body<KIND, CAP, true>(d2, r.n2, d1, r.n1, g.b_sq + o2, g.a_sq + o1, g.p2 + o2, g.p1 + o1, r2, gate, tpc, out_d + o, out_i + o, blockIdx.x,
+                                          blockIdx.y, gridDim.y);
+    else
+        guided_tile_body<KIND, CAP, false>(d1, r.n1, d2, r.n2, g.a_sq + o1, g.b_sq + o2, g.p1 + o1, g.p2 + o2, r2, gate, tpc, out_d + o, out_i + o, blockIdx.x,
+                                           blockIdx.y, gridDim.y);
+}
+
+// grid (P).  dist / idx: (P, n1_max, 2); tent (P, n1_max, 2); count (P)
+__global__ __launch_bounds__(1024) void guided_many_select_kernel(GuidedMany g, const float* __restrict__ dist, const int32_t* __restrict__ idx, int mutual,
+                                                                  float thr, float max_dist, int32_t* __restrict__ tent, int32_t* __restrict__ count) {
+    const int p = blockIdx.x;
+    AffPairRow r;
+    if (!guided_many_row(g, p, r)) return;
+    const size_t o = (size_t)p * g.n1_max;
+    guided_select_body(dist + 2 * o, idx + 2 * o, mutual ? g.back_i + (size_t)p * g.n2_max : (const int32_t*)nullptr, r.n1, thr, max_dist, tent + 2 * o,
+                       count + p);
+}
+
+// scratch: terms of image 1 float4 (P, n1_max) | terms of image 2 float4 (P, n2_max) | a_sq float (P, n1_max) | b_sq float (P, n2_max) |
+// back distance float (P, n2_max) | back row int32 (P, n2_max) | partial distances float | partial rows int32 - the partial lists of the larger of
+// (P, n1_max, chunks, 2) and (P, n2_max, chunks, 1)
+extern "C" size_t affnet_match_guided_many_scratch_bytes(int n_pairs, int n1_max, int n2_max, int n_chunks) {
+    const size_t P = n_pairs > 0 ? (size_t)n_pairs : 0, a = n1_max > 0 ? (size_t)n1_max : 0, b = n2_max > 0 ? (size_t)n2_max : 0;
+    const size_t ncf = n_chunks > 0 ? (size_t)n_chunks : (n_chunks == 0 ? guided_most_chunks(b) : 0);
+    const size_t ncb = n_chunks > 0 ? (size_t)n_chunks : (n_chunks == 0 ? guided_most_chunks(a) : 0);
+    const size_t fwd = a * ncf * 2, bwd = b * ncb;
+    return P * (guided_head_bytes(a, b) + (fwd > bwd ? fwd : bwd) * (sizeof(float) + sizeof(int32_t))) + 64;
+}
+
+template <int KIND>
+static void guided_many_launch(hipStream_t st, const GuidedMany& g, int n_pairs, float r2, int ncf, int ncb, bool mutual, float* part_d, int32_t* part_i,
+                               float* d_dist, int32_t* d_idx) {
+    const unsigned gp = (unsigned)n_pairs;
+    const int n1 = g.n1_max, n2 = g.n2_max;
+    hipLaunchKernelGGL(guided_many_prep_kernel<KIND>, dim3(aff_cdiv(n1 > n2 ? n1 : n2, 256), 2, gp), dim3(256), 0, st, g);
+    {
+        const int tpc = aff_cdiv(aff_cdiv(n2, 16), ncf);
+        hipLaunchKernelGGL((guided_many_tile_kernel<KIND, 2, false>), dim3(aff_cdiv(n1, 64), ncf, gp), dim3(256), 0, st, g, r2, tpc, ncf == 1 ? d_dist : part_d,
+                           ncf == 1 ? d_idx : part_i);
+        if (ncf > 1) aff_knn_merge_pairs_launch(st, part_d, part_i, g.pairs, n_pairs, g.rows1, g.rows2, n1, n2, 0, ncf, 2, d_dist, d_idx);
+    }
+    if (mutual && n2 > 0) {
+        const int tpc = aff_cdiv(aff_cdiv(n1, 16), ncb);
+        hipLaunchKernelGGL((guided_many_tile_kernel<KIND, 1, true>), dim3(aff_cdiv(n2, 64), ncb, gp), dim3(256), 0, st, g, r2, tpc, ncb == 1 ? g.back_d : part_d,
+                           ncb == 1 ? g.back_i : part_i);
+        if (ncb > 1) aff_knn_merge_pairs_launch(st, part_d, part_i, g.pairs, n_pairs, g.rows1, g.rows2, n1, n2, 1, ncb, 1, g.back_d, g.back_i);
+    }
+}
+
+extern "C" int affnet_match_guided_many(affnet_ctx* ctx, const float* d_desc1, int rows1, const float* d_desc2, int rows2, int dim, const float* d_lafs1,
+                                        const float* d_lafs2, const int32_t* d_pairs, int n_pairs, int n1_max, int n2_max, const double* d_model, int kind,
+                                        float radius, float snn_threshold, float max_dist, int flags, int n_chunks, const int32_t* d_gate, float* d_dist,
+                                        int32_t* d_idx, int32_t* d_tent, int32_t* d_count, void* d_scratch, void* stream) {
+    AFF_DEVICE(ctx);
+    if (!ctx || !d_desc1 || !d_desc2 || !d_lafs1 || !d_lafs2 || !d_pairs || !d_model || !d_dist || !d_idx || !d_tent || !d_count || !d_scratch || rows1 < 0 ||
+        rows2 < 0 || n_pairs < 0 || n1_max < 0 || n2_max < 0)
+        return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: bad argument");
+    if (((uintptr_t)d_scratch & 15) != 0) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: d_scratch must be 16-byte aligned");
+    if (dim != 128) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: descriptor length %d (only 128 is built)", dim);
+    if (n_pairs > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: %d pairs (at most 65535 per call)", n_pairs);
+    if (kind != AFFNET_GUIDED_PLANAR && kind != AFFNET_GUIDED_EPIPOLAR) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: kind %d", kind);
+    if (flags & ~AFFNET_GUIDED_MUTUAL) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: flags %d", flags);
+    if (!guided_radius_ok(radius)) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: the radius must be finite and > 0");
+    if (max_dist != max_dist) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: max_dist is NaN");
+    if (n_chunks < 0 || n_chunks > 65535) return aff_fail(ctx, AFFNET_ERR_INVALID, "match_guided_many: %d chunks (0..65535)", n_chunks);
+    if (n_pairs == 0) return AFFNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t P = (size_t)n_pairs, a = (size_t)n1_max, b = (size_t)n2_max;
+    { int zrc = aff_zero_async(ctx, d_count, P * sizeof(int32_t), st); if (zrc) return zrc; }
+    if (n1_max == 0) return AFFNET_OK;               // image 1 of every pair is empty, or the pair is out of range
+    const bool mutual = (flags & AFFNET_GUIDED_MUTUAL) != 0;
+    GuidedMany g;
+    g.desc1 = d_desc1; g.rows1 = rows1; g.desc2 = d_desc2; g.rows2 = rows2; g.lafs1 = d_lafs1; g.lafs2 = d_lafs2; g.pairs = d_pairs;
+    g.n1_max = n1_max; g.n2_max = n2_max; g.model = d_model; g.gate = d_gate;
+    g.p1 = (float4*)d_scratch;
+    g.p2 = g.p1 + P * a;
+    g.a_sq = (float*)(g.p2 + P * b);
+    g.b_sq = g.a_sq + P * a;
+    g.back_d = g.b_sq + P * b;
+    g.back_i = (int32_t*)(g.back_d + P * b);
+    const int ncf = guided_chunks(ctx, n1_max, n2_max, n_chunks, n_pairs), ncb = guided_chunks(ctx, n2_max, n1_max, n_chunks, n_pairs);
+    const size_t fwd = P * a * ncf * 2, bwd = P * b * ncb;
+    float* part_d = (float*)((char*)d_scratch + P * guided_head_bytes(a, b));
+    int32_t* part_i = (int32_t*)(part_d + (fwd > bwd ? fwd : bwd));
+    const float r2 = radius * radius;
+    aff_sqnorm_many_launch(st, d_desc1, rows1, d_desc2, rows2, dim, d_pairs, n_pairs, n1_max, n2_max, g.a_sq, g.b_sq);
+    if (kind == AFFNET_GUIDED_PLANAR) guided_many_launch<AFFNET_GUIDED_PLANAR>(st, g, n_pairs, r2, ncf, ncb, mutual, part_d, part_i, d_dist, d_idx);
+    else guided_many_launch<AFFNET_GUIDED_EPIPOLAR>(st, g, n_pairs, r2, ncf, ncb, mutual, part_d, part_i, d_dist, d_idx);
+    hipLaunchKernelGGL(guided_many_select_kernel, dim3((unsigned)n_pairs), dim3(1024), 0, st, g, (const float*)d_dist, (const int32_t*)d_idx, mutual ? 1 : 0,
                        snn_threshold, max_dist, d_tent, d_count);
     AFF_LAUNCH_CHECK(ctx);
     return AFFNET_OK;

@@ -137,9 +137,9 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__
 
 // One wavefront per row: the n_lists partial lists of the row (the chunks of a search here, the probed cells of one in ivf.hip) -> its k neighbours.
 template <int CAP>
-__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_lists,
-                                                        int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+__device__ __forceinline__ void knn_merge_body(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_lists, int k,
+                                               float* __restrict__ out_d, int32_t* __restrict__ out_i, int blk) {
+    const int row = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n1) return;      // uniform over the wave
     TopkList<float, CAP> L;
     L.clear();
@@ -152,9 +152,40 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
     knn_lanes_store<64>(L, k, lane == 0, out_d + (size_t)row * k, out_i + (size_t)row * k);
 }
 
+template <int CAP>
+__global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i, int n1, int n_lists,
+                                                        int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+    knn_merge_body<CAP>(part_d, part_i, n1, n_lists, k, out_d, out_i, blockIdx.x);
+}
+
 void aff_knn_merge_launch(hipStream_t st, const float* part_d, const int32_t* part_i, int n1, int n_lists, int k, float* out_d, int32_t* out_i) {
     aff_topk_dispatch(k, [&](auto cap) {
         hipLaunchKernelGGL((knn_merge_kernel<decltype(cap)::value>), dim3(aff_cdiv(n1, 4)), dim3(256), 0, st, part_d, part_i, n1, n_lists, k, out_d, out_i);
+    });
+}
+
+// The same merge for the pairs of a *_many call, grid (rows_max / 4, P): pair p merges the rows of its side `side` (0: n1 rows, pitch n1_max;
+// 1: n2 rows, pitch n2_max) of pair-major partial lists (P, pitch, n_lists, k) into pair-major outputs (P, pitch, k).  The table row is tested
+// before anything is loaded; a pair out of range or with an empty side 1 (it has no lists on either side) and the rows at or beyond the pair's
+// own count are neither read nor written.
+template <int CAP>
+__global__ __launch_bounds__(256) void knn_merge_pairs_kernel(const float* __restrict__ part_d, const int32_t* __restrict__ part_i,
+                                                              const int32_t* __restrict__ pairs, int rows1, int rows2, int n1_max, int n2_max, int side,
+                                                              int n_lists, int k, float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+    const int p = blockIdx.y;
+    AffPairRow r;
+    if (!aff_pair_row(pairs, p, rows1, rows2, n1_max, n2_max, r) || r.n1 == 0) return;
+    const size_t o = (size_t)p * (side ? n2_max : n1_max);
+    knn_merge_body<CAP>(part_d + o * n_lists * k, part_i + o * n_lists * k, side ? r.n2 : r.n1, n_lists, k, out_d + o * k, out_i + o * k, blockIdx.x);
+}
+
+void aff_knn_merge_pairs_launch(hipStream_t st, const float* part_d, const int32_t* part_i, const int32_t* pairs, int n_pairs, int rows1, int rows2,
+                                int n1_max, int n2_max, int side, int n_lists, int k, float* out_d, int32_t* out_i) {
+    const int rows_max = side ? n2_max : n1_max;
+    if (n_pairs <= 0 || rows_max <= 0) return;
+    aff_topk_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL((knn_merge_pairs_kernel<decltype(cap)::value>), dim3(aff_cdiv(rows_max, 4), (unsigned)n_pairs), dim3(256), 0, st, part_d, part_i,
+                           pairs, rows1, rows2, n1_max, n2_max, side, n_lists, k, out_d, out_i);
     });
 }
 

@@ -280,6 +280,15 @@ __global__ __launch_bounds__(256) void sqnorm_many_kernel(SnnMany m, int dim) {
     else sqnorm_body(m.desc2 + (size_t)r.row2 * dim, r.n2, dim, m.b_sq + (size_t)p * m.n2_max, blockIdx.x);
 }
 
+void aff_sqnorm_many_launch(hipStream_t st, const float* desc1, int rows1, const float* desc2, int rows2, int dim, const int32_t* pairs, int n_pairs,
+                            int n1_max, int n2_max, float* a_sq, float* b_sq) {
+    if (n_pairs <= 0 || n1_max <= 0 || n2_max <= 0) return;
+    SnnMany m;
+    m.desc1 = desc1; m.rows1 = rows1; m.desc2 = desc2; m.rows2 = rows2; m.pairs = pairs; m.n1_max = n1_max; m.n2_max = n2_max;
+    m.a_sq = a_sq; m.b_sq = b_sq; m.used = nullptr; m.used_pitch = 0;
+    hipLaunchKernelGGL(sqnorm_many_kernel, dim3(aff_cdiv(n1_max > n2_max ? n1_max : n2_max, 4), (unsigned)n_pairs, 2), dim3(256), 0, st, m, dim);
+}
+
 // grid (n1_max / 64, P); masked != 0: the second pass, over the columns that are nobody's nearest neighbour in THIS pair
 template <int DIM>
 __global__ __launch_bounds__(256) void rowmin_many_kernel(SnnMany m, int masked, float* __restrict__ out_min, int32_t* __restrict__ out_idx) {

@@ -379,29 +379,7 @@ extern "C" int affnet_verify_matches(affnet_ctx* ctx, const float* d_lafs1, int 
 // the four launches of one pair.  Every kernel reads its row of the pair table, tests it (aff_pair_row, before any load through it), builds the
 // pair's SpvIn from the segments and runs the single-pair body above: per pair the outputs are affnet_verify_matches' bit for bit.
 // The tentative lists are (P, t_max, 2) as affnet_match_snn_many writes them with n1_max = t_max, which is this call's cap on n1; n2 has none.
-struct SpvMany {
-    const float* lafs1; int rows1;
-    const float* lafs2; int rows2;
-    const int32_t* pairs;
-    const int32_t* tent;       // (P, t_max, 2)
-    const int32_t* count;      // (P) or NULL
-    int t_max;
-    float4* pts; float4* hyp;  // scratch: (P, t_max) each
-    int32_t* best;             // scratch: (P, 4), {index, count} of the pair in the first two
-};
-
-// false: pair row out of range
-__device__ __forceinline__ bool spv_many_in(const SpvMany& m, int p, SpvIn& in) {
-    AffPairRow r;
-    if (!aff_pair_row(m.pairs, p, m.rows1, m.rows2, m.t_max, 0x7fffffff, r)) return false;
-    in.lafs1 = m.lafs1 + 6 * (size_t)r.row1; in.n1 = r.n1;
-    in.lafs2 = m.lafs2 + 6 * (size_t)r.row2; in.n2 = r.n2;
-    in.tent = m.tent + 2 * (size_t)p * m.t_max;
-    in.count = m.count ? m.count + p : nullptr;
-    in.t_max = m.t_max;
-    return true;
-}
-
+// SpvMany and spv_many_in (the pair's SpvIn from its table row) are in spatial_dev.h: epipolar.hip builds its pairs with them too.
 // grid (t_max / 256, P)
 __global__ __launch_bounds__(256) void spv_many_prep_kernel(SpvMany m, int32_t* __restrict__ counts) {
     const int p = blockIdx.y;

@@ -11,6 +11,31 @@ struct SpvIn {
     int t_max;
 };
 
+// The arguments that every kernel of a *_many verification shares (affnet_verify_matches_many, affnet_epipolar_verify_many): the two sides, the
+// pair table, the pair-major tentative lists and the pair-major scratch that both model families keep.
+struct SpvMany {
+    const float* lafs1; int rows1;
+    const float* lafs2; int rows2;
+    const int32_t* pairs;
+    const int32_t* tent;       // (P, t_max, 2)
+    const int32_t* count;      // (P) or NULL
+    int t_max;
+    float4* pts; float4* hyp;  // scratch: (P, t_max) each; epipolar.hip keeps the frames in hyp, (P, 3 t_max)
+    int32_t* best;             // scratch: (P, 4), {index, count} of the pair in the first two
+};
+
+// false: pair row out of range
+__device__ __forceinline__ bool spv_many_in(const SpvMany& m, int p, SpvIn& in) {
+    AffPairRow r;
+    if (!aff_pair_row(m.pairs, p, m.rows1, m.rows2, m.t_max, 0x7fffffff, r)) return false;
+    in.lafs1 = m.lafs1 + 6 * (size_t)r.row1; in.n1 = r.n1;
+    in.lafs2 = m.lafs2 + 6 * (size_t)r.row2; in.n2 = r.n2;
+    in.tent = m.tent + 2 * (size_t)p * m.t_max;
+    in.count = m.count ? m.count + p : nullptr;
+    in.t_max = m.t_max;
+    return true;
+}
+
 __device__ __forceinline__ int spv_rows(const int32_t* count, int t_max) {
     if (!count) return t_max;
     return min(max(*count, 0), t_max);

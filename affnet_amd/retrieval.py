@@ -152,11 +152,15 @@ class DescriptorIndex(object):
         order = sorted((i for i, v in enumerate(votes) if v > 0), key=lambda i: (-votes[i], i))[:max(int(top), 0)]
         return order, [votes[i] for i in order]
 
-    def retrieve(self, desc_q, LAFs_q, top=10, k=4, ratio=0.8, exclude=None, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3):
-        """shortlist, then every shortlisted image matched against the query and spatially verified in one device call
-        (enqueue_match_and_verify_many: the query is side 1, the index side 2).  Returns a list of dicts {image, votes, num_inliers, H, tent_in_1,
-        tent_in_2, inliers}, by descending num_inliers, ties in shortlist order; each entry's matching and verification outputs are what
-        match_and_verify(desc_q, descs[image], LAFs_q, LAFs[image]) returns."""
+    def retrieve(self, desc_q, LAFs_q, top=10, k=4, ratio=0.8, exclude=None, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0,
+                 guided=False, guided_threshold=0.9, radius=None):
+        """shortlist, then every shortlisted image matched against the query and verified in one device call chain
+        (enqueue_match_and_verify_many: the query is side 1, the index side 2).  model: 'homography', 'affine' or 'fundamental' (a scene with
+        depth; it alone reads `rounds` and `seed`).  Returns a list of dicts {image, votes, num_inliers, H, tent_in_1, tent_in_2, inliers}, by
+        descending num_inliers, ties in shortlist order; each entry's matching and verification outputs are what
+        match_and_verify(desc_q, descs[image], LAFs_q, LAFs[image]) returns.
+        guided=True: the chain is enqueue_match_verify_guided_many (guided_threshold, radius as in match_verify_guided), each entry's outputs are
+        what match_verify_guided returns for the image, and the entry also has seed_stage = {tentatives, num_inliers, flags} of the first stage."""
         if self.L is None:
             raise ValueError("retrieve: the index was built without LAFs")
         _check_k(k, "retrieve")
@@ -169,14 +173,24 @@ class DescriptorIndex(object):
         images, votes = self.shortlist(q, top, k, ratio, exclude)
         if not images:
             return []
-        tent, cnt, H, inl, _, summary = RS.enqueue_match_and_verify_many(q, lq, [q.size(0)], self.D, self.L, self.counts, [(0, s) for s in images],
-                                                                         SNN_threshold, inl_th, model, lo_iters)
-        host = torch.cat([cnt.view(-1, 1), summary], 1).cpu().tolist()
+        pairs = [(0, s) for s in images]
+        if guided:
+            tent, cnt, H, inl, _, summary, cnt0, summary0 = RS.enqueue_match_verify_guided_many(q, lq, [q.size(0)], self.D, self.L, self.counts, pairs, SNN_threshold,
+                                                                                                inl_th, model, guided_threshold, radius, True, lo_iters, rounds,
+                                                                                                seed)
+            first = torch.cat([cnt0.view(-1, 1), summary0], 1)
+        else:
+            tent, cnt, H, inl, _, summary = RS.enqueue_match_and_verify_many(q, lq, [q.size(0)], self.D, self.L, self.counts, pairs, SNN_threshold, inl_th, model,
+                                                                             lo_iters, rounds, seed)
+            first = summary[:, :0]
+        host = torch.cat([cnt.view(-1, 1), summary, first], 1).cpu().tolist()
         out = []
         for p, row in enumerate(host):
             t = row[0]
             out.append({"image": images[p], "votes": votes[p], "num_inliers": row[3], "H": H[p], "tent_in_1": tent[p, :t, 0].long(),
                         "tent_in_2": tent[p, :t, 1].long(), "inliers": inl[p, :t].bool()})
+            if guided:
+                out[-1]["seed_stage"] = {"tentatives": row[5], "num_inliers": row[8], "flags": row[9]}
         return sorted(out, key=lambda e: -e["num_inliers"])          # sorted() is stable: ties keep the shortlist's order
 
 

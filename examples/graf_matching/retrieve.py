@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Retrieval of one query image from a set of images: descriptor index -> vote shortlist -> spatial verification, on the MI355X.
 
-    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] [--ivf [--cells N --nprobe P]] QUERY IMG [IMG ...]
+    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] [--ivf [--cells N --nprobe P]] [--model homography|affine|fundamental] [--guided] QUERY IMG [IMG ...]
 
 Every image goes through the fused path (detect + AffNet + OriNet + descriptor, N = 1000 keypoints by default).  The IMGs become one
 DescriptorIndex; the query's descriptors are searched against all of them at once (affnet_knn, --k neighbours per descriptor, default 4), every image
@@ -12,7 +12,9 @@ shortlist and the verified order.  Without a HardNet checkpoint the seeded synth
 (affnet_quantize_desc, affnet_knn_q8), the matching and verification of the shortlist on the float ones as before.  --ivf builds an IVFDescriptorIndex: a k-means codebook of --cells
 cells (default: the power of two nearest the square root of the number of descriptors) is trained on the index's descriptors, and every query descriptor
 is compared with the descriptors of its --nprobe (default 8, at most 8) nearest cells only (affnet_ivf_search).  --q8 --ivf together build
-an IVFQuantizedDescriptorIndex: the same codebook, the cells hold the int8 rows (affnet_ivf_search_q8).  A demonstration of the calls, not a retrieval-quality claim.
+an IVFQuantizedDescriptorIndex: the same codebook, the cells hold the int8 rows (affnet_ivf_search_q8).  --model fundamental verifies the shortlist
+with the epipolar model of a scene with depth (affnet_epipolar_verify_many); --guided re-matches every shortlisted image under its verified model
+and verifies again (affnet_match_guided_many), still in one chain with one read-back.  A demonstration of the calls, not a retrieval-quality claim.
 
     python examples/graf_matching/retrieve.py --desc sift tests/golden/graf_img1.png tests/golden/graf_img6.png tests/golden/graf_img1.png"""
 import os
@@ -49,9 +51,10 @@ def main(argv):
     hardnet_path, argv = take(argv, "--hardnet", None)
     cells, argv = take(argv, "--cells", None)
     nprobe, argv = take(argv, "--nprobe", "8")
-    q8, ivf = "--q8" in argv, "--ivf" in argv
-    argv = [a for a in argv if a not in ("--q8", "--ivf")]
-    if desc_kind not in ("hardnet", "sift") or len(argv) < 2:
+    model, argv = take(argv, "--model", "homography")
+    q8, ivf, guided = "--q8" in argv, "--ivf" in argv, "--guided" in argv
+    argv = [a for a in argv if a not in ("--q8", "--ivf", "--guided")]
+    if desc_kind not in ("hardnet", "sift") or model not in ("homography", "affine", "fundamental") or len(argv) < 2:
         sys.exit(__doc__)
     dev = torch.device("cuda:0")
     ld = lambda p: torch.load(p, map_location="cpu", weights_only=False)["state_dict"]
@@ -83,9 +86,10 @@ def main(argv):
     print("vote shortlist (k = %d):" % int(k))
     for rank, (i, v) in enumerate(zip(images, votes)):
         print("%2d. %s  %d votes (%d keypoints)" % (rank + 1, names[i], v, index.counts[i]))
-    print("verified order:")
-    for rank, r in enumerate(index.retrieve(descs[0], lafs[0], top=int(top), k=int(k), SNN_threshold=0.8, inl_th=3.0)):
-        print("%2d. %s  %d verified inliers of %d tentatives (%d votes)" % (rank + 1, names[r["image"]], r["num_inliers"], r["tent_in_1"].numel(), r["votes"]))
+    print("verified order (model %s%s):" % (model, ", guided" if guided else ""))
+    for rank, r in enumerate(index.retrieve(descs[0], lafs[0], top=int(top), k=int(k), SNN_threshold=0.8, inl_th=3.0, model=model, guided=guided)):
+        first = " (first stage: %d inliers of %d tentatives)" % (r["seed_stage"]["num_inliers"], r["seed_stage"]["tentatives"]) if guided else ""
+        print("%2d. %s  %d verified inliers of %d tentatives (%d votes)%s" % (rank + 1, names[r["image"]], r["num_inliers"], r["tent_in_1"].numel(), r["votes"], first))
 
 
 if __name__ == "__main__":

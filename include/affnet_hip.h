@@ -680,6 +680,51 @@ int affnet_match_guided(affnet_ctx* ctx, const float* d_desc1, int n1, const flo
 int affnet_guided_mask(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const double* d_model, int kind,
                        float radius, uint8_t* d_mask, void* d_scratch, void* stream);
 
+/* ---- epipolar verification and guided matching for many image pairs in one call ----
+ *
+ * The rules of the *_many block above hold here word for word: the same pair table d_pairs (P,4) = {row1, n1, row2, n2} on the device, every
+ * kernel tests its table row BEFORE any load through it, indices are LOCAL to the pair's segments, outputs are pair-major with the caps as
+ * row pitch, rows at or beyond a pair's n1 / count are neither read nor written.  Per pair the kernels run the device code of the
+ * single-pair calls (the same functions): every output of pair p is, bit for bit, what affnet_epipolar_verify / affnet_match_guided write
+ * for that pair's segments.  n_pairs == 0 is valid and launches nothing; n_pairs <= 65535.  No allocation, no synchronisation, all work on
+ * `stream`; the number of launches does not depend on P. */
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_epipolar_verify_many.  Negative arguments count as 0. */
+size_t affnet_epipolar_many_scratch_bytes(int n_pairs, int t_max, int rounds);
+
+/* affnet_epipolar_verify per pair, with one inl_th, rounds, seed and lo_iters for all.  d_tent (P,t_max,2) as affnet_match_snn_many /
+ * affnet_match_guided_many write it with n1_max = t_max (so a row with n1 > t_max is out of range here as it is there; there is no cap on
+ * n2); d_count (P) or NULL (= t_max rows are valid in every pair).  d_counts (P,t_max*rounds), hypothesis h = s * rounds + r of pair p at
+ * d_counts[p * t_max * rounds + h]; d_model (P,9) double; d_inlier (P,t_max) uint8; d_summary (P,4).
+ * A row out of range: summary {-1, 0, 0, 1 | AFFNET_VERIFY_FLAG_PAIR_RANGE}, the model all zero (what flag 1 leaves in
+ * affnet_epipolar_verify, not the identity), nothing written to d_counts or d_inlier.  A valid empty pair (count 0): {-1, 0, 0, 1}.
+ * AFFNET_ERR_INVALID in front of the first launch: every check of affnet_epipolar_verify, a NULL d_pairs, a negative rows1, rows2,
+ * n_pairs or t_max, n_pairs > 65535, t_max * rounds above INT32_MAX. */
+int affnet_epipolar_verify_many(affnet_ctx* ctx, const float* d_lafs1, int rows1, const float* d_lafs2, int rows2, const int32_t* d_pairs,
+                                int n_pairs, const int32_t* d_tent, const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed,
+                                int lo_iters, int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch,
+                                void* stream);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_match_guided_many called with this n_chunks (0: enough for whatever the
+ * library may choose).  Negative arguments count as 0. */
+size_t affnet_match_guided_many_scratch_bytes(int n_pairs, int n1_max, int n2_max, int n_chunks);
+
+/* affnet_match_guided per pair, with one kind, radius, snn_threshold, max_dist and flags for all.  Descriptors and frames of a side lie
+ * in one (rows,128) and one (rows,2,3) buffer as for affnet_match_snn_many.  Per pair: its own model, row p of d_model (P,9) double, read
+ * on the device where a *_many verification left it; its own gate, row p of d_gate (P,4) - the d_summary of that verification - or NULL;
+ * its own per-point terms, squared norms and backward lists (in the scratch).  d_dist, d_idx (P,n1_max,2); d_tent (P,n1_max,2);
+ * d_count (P).  n_chunks column chunks per launch, 0: the library chooses, counting the row blocks of all P pairs; the result does not
+ * depend on it.
+ * A row out of range (the rule above, with both caps): count 0, nothing else written.  n1 == 0: count 0, nothing else written; n2 == 0
+ * or a gate row with d_gate[4 p + 3] & 1 (which an out-of-range row of a *_many verification carries too): count 0, the pair's lists
+ * unfilled.
+ * AFFNET_ERR_INVALID in front of the first launch: every check of affnet_match_guided, a NULL d_pairs, a negative rows1, rows2, n_pairs,
+ * n1_max or n2_max, n_pairs > 65535, a d_scratch that is not 16-byte aligned. */
+int affnet_match_guided_many(affnet_ctx* ctx, const float* d_desc1, int rows1, const float* d_desc2, int rows2, int dim, const float* d_lafs1,
+                             const float* d_lafs2, const int32_t* d_pairs, int n_pairs, int n1_max, int n2_max, const double* d_model, int kind,
+                             float radius, float snn_threshold, float max_dist, int flags, int n_chunks, const int32_t* d_gate, float* d_dist,
+                             int32_t* d_idx, int32_t* d_tent, int32_t* d_count, void* d_scratch, void* stream);
+
 /* ---- descriptor index: k nearest neighbours over many images, shortlist by votes ---- */
 
 /* The front of the retrieval loop extract -> index -> shortlist -> verify: the rows of all database images lie back to back in one (n2,128)

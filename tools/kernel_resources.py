@@ -137,6 +137,13 @@ DESIGN_KERNELS = [
     ("rowmin_many_kernel<128>", "SNN matching of many pairs per call: the same row-minimum body, pair index on the grid"),
     ("spv_many_score_kernel", "spatial verification of many pairs per call: the same scoring body, pair index on the grid"),
     ("spv_many_lo_kernel", "spatial verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
+    ("epi_many_solve_kernel", "epipolar verification of many pairs per call: the same 8-point solve body, pair index on the grid"),
+    ("epi_many_score_kernel", "epipolar verification of many pairs per call: the same scoring body, pair index on the grid"),
+    ("epi_many_lo_kernel", "epipolar verification of many pairs per call: the same fp64 local optimisation, one workgroup per pair"),
+    ("guided_many_tile_kernel<0, 2, false>", "guided matching of many pairs per call, planar model, forward pass: the same tile body, pair index on the grid"),
+    ("guided_many_tile_kernel<0, 1, true>", "guided matching of many pairs per call, planar model, backward pass"),
+    ("guided_many_tile_kernel<1, 2, false>", "guided matching of many pairs per call, epipolar model, forward pass"),
+    ("guided_many_tile_kernel<1, 1, true>", "guided matching of many pairs per call, epipolar model, backward pass"),
     ("knn_tile_kernel<128, 1>", "descriptor index, k = 1: the matcher's distance tiles over one column chunk, one neighbour per row and lane"),
     ("knn_tile_kernel<128, 2>", "descriptor index, k = 2: two neighbours per row and lane in registers"),
     ("knn_tile_kernel<128, 4>", "descriptor index, k = 3, 4: four neighbours per row and lane"),
