@@ -126,6 +126,20 @@ def run(fast=False):
         L2, r2 = o(xx, do_ori=do_ori)
         ok &= same("OnePassSIR %dx%d N=%d LAFs" % (xx.size(3), xx.size(2), n), L.numpy(), L2.numpy())
         ok &= same("OnePassSIR responses", r.numpy(), r2.numpy())
+    # the oracle's RespNet / AffNet slots (resp_fn, aff_fn) against the reference's own: planted responses and planted affine maps
+    # (tests/_planted_onepass.py) on an all-zero image; cases without tied responses at a cut (torch.topk leaves ties open)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import _planted_onepass as po
+    for p, n in ((po.cut_before_filter(), po.BEFORE_N), (po.boundary(), 100), (po.cut_switch(2, 4), po.CUT_P - 1), (po.offdiag(), 4)):
+        rf, af = po.slots(p)
+        kw = dict(mrSize=po.MR, num_features=n, border=po.BORDER, num_Baum_iters=0, nlevels=p.case.kw.get("nlevels", 3))
+        det = sir.OnePassSIR(RespNet=rf, AffNet=af, **kw)
+        xx = torch.zeros(1, 1, p.case.H, p.case.W)
+        with torch.no_grad(), rh.quiet():
+            L, r = det(xx, do_ori=False)
+        L2, r2 = po.run_oracle(p, n)[1:]
+        ok &= same("planted %s N=%d LAFs" % (p.case.name, n), L.numpy(), L2.numpy())
+        ok &= same("planted responses", r.numpy(), r2.numpy())
     print("ALL IDENTICAL" if ok else "MISMATCH")
     return ok
 

@@ -82,9 +82,11 @@ def nms3d_compose_aff(low, cur, high, num_features, octave_map, scales, mr_size,
 
 class OnePassOracle(object):
     """OnePassSIR (OnePassSIR.py:14-153) with RespNet = HessianResp, AffNet = AffNetFastFullConv state dict, OriNet = OriNetFast
-    state dict (None: the default OrientationDetector(19))."""
+    state dict (None: the default OrientationDetector(19)).  resp_fn / aff_fn replace the first two by any callable of the reference's slot
+    signatures (tests/_planted_onepass.py hands both hand-built maps); with both None nothing changes."""
 
-    def __init__(self, border=16, num_features=500, mrSize=3.0, nlevels=3, init_sigma=1.6, th=None, affnet_sd=None, orinet_sd=None):
+    def __init__(self, border=16, num_features=500, mrSize=3.0, nlevels=3, init_sigma=1.6, th=None, affnet_sd=None, orinet_sd=None,
+                 resp_fn=None, aff_fn=None):
         self.mrSize, self.b, self.num = mrSize, border, num_features
         self.nlevels, self.init_sigma = nlevels, init_sigma
         self.th = th
@@ -93,6 +95,10 @@ class OnePassOracle(object):
         else:
             self.th = 0
         self.aff, self.ori = affnet_sd, orinet_sd
+        # the reference's slots: resp_fn(level (1,1,h,w), sigma) -> (1,1,h,w) = RespNet (OnePassSIR.py:38-41,79-86; None: HessianResp),
+        # aff_fn(level 0 of an octave (1,1,h,w)) -> (1,4,h,w) = AffNet (OnePassSIR.py:76; None: AffNetFastFullConv with affnet_sd)
+        self.resp_fn, self.aff_fn = resp_fn, aff_fn
+        self.level_rows = None
         self.scale_pyr = self.sigmas = self.pix_dists = None
         self.keys = None
         self.aff_maps = None
@@ -102,12 +108,16 @@ class OnePassOracle(object):
         pyr, sigmas, dists = orc.scale_pyramid(x, self.nlevels, self.init_sigma, self.b)
         self.scale_pyr, self.sigmas, self.pix_dists = pyr, sigmas, dists
         self.aff_maps = []
+        # one entry per (octave, detection level) that yields rows, BEFORE the boundary filter: what NMS3dAndComposeAAff returned
+        # (with num_features <= 0 every non-zero row of the level, negative ones included) and the flag of checkTouchBoundary
+        self.level_rows = []
+        respond = orc.hessian_response if self.resp_fn is None else self.resp_fn
         resp_l, laf_l, oct_l, lev_l, pix_l = [], [], [], [], []
         for o, levels in enumerate(pyr):
             omap = (levels[0] * 0).byte()
-            amap = affnet_fullconv_forward(self.aff, levels[0])                      # :69 AffNet(octave[0])
+            amap = affnet_fullconv_forward(self.aff, levels[0]) if self.aff_fn is None else self.aff_fn(levels[0])      # :76 AffNet(octave[0])
             self.aff_maps.append(amap)
-            rmaps = [torch.clamp(orc.hessian_response(levels[l], sigmas[o][l]) - self.th, min=0) for l in range(len(levels))]
+            rmaps = [torch.clamp(respond(levels[l], sigmas[o][l]) - self.th, min=0) for l in range(len(levels))]
             for l in range(1, len(levels) - 1):
                 r, lafs, om, pix = nms3d_compose_aff(rmaps[l - 1], rmaps[l], rmaps[l + 1], num_features, omap, sigmas[o][l - 1:l + 2],
                                                      self.mrSize, amap)
@@ -115,6 +125,8 @@ class OnePassOracle(object):
                     continue
                 omap = om
                 ok = orc.inside_image(torch.cat([lafs[:, :2, :2] * 3.0, lafs[:, :, 2:]], dim=2))      # :91 (the 3.0 is hard-coded)
+                self.level_rows.append({"octave": o, "level": l - 1, "pix": pix.long().clone(), "resp": r.clone(), "lafs": lafs.clone(),
+                                        "inside": ok.clone()})
                 resp_l.append(r[ok])
                 laf_l.append(lafs[ok])
                 oct_l.append(torch.full((int(ok.sum()),), float(o)))
