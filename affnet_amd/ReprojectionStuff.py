@@ -5,7 +5,9 @@ enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank).  The epip
 (verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance).  Guided matching under a
 verified model of either family is csrc/guided.hip (match_guided, enqueue_match_guided, guided_mask, match_verify_guided).  Both have their
 many-pairs form too (affnet_epipolar_verify_many, affnet_match_guided_many): model="fundamental" of the *_many functions,
-enqueue_match_verify_guided_many, match_verify_guided_many, guided=True of spatial_rerank."""
+enqueue_match_verify_guided_many, match_verify_guided_many, guided=True of spatial_rerank.  The ratio-test matcher with a per-row second
+neighbour, FGINN and a mutual check is csrc/ratio_match.hip (match_ratio, match_fginn, enqueue_match_ratio, matcher="snn" / "fginn" of the
+match-and-verify chains)."""
 import ctypes as C
 
 import numpy as np
@@ -77,6 +79,78 @@ def match_snn(descriptors1, descriptors2, SNN_threshold=0.8):
     check(rc, ctx, "affnet_match_snn")
     k = int(cnt.item())
     return tent[:k, 0].long(), tent[:k, 1].long(), md, md2
+
+
+# ---- ratio-test matching (csrc/ratio_match.hip: affnet_match_ratio, affnet_match_ratio_many) -----------------------------------------------------
+
+MATCHERS = ("reference", "snn", "fginn")
+
+
+def _matcher_radius(what, matcher, fginn_radius, mutual=False, guided=False):
+    """The radius affnet_match_ratio takes for `matcher` ('snn': -1, 'fginn': fginn_radius), None for 'reference' (affnet_match_snn)."""
+    if matcher not in MATCHERS:
+        raise ValueError("%s: matcher must be 'reference', 'snn' or 'fginn'" % what)
+    if matcher == "reference":
+        if mutual:
+            raise ValueError("%s: the reference matcher has no mutual check (matcher='snn' or 'fginn')" % what)
+        return None
+    if guided:
+        raise ValueError("%s: the guided chains keep the reference matcher as their first stage" % what)
+    if matcher == "snn":
+        return -1.0
+    r = float(np.float32(fginn_radius))
+    if not (np.isfinite(r) and r >= 0):
+        raise ValueError("%s: fginn_radius must be a finite number >= 0" % what)
+    return r
+
+
+def enqueue_match_ratio(desc1, desc2, LAFs2=None, radius=None, SNN_threshold=0.8, max_dist=float("inf"), mutual=False, n_chunks=0):
+    """Ratio-test matching (affnet_match_ratio) enqueued on the current stream with no synchronisation.  Every row of desc1 takes its nearest
+    row of desc2 and, as the second distance of the ratio, the nearest OTHER row - radius None or < 0, Lowe's test - or the nearest row whose
+    frame centre lies more than `radius` px from the nearest one's (radius >= 0, needs LAFs2: the first geometrically inconsistent neighbour).
+    A pair is kept when its distance is <= max_dist, the ratio is <= SNN_threshold and, with `mutual`, the row is also the nearest row of its
+    column.
+    Returns capacity-sized device tensors (tent (n1,2) int32, count (1,) int32, dist (n1,2), idx (n1,2) int32: the two slots per row,
+    (+inf, -1) where there is none); rows of tent at or beyond the count are zero."""
+    engine.require_cuda(desc1, "desc1")
+    engine.require_cuda(desc2, "desc2")
+    a, b = desc1.contiguous().float(), desc2.contiguous().float()
+    n1, n2, dev = a.size(0), b.size(0), a.device
+    radius = -1.0 if radius is None else float(radius)
+    l2 = None
+    if radius >= 0:
+        if LAFs2 is None:
+            raise ValueError("enqueue_match_ratio: a radius >= 0 needs LAFs2")
+        engine.require_cuda(LAFs2, "LAFs2")
+        if LAFs2.numel() != 6 * n2:
+            raise ValueError("enqueue_match_ratio: one LAF per row of desc2 (%d frames for %d descriptors)" % (LAFs2.numel() // 6, n2))
+        l2 = LAFs2.contiguous().float()
+    tent = torch.zeros(max(n1, 1), 2, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    dist = torch.full((max(n1, 1), 2), float("inf"), dtype=torch.float32, device=dev)
+    idx = torch.full((max(n1, 1), 2), -1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib.affnet_match_ratio_scratch_bytes(n1, n2, int(n_chunks)), dtype=torch.uint8, device=dev)
+    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty side: never read, but the boundary refuses NULL
+    ctx = engine.utility_ctx(dev)
+    rc = lib.affnet_match_ratio(ctx, ptr(a if n1 else one), n1, ptr(b if n2 else one), n2, a.size(1), ptr(one if l2 is not None and not n2 else l2), radius,
+                                float(SNN_threshold), float(max_dist), _lib.RATIO_MUTUAL if mutual else 0, int(n_chunks), ptr(dist), ptr(idx), ptr(tent),
+                                ptr(cnt), ptr(scratch), engine.stream_of(dev))
+    check(rc, ctx, "affnet_match_ratio")
+    return tent[:n1], cnt, dist[:n1], idx[:n1]
+
+
+def match_ratio(desc1, desc2, LAFs2=None, radius=None, SNN_threshold=0.8, max_dist=float("inf"), mutual=False, n_chunks=0):
+    """enqueue_match_ratio and one read-back.  Returns (tent_matches_in_1, tent_matches_in_2, dist (n1,2), idx (n1,2)) - the first two int64, as
+    match_snn returns them.  radius=None means -1: the plain per-row ratio test."""
+    tent, cnt, dist, idx = enqueue_match_ratio(desc1, desc2, LAFs2, radius, SNN_threshold, max_dist, mutual, n_chunks)
+    k = int(cnt.item())
+    return tent[:k, 0].long(), tent[:k, 1].long(), dist, idx
+
+
+def match_fginn(desc1, desc2, LAFs2, radius=10.0, SNN_threshold=0.8, max_dist=float("inf"), mutual=False, n_chunks=0):
+    """match_ratio with the radius of MODS: the ratio is taken against the nearest descriptor whose centre lies more than 10 px from the nearest
+    neighbour's, so a second detection of the same structure does not refuse a good match."""
+    return match_ratio(desc1, desc2, LAFs2, radius, SNN_threshold, max_dist, mutual, n_chunks)
 
 
 VERIFY_MODELS = {"affine": _lib.VERIFY_AFFINE, "homography": _lib.VERIFY_HOMOGRAPHY}
@@ -201,11 +275,15 @@ def sampson_distance(F, LAFs1, LAFs2, tent_in_1, tent_in_2):
     return torch.sqrt(r * r / (l[:, 0] ** 2 + l[:, 1] ** 2 + m[:, 0] ** 2 + m[:, 1] ** 2))
 
 
-def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
+def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0,
+                     matcher="reference", fginn_radius=10.0, mutual=False):
     """match_snn followed by verify_matches as one chain on the stream: the tentative list and its device-side count go from
     affnet_match_snn straight into affnet_verify_matches (model='fundamental': affnet_epipolar_verify, which alone reads `rounds` and
     `seed`), and the host reads back once, at the end.
+    matcher: 'reference' is affnet_match_snn; 'snn' (the per-row ratio test) and 'fginn' (the ratio against the first neighbour more than
+    fginn_radius px from the nearest one) put affnet_match_ratio in its place, with `mutual` as in match_ratio.
     Returns (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info) - the pieces of match_snn and verify_matches."""
+    ratio_radius = _matcher_radius("match_and_verify", matcher, fginn_radius, mutual)
     engine.require_cuda(descriptors1, "descriptors1")
     engine.require_cuda(descriptors2, "descriptors2")
     a, b = descriptors1.contiguous().float(), descriptors2.contiguous().float()
@@ -216,7 +294,9 @@ def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8
         raise ValueError("match_and_verify: one LAF per descriptor row (%d / %d frames for %d / %d descriptors)" % (LAFs1.size(0), LAFs2.size(0), n1, n2))
     tent = torch.empty(n1, 2, dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    if n1:
+    if ratio_radius is not None:
+        tent, cnt, _, _ = enqueue_match_ratio(a, b, LAFs2 if ratio_radius >= 0 else None, ratio_radius, SNN_threshold, float("inf"), mutual)
+    elif n1:
         md = torch.empty(n1, dtype=torch.float32, device=dev)
         md2 = torch.empty(n1, dtype=torch.float32, device=dev)
         idx = torch.empty(n1, dtype=torch.int32, device=dev)
@@ -303,7 +383,7 @@ class _ManyCall:
         self.d_pairs = torch.from_numpy(table).to(self.dev)
         verify_bytes = lib.affnet_epipolar_many_scratch_bytes(P, cap, rounds) if epi else lib.affnet_verify_many_scratch_bytes(P, cap)
         self.scratch = torch.empty(max(lib.affnet_match_many_scratch_bytes(P, cap, n2_max), lib.affnet_match_guided_many_scratch_bytes(P, cap, n2_max, 0),
-                                       verify_bytes), dtype=torch.uint8, device=self.dev)
+                                       lib.affnet_match_ratio_many_scratch_bytes(P, cap, n2_max, 0), verify_bytes), dtype=torch.uint8, device=self.dev)
         self.one = torch.zeros(8, dtype=torch.float32, device=self.dev)           # stands in for an empty side: never read, but the boundary refuses NULL
         self.ctx, self.st = engine.utility_ctx(self.dev), engine.stream_of(self.dev)
 
@@ -318,6 +398,17 @@ class _ManyCall:
                                        ptr(self.d_pairs), P, cap, self.n2_max, float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt),
                                        ptr(self.scratch), self.st)
         check(rc, self.ctx, "affnet_match_snn_many")
+        return tent, cnt
+
+    def match_ratio(self, SNN_threshold, radius, mutual):
+        P, cap, dev = self.P, self.cap, self.dev
+        tent, cnt = _many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P)
+        dist, idx = _many_buf(dev, torch.float32, P, cap, 2), _many_buf(dev, torch.int32, P, cap, 2)
+        rc = lib.affnet_match_ratio_many(self.ctx, self._side(self.a, self.rows1), self.rows1, self._side(self.b, self.rows2), self.rows2, self.a.size(1),
+                                         self._side(self.l2, self.rows2) if radius >= 0 else None, ptr(self.d_pairs), P, cap, self.n2_max, radius,
+                                         float(SNN_threshold), float("inf"), _lib.RATIO_MUTUAL if mutual else 0, 0, ptr(dist), ptr(idx), ptr(tent), ptr(cnt),
+                                         ptr(self.scratch), self.st)
+        check(rc, self.ctx, "affnet_match_ratio_many")
         return tent, cnt
 
     def verify(self, tent, cnt):
@@ -348,15 +439,17 @@ class _ManyCall:
 
 
 def enqueue_match_and_verify_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3,
-                                  rounds=8, seed=0):
+                                  rounds=8, seed=0, matcher="reference", fginn_radius=10.0, mutual=False):
     """match_and_verify for P image pairs in one chain of launches on the current stream, no synchronisation.  desc1 (rows1,128) / LAFs1 (rows1,2,3)
     hold the images of side 1 back to back, counts1[i] rows for image i; side 2 likewise (it may be the same tensors); pairs = [(a, b), ...] image
     indices into the two sides.  Returns capacity-sized device tensors, cap = the largest n1 of a pair: (tent (P,cap,2) int32 with indices local to
     the pair's images, count (P,) int32, H (P,3,3) float64, inliers (P,cap) uint8, counts (P,cap) int32, summary (P,4) int32); per pair, rows below
     count[p] are what match_and_verify gives for that pair, bit for bit, rows at or beyond it are zero.
     model='fundamental' verifies with affnet_epipolar_verify_many, which alone reads `rounds` and `seed`: H is then F, and counts is (P, cap*rounds),
-    hypothesis h = s * rounds + r of pair p in counts[p, h]."""
+    hypothesis h = s * rounds + r of pair p in counts[p, h].
+    matcher, fginn_radius, mutual: as in match_and_verify; 'snn' and 'fginn' put affnet_match_ratio_many in the place of affnet_match_snn_many."""
     what = "enqueue_match_and_verify_many"
+    ratio_radius = _matcher_radius(what, matcher, fginn_radius, mutual)
     epi, code, rounds, seed, per = _many_model(model, rounds, seed, what)
     a, b, l1, l2 = _many_sides(what, desc1, LAFs1, counts1, desc2, LAFs2, counts2)
     table, cap, n2_max = pair_table(counts1, counts2, pairs)
@@ -365,7 +458,7 @@ def enqueue_match_and_verify_many(desc1, LAFs1, counts1, desc2, LAFs2, counts2, 
         return (_many_buf(dev, torch.int32, P, cap, 2), _many_buf(dev, torch.int32, P), _many_buf(dev, torch.float64, P, 3, 3), _many_buf(dev, torch.uint8, P, cap),
                 _many_buf(dev, torch.int32, P, cap * per), _many_buf(dev, torch.int32, P, 4))
     call = _ManyCall(a, b, l1, l2, table, cap, n2_max, epi, code, rounds, seed, inl_th, lo_iters)
-    tent, cnt = call.match(SNN_threshold)
+    tent, cnt = call.match(SNN_threshold) if ratio_radius is None else call.match_ratio(SNN_threshold, ratio_radius, mutual)
     H, inl, counts, summary = call.verify(tent, cnt)
     return tent, cnt, H, inl, counts, summary
 
@@ -388,17 +481,20 @@ def _many_lists(what, descs, LAFs, pairs):
     return D, L, counts
 
 
-def match_and_verify_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
+def match_and_verify_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0, matcher="reference",
+                          fginn_radius=10.0, mutual=False):
     """match_and_verify for every pair (a, b) of `pairs`, image indices into the lists descs / LAFs (one (n_i,128) / (n_i,2,3) device tensor per
     image; both sides of a pair come from the same lists), as one device call chain and ONE read-back.  model: 'homography', 'affine' or
-    'fundamental' (which alone reads `rounds` and `seed`).
+    'fundamental' (which alone reads `rounds` and `seed`); matcher, fginn_radius, mutual as in match_and_verify.
     Returns a list of P tuples (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), each what match_and_verify returns for that pair."""
+    _matcher_radius("match_and_verify_many", matcher, fginn_radius, mutual)
     epi, _, rounds, seed, per = _many_model(model, rounds, seed, "match_and_verify_many")
     side = _many_lists("match_and_verify_many", descs, LAFs, pairs)
     if side is None:
         return []
     D, L, counts = side
-    tent, cnt, H, inl, hyp_counts, summary = enqueue_match_and_verify_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed)
+    tent, cnt, H, inl, hyp_counts, summary = enqueue_match_and_verify_many(D, L, counts, D, L, counts, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed,
+                                                                            matcher, fginn_radius, mutual)
     host = torch.cat([cnt.view(-1, 1), summary], 1).cpu().tolist()          # the one read-back
     out = []
     for p, row in enumerate(host):
@@ -462,17 +558,20 @@ def match_verify_guided_many(descs, LAFs, pairs, SNN_threshold=0.8, inl_th=3.0, 
     return out
 
 
-def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0, guided=False):
+def spatial_rerank(descs, LAFs, query, shortlist, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0, guided=False,
+                   matcher="reference", fginn_radius=10.0, mutual=False):
     """Re-ranks `shortlist` (image indices into descs / LAFs) by the number of verified inliers against image `query`, all pairs in one device call
     chain.  model: 'homography', 'affine' or 'fundamental' (a scene with depth; it alone reads `rounds` and `seed`); guided: the inliers of
-    match_verify_guided_many (defaults of its guided_threshold and radius) instead of match_and_verify_many's.
+    match_verify_guided_many (defaults of its guided_threshold and radius) instead of match_and_verify_many's.  matcher, fginn_radius, mutual: the
+    first stage of the unguided chain, as in match_and_verify.
     Returns (order, num_inliers): the shortlist sorted by descending inlier count, ties in shortlist order, and the counts in that order."""
+    _matcher_radius("spatial_rerank", matcher, fginn_radius, mutual, guided)
     shortlist = [int(s) for s in shortlist]
     pairs = [(int(query), s) for s in shortlist]
     if guided:
         res = match_verify_guided_many(descs, LAFs, pairs, SNN_threshold, inl_th, model, lo_iters=lo_iters, rounds=rounds, seed=seed)
     else:
-        res = match_and_verify_many(descs, LAFs, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed)
+        res = match_and_verify_many(descs, LAFs, pairs, SNN_threshold, inl_th, model, lo_iters, rounds, seed, matcher, fginn_radius, mutual)
     n = [r[4]["num_inliers"] for r in res]
     rank = sorted(range(len(shortlist)), key=lambda i: -n[i])          # sorted() is stable: ties keep the shortlist's order
     return [shortlist[i] for i in rank], [n[i] for i in rank]

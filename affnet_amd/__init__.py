@@ -12,6 +12,7 @@ from . import LAF, HandCraftedModules, Losses, ReprojectionStuff, pytorch_sift  
 from .ReprojectionStuff import verify_matches, enqueue_verify, match_and_verify  # noqa: F401
 from .ReprojectionStuff import verify_epipolar, enqueue_verify_epipolar, sampson_distance  # noqa: F401
 from .ReprojectionStuff import enqueue_match_guided, match_guided, guided_mask, match_verify_guided  # noqa: F401
+from .ReprojectionStuff import enqueue_match_ratio, match_ratio, match_fginn  # noqa: F401
 from .ReprojectionStuff import pair_table, enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank  # noqa: F401
 from .ReprojectionStuff import enqueue_match_verify_guided_many, match_verify_guided_many  # noqa: F401
 from . import retrieval  # noqa: F401

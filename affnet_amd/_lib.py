@@ -40,6 +40,7 @@ KNN_MAX_K = 8                                                                   
 IVF_MAX_PROBE = 8                                                                                # AFFNET_IVF_MAX_PROBE: cells per query row of affnet_ivf_search
 EPI_MAX_ROUNDS, EPI_TILE, EPI_CHUNK, EPI_SOLVE_TILE = 64, 128, 128, 64                            # include/affnet_hip.h AFFNET_EPI_*
 GUIDED_PLANAR, GUIDED_EPIPOLAR, GUIDED_MUTUAL = 0, 1, 1                                           # include/affnet_hip.h AFFNET_GUIDED_*
+RATIO_MUTUAL = 1                                                                                  # include/affnet_hip.h AFFNET_RATIO_MUTUAL
 VERIFY_FLAG_PAIR_RANGE = 8                                                                    # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
 
 
@@ -145,6 +146,10 @@ SYMBOLS = {
     "affnet_match_guided_many_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_match_guided_many": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P,
                                       _P, _P]),
+    "affnet_match_ratio_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "affnet_match_ratio": (_I, [_P, _P, _I, _P, _I, _I, _P, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "affnet_match_ratio_many_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "affnet_match_ratio_many": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_knn_chunks": (_I, [_P, _I, _I]),
     "affnet_knn_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "affnet_knn": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -153,14 +153,16 @@ class DescriptorIndex(object):
         return order, [votes[i] for i in order]
 
     def retrieve(self, desc_q, LAFs_q, top=10, k=4, ratio=0.8, exclude=None, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0,
-                 guided=False, guided_threshold=0.9, radius=None):
+                 guided=False, guided_threshold=0.9, radius=None, matcher="reference", fginn_radius=10.0, mutual=False):
         """shortlist, then every shortlisted image matched against the query and verified in one device call chain
         (enqueue_match_and_verify_many: the query is side 1, the index side 2).  model: 'homography', 'affine' or 'fundamental' (a scene with
         depth; it alone reads `rounds` and `seed`).  Returns a list of dicts {image, votes, num_inliers, H, tent_in_1, tent_in_2, inliers}, by
         descending num_inliers, ties in shortlist order; each entry's matching and verification outputs are what
         match_and_verify(desc_q, descs[image], LAFs_q, LAFs[image]) returns.
         guided=True: the chain is enqueue_match_verify_guided_many (guided_threshold, radius as in match_verify_guided), each entry's outputs are
-        what match_verify_guided returns for the image, and the entry also has seed_stage = {tentatives, num_inliers, flags} of the first stage."""
+        what match_verify_guided returns for the image, and the entry also has seed_stage = {tentatives, num_inliers, flags} of the first stage.
+        matcher, fginn_radius, mutual: the first stage of the unguided chain, as in match_and_verify ('reference', 'snn' or 'fginn')."""
+        RS._matcher_radius("retrieve", matcher, fginn_radius, mutual, guided)
         if self.L is None:
             raise ValueError("retrieve: the index was built without LAFs")
         _check_k(k, "retrieve")
@@ -181,7 +183,7 @@ class DescriptorIndex(object):
             first = torch.cat([cnt0.view(-1, 1), summary0], 1)
         else:
             tent, cnt, H, inl, _, summary = RS.enqueue_match_and_verify_many(q, lq, [q.size(0)], self.D, self.L, self.counts, pairs, SNN_threshold, inl_th, model,
-                                                                             lo_iters, rounds, seed)
+                                                                             lo_iters, rounds, seed, matcher, fginn_radius, mutual)
             first = summary[:, :0]
         host = torch.cat([cnt.view(-1, 1), summary, first], 1).cpu().tolist()
         out = []

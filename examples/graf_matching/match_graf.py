@@ -3,7 +3,8 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental] [--guided]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental] [--guided]]
+                                                 [--matcher reference|snn|fginn [--mutual] [--fginn-radius R]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
 missing blob; without a checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative (few matches).
@@ -23,7 +24,12 @@ explains the wall, so the F printed here is one of a family - good as an inlier 
 meant for two views of a scene with depth, where a homography keeps only the dominant plane.
 --guided (with --verify): guided matching behind the verification (match_verify_guided: the descriptors are searched again, every keypoint among
 the keypoints the verified model allows, and the result is verified once more); a further line gives the guided tentatives, their verified
-inliers and how many of each the ground-truth homography confirms, by the same 6 px rule."""
+inliers and how many of each the ground-truth homography confirms, by the same 6 px rule.
+--matcher: the matcher in front of everything else.  reference (the default) is the evaluation script's (match_snn: the second minimum runs over
+the columns that are nobody's nearest neighbour); snn is the per-row ratio test (match_ratio); fginn takes the ratio against the nearest
+descriptor whose centre lies more than --fginn-radius px (default 10) from the nearest neighbour's (match_fginn), so that a second detection of
+the same structure does not refuse a good match.  --mutual (snn, fginn): keep a match only if it is also the nearest one backwards.  --verify
+passes the choice to match_and_verify; --guided keeps the reference matcher as its first stage and goes with it only."""
 import os
 import sys
 
@@ -34,7 +40,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import affnet_amd  # noqa: E402
-from affnet_amd.ReprojectionStuff import match_snn, match_and_verify, match_verify_guided, get_GT_correspondence_indexes, sampson_distance  # noqa: E402
+from affnet_amd.ReprojectionStuff import match_snn, match_ratio, match_and_verify, match_verify_guided, get_GT_correspondence_indexes, sampson_distance  # noqa: E402
 
 
 def load_grayscale_var(fname):        # train_AffNet_test_on_graffity.py:246-253
@@ -61,7 +67,30 @@ def main(argv):
     guided = "--guided" in argv
     if guided and not verify:
         sys.exit("--guided goes with --verify")
-    argv = [a for a in argv if a not in ("--verify", "--guided")]
+    mutual = "--mutual" in argv
+    argv = [a for a in argv if a not in ("--verify", "--guided", "--mutual")]
+    matcher, fginn_radius = "reference", 10.0
+    if "--matcher" in argv:
+        i = argv.index("--matcher")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("reference", "snn", "fginn"):
+            sys.exit("--matcher takes reference, snn or fginn")
+        matcher = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    if "--fginn-radius" in argv:
+        i = argv.index("--fginn-radius")
+        try:
+            fginn_radius = float(argv[i + 1])
+        except (IndexError, ValueError):
+            sys.exit("--fginn-radius takes a number of pixels")
+        if not 0 <= fginn_radius < float("inf"):
+            sys.exit("--fginn-radius takes a finite number >= 0")
+        argv = argv[:i] + argv[i + 2:]
+    if matcher == "reference" and mutual:
+        sys.exit("--mutual goes with --matcher snn or fginn")
+    if matcher != "reference" and guided:
+        sys.exit("--guided keeps the reference matcher as its first stage: it goes with --matcher reference")
+    mkw = {} if matcher == "reference" else dict(matcher=matcher, fginn_radius=fginn_radius, mutual=mutual)
+    mtag = "" if matcher == "reference" else " [%s%s%s]" % (matcher, " radius %g" % fginn_radius if matcher == "fginn" else "", " mutual" if mutual else "")
     if "--tfeat-weights" in argv:
         i = argv.index("--tfeat-weights")
         if i + 1 >= len(argv):
@@ -104,11 +133,14 @@ def main(argv):
             r1, r2 = det.run_batch(torch.cat([img1, img2], 0), do_ori=do_ori, desc=desc)
         else:
             r1, r2 = det.run(img1, do_ori=do_ori, desc=desc), det.run(img2, do_ori=do_ori, desc=desc)
-        t1, t2, _, _ = match_snn(r1["descriptors"], r2["descriptors"], 0.8)
+        if matcher == "reference":
+            t1, t2, _, _ = match_snn(r1["descriptors"], r2["descriptors"], 0.8)
+        else:
+            t1, t2, _, _ = match_ratio(r1["descriptors"], r2["descriptors"], r2["LAFs"], fginn_radius if matcher == "fginn" else None, 0.8, mutual=mutual)
         _, plain, _ = get_GT_correspondence_indexes(r1["LAFs"][t1], r2["LAFs"][t2], H1to2, dist_threshold=6)
-        print("Test on %s, %d tentatives %d true matches %s  inl.ratio" % (tag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))
+        print("Test on %s%s, %d tentatives %d true matches %s  inl.ratio" % (tag, mtag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))
         if verify and model == "fundamental":
-            v1, v2, F, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0, model="fundamental")
+            v1, v2, F, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0, model="fundamental", **mkw)
             assert torch.equal(v1, t1) and torch.equal(v2, t2)
             _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)
             d = sampson_distance(F, r1["LAFs"], r2["LAFs"], t1[plain], t2[plain])
@@ -116,7 +148,7 @@ def main(argv):
                   "true matches, median Sampson distance of the %d true matches %.2f px"
                   % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), plain.numel(), d.median().item() if d.numel() else float("nan")))
         elif verify:
-            v1, v2, H, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0)
+            v1, v2, H, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0, **mkw)
             assert torch.equal(v1, t1) and torch.equal(v2, t2)
             _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)
             h, w = img1.shape[2], img1.shape[3]

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Spatial re-ranking of a shortlist: one query image against K images, matched and verified in one device call, on the MI355X.
 
-    python examples/graf_matching/rerank.py [--n N] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--model homography|affine|fundamental] [--guided] QUERY IMG [IMG ...]
+    python examples/graf_matching/rerank.py [--n N] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--model homography|affine|fundamental] [--guided] [--matcher reference|snn|fginn] QUERY IMG [IMG ...]
 
 Every image goes through the fused path (detect + AffNet + OriNet + descriptor, N = 1000 keypoints by default), then
 spatial_rerank(descs, LAFs, 0, [1 .. K]): SNN matching and verification of all K pairs from their affine frames as ONE chain of launches
 (affnet_match_snn_many / affnet_verify_matches_many) with one read-back.  Prints the shortlist by descending number of verified inliers
 (ties in the order given).  Without a HardNet checkpoint the seeded synthetic HardNet is used, whose descriptors are not discriminative;
 --desc sift needs no weights.  --model fundamental verifies with the epipolar model of a scene with depth (affnet_epipolar_verify_many); --guided
-re-matches every pair under its verified model and verifies again (affnet_match_guided_many), still one chain and one read-back.  A
+re-matches every pair under its verified model and verifies again (affnet_match_guided_many), still one chain and one read-back.  --matcher snn / fginn
+puts the per-row ratio test / the first geometrically inconsistent neighbour at 10 px (affnet_match_ratio_many) in the place of the reference's
+matcher (not with --guided, whose first stage stays).  A
 demonstration of the call, not a retrieval-quality claim.
 
     python examples/graf_matching/rerank.py tests/golden/graf_img1.png tests/golden/graf_img6.png tests/golden/graf_img1.png"""
@@ -43,9 +45,11 @@ def main(argv):
     desc_kind, argv = take(argv, "--desc", "hardnet")
     hardnet_path, argv = take(argv, "--hardnet", None)
     model, argv = take(argv, "--model", "homography")
+    matcher, argv = take(argv, "--matcher", "reference")
     guided = "--guided" in argv
     argv = [a for a in argv if a != "--guided"]
-    if desc_kind not in ("hardnet", "sift") or model not in ("homography", "affine", "fundamental") or len(argv) < 2:
+    if desc_kind not in ("hardnet", "sift") or model not in ("homography", "affine", "fundamental") or matcher not in ("reference", "snn", "fginn") or \
+            (guided and matcher != "reference") or len(argv) < 2:
         sys.exit(__doc__)
     dev = torch.device("cuda:0")
     ld = lambda p: torch.load(p, map_location="cpu", weights_only=False)["state_dict"]
@@ -64,8 +68,9 @@ def main(argv):
         descs.append(r["descriptors"])
         lafs.append(r["LAFs"])
     shortlist = list(range(1, len(argv)))
-    order, num = affnet_amd.spatial_rerank(descs, lafs, 0, shortlist, SNN_threshold=0.8, inl_th=3.0, model=model, guided=guided)
-    print("query %s: %d keypoints; %d pairs in one device call chain (model %s%s)" % (argv[0], descs[0].size(0), len(shortlist), model, ", guided" if guided else ""))
+    order, num = affnet_amd.spatial_rerank(descs, lafs, 0, shortlist, SNN_threshold=0.8, inl_th=3.0, model=model, guided=guided, matcher=matcher)
+    print("query %s: %d keypoints; %d pairs in one device call chain (model %s%s%s)" % (argv[0], descs[0].size(0), len(shortlist), model, ", guided" if guided else "",
+                                                                                        ", matcher " + matcher if matcher != "reference" else ""))
     for rank, (i, k) in enumerate(zip(order, num)):
         print("%2d. %s  %d verified inliers (%d keypoints, shortlist position %d)" % (rank + 1, argv[i], k, descs[i].size(0), i))
 

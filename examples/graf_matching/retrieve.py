@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Retrieval of one query image from a set of images: descriptor index -> vote shortlist -> spatial verification, on the MI355X.
 
-    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] [--ivf [--cells N --nprobe P]] [--model homography|affine|fundamental] [--guided] QUERY IMG [IMG ...]
+    python examples/graf_matching/retrieve.py [--n N] [--top K] [--k K] [--desc hardnet|sift] [--hardnet HARDNET.pth] [--q8] [--ivf [--cells N --nprobe P]] [--model homography|affine|fundamental] [--guided] [--matcher reference|snn|fginn] QUERY IMG [IMG ...]
 
 Every image goes through the fused path (detect + AffNet + OriNet + descriptor, N = 1000 keypoints by default).  The IMGs become one
 DescriptorIndex; the query's descriptors are searched against all of them at once (affnet_knn, --k neighbours per descriptor, default 4), every image
@@ -14,7 +14,9 @@ cells (default: the power of two nearest the square root of the number of descri
 is compared with the descriptors of its --nprobe (default 8, at most 8) nearest cells only (affnet_ivf_search).  --q8 --ivf together build
 an IVFQuantizedDescriptorIndex: the same codebook, the cells hold the int8 rows (affnet_ivf_search_q8).  --model fundamental verifies the shortlist
 with the epipolar model of a scene with depth (affnet_epipolar_verify_many); --guided re-matches every shortlisted image under its verified model
-and verifies again (affnet_match_guided_many), still in one chain with one read-back.  A demonstration of the calls, not a retrieval-quality claim.
+and verifies again (affnet_match_guided_many), still in one chain with one read-back.  --matcher snn / fginn matches the shortlist with
+the per-row ratio test / the first geometrically inconsistent neighbour at 10 px (affnet_match_ratio_many) instead of the reference's matcher (not
+with --guided, whose first stage stays).  A demonstration of the calls, not a retrieval-quality claim.
 
     python examples/graf_matching/retrieve.py --desc sift tests/golden/graf_img1.png tests/golden/graf_img6.png tests/golden/graf_img1.png"""
 import os
@@ -52,9 +54,11 @@ def main(argv):
     cells, argv = take(argv, "--cells", None)
     nprobe, argv = take(argv, "--nprobe", "8")
     model, argv = take(argv, "--model", "homography")
+    matcher, argv = take(argv, "--matcher", "reference")
     q8, ivf, guided = "--q8" in argv, "--ivf" in argv, "--guided" in argv
     argv = [a for a in argv if a not in ("--q8", "--ivf", "--guided")]
-    if desc_kind not in ("hardnet", "sift") or model not in ("homography", "affine", "fundamental") or len(argv) < 2:
+    if desc_kind not in ("hardnet", "sift") or model not in ("homography", "affine", "fundamental") or matcher not in ("reference", "snn", "fginn") or \
+            (guided and matcher != "reference") or len(argv) < 2:
         sys.exit(__doc__)
     dev = torch.device("cuda:0")
     ld = lambda p: torch.load(p, map_location="cpu", weights_only=False)["state_dict"]
@@ -86,8 +90,8 @@ def main(argv):
     print("vote shortlist (k = %d):" % int(k))
     for rank, (i, v) in enumerate(zip(images, votes)):
         print("%2d. %s  %d votes (%d keypoints)" % (rank + 1, names[i], v, index.counts[i]))
-    print("verified order (model %s%s):" % (model, ", guided" if guided else ""))
-    for rank, r in enumerate(index.retrieve(descs[0], lafs[0], top=int(top), k=int(k), SNN_threshold=0.8, inl_th=3.0, model=model, guided=guided)):
+    print("verified order (model %s%s%s):" % (model, ", guided" if guided else "", ", matcher " + matcher if matcher != "reference" else ""))
+    for rank, r in enumerate(index.retrieve(descs[0], lafs[0], top=int(top), k=int(k), SNN_threshold=0.8, inl_th=3.0, model=model, guided=guided, matcher=matcher)):
         first = " (first stage: %d inliers of %d tentatives)" % (r["seed_stage"]["num_inliers"], r["seed_stage"]["tentatives"]) if guided else ""
         print("%2d. %s  %d verified inliers of %d tentatives (%d votes)%s" % (rank + 1, names[r["image"]], r["num_inliers"], r["tent_in_1"].numel(), r["votes"], first))
 

@@ -725,6 +725,69 @@ int affnet_match_guided_many(affnet_ctx* ctx, const float* d_desc1, int rows1, c
                              float radius, float snn_threshold, float max_dist, int flags, int n_chunks, const int32_t* d_gate, float* d_dist,
                              int32_t* d_idx, int32_t* d_tent, int32_t* d_count, void* d_scratch, void* stream);
 
+/* ---- ratio-test matching: per-row second nearest, first geometrically inconsistent neighbour, mutual check ----
+ *
+ * affnet_match_snn reproduces the reference's evaluation script, whose "second nearest" is the row minimum after the columns of EVERY row's
+ * nearest neighbour were struck out; affnet_match_guided has the per-row list of two but needs a verified model.  This is the matcher in
+ * front of verification: Lowe's ratio test against the row's own second neighbour, or - radius >= 0 - against the first neighbour that is
+ * geometrically inconsistent with the nearest one (FGINN, Mishkin et al., MODS 2015): a detector that fires several times on one structure
+ * makes the second nearest descriptor of a good match the same physical point, and the plain ratio then refuses the match.
+ *
+ * Inputs: d_desc1 (n1,128), d_desc2 (n2,128); d_lafs2 (n2,2,3), of which the centres u = lafs2[6j+2], v = lafs2[6j+5] are read, may be NULL
+ * iff radius < 0; radius r in px; snn_threshold thr; max_dist; flags.  Everything below is fp32, one rounding per written operation (no
+ * fused multiply-add).
+ *
+ * Distance of a pair: the element affnet_distance_matrix writes for it, bit for bit.  Order of candidates: a NaN distance in front of
+ * every number, then the smaller distance, then the smaller index (affnet_knn's order).
+ *   d_dist (n1,2), d_idx (n1,2): slot 0 of row i is the first column in that order over all columns - for every radius what
+ *   affnet_knn(k = 1) writes.  Slot 1 is the first column j != idx[i][0] that is inconsistent with slot 0:
+ *     radius < 0: every such column is inconsistent; the two slots are what affnet_knn(k = 2) writes.
+ *     radius >= 0, j1 = idx[i][0]: du = u[j] - u[j1], dv = v[j] - v[j1]; inconsistent iff !((du*du + dv*dv) <= r*r).  A non-finite centre
+ *     makes the comparison false, so the column counts as inconsistent.
+ *   An unfilled slot is (+inf, -1).
+ *   With AFFNET_RATIO_MUTUAL, back[j] = the first row of column j in that order, with no geometry, or -1 (kept in the scratch).
+ *
+ * Selection, in row order: (i, idx[i][0]) is kept iff idx[i][0] >= 0 && dist[i][0] <= max_dist &&
+ * dist[i][0] / (dist[i][1] + 1e-8f) <= thr (with no inconsistent column the ratio is 0) && (no AFFNET_RATIO_MUTUAL || back[idx[i][0]] == i).
+ * A NaN nearest distance is refused, as affnet_match_snn refuses it.  d_tent (n1,2) int32 receives the kept pairs, d_count their number;
+ * rows of d_tent at or beyond the count are not written.
+ *
+ * The search runs like affnet_knn's: row blocks x n_chunks column chunks, a merge over the chunks; n_chunks = 0: the library chooses
+ * (affnet_knn_chunks); the result does not depend on it.  radius < 0 is one pass with lists of two; radius >= 0 is exact too and takes two
+ * passes (the nearest column, then the first inconsistent one: no list of fixed length holds it once enough detections share a place).
+ * The backward pass is the forward kernel with the sides exchanged.  One linear chain of launches on `stream`, no allocation, no
+ * synchronisation.  n1 == 0 or n2 == 0 is valid and gives count 0.
+ * AFFNET_ERR_INVALID in front of the first launch: dim != 128, an unknown flag bit, a radius that is NaN or +inf, d_lafs2 == NULL with
+ * radius >= 0, a NaN max_dist, a negative size, n_chunks outside 0..65535, any other NULL pointer, a d_scratch that is not 16-byte aligned. */
+#define AFFNET_RATIO_MUTUAL 1    /* flags bit 0: keep (i, j) only if i is also the first row of column j */
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_match_ratio called with this n_chunks (0: enough for whatever the library
+ * may choose).  Negative arguments count as 0. */
+size_t affnet_match_ratio_scratch_bytes(int n1, int n2, int n_chunks);
+
+int affnet_match_ratio(affnet_ctx* ctx, const float* d_desc1, int n1, const float* d_desc2, int n2, int dim, const float* d_lafs2, float radius,
+                       float snn_threshold, float max_dist, int flags, int n_chunks, float* d_dist, int32_t* d_idx, int32_t* d_tent,
+                       int32_t* d_count, void* d_scratch, void* stream);
+
+/* Host only.  Bytes of d_scratch (16-byte aligned) of affnet_match_ratio_many called with this n_chunks (0: enough for whatever the
+ * library may choose).  Negative arguments count as 0. */
+size_t affnet_match_ratio_many_scratch_bytes(int n_pairs, int n1_max, int n2_max, int n_chunks);
+
+/* affnet_match_ratio per pair, with one radius, snn_threshold, max_dist and flags for all; the rules of the *_many blocks above hold word
+ * for word.  Descriptors of a side lie in one (rows,128) buffer, the frames of side 2 in one (rows2,2,3) buffer, as for
+ * affnet_match_snn_many.  Per pair: its own squared norms, nearest columns and backward lists (in the scratch).  d_dist, d_idx
+ * (P,n1_max,2); d_tent (P,n1_max,2); d_count (P).  Every output of pair p is, bit for bit, what affnet_match_ratio writes for that pair's
+ * segments, with indices LOCAL to the segments.  n_chunks column chunks per launch, 0: the library chooses, counting the row blocks of all
+ * P pairs; the result does not depend on it.  The number of launches does not depend on P.
+ * A row out of range (the rule above, with both caps): count 0, nothing else written.  n1 == 0: count 0, nothing else written; n2 == 0:
+ * count 0, the pair's lists unfilled.
+ * AFFNET_ERR_INVALID in front of the first launch: every check of affnet_match_ratio, a NULL d_pairs, a negative rows1, rows2, n_pairs,
+ * n1_max or n2_max, n_pairs > 65535. */
+int affnet_match_ratio_many(affnet_ctx* ctx, const float* d_desc1, int rows1, const float* d_desc2, int rows2, int dim, const float* d_lafs2,
+                            const int32_t* d_pairs, int n_pairs, int n1_max, int n2_max, float radius, float snn_threshold, float max_dist,
+                            int flags, int n_chunks, float* d_dist, int32_t* d_idx, int32_t* d_tent, int32_t* d_count, void* d_scratch,
+                            void* stream);
+
 /* ---- descriptor index: k nearest neighbours over many images, shortlist by votes ---- */
 
 /* The front of the retrieval loop extract -> index -> shortlist -> verify: the rows of all database images lie back to back in one (n2,128)

@@ -144,6 +144,15 @@ DESIGN_KERNELS = [
     ("guided_many_tile_kernel<0, 1, true>", "guided matching of many pairs per call, planar model, backward pass"),
     ("guided_many_tile_kernel<1, 2, false>", "guided matching of many pairs per call, epipolar model, forward pass"),
     ("guided_many_tile_kernel<1, 1, true>", "guided matching of many pairs per call, epipolar model, backward pass"),
+    ("ratio_tile_kernel<2, false>", "ratio-test matching without a radius: the matcher's distance tiles over one column chunk, two neighbours per row and lane"),
+    ("ratio_tile_kernel<1, false>", "ratio-test matching: the nearest column per row (forward pass with a radius) or the nearest row per column (backward pass)"),
+    ("ratio_tile_kernel<1, true>", "ratio-test matching, FGINN pass: the first neighbour whose centre is inconsistent with the nearest column's"),
+    ("ratio_select_kernel<true>", "ratio-test matching with a radius: the two slots to (n1, 2), distance bound, ratio and mutual test, compaction in row order"),
+    ("ratio_select_kernel<false>", "ratio-test matching without a radius: distance bound, ratio and mutual test, compaction in row order, one workgroup"),
+    ("ratio_many_tile_kernel<2, false, false>", "ratio-test matching of many pairs per call, no radius: the same tile body, pair index on the grid"),
+    ("ratio_many_tile_kernel<1, false, false>", "ratio-test matching of many pairs per call: the nearest column per row"),
+    ("ratio_many_tile_kernel<1, true, false>", "ratio-test matching of many pairs per call, FGINN pass"),
+    ("ratio_many_tile_kernel<1, false, true>", "ratio-test matching of many pairs per call, backward pass"),
     ("knn_tile_kernel<128, 1>", "descriptor index, k = 1: the matcher's distance tiles over one column chunk, one neighbour per row and lane"),
     ("knn_tile_kernel<128, 2>", "descriptor index, k = 2: two neighbours per row and lane in registers"),
     ("knn_tile_kernel<128, 4>", "descriptor index, k = 3, 4: four neighbours per row and lane"),
