@@ -70,6 +70,15 @@ class Nets(C.Structure):
                 ("h_orientation_window", C.c_void_p), ("h_baumberg_window", C.c_void_p)]
 
 
+WS_F32, WS_I32, WS_U8, WS_RECORDS, WS_GROUP = 0, 1, 2, 3, 4         # include/affnet_hip_probes.h AFFNET_WS_*
+
+
+class WsArea(C.Structure):
+    """affnet_ws_area (include/affnet_hip_probes.h): one record of affnet_probe_workspace_areas."""
+    _fields_ = [("name", C.c_char * 40), ("offset", C.c_int64), ("bytes", C.c_int64),
+                ("kind", C.c_int32), ("cleared", C.c_int32), ("parent", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/affnet_hip.h
 _P, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -202,6 +211,7 @@ PROBE_SYMBOLS = {
     "affnet_split3_rate": (_I, [_I, _I, _I, _P, _P]),
     "affnet_debug_stream": (_I, [_P, _P, _SZ, _I, _I, _I, _P]),
     "affnet_probe_shape_offsets": (_I, [_P, C.POINTER(C.c_int64 * 3)]),
+    "affnet_probe_workspace_areas": (_I, [_P, _I, _P]),                 # (ctx, max, WsArea[max]) -> number of records
     "affnet_probe_affnet_wino_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),
     "affnet_probe_affnet_wino_partials": (_I, [_P, _P, _P, _I, _P, _P]),
     "affnet_probe_affnet_poly_layer": (_I, [_P, _I, _P, _P, _I, _P, _P]),

@@ -315,8 +315,28 @@ struct Conv5Args {
     unsigned long long* dbg_time;    // stamped instantiation: stamps 24 .. 31 of every wave in the record of the group's first patch (the trunk writes 0 .. 23 of the same record)
 };
 
+// One area of the workspace: THE table that affnet_ctx_create sizes the workspace from, affnet_bind_workspace takes its pointers from and
+// affnet_probe_workspace_areas (debug.hip) reports - aff_ws_layout (context.hip) is the only place that knows the carve.
+// parent < 0: a carve unit; units start on the library's alignment (aff_align), in table order, and tile the workspace.  parent >= 0: a view inside
+// that unit (off is still from the workspace base); the views of a list unit lie back to back, the views of the CNN scratch overlap (a union).
+enum { AFF_WS_F32 = 0, AFF_WS_I32 = 1, AFF_WS_U8 = 2, AFF_WS_RECORDS = 3, AFF_WS_GROUP = 4 };   // = AFFNET_WS_* (include/affnet_hip_probes.h)
+struct AffWsArea {
+    const char* name;
+    size_t off, bytes;
+    int kind;              // AFF_WS_*; GROUP: a unit of mixed kinds, described by its views
+    int cleared;           // 1: the detector half of every fused call clears it (detect.hip: detect_candidates / clear_outputs)
+    int parent;
+};
+#define AFF_WS_MAX_AREAS 64
+// The detector's replay of the octaveMap (detect.hip): up to 3 detection levels run as resolve_count / resolve_apply from RawMax::prev, with no octaveMap in
+// memory; more levels run level_resolve_kernel on the octaveMap area, which the call then clears.  One predicate for the detector and for the ledger's flag.
+static inline bool aff_detect_two_pass(const affnet_config& c) { return c.levels_per_octave - 2 <= 3; }
+
 // context.hip
 int aff_fail(affnet_ctx* ctx, int code, const char* fmt, ...);
+// the areas of ctx's workspace from its capacities, strides and config (set by affnet_ctx_create before the call) -> out[AFF_WS_MAX_AREAS]; returns their number,
+// or -1 when the table holds more than AFF_WS_MAX_AREAS (nothing is written past the array)
+int aff_ws_layout(const affnet_ctx* ctx, AffWsArea* out);
 // Device-side fills and copies as plain kernels of this library instead of hipMemsetAsync / hipMemcpyAsync: the runtime's blit
 // path shares per-queue state with captured graph nodes (replaying a captured graph after eager null-stream memsets faulted on
 // ROCm 7.2), and a kernel of our own is also what a stream capture records most cheaply.

@@ -133,6 +133,107 @@ static int validate(affnet_ctx* ctx, const affnet_config* c) {
     return AFFNET_OK;
 }
 
+// ---- the workspace carve -----------------------------------------------------------------------------------
+// Every area of the workspace, in order.  A unit starts at the aligned end of the unit before it; a view lies at a byte offset inside its unit.
+// DESIGN.md section 3 describes each area by these names (who writes it, who reads it, why no read precedes the write).
+namespace {
+struct WsBuilder {
+    AffWsArea* a; int n = 0; size_t end = 0;
+    bool overflow = false;       // more than AFF_WS_MAX_AREAS records: nothing is written past the array, aff_ws_layout answers -1
+    int unit(const char* name, size_t bytes, int kind, int cleared) {
+        if (n >= AFF_WS_MAX_AREAS) { overflow = true; return AFF_WS_MAX_AREAS - 1; }
+        const size_t off = aff_align(end);
+        a[n] = AffWsArea{name, off, bytes, kind, cleared, -1};
+        end = off + bytes;
+        return n++;
+    }
+    void view(int parent, const char* name, size_t rel, size_t bytes, int kind) {
+        if (n >= AFF_WS_MAX_AREAS) { overflow = true; return; }
+        a[n++] = AffWsArea{name, a[parent].off + rel, bytes, kind, a[parent].cleared, parent};
+    }
+    // a list of `rows` rows as struct of arrays: resp (1 float), a float part (nf floats per row), ids (3 int32)
+    void list_views(int parent, const char* r, const char* f, const char* i, size_t rows, int nf) {
+        view(parent, r, 0, rows * 4, AFF_WS_F32);
+        view(parent, f, rows * 4, rows * nf * 4, AFF_WS_F32);
+        view(parent, i, rows * (1 + nf) * 4, rows * 3 * 4, AFF_WS_I32);
+    }
+};
+}  // namespace
+
+int aff_ws_layout(const affnet_ctx* ctx, AffWsArea* out) {
+    const affnet_config& c = ctx->cfg;
+    const size_t B = (size_t)ctx->B, CC = B * ctx->cand_cap, P = B * (size_t)ctx->cap_pre, F = B * (size_t)ctx->cap_final;
+    const size_t f4 = sizeof(float);
+    const int omap_cleared = aff_detect_two_pass(c) ? 0 : 1;   // the detector's own predicate: only the many-level replay keeps an octaveMap in memory
+    WsBuilder w{out};
+    w.unit("pyramid", B * ctx->pyr_stride * f4, AFF_WS_F32, 0);
+    w.unit("octave_map", B * ctx->map_stride, AFF_WS_U8, omap_cleared);
+    w.unit("raw", B * ctx->raw_total * sizeof(RawMax), AFF_WS_RECORDS, 0);
+    w.unit("counters", B * CNT_TOTAL * sizeof(int32_t), AFF_WS_I32, 1);
+    w.unit("sel_hist", B * SEL_HIST_BINS * sizeof(uint32_t), AFF_WS_I32, 1);       // top-digit histogram of the global top-k (detect.hip)
+    w.list_views(w.unit("cand", CC * 7 * f4, AFF_WS_GROUP, 0), "cand.resp", "cand.syx", "cand.ids", CC, 3);
+    w.list_views(w.unit("sel", P * 7 * f4, AFF_WS_GROUP, 0), "sel.resp", "sel.syx", "sel.ids", P, 3);
+    w.list_views(w.unit("det", P * 10 * f4, AFF_WS_GROUP, 1), "det.resp", "det.lafs", "det.ids", P, 6);
+    w.unit("shape_A", P * 4 * f4, AFF_WS_F32, 0);
+    {   // A of the current iteration + re-extraction LAFs (num_Baum_iters > 1)
+        const int u = w.unit("shape_iter", P * 10 * f4, AFF_WS_GROUP, 0);
+        w.view(u, "shape_iter.A2", 0, P * 4 * f4, AFF_WS_F32);
+        w.view(u, "shape_iter.lafs", P * 4 * f4, P * 6 * f4, AFF_WS_F32);
+    }
+    {
+        const int u = w.unit("shape_key_good", P * 2 * f4, AFF_WS_GROUP, 0);
+        w.view(u, "shape_key_good.key", 0, P * f4, AFF_WS_F32);
+        w.view(u, "shape_key_good.good", P * f4, P * f4, AFF_WS_I32);
+    }
+    w.unit("rank", P * sizeof(int32_t), AFF_WS_I32, 1);
+    w.unit("det_count", B * sizeof(int32_t), AFF_WS_I32, 0);
+    w.unit("lafs_shaped", F * 6 * f4, AFF_WS_F32, 0);
+    w.unit("ori_R", F * 4 * f4, AFF_WS_F32, 0);
+    {
+        const int u = w.unit("desc_frames", F * 9 * f4, AFF_WS_GROUP, 0);
+        w.view(u, "desc_frames.lafs_norm", 0, F * 6 * f4, AFF_WS_F32);
+        w.view(u, "desc_frames.lvl_ids", F * 6 * f4, F * 3 * f4, AFF_WS_I32);
+    }
+    {   // one scratch for the three CNNs, used one after the other: AffNet's head partials of the P candidates with the margin rule's flags behind them,
+        // OriNet's head partials of the F rows, HardNet's conv5 tensor with the head GEMM's split-K partials behind it
+        const size_t hard = F * (size_t)(HEAD_K + HEAD_KSPLIT * 128), aff = P * HEAD_PART_ORI;
+        const int u = w.unit("cnn_scratch", (hard > aff ? hard : aff) * f4, AFF_WS_GROUP, 0);
+        w.view(u, "cnn_scratch.aff_partials", 0, P * HEAD_PART_AFF * f4, AFF_WS_F32);
+        w.view(u, "cnn_scratch.aff_reeval_flags", P * HEAD_PART_AFF * f4, P * sizeof(int32_t), AFF_WS_I32);
+        w.view(u, "cnn_scratch.ori_partials", 0, F * HEAD_PART_ORI * f4, AFF_WS_F32);
+        w.view(u, "cnn_scratch.hard_conv5", 0, F * HEAD_K * f4, AFF_WS_F32);
+        w.view(u, "cnn_scratch.hard_head_partials", F * HEAD_K * f4, F * HEAD_KSPLIT * 128 * f4, AFF_WS_F32);
+    }
+    if (c.onepass) {
+        // OnePassSIR: dense affine-shape maps of every octave, the dense net's scratch (octave 0 is the largest), a second
+        // candidate list (7 floats per row like the first) and the per-(octave, level) top-k table
+        w.unit("affmap", B * ctx->aff_stride * f4, AFF_WS_F32, 0);
+        w.unit("dense", B * ctx->dense_stride * f4, AFF_WS_F32, 0);
+        w.list_views(w.unit("cand2", CC * 7 * f4, AFF_WS_GROUP, 0), "cand2.resp", "cand2.syx", "cand2.ids", CC, 3);
+        w.unit("lvltab", B * (size_t)AFFNET_MAX_OCTAVES * AFFNET_MAX_LEVELS * 4 * sizeof(int32_t), AFF_WS_I32, 0);
+    }
+    return w.overflow ? -1 : w.n;
+}
+
+// The table of a context and the offsets of its areas by name.  A table that does not fit, or a name that it does not hold (a slip inside this file), is remembered in
+// `bad`: the caller fails with an error instead of carving or binding anything.
+namespace {
+struct WsTable {
+    AffWsArea ar[AFF_WS_MAX_AREAS];
+    int n;
+    const char* bad = nullptr;
+    explicit WsTable(const affnet_ctx* ctx) : n(aff_ws_layout(ctx, ar)) {
+        if (n < 0) { bad = "(more areas than AFF_WS_MAX_AREAS)"; n = 0; }
+    }
+    size_t off(const char* name) {
+        for (int i = 0; i < n; ++i)
+            if (!strcmp(ar[i].name, name)) return ar[i].off;
+        if (!bad) bad = name;
+        return 0;
+    }
+};
+}  // namespace
+
 extern "C" int affnet_ctx_create(affnet_ctx** out, int device, const affnet_config* cfg) {
     if (!out) return AFFNET_ERR_INVALID;
     affnet_ctx* ctx = new affnet_ctx();
@@ -158,7 +259,6 @@ extern "C" int affnet_ctx_create(affnet_ctx** out, int device, const affnet_conf
         g.raw_off = (int64_t)raw; g.raw_cap = cap; raw += cap;
     }
     ctx->B = c.batch > 0 ? c.batch : 1;
-    const size_t B = (size_t)ctx->B;
     ctx->pyr_floats = pyr; ctx->map_bytes = mapb; ctx->raw_total = raw; ctx->cand_cap = raw;
     ctx->pyr_stride = aff_align(pyr * sizeof(float)) / sizeof(float);
     ctx->map_stride = aff_align(mapb);
@@ -167,29 +267,6 @@ extern "C" int affnet_ctx_create(affnet_ctx** out, int device, const affnet_conf
     ctx->cap_pre = c.num_prefilter > 0 ? c.num_prefilter : keep;
     ctx->cap_final = c.num_features > 0 ? c.num_features : ctx->cap_pre;
     if (ctx->cap_final > ctx->cap_pre) ctx->cap_final = ctx->cap_pre;
-    size_t off = 0;
-    ctx->off_pyr = off; off += B * ctx->pyr_stride * sizeof(float);
-    ctx->off_map = off; off += B * ctx->map_stride;
-    ctx->off_raw = off; off += aff_align(B * raw * sizeof(RawMax));
-    ctx->off_cnt = off; off += aff_align(B * CNT_TOTAL * sizeof(int32_t));
-    ctx->off_hist = off; off += aff_align(B * SEL_HIST_BINS * sizeof(uint32_t));   // top-digit histogram of the global top-k (detect.hip)
-    ctx->off_cand = off; off += aff_align(B * ctx->cand_cap * 7 * sizeof(float));   // resp + syx[3] + ids[3]
-    ctx->off_sel = off; off += aff_align(B * (size_t)ctx->cap_pre * 7 * sizeof(float));
-    ctx->off_stage = off;
-    const size_t P = B * (size_t)ctx->cap_pre, F = B * (size_t)ctx->cap_final;
-    off += aff_align(P * 10 * sizeof(float));          // det resp(1) + lafs(6) + ids(3)
-    off += aff_align(P * 4 * sizeof(float));           // A
-    off += aff_align(P * 10 * sizeof(float));          // A of the current iteration (4) + re-extraction LAFs (6)
-    off += aff_align(P * 2 * sizeof(float));           // key, good
-    off += aff_align(P * sizeof(int32_t));             // rank / pos
-    off += aff_align(B * sizeof(int32_t));             // detector row counts
-    off += aff_align(F * 6 * sizeof(float));           // shaped lafs (normalised)
-    off += aff_align(F * 4 * sizeof(float));           // R
-    off += aff_align(F * 9 * sizeof(float));           // lafs_norm(6) + lvl ids(3)
-    {   // HardNet trunk output + split-K head partials; also holds the AffNet (P rows) / OriNet head partials (144 floats each)
-        const size_t hard = F * (8192 + 4 * 128), aff = P * 144;
-        off += aff_align((hard > aff ? hard : aff) * sizeof(float));
-    }
     if (c.onepass) {
         // OnePassSIR: dense affine-shape maps of every octave, the dense net's scratch (octave 0 is the largest), a second
         // candidate list (7 floats per row like the first) and the per-(octave, level) top-k table
@@ -205,13 +282,22 @@ extern "C" int affnet_ctx_create(affnet_ctx** out, int device, const affnet_conf
         }
         ctx->aff_stride = aff;
         ctx->dense_stride = affnet_fullconv_scratch_bytes(c.oct_h[0], c.oct_w[0]) / sizeof(float);
-        ctx->off_affmap = off; off += aff_align(B * aff * sizeof(float));
-        ctx->off_dense = off; off += aff_align(B * ctx->dense_stride * sizeof(float));
-        ctx->off_cand2 = off; off += aff_align(B * ctx->cand_cap * 7 * sizeof(float));
-        ctx->off_lvltab = off; off += aff_align(B * (size_t)AFFNET_MAX_OCTAVES * AFFNET_MAX_LEVELS * 4 * sizeof(int32_t));
     }
-    ctx->ws_bytes = off;
+    // the carve: offsets and the workspace size come from the table, as affnet_bind_workspace's pointers do
+    WsTable t(ctx);
+    ctx->off_pyr = t.off("pyramid"); ctx->off_map = t.off("octave_map"); ctx->off_raw = t.off("raw");
+    ctx->off_cnt = t.off("counters"); ctx->off_hist = t.off("sel_hist"); ctx->off_cand = t.off("cand");
+    ctx->off_sel = t.off("sel"); ctx->off_stage = t.off("det");
+    if (c.onepass) {
+        ctx->off_affmap = t.off("affmap"); ctx->off_dense = t.off("dense");
+        ctx->off_cand2 = t.off("cand2"); ctx->off_lvltab = t.off("lvltab");
+    }
     *out = ctx;
+    if (t.bad) return aff_fail(ctx, AFFNET_ERR_INVALID, "internal: workspace table has no area %s (aff_ws_layout)", t.bad);   // ws_bytes stays 0: nothing can be bound
+    size_t end = 0;
+    for (int i = 0; i < t.n; ++i)
+        if (t.ar[i].parent < 0) end = t.ar[i].off + t.ar[i].bytes;
+    ctx->ws_bytes = aff_align(end);
     return AFFNET_OK;
 }
 
@@ -289,38 +375,33 @@ extern "C" int affnet_bind_workspace(affnet_ctx* ctx, void* d_workspace, size_t 
         }
     }
     char* b = (char*)d_workspace;
-    ctx->ws = b;
-    ctx->pyr = (float*)(b + ctx->off_pyr);
-    ctx->omap = (uint8_t*)(b + ctx->off_map);
-    ctx->raw = (RawMax*)(b + ctx->off_raw);
-    ctx->cnt = (int32_t*)(b + ctx->off_cnt);
-    ctx->sel_hist = (uint32_t*)(b + ctx->off_hist);
-    const size_t B = (size_t)ctx->B;
-    float* cand = (float*)(b + ctx->off_cand);
-    const size_t CC = B * ctx->cand_cap;
-    ctx->cand_resp = cand; ctx->cand_syx = cand + CC; ctx->cand_ids = (int32_t*)(cand + 4 * CC);
-    float* sel = (float*)(b + ctx->off_sel);
-    const size_t P = B * (size_t)ctx->cap_pre, F = B * (size_t)ctx->cap_final;
-    ctx->sel_resp = sel; ctx->sel_syx = sel + P; ctx->sel_ids = (int32_t*)(sel + 4 * P);
-    char* s = b + ctx->off_stage;
-    ctx->st_det_resp = (float*)s; ctx->st_det_lafs = (float*)s + P; ctx->st_det_ids = (int32_t*)((float*)s + 7 * P);
-    s += aff_align(P * 10 * sizeof(float));
-    ctx->st_A = (float*)s; s += aff_align(P * 4 * sizeof(float));
-    ctx->st_A2 = (float*)s; ctx->st_lafs_iter = (float*)s + 4 * P; s += aff_align(P * 10 * sizeof(float));
-    ctx->st_key = (float*)s; ctx->st_good = (int32_t*)((float*)s + P); s += aff_align(P * 2 * sizeof(float));
-    ctx->st_rank = (int32_t*)s; s += aff_align(P * sizeof(int32_t));
-    ctx->st_det_count = (int32_t*)s; s += aff_align(B * sizeof(int32_t));
-    ctx->st_lafs_shaped = (float*)s; s += aff_align(F * 6 * sizeof(float));
-    ctx->st_R = (float*)s; s += aff_align(F * 4 * sizeof(float));
-    ctx->st_lafs_norm = (float*)s; ctx->st_lvl_ids = (int32_t*)((float*)s + 6 * F); s += aff_align(F * 9 * sizeof(float));
-    ctx->st_hard_scratch = (float*)s;
+    WsTable t(ctx);
+    auto at = [&](const char* name) { return (void*)(b + t.off(name)); };
+    ctx->pyr = (float*)at("pyramid");
+    ctx->omap = (uint8_t*)at("octave_map");
+    ctx->raw = (RawMax*)at("raw");
+    ctx->cnt = (int32_t*)at("counters");
+    ctx->sel_hist = (uint32_t*)at("sel_hist");
+    ctx->cand_resp = (float*)at("cand.resp"); ctx->cand_syx = (float*)at("cand.syx"); ctx->cand_ids = (int32_t*)at("cand.ids");
+    ctx->sel_resp = (float*)at("sel.resp"); ctx->sel_syx = (float*)at("sel.syx"); ctx->sel_ids = (int32_t*)at("sel.ids");
+    ctx->st_det_resp = (float*)at("det.resp"); ctx->st_det_lafs = (float*)at("det.lafs"); ctx->st_det_ids = (int32_t*)at("det.ids");
+    ctx->st_A = (float*)at("shape_A");
+    ctx->st_A2 = (float*)at("shape_iter.A2"); ctx->st_lafs_iter = (float*)at("shape_iter.lafs");
+    ctx->st_key = (float*)at("shape_key_good.key"); ctx->st_good = (int32_t*)at("shape_key_good.good");
+    ctx->st_rank = (int32_t*)at("rank");
+    ctx->st_det_count = (int32_t*)at("det_count");
+    ctx->st_lafs_shaped = (float*)at("lafs_shaped");
+    ctx->st_R = (float*)at("ori_R");
+    ctx->st_lafs_norm = (float*)at("desc_frames.lafs_norm"); ctx->st_lvl_ids = (int32_t*)at("desc_frames.lvl_ids");
+    ctx->st_hard_scratch = (float*)at("cnn_scratch");
     if (ctx->cfg.onepass) {
-        ctx->affmap = (float*)(b + ctx->off_affmap);
-        ctx->dense = (float*)(b + ctx->off_dense);
-        float* c2 = (float*)(b + ctx->off_cand2);
-        ctx->cand2_resp = c2; ctx->cand2_syx = c2 + CC; ctx->cand2_ids = (int32_t*)(c2 + 4 * CC);
-        ctx->lvltab = (int32_t*)(b + ctx->off_lvltab);
+        ctx->affmap = (float*)at("affmap");
+        ctx->dense = (float*)at("dense");
+        ctx->cand2_resp = (float*)at("cand2.resp"); ctx->cand2_syx = (float*)at("cand2.syx"); ctx->cand2_ids = (int32_t*)at("cand2.ids");
+        ctx->lvltab = (int32_t*)at("lvltab");
     }
+    if (t.bad) return aff_fail(ctx, AFFNET_ERR_INVALID, "internal: workspace table has no area %s (aff_ws_layout)", t.bad);   // ctx->ws stays unset: not bound
+    ctx->ws = b;
     return AFFNET_OK;
 }
 

@@ -80,6 +80,23 @@ extern "C" int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3])
     return AFFNET_OK;
 }
 
+// The ledger of the workspace: the table affnet_ctx_create and affnet_bind_workspace carve it from (context.hip: aff_ws_layout), record by record
+extern "C" int affnet_probe_workspace_areas(const affnet_ctx* ctx, int max, affnet_ws_area* out) {
+    if (!ctx || ctx->ws_bytes == 0 || max < 0 || (max > 0 && !out)) return AFFNET_ERR_INVALID;
+    static_assert(AFF_WS_F32 == AFFNET_WS_F32 && AFF_WS_I32 == AFFNET_WS_I32 && AFF_WS_U8 == AFFNET_WS_U8 && AFF_WS_RECORDS == AFFNET_WS_RECORDS &&
+                  AFF_WS_GROUP == AFFNET_WS_GROUP, "kinds of the ledger");
+    AffWsArea ar[AFF_WS_MAX_AREAS];
+    const int n = aff_ws_layout(ctx, ar);
+    if (n < 0) return AFFNET_ERR_INVALID;
+    for (int i = 0; i < n && i < max; ++i) {
+        memset(&out[i], 0, sizeof(out[i]));
+        strncpy(out[i].name, ar[i].name, sizeof(out[i].name) - 1);
+        out[i].offset = (int64_t)ar[i].off; out[i].bytes = (int64_t)ar[i].bytes;
+        out[i].kind = ar[i].kind; out[i].cleared = ar[i].cleared; out[i].parent = ar[i].parent;
+    }
+    return n;
+}
+
 // The Winograd AffNet trunk (the first trunk of shape form 1) on a patch tensor, which no entry point of the product library runs: cnn32.hip's trunk launch (U derived in
 // front of it; the stamped instantiation when a layer dump is asked for or the context has a stamp buffer, affnet_cnn32_debug_timing) without a finish stage.
 // poly: the first trunk of shape form 2 (conv2 / conv4 polyphase) instead.

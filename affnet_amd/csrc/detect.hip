@@ -1055,7 +1055,7 @@ static int detect_candidates(affnet_ctx* ctx, const float* d_responses, AffZeroS
     const int NLv = c.levels_per_octave;
     if (NLv < 3 || NLv > 8) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect: levels_per_octave = %d (3..8 supported)", NLv);
     const int B = ctx->B;
-    const bool two_pass = NLv - 2 <= 3;          // <= 3 detection levels: resolve_count / resolve_apply, no octaveMap in memory
+    const bool two_pass = aff_detect_two_pass(c);   // <= 3 detection levels: resolve_count / resolve_apply, no octaveMap in memory
     z.add(ctx->cnt, (size_t)B * CNT_TOTAL * sizeof(int32_t));
     if (!two_pass) z.add(ctx->omap, (size_t)B * ctx->map_stride);
     z.add(ctx->sel_hist, (size_t)B * SEL_HIST_BINS * sizeof(uint32_t));
@@ -1164,7 +1164,7 @@ static AffZeroSegs clear_outputs(affnet_ctx* ctx, float* d_resp, float* d_lafs, 
 int aff_detect_impl(affnet_ctx* ctx, const float* d_responses, float* d_resp, float* d_lafs, int32_t* d_ids, int32_t* d_count, void* stream) {
     if (!ctx || !ctx->ws || !d_resp || !d_lafs || !d_ids) return aff_fail(ctx, AFFNET_ERR_INVALID, "detect: context not bound or null output");
     hipStream_t st = (hipStream_t)stream;
-    const bool fold = ctx->cfg.levels_per_octave - 2 <= 3;
+    const bool fold = aff_detect_two_pass(ctx->cfg);
     int rc = detect_candidates(ctx, d_responses, clear_outputs(ctx, d_resp, d_lafs, d_ids), st, fold);
     if (rc) return rc;
     rc = select_top(ctx, ctx->cand_resp, ctx->cand_syx, ctx->cand_ids, st, fold);

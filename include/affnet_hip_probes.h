@@ -49,6 +49,23 @@ int affnet_split3_rate(int reps, int terms, int n_blocks, float* d_out, void* st
  * offsets from the workspace base, in 4-byte units.  Host only; the context may come from libaffnet_hip.so of the same build. */
 int affnet_probe_shape_offsets(const affnet_ctx* ctx, int64_t out[3]);
 
+/* Ledger of the workspace of a context (affnet_workspace_bytes), for the tests: one record per area, from the table that affnet_ctx_create sizes the
+ * workspace from and affnet_bind_workspace takes its pointers from.  Records with parent < 0 are the carve units: in offset order, each on a 256-byte
+ * boundary, tiling [0, affnet_workspace_bytes) with nothing but alignment padding between them.  A record with parent >= 0 is a view inside that unit
+ * (offset still from the workspace base): the resp / syx (lafs) / ids arrays of a list lie back to back from the unit's start; the views of "cnn_scratch" are
+ * a union - AffNet's head partials with the margin rule's flags behind them, OriNet's head partials, HardNet's conv5 tensor with the split-K partials
+ * behind it - used one after the other.  kind: the element type (AFFNET_WS_RECORDS: the detector's 32-byte raw maxima; AFFNET_WS_GROUP: a unit of mixed
+ * kinds, see its views).  cleared: 1 when the detector half of every fused call clears the area itself; every other area holds what the call's kernels wrote
+ * (DESIGN.md section 3 says who, and why no read comes first).  Writes min(max, n) records and returns n, the number of records; < 0: an AFFNET_ERR_* code.
+ * Host only; the context need not be bound and may come from libaffnet_hip.so of the same build. */
+enum { AFFNET_WS_F32 = 0, AFFNET_WS_I32 = 1, AFFNET_WS_U8 = 2, AFFNET_WS_RECORDS = 3, AFFNET_WS_GROUP = 4 };
+typedef struct affnet_ws_area {
+    char name[40];
+    int64_t offset, bytes;
+    int32_t kind, cleared, parent, reserved;
+} affnet_ws_area;
+int affnet_probe_workspace_areas(const affnet_ctx* ctx, int max, affnet_ws_area* out);
+
 /* Layer dump of the Winograd AffNet trunk (conv1 / conv3 / conv5 as F(2x2, 3x3): what shape form AFFNET_SHAPE_FORM_WINOGRAD runs on every candidate), for the
  * tests: affnet_cnn32_debug_layer's arguments and output (the activations after trunk layer `layer` = 0 .. 5 of the one 32 x 32 patch, [channel][y][x]), which
  * always answers with the direct trunk for AffNet.  net_kind must be AFFNET_NET_AFFNET, the context in AFFNET_ARITH_FP32_MFMA; it may come from
