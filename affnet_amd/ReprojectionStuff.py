@@ -2,7 +2,8 @@
 (ReprojectionStuff.py:23-40,126-137), plus the SNN matcher of train_AffNet_test_on_graffity.py:292-300 as one call, and the geometric
 verification of its tentative matches from the affine frames themselves (csrc/spatial.hip: verify_matches, enqueue_verify, match_and_verify), and both for many image pairs per device call (pair_table,
 enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank).  The epipolar model of a scene with depth is csrc/epipolar.hip
-(verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance).  Guided matching under a
+(verify_epipolar, enqueue_verify_epipolar, model="fundamental" of verify_matches / match_and_verify, sampson_distance); its plane-aware form for scenes whose matches lie mostly on one plane is csrc/epipolar_planar.hip (verify_epipolar_planar,
+enqueue_verify_epipolar_planar, model="fundamental_planar" of the single-pair functions).  Guided matching under a
 verified model of either family is csrc/guided.hip (match_guided, enqueue_match_guided, guided_mask, match_verify_guided).  Both have their
 many-pairs form too (affnet_epipolar_verify_many, affnet_match_guided_many): model="fundamental" of the *_many functions,
 enqueue_match_verify_guided_many, match_verify_guided_many, guided=True of spatial_rerank.  The ratio-test matcher with a per-row second
@@ -202,16 +203,19 @@ def _tent_tensor(LAFs1, tent_in_1, tent_in_2):
     return tent.to(torch.int32).contiguous()
 
 
-def verify_matches(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0):
+def verify_matches(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0, plane_th=3.0):
     """Geometric verification of tentative matches without ground truth.  Every tentative (tent_in_1[t], tent_in_2[t]) - the index tensors
     match_snn returns - is one affine hypothesis LAFs2[j] LAFs1[i]^-1; all are scored against all matches (centre error <= inl_th px), the
     best one is refined by lo_iters least-squares refits of `model` ('homography' or 'affine') on its inliers.  Deterministic.
     Returns (H (3,3) float64 device tensor mapping image 1 to image 2, inliers (T,) bool, info) with info = {counts (T,) int32 inliers per
     hypothesis, best, best_count, num_inliers, flags: 1 no valid hypothesis, 2 too few inliers to refit, 4 degenerate system}.
-    model='fundamental' is verify_epipolar (a scene with depth; `rounds` and `seed` are read by that model only)."""
+    model='fundamental' is verify_epipolar (a scene with depth; `rounds` and `seed` are read by that model only); model='fundamental_planar' is
+    verify_epipolar_planar (a scene with depth whose matches lie mostly on one plane; it alone reads `plane_th`)."""
     engine.require_cuda(LAFs1, "LAFs1")
     if model == "fundamental":
         return verify_epipolar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th, rounds, seed, lo_iters)
+    if model == "fundamental_planar":
+        return verify_epipolar_planar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th, plane_th, rounds, seed, lo_iters)
     H, inl, counts, summary = enqueue_verify(LAFs1, LAFs2, _tent_tensor(LAFs1, tent_in_1, tent_in_2), None, inl_th, model, lo_iters)
     return H, inl.bool(), _verify_info(counts, summary.cpu().tolist())
 
@@ -262,6 +266,68 @@ def verify_epipolar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=2.0, rounds=8, se
     return F, inl.bool(), dict(_verify_info(counts, summary.cpu().tolist()), rounds=int(rounds), seed=int(seed))
 
 
+def enqueue_verify_epipolar_planar(LAFs1, LAFs2, tent, count=None, inl_th=2.0, plane_th=3.0, rounds=8, seed=0, lo_iters=3):
+    """Plane-aware epipolar verification (affnet_epipolar_verify_planar) of the tentative matches `tent`, with the arguments of
+    enqueue_verify_epipolar plus plane_th, enqueued on the current stream with no synchronisation.  Returns capacity-sized device tensors:
+    enqueue_verify_epipolar's four (F, inliers, counts, summary - summary[3] carries flag 16 when the plane-and-parallax model was kept),
+    then H (3,3) float64 of the dominant plane, plane_inliers (cap,) uint8, plane_summary (4,) int32 and planar_info (4,) int32 =
+    [matches off the plane, best plane-and-parallax hypothesis, its count, its final inlier count].
+    counts is always the 8-point call's (cap*rounds entries, h = s * rounds + r over the tentatives).  With flag 16, summary[0] and summary[1]
+    are the best PLANE-AND-PARALLAX hypothesis (h = a * rounds + r over the off-plane list) and its count: they do not index counts then."""
+    engine.require_cuda(LAFs1, "LAFs1")
+    engine.require_cuda(LAFs2, "LAFs2")
+    engine.require_cuda(tent, "tent")
+    if tent.dtype != torch.int32 or tent.dim() != 2 or tent.size(1) != 2 or not tent.is_contiguous():
+        raise ValueError("enqueue_verify_epipolar_planar: tent must be a contiguous (cap,2) int32 tensor")
+    if count is not None and (count.dtype != torch.int32 or count.numel() != 1 or not count.is_cuda):
+        raise ValueError("enqueue_verify_epipolar_planar: count must be a (1,) int32 device tensor or None")
+    rounds, seed = int(rounds), int(seed)
+    if not 1 <= rounds <= _lib.EPI_MAX_ROUNDS:
+        raise ValueError("enqueue_verify_epipolar_planar: rounds must be in 1..%d" % _lib.EPI_MAX_ROUNDS)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("enqueue_verify_epipolar_planar: seed must fit 32 unsigned bits")
+    l1, l2 = LAFs1.contiguous().float(), LAFs2.contiguous().float()
+    dev, cap = l1.device, tent.size(0)
+    F = torch.zeros(3, 3, dtype=torch.float64, device=dev)
+    H = torch.zeros(3, 3, dtype=torch.float64, device=dev)
+    inl = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+    pinl = torch.zeros(max(cap, 1), dtype=torch.uint8, device=dev)
+    counts = torch.zeros(max(cap * rounds, 1), dtype=torch.int32, device=dev)
+    ints = torch.zeros(3, 4, dtype=torch.int32, device=dev)          # summary, plane summary, planar info
+    scratch = torch.empty(lib.affnet_epipolar_planar_scratch_bytes(cap, rounds), dtype=torch.uint8, device=dev)
+    one = torch.zeros(8, dtype=torch.float32, device=dev)           # stands in for an empty frame / match list: never read, but the boundary refuses NULL
+    ctx = engine.utility_ctx(dev)
+    rc = lib.affnet_epipolar_verify_planar(ctx, ptr(l1 if l1.numel() else one), l1.size(0), ptr(l2 if l2.numel() else one), l2.size(0),
+                                           ptr(tent if cap else one), ptr(count), cap, float(inl_th), float(plane_th), rounds, seed, int(lo_iters),
+                                           ptr(counts), ptr(F), ptr(inl), ptr(ints[0]), ptr(H), ptr(pinl), ptr(ints[1]), ptr(ints[2]), ptr(scratch),
+                                           engine.stream_of(dev))
+    check(rc, ctx, "affnet_epipolar_verify_planar")
+    return F, inl[:cap], counts[:cap * rounds], ints[0], H, pinl[:cap], ints[1], ints[2]
+
+
+def _planar_info(info, H, plane_inliers, n_off):
+    info.update(planar=bool(info["flags"] & _lib.EPI_FLAG_PLANAR), H=H, plane_inliers=plane_inliers.bool(), n_off_plane=int(n_off))
+    return info
+
+
+def verify_epipolar_planar(LAFs1, LAFs2, tent_in_1, tent_in_2, inl_th=2.0, plane_th=3.0, rounds=8, seed=0, lo_iters=3):
+    """verify_epipolar for the scene that defeats it: a wall with a few things in front of it, where most matches lie on one plane and the
+    8-point F is one of a family.  The dominant plane's homography H is found first (verify_matches, plane_th px); every match off that plane
+    gives a line through the epipole, two lines give it, F = [e]x H; all (matches off the plane) * rounds such hypotheses are scored against
+    all matches and the best is refitted on its inliers off the plane.  The result is this model when it has strictly more inliers than
+    verify_epipolar's, else verify_epipolar's own bytes.  Deterministic.
+    Returns (F, inliers, info) as verify_epipolar, with info additionally holding planar (bool: the plane-and-parallax model was kept;
+    flags then carries 16), H (3,3) float64 device tensor, plane_inliers (T,) bool and n_off_plane.
+    info["counts"] is always the 8-point model's per-hypothesis counts.  When planar is True, best and best_count describe the best
+    plane-and-parallax hypothesis (a * rounds + r over the matches off the plane, in ascending order) instead, so counts[best] is not
+    best_count then."""
+    engine.require_cuda(LAFs1, "LAFs1")
+    F, inl, counts, summary, H, pinl, _, pinfo = enqueue_verify_epipolar_planar(LAFs1, LAFs2, _tent_tensor(LAFs1, tent_in_1, tent_in_2), None, inl_th, plane_th,
+                                                                                  rounds, seed, lo_iters)
+    host = torch.cat([summary, pinfo]).cpu().tolist()
+    return F, inl.bool(), _planar_info(dict(_verify_info(counts, host[:4]), rounds=int(rounds), seed=int(seed)), H, pinl, host[4])
+
+
 def sampson_distance(F, LAFs1, LAFs2, tent_in_1, tent_in_2):
     """Square root of the Sampson error (pixels) of every tentative match's two centres under F (x2^T F x1 = 0): (T,) float64 on LAFs1's device."""
     F = torch.as_tensor(F, dtype=torch.float64, device=LAFs1.device).reshape(3, 3)
@@ -276,10 +342,11 @@ def sampson_distance(F, LAFs1, LAFs2, tent_in_1, tent_in_2):
 
 
 def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", lo_iters=3, rounds=8, seed=0,
-                     matcher="reference", fginn_radius=10.0, mutual=False):
+                     matcher="reference", fginn_radius=10.0, mutual=False, plane_th=3.0):
     """match_snn followed by verify_matches as one chain on the stream: the tentative list and its device-side count go from
     affnet_match_snn straight into affnet_verify_matches (model='fundamental': affnet_epipolar_verify, which alone reads `rounds` and
-    `seed`), and the host reads back once, at the end.
+    `seed`; model='fundamental_planar': affnet_epipolar_verify_planar, which reads `plane_th` too and adds verify_epipolar_planar's keys to
+    info), and the host reads back once, at the end.
     matcher: 'reference' is affnet_match_snn; 'snn' (the per-row ratio test) and 'fginn' (the ratio against the first neighbour more than
     fginn_radius px from the nearest one) put affnet_match_ratio in its place, with `mutual` as in match_ratio.
     Returns (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info) - the pieces of match_snn and verify_matches."""
@@ -305,6 +372,12 @@ def match_and_verify(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8
         rc = lib.affnet_match_snn(ctx, ptr(a), n1, ptr(b), n2, a.size(1), float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent), ptr(cnt),
                                   ptr(scratch), engine.stream_of(dev))
         check(rc, ctx, "affnet_match_snn")
+    if model == "fundamental_planar":
+        H, inl, counts, summary, Hp, pinl, _, pinfo = enqueue_verify_epipolar_planar(LAFs1, LAFs2, tent, cnt, inl_th, plane_th, rounds, seed, lo_iters)
+        host = torch.cat([cnt, summary, pinfo]).cpu().tolist()          # the one read-back
+        k = host[0]
+        info = dict(_verify_info(counts[:k * int(rounds)], host[1:5]), rounds=int(rounds), seed=int(seed))
+        return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), _planar_info(info, Hp, pinl[:k], host[5])
     if model == "fundamental":
         H, inl, counts, summary = enqueue_verify_epipolar(LAFs1, LAFs2, tent, cnt, inl_th, rounds, seed, lo_iters)
     else:
@@ -667,20 +740,26 @@ def guided_mask(LAFs1, LAFs2, model, kind="homography", radius=None):
 
 
 def match_verify_guided(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=0.8, inl_th=3.0, model="homography", guided_threshold=0.9, radius=None,
-                        mutual=True, lo_iters=3, rounds=8, seed=0):
+                        mutual=True, lo_iters=3, rounds=8, seed=0, plane_th=3.0):
     """match_snn, verification, guided matching under the verified model, verification of the guided matches - one chain on the stream: the
     tentative lists, their device-side counts, the first model and its summary (the guided call's gate) pass from call to call on the device,
-    and the host reads back once, at the end.  model: 'homography', 'affine' or 'fundamental', as in match_and_verify.
+    and the host reads back once, at the end.  model: 'homography', 'affine', 'fundamental' or 'fundamental_planar' (both stages verify with
+    affnet_epipolar_verify_planar, the guided stage reads its F as kind 'fundamental'), as in match_and_verify.
     Returns match_and_verify's tuple for the final stage: (tent_matches_in_1, tent_matches_in_2, H, inliers (T,) bool, info), with
     info["seed_stage"] = {tentatives, num_inliers, flags} of the first stage.  When the first stage found no model (its flags & 1) the final
     lists are empty and the final flags say so too."""
     a, b, l1, l2 = _guided_frames("match_verify_guided", descriptors1, descriptors2, LAFs1, LAFs2)
+    planar = model == "fundamental_planar"
+    if planar:
+        model = "fundamental"
     if model not in GUIDED_KINDS:
-        raise ValueError("model must be 'homography', 'affine' or 'fundamental'")
+        raise ValueError("model must be 'homography', 'affine', 'fundamental' or 'fundamental_planar'")
     n1, n2, dev = a.size(0), b.size(0), a.device
     epi = model == "fundamental"
 
     def verify(tent, cnt):
+        if planar:
+            return enqueue_verify_epipolar_planar(l1, l2, tent, cnt, inl_th, plane_th, rounds, seed, lo_iters)
         if epi:
             return enqueue_verify_epipolar(l1, l2, tent, cnt, inl_th, rounds, seed, lo_iters)
         return enqueue_verify(l1, l2, tent, cnt, inl_th, model, lo_iters)
@@ -696,15 +775,18 @@ def match_verify_guided(descriptors1, descriptors2, LAFs1, LAFs2, SNN_threshold=
         rc = lib.affnet_match_snn(ctx, ptr(a), n1, ptr(b), n2, a.size(1), float(SNN_threshold), ptr(md), ptr(idx), ptr(md2), ptr(tent0), ptr(cnt0),
                                   ptr(scratch), engine.stream_of(dev))
         check(rc, ctx, "affnet_match_snn")
-    H0, _, _, summary0 = verify(tent0, cnt0)
+    H0, _, _, summary0 = verify(tent0, cnt0)[:4]
     tent, cnt, _, _ = enqueue_match_guided(a, b, l1, l2, H0, model, radius, guided_threshold, float("inf"), mutual, summary0)
     tent = tent.contiguous()
-    H, inl, counts, summary = verify(tent, cnt)
-    host = torch.cat([cnt0, summary0, cnt, summary]).cpu().tolist()          # the one read-back
+    final = verify(tent, cnt)
+    H, inl, counts, summary = final[:4]
+    host = torch.cat([cnt0, summary0, cnt, summary] + ([final[7]] if planar else [])).cpu().tolist()          # the one read-back
     k = host[5]
     per = int(rounds) if epi else 1
-    info = _verify_info(counts[:k * per], host[6:])
+    info = _verify_info(counts[:k * per], host[6:10])
     if epi:
         info.update(rounds=int(rounds), seed=int(seed))
+    if planar:
+        _planar_info(info, final[4], final[5][:k], host[10])
     info["seed_stage"] = {"tentatives": host[0], "num_inliers": host[3], "flags": host[4]}
     return tent[:k, 0].long(), tent[:k, 1].long(), H, inl[:k].bool(), info

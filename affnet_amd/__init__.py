@@ -11,6 +11,7 @@ from .pytorch_sift import SIFTNet  # noqa: F401
 from . import LAF, HandCraftedModules, Losses, ReprojectionStuff, pytorch_sift  # noqa: F401
 from .ReprojectionStuff import verify_matches, enqueue_verify, match_and_verify  # noqa: F401
 from .ReprojectionStuff import verify_epipolar, enqueue_verify_epipolar, sampson_distance  # noqa: F401
+from .ReprojectionStuff import verify_epipolar_planar, enqueue_verify_epipolar_planar  # noqa: F401
 from .ReprojectionStuff import enqueue_match_guided, match_guided, guided_mask, match_verify_guided  # noqa: F401
 from .ReprojectionStuff import enqueue_match_ratio, match_ratio, match_fginn  # noqa: F401
 from .ReprojectionStuff import pair_table, enqueue_match_and_verify_many, match_and_verify_many, spatial_rerank  # noqa: F401

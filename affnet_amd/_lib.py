@@ -39,6 +39,7 @@ VERIFY_AFFINE, VERIFY_HOMOGRAPHY, VERIFY_TILE, VERIFY_CHUNK = 0, 1, 128, 128    
 KNN_MAX_K = 8                                                                                    # AFFNET_KNN_MAX_K: neighbours per query row of affnet_knn
 IVF_MAX_PROBE = 8                                                                                # AFFNET_IVF_MAX_PROBE: cells per query row of affnet_ivf_search
 EPI_MAX_ROUNDS, EPI_TILE, EPI_CHUNK, EPI_SOLVE_TILE = 64, 128, 128, 64                            # include/affnet_hip.h AFFNET_EPI_*
+EPI_FLAG_PLANAR = 16                                                                              # AFFNET_EPI_FLAG_PLANAR: the plane-and-parallax model was kept
 GUIDED_PLANAR, GUIDED_EPIPOLAR, GUIDED_MUTUAL = 0, 1, 1                                           # include/affnet_hip.h AFFNET_GUIDED_*
 RATIO_MUTUAL = 1                                                                                  # include/affnet_hip.h AFFNET_RATIO_MUTUAL
 VERIFY_FLAG_PAIR_RANGE = 8                                                                    # AFFNET_VERIFY_FLAG_PAIR_RANGE: pair row out of range (the *_many calls)
@@ -150,6 +151,9 @@ SYMBOLS = {
     "affnet_match_guided_scratch_bytes": (_SZ, [_I, _I, _I]),
     "affnet_match_guided": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "affnet_guided_mask": (_I, [_P, _P, _I, _P, _I, _P, _I, C.c_float, _P, _P, _P]),
+    "affnet_epipolar_planar_scratch_bytes": (_SZ, [_I, _I]),
+    "affnet_epipolar_planar_score": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, C.c_float, C.c_float, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "affnet_epipolar_verify_planar": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, C.c_float, C.c_float, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "affnet_epipolar_many_scratch_bytes": (_SZ, [_I, _I, _I]),
     "affnet_epipolar_verify_many": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, C.c_float, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P]),
     "affnet_match_guided_many_scratch_bytes": (_SZ, [_I, _I, _I, _I]),

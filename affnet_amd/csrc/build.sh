@@ -10,7 +10,7 @@ set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function $EXTRA_HIPCC_FLAGS"
-FILES="config_fill context pyramid detect laf_ops weights_pack cnn32 derive_u cnn_trunk_affnet cnn_trunk_affnet_poly cnn_trunk_orinet cnn_trunk_hardnet cnn_trunk_hardnet_poly cnn_trunk_hardnet_f43 cnn_trunk_hardnet_c5 cnn_trunk_hardnet_c1 hardnet_conv5_f43 cnn_heads pipeline match knn knn_q8 ivf spatial epipolar guided ratio_match handcrafted sift tfeat fullconv"
+FILES="config_fill context pyramid detect laf_ops weights_pack cnn32 derive_u cnn_trunk_affnet cnn_trunk_affnet_poly cnn_trunk_orinet cnn_trunk_hardnet cnn_trunk_hardnet_poly cnn_trunk_hardnet_f43 cnn_trunk_hardnet_c5 cnn_trunk_hardnet_c1 hardnet_conv5_f43 cnn_heads pipeline match knn knn_q8 ivf spatial epipolar epipolar_planar guided ratio_match handcrafted sift tfeat fullconv"
 PROBE_FILES="debug split_probe cnn_probe"
 pids=()
 objs=""

@@ -3,7 +3,7 @@
 detect + AffNet + OriNet + HardNet on both images (one batched call when they have the same size), SNN ratio matching
 (MFMA distance kernel, no N x N matrix in HBM), homography consistency at 6 px.
 
-    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental] [--guided]]
+    python examples/graf_matching/match_graf.py [--desc hardnet|sift|tfeat] [--tfeat-weights PATH] [--verify [--model homography|fundamental|fundamental_planar] [--guided]]
                                                  [--matcher reference|snn|fginn [--mutual] [--fginn-radius R]] [IMG1 IMG2 H1to2 [N [HARDNET.pth]]]
 
 Defaults: tests/golden/graf_img1.png, graf_img6.png, graf_H1to6p, N = 3000, --desc hardnet.  The reference's HardNet++.pth is a
@@ -22,6 +22,10 @@ best refined as a rank-2 fundamental matrix, Sampson error <= 2 px); the line gi
 median Sampson distance of the ground-truth matches under the recovered F.  graf is a PLANAR scene: every F compatible with its homography
 explains the wall, so the F printed here is one of a family - good as an inlier test, not as the pair's epipolar geometry.  The model is
 meant for two views of a scene with depth, where a homography keeps only the dominant plane.
+--model fundamental_planar (with --verify): the plane-aware epipolar model (verify_epipolar_planar: the dominant plane's homography first, then
+F = [e]x H from the matches off that plane, kept when it has more inliers than the 8-point F); the line says which of the two models was kept,
+how many matches lie off the plane and how many inliers the plane has.  On graf, a wall, there is next to nothing off the plane: the 8-point
+model is expected to stay.
 --guided (with --verify): guided matching behind the verification (match_verify_guided: the descriptors are searched again, every keypoint among
 the keypoints the verified model allows, and the result is verified once more); a further line gives the guided tentatives, their verified
 inliers and how many of each the ground-truth homography confirms, by the same 6 px rule.
@@ -100,8 +104,8 @@ def main(argv):
     model = "homography"
     if "--model" in argv:
         i = argv.index("--model")
-        if i + 1 >= len(argv) or argv[i + 1] not in ("homography", "fundamental"):
-            sys.exit("--model takes homography or fundamental")
+        if i + 1 >= len(argv) or argv[i + 1] not in ("homography", "fundamental", "fundamental_planar"):
+            sys.exit("--model takes homography, fundamental or fundamental_planar")
         model = argv[i + 1]
         argv = argv[:i] + argv[i + 2:]
     if "--desc" in argv:
@@ -139,14 +143,17 @@ def main(argv):
             t1, t2, _, _ = match_ratio(r1["descriptors"], r2["descriptors"], r2["LAFs"], fginn_radius if matcher == "fginn" else None, 0.8, mutual=mutual)
         _, plain, _ = get_GT_correspondence_indexes(r1["LAFs"][t1], r2["LAFs"][t2], H1to2, dist_threshold=6)
         print("Test on %s%s, %d tentatives %d true matches %s  inl.ratio" % (tag, mtag, t1.numel(), plain.numel(), str(plain.numel() / max(1, t1.numel()))[:5]))
-        if verify and model == "fundamental":
-            v1, v2, F, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0, model="fundamental", **mkw)
+        if verify and model in ("fundamental", "fundamental_planar"):
+            v1, v2, F, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0, model=model, **mkw)
             assert torch.equal(v1, t1) and torch.equal(v2, t2)
             _, ok, _ = get_GT_correspondence_indexes(r1["LAFs"][v1[inl]], r2["LAFs"][v2[inl]], H1to2, dist_threshold=6)
             d = sampson_distance(F, r1["LAFs"], r2["LAFs"], t1[plain], t2[plain])
             print("Verified on %s (fundamental; planar scene: F is one of a family), %d epipolar inliers of %d tentatives (best hypothesis %d, flags %d), %d of them "
                   "true matches, median Sampson distance of the %d true matches %.2f px"
                   % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), plain.numel(), d.median().item() if d.numel() else float("nan")))
+            if model == "fundamental_planar":
+                print("Plane-aware on %s: kept the %s model; plane with %d inliers, %d matches off the plane"
+                      % (tag, "plane-and-parallax" if info["planar"] else "8-point", int(info["plane_inliers"].sum()), info["n_off_plane"]))
         elif verify:
             v1, v2, H, inl, info = match_and_verify(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0, **mkw)
             assert torch.equal(v1, t1) and torch.equal(v2, t2)
@@ -158,7 +165,7 @@ def main(argv):
             print("Verified on %s, %d inliers of %d tentatives (best hypothesis %d, flags %d), %d of them true matches, corner error vs H1to2 %.1f px"
                   % (tag, info["num_inliers"], v1.numel(), info["best_count"], info["flags"], ok.numel(), err))
         if verify and guided:
-            g1, g2, _, ginl, ginfo = match_verify_guided(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=2.0 if model == "fundamental" else 3.0,
+            g1, g2, _, ginl, ginfo = match_verify_guided(r1["descriptors"], r2["descriptors"], r1["LAFs"], r2["LAFs"], 0.8, inl_th=3.0 if model == "homography" else 2.0,
                                                          model=model)
             gt = lambda a, b: get_GT_correspondence_indexes(r1["LAFs"][a], r2["LAFs"][b], H1to2, dist_threshold=6)[1].numel() if a.numel() else 0
             print("Guided on %s (%s), %d guided tentatives %d true matches, %d inliers (flags %d, seed stage flags %d), %d of them true matches"

@@ -561,6 +561,8 @@ int affnet_verify_matches_many(affnet_ctx* ctx, const float* d_lafs1, int rows1,
  *
  * Known limit (not detected here): when most matches lie on one plane, F is one of a family - every F compatible with the plane's
  * homography explains them - and the matches off the plane decide which; the returned F is then reliable only as an inlier test.
+ * affnet_epipolar_verify_planar (the section after this one) is the call for such scenes: it estimates the plane first and takes F
+ * from the matches off it.
  *
  * Prep, per tentative t: indices are tested before any load.  Match t is usable (can be an inlier) when its indices are in range and
  * its two centres are finite, otherwise its points are NaN; it is usable as a MEMBER of a hypothesis when all twelve numbers of its
@@ -621,6 +623,68 @@ int affnet_epipolar_score(affnet_ctx* ctx, const float* d_lafs1, int n1, const f
 int affnet_epipolar_verify(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
                            const int32_t* d_count, int t_max, float inl_th, int rounds, uint32_t seed, int lo_iters, int32_t* d_counts,
                            double* d_model, uint8_t* d_inlier, int32_t* d_summary, void* d_scratch, void* stream);
+
+/* ---- plane-aware epipolar verification: plane-and-parallax F ----
+ *
+ * A wall with a few things in front of it: most matches lie on one plane, and the 8-point F above is then one of a family.  With the
+ * plane's homography H known, every match (x1, x2) OFF the plane gives a line l = (H x1) x x2 through the epipole e of image 2; two
+ * lines give e, and F = [e]x H.  This call runs the two existing verifications, builds that model from the matches off the plane and
+ * keeps whichever has more inliers.  Deterministic, bounded work, no host synchronisation, all buffers the caller's.  Inputs as for
+ * affnet_epipolar_verify plus plane_th (pixels, finite and > 0); d_scratch affnet_epipolar_planar_scratch_bytes(t_max, rounds) bytes,
+ * 16-byte aligned.  fp64 below is without fused multiply-add, in the written order.  T is the device-side row count.
+ *
+ * 1. Plane: affnet_verify_matches(model = AFFNET_VERIFY_HOMOGRAPHY, inl_th = plane_th, lo_iters) -> d_plane double[9] (H),
+ *    d_plane_inlier (t_max) uint8, d_plane_summary int32[4], with the bytes of that call.
+ * 2. Plain F: affnet_epipolar_verify(inl_th, rounds, seed, lo_iters) -> d_model, d_inlier, d_counts, d_summary, with the bytes of that call.
+ * 3. Off-plane list: match t is off the plane when it is usable (indices in range, tested before any load, and both centres finite) and
+ *    d_plane_inlier[t] == 0.  The list holds these t in ascending order; U is its length.  Stages 4 to 7 are skipped - the result is
+ *    the plain one - when d_plane_summary[3] has flag 1 or U < 2.
+ * 4. Parallax line (fp64) of a match with centres (x, y), (u, v): p_k = (H[k][0]*x + H[k][1]*y) + H[k][2]; l0 = p1 - p2*v,
+ *    l1 = p2*u - p0, l2 = p0*v - p1*u; n = sqrt(l0*l0 + l1*l1); the line is unusable when n is zero or not finite, else l^ = l / n.
+ * 5. Hypotheses: h = a * rounds + r, a in [0,U), r in [0,rounds); partner b = ((uint64)x * U) >> 32 with
+ *    x = lowbias32((a * 0x9E3779B1) ^ (r * 0x85EBCA77) ^ (1 * 0xC2B2AE3D) ^ seed) (the hash above), and b = (b + 1) % U when b == a.
+ *    a and b index the list.  e = l^_a x l^_b: e0 = la1*lb2 - la2*lb1, e1 = la2*lb0 - la0*lb2, e2 = la0*lb1 - la1*lb0.  F = [e]x H:
+ *    F[0][c] = e1*H[2][c] - e2*H[1][c], F[1][c] = e2*H[0][c] - e0*H[2][c], F[2][c] = e0*H[1][c] - e1*H[0][c].  Then F / sqrt(sum of
+ *    squares) and the sign rule, as above; stored as nine fp32.  Invalid - NaN model, count 0, never chosen - when a line is unusable
+ *    or the norm is zero or not finite.  Hypotheses at or beyond U * rounds are neither read nor written.
+ * 6. Score and select: the fp32 Sampson scoring above of the U * rounds hypotheses against all T matches, and the same selection.
+ * 7. Refit (fp64), model 0 = the best hypothesis widened to double with its fp32 inlier set as mask; lo_iters times { S = matches in the
+ *    current mask that are off the plane and have a usable line; fewer than 2: stop with flag 2; N = sum over S of l^ l^T (3 x 3);
+ *    eigenvectors by the cyclic Jacobi above with n = 3; e = the eigenvector of the smallest diagonal entry (the first on ties); stop
+ *    with flag 4 when the second-smallest entry is <= 1e-12 x the largest or anything is not finite; F = [e]x H, unit norm, sign (a
+ *    zero or non-finite norm: flag 4); new mask = Sampson error in fp64 <= inl_th^2 over all T }, keeping the model with the largest
+ *    mask (ties: the earliest).
+ * 8. Decision: when the final inlier count of stage 7 is strictly larger than d_summary[2] of stage 2, d_model and d_inlier become the
+ *    plane-and-parallax model and mask, and d_summary = {best h of stage 6, its count, final inlier count, flags of stage 7 |
+ *    AFFNET_EPI_FLAG_PLANAR}.  Otherwise they stay affnet_epipolar_verify's bytes.  d_counts is always stage 2's.
+ *
+ * d_planar_info int32[4] = {U, best hypothesis of stage 6, its count, final inlier count of stage 7}; {U, -1, 0, 0} when the stages
+ * did not run or no hypothesis was valid.  t_max == 0, T < 3, U in {0, 1}, a plane summary with flag 1 and a pure plane are valid
+ * inputs and give the plain result.  An input of random matches only is valid too, but not special: every match is an affine
+ * hypothesis that counts itself, so stage 1 reports "a plane" of one or a few matches, the stages run (two lines always meet, so a
+ * hypothesis has at least its two members as inliers) and rule 8 decides - such an input may return AFFNET_EPI_FLAG_PLANAR with a
+ * handful of inliers, as affnet_epipolar_verify returns a handful for it. */
+#define AFFNET_EPI_FLAG_PLANAR 16   /* d_summary[3]: the result is the plane-and-parallax model */
+
+/* Host only.  Negative arguments count as 0. */
+size_t affnet_epipolar_planar_scratch_bytes(int t_max, int rounds);
+
+/* Stages 1 and 3 to 6, for tests.  d_list (t_max) int32: the off-plane list, U entries; d_n_off int32[2] = {U, U as stages 4 to 7 use
+ * it: 0 when they are skipped}; d_hyp (t_max*rounds, 9) fp32 or NULL; d_counts (t_max*rounds) int32; d_best int32[2] as in
+ * affnet_epipolar_score.  List rows at or beyond U and hypotheses at or beyond U * rounds are neither read nor written.
+ * AFFNET_ERR_INVALID as for affnet_epipolar_verify_planar. */
+int affnet_epipolar_planar_score(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                                 const int32_t* d_count, int t_max, float inl_th, float plane_th, int rounds, uint32_t seed, int lo_iters,
+                                 double* d_plane, uint8_t* d_plane_inlier, int32_t* d_plane_summary, int32_t* d_list, int32_t* d_n_off,
+                                 float* d_hyp, int32_t* d_counts, int32_t* d_best, void* d_scratch, void* stream);
+
+/* All eight stages.  AFFNET_ERR_INVALID in front of the first launch: every check of affnet_epipolar_verify, plane_th not finite or
+ * <= 0, a NULL d_plane, d_plane_inlier, d_plane_summary or d_planar_info. */
+int affnet_epipolar_verify_planar(affnet_ctx* ctx, const float* d_lafs1, int n1, const float* d_lafs2, int n2, const int32_t* d_tent,
+                                  const int32_t* d_count, int t_max, float inl_th, float plane_th, int rounds, uint32_t seed,
+                                  int lo_iters, int32_t* d_counts, double* d_model, uint8_t* d_inlier, int32_t* d_summary,
+                                  double* d_plane, uint8_t* d_plane_inlier, int32_t* d_plane_summary, int32_t* d_planar_info,
+                                  void* d_scratch, void* stream);
 
 /* ---- guided matching: the descriptors searched again under a verified model ----
  *

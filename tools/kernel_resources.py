@@ -129,6 +129,10 @@ DESIGN_KERNELS = [
     ("epi_solve_kernel", "epipolar verification: one 8-point solve per thread in fp64, the 8 x 9 system in LDS as [element][thread]"),
     ("epi_score_kernel", "epipolar verification: (T x rounds) x T scoring of the hypotheses by the Sampson error"),
     ("epi_lo_kernel", "epipolar verification: fp64 local optimisation (9 x 9 and 3 x 3 Jacobi in LDS), one workgroup"),
+    ("epp_list_kernel", "plane-aware epipolar verification: centres and the stable compaction of the matches off the plane, one workgroup"),
+    ("epp_hyp_kernel", "plane-aware epipolar verification: one plane-and-parallax hypothesis per thread in fp64, registers only"),
+    ("epp_score_kernel", "plane-aware epipolar verification: (U x rounds) x T scoring by the shared Sampson body"),
+    ("epp_refit_kernel", "plane-aware epipolar verification: fp64 refit of the epipole (3 x 3 Jacobi in LDS) and the decision, one workgroup"),
     ("guided_tile_kernel<0, 2, false>", "guided matching, planar model, forward pass: the matcher's distance tiles over one column chunk, two admissible neighbours per row and lane"),
     ("guided_tile_kernel<0, 1, true>", "guided matching, planar model, backward pass: the sides exchanged, one admissible neighbour"),
     ("guided_tile_kernel<1, 2, false>", "guided matching, epipolar model, forward pass"),
